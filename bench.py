@@ -20,6 +20,16 @@ of a data-parallel model; the optional all-gather of the outputs along B
 as ``ms_per_step_with_output_allgather``.
 
 Prints ONE JSON line on rank 0.
+
+A plain run (``python bench.py --gpus G --steps K --warmup W``) sets up, warms up, times the K steps and prints the
+headline fields (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, ``config``).
+Everything else - the other arithmetic engines, per-stage event times and the roofline objects, the selector-only
+timing, the output all-gather and strong-scaling figures of a multi-rank run, the batch sweep, HIP-graph replay, the
+stock PyTorch-ROCm composition, LRTC, whole-model forwards and the CPU baseline - runs only with ``--full``
+(``--no-extras`` / ``--no-cpu-baseline`` then drop parts of it).
+
+``--dump-outputs DIR`` writes what the timed path returned in its last timed step as ``DIR/<name>.npy`` (float32; rank
+0's rows in a multi-rank run).  Inputs and weights are seeded, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -51,13 +61,42 @@ def parse_args():
     ap.add_argument("--series", type=int, default=512)
     ap.add_argument("--d-model", type=int, default=64)
     ap.add_argument("--k-periods", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the LRTC / whole-model extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the LRTC / whole-model extras")
     ap.add_argument("--act", default="gelu", help="diagnostic: activation (gelu = reference default)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --batch rows per rank (default); strong: --batch rows in total, split over the ranks "
                          "(BASELINE configs[3] / the metric's fixed B=256)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays) -> None:
+    """``arrays``: name -> tensor.  Each is written as ``dirname/<name>.npy`` in float32.  Should the total exceed
+    DUMP_LIMIT_BYTES, every array keeps the same fixed, seeded sample of its leading-axis rows."""
+    import numpy as np
+
+    host = {k: v.detach().to("cpu").float().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total
+        for k, a in host.items():
+            keep = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            host[k] = np.ascontiguousarray(a[rows])
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    for k, a in host.items():
+        np.save(out / f"{k}.npy", a)
 
 
 RUN_IN_STEPS = 200            # untimed steps in front of the caller's --warmup (clock ramp, see run_rank)
@@ -250,7 +289,7 @@ def run_rank(args) -> None:
 
     engine = blk.engine or pkg.pack.default_engine()
     alt_ms = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # the other conv/chain arithmetic, timed briefly for comparison (same weights, same input)
         for alt in ("f32", "bf16x3", "f16x2", "bf16"):    # "bf16" = BASELINE configs[2] (plain bf16 operands, fp32 accumulate)
             if alt == engine:
@@ -270,10 +309,11 @@ def run_rank(args) -> None:
     with torch.inference_mode():
         # everything that costs host time goes in front of the warm-up: the GPU drops its clocks while it idles, and
         # a timed region that starts behind a few ms of host work (creating the stage events did that) measures the
-        # ramp back up.  Stage events (HIP events on the launch stream, inside the timed region) bracket every 4th
-        # forward: each record costs ~3 us on the stream.
-        pkg.lib.check(lib.ftn_stage_timing(1), "ftn_stage_timing")      # creates the events
-        lib.ftn_stage_timing(0)
+        # ramp back up.  Stage events (HIP events on the launch stream, inside the timed region; --full only) bracket
+        # every 4th forward: each record costs ~3 us on the stream.
+        if args.full:
+            pkg.lib.check(lib.ftn_stage_timing(1), "ftn_stage_timing")      # creates the events
+            lib.ftn_stage_timing(0)
         # bring the clocks up before the W warm-up steps the caller asked for (a W of 2-5 steps is 1-3 ms: the
         # same K steps then time 10-25 % slower than behind a 0.1 s run-in - measured, round 2)
         for _ in range(RUN_IN_STEPS):  # a fixed count, not a time: every rank must issue the same number of exchanges
@@ -289,8 +329,10 @@ def run_rank(args) -> None:
         os.close(saved_stdout)
         # six event records cost ~16 us of stream time per instrumented step: every 16th step of a long run (18 samples
         # of every stage at the default K = 300), every 4th of a short one
-        events_every = 16 if args.steps >= 128 else (4 if args.steps >= 16 else 1)
-        pkg.lib.check(lib.ftn_stage_timing(events_every), "ftn_stage_timing")
+        events_every = None
+        if args.full:
+            events_every = 16 if args.steps >= 128 else (4 if args.steps >= 16 else 1)
+            pkg.lib.check(lib.ftn_stage_timing(events_every), "ftn_stage_timing")
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -300,52 +342,55 @@ def run_rank(args) -> None:
         t1 = time.perf_counter()
         ms_sum = (ctypes.c_float * 6)()
         ncalls = ctypes.c_int(0)
-        pkg.lib.check(lib.ftn_stage_times(ms_sum, 6, ctypes.byref(ncalls)), "ftn_stage_times")
-        lib.ftn_stage_timing(0)
-        ms_gather = None
-        if step_gather is not None:
-            for _ in range(2):
-                step_gather()
-            drain()
-            torch.cuda.synchronize()
-            barrier()
-            g0 = time.perf_counter()
-            for _ in range(args.steps):
-                step_gather()
-            drain()
-            torch.cuda.synchronize()
-            barrier()
-            ms_gather = (time.perf_counter() - g0) * 1e3 / args.steps
-        # the selector alone (S1-S5: spectrum, median, batch mean, top-k, grouping, weights), HIP events on
-        # the launch stream (= torch's current stream: runtime.py passes it to every C-ABI call)
-        sel_mod = blk.period_selector
-        for _ in range(3):
-            sel_mod.select_device(x)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            sel_mod.select_device(x)
-        e1.record()
-        torch.cuda.synchronize()
-        sel_us = e0.elapsed_time(e1) / 20 * 1e3
-        # a weak-scaling run over several ranks also times the metric's fixed batch split over them (B/world rows
-        # per rank, the same exchange): the strong-scaling figure of the same launch, every rank takes part
-        strong = None
-        if use_dist and dist_world > 1 and args.scaling == "weak" and B % dist_world == 0:
-            xs = x[: B // dist_world].contiguous()
+        if args.full:
+            pkg.lib.check(lib.ftn_stage_times(ms_sum, 6, ctypes.byref(ncalls)), "ftn_stage_times")
+            lib.ftn_stage_timing(0)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"timesblock_out": y})
+        ms_gather = sel_us = strong = None
+        if args.full:
+            if step_gather is not None:
+                for _ in range(2):
+                    step_gather()
+                drain()
+                torch.cuda.synchronize()
+                barrier()
+                g0 = time.perf_counter()
+                for _ in range(args.steps):
+                    step_gather()
+                drain()
+                torch.cuda.synchronize()
+                barrier()
+                ms_gather = (time.perf_counter() - g0) * 1e3 / args.steps
+            # the selector alone (S1-S5: spectrum, median, batch mean, top-k, grouping, weights), HIP events on
+            # the launch stream (= torch's current stream: runtime.py passes it to every C-ABI call)
+            sel_mod = blk.period_selector
+            for _ in range(3):
+                sel_mod.select_device(x)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
             for _ in range(20):
-                step(xs)
+                sel_mod.select_device(x)
+            e1.record()
             torch.cuda.synchronize()
-            barrier()
-            s0 = time.perf_counter()
-            for _ in range(args.steps):
-                step(xs)
-            torch.cuda.synchronize()
-            barrier()
-            strong = time.perf_counter() - s0
-        step()                                       # leave the block's lazy counters on a full forward
+            sel_us = e0.elapsed_time(e1) / 20 * 1e3
+            # a weak-scaling run over several ranks also times the metric's fixed batch split over them (B/world rows
+            # per rank, the same exchange): the strong-scaling figure of the same launch, every rank takes part
+            if use_dist and dist_world > 1 and args.scaling == "weak" and B % dist_world == 0:
+                xs = x[: B // dist_world].contiguous()
+                for _ in range(20):
+                    step(xs)
+                torch.cuda.synchronize()
+                barrier()
+                s0 = time.perf_counter()
+                for _ in range(args.steps):
+                    step(xs)
+                torch.cuda.synchronize()
+                barrier()
+                strong = time.perf_counter() - s0
+            step()                                   # leave the block's lazy counters on a full forward
     batch_sweep = None
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # what a rank of an N-GPU strong-scaling run sees: the same block at B / N rows (eager launches and one
         # hipGraphLaunch per step); t(256) / t(32) bounds the 8-GPU strong-scaling speed-up of the compute
         batch_sweep = {}
@@ -378,7 +423,7 @@ def run_rank(args) -> None:
         with torch.inference_mode():
             step()
     torch_rocm = None
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # the same block as stock PyTorch-ROCm ops on the same tensor (the mirror's torch backend: rfft / median /
         # topk, F.pad + reshape, nn.Conv2d via MIOpen, GELU, stack / sum): what this chip gives without these kernels
         try:
@@ -400,7 +445,7 @@ def run_rank(args) -> None:
         with torch.inference_mode():
             step()
     ms_graph = None
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # the same step captured once and replayed as ONE hipGraphLaunch: what remains of the eager step's
         # inter-kernel launch gaps (extra; `value` is the eager number)
         gf = pkg.graph.GraphedForward(blk, x)
@@ -437,92 +482,10 @@ def run_rank(args) -> None:
     if rank == 0:
         periods = blk.period_selector.last_selected_periods.tolist()
         G = int(blk._last_group_count)
-        # pixels one launch processes: B * sum_g (L + pad_g)
-        pads = [(-L) % p for p in sorted(set(periods))]
-        px = B * sum(L + pd for pd in pads)
-        stage_ms = [ms_sum[i] / max(1, ncalls.value) for i in range(6)]
-        macs = stage_macs(C, F, ks, ratio)
-        dom = int(np.argmax(stage_ms))
-        # executed multiply-adds per launch.  Stage A runs once per window position; so do two of stage C's four
-        # products in its position-major form (k_mlp_pos, the d_model-64 split-engine shape: res1 and res2 once per
-        # (b, t), W_out1 / W_in2 per grid pixel) - FTN_MLP_POS=0 or another shape keeps all four per grid pixel
-        from math import ceil
-        nk, mid = len(ks), max(1, int(ceil(min(C, F) / ratio)))
-        pos_major = (os.environ.get("FTN_MLP_POS", "1") != "0" and engine != "f32" and C == 64 and nk * 16 == 48
-                     and mid <= 16)
-        mac_launch = [macs[0] * B * L, macs[1] * px,
-                      (2 * C * F * B * L + 2 * nk * mid * F * px) if pos_major else macs[2] * px,
-                      macs[3] * px, macs[4] * px, 0]
-        # ALGORITHMIC work of the dominant launch: executed (folded, unpadded) multiply-adds, each an fp32
-        # product.  Peak: the dense MFMA peak of the pipe the stage runs on - fp32 MFMA for engine f32; for
-        # bf16x3 every fp32 product costs six bf16 partial products, so the ceiling of fp32-equivalent work on
-        # the bf16 pipe is 2500/6; plain bf16 (one product) 2500.  `frac_pipe` is the pipe-occupancy view of the
-        # same launch (all six products and the K padding counted against 2500).
-        flops_alg = 2.0 * mac_launch[dom]
-        nprod = {"f32": 1, "bf16x3": 6, "f16x2": 3, "bf16": 1}[engine]
-        on_mfma = dom in (1, 2, 3)
-        peak_tf = FP32_MFMA_PEAK_TF if (engine == "f32" or not on_mfma) else BF16_MFMA_PEAK_TF / nprod
-        achieved = flops_alg / (stage_ms[dom] * 1e-3) / 1e12 if stage_ms[dom] > 0 else 0.0
-        frac_pipe = None
-        if engine != "f32" and on_mfma:
-            mid2 = macs[1] // sum(kh * kw for kh, kw in ks)          # mid*mid
-            if dom == 2:
-                kpad = lambda v: (v + 31) // 32 * 32
-                nbm = len(ks) * int(round(mid2 ** 0.5))
-                if pos_major:                                  # per launch: K padded to 32, per-position and per-pixel parts
-                    mac_pad_launch = (kpad(C) * F + F * C) * B * L + (kpad(nbm) * F + F * nbm) * px
-                else:
-                    mac_pad_launch = (kpad(nbm) * F + kpad(C) * F + F * (nbm + C)) * px
-            else:
-                mac_pad_launch = mid2 * sum((kh * kw + 1) // 2 * 2 for kh, kw in ks) * px
-            frac_pipe = 2.0 * mac_pad_launch * nprod / (stage_ms[dom] * 1e-3) / 1e12 / BF16_MFMA_PEAK_TF
-        nominal = 2.0 * pkg.pack.macs_per_pixel(C, F, ks, ratio) * px
-        executed = 2.0 * sum(mac_launch)
-        conv_ms = sum(stage_ms)
-        # HBM traffic per launch from the committed rocprofv3 PMC passes of this same command (tools/profile2.sh:
-        # FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, separate --pmc runs); keys are kernel names, matched by prefix
-        pmc_k = {}
-        pmc = ROOT / "profiles" / "pmc_latest.json"
-        if pmc.exists():
-            try:
-                pmc_k = json.loads(pmc.read_text())["kernels"]
-            except Exception:
-                pmc_k = {}
-
-        def pmc_bytes(prefixes):
-            tot = 0.0
-            for k, v in pmc_k.items():
-                if any((k + "(").startswith(pf) for pf in prefixes) and v.get("hbm_bytes") is not None:
-                    tot += float(v["hbm_bytes"])
-            return tot or None
-
-        kname = STAGES[dom].split("(")[-1].rstrip(")")
-        traffic = pmc_bytes([kname])
-        traffic_source = ("profiles/pmc_latest.json (committed rocprofv3 --pmc passes of this command on another run, "
-                          "FETCH_SIZE x2 + WRITE_SIZE per launch; not measured in this run)" if traffic else None)
-
-        def pmc_field(prefix, field):
-            for k, v in pmc_k.items():
-                if (k + "(").startswith(prefix) and v.get(field) is not None:
-                    return float(v[field])
-            return None
-
-        # the two conv launches (stages B and D): north_star's "MFMA utilisation on the conv against chip peak"
-        conv_us = 0.5 * (stage_ms[1] + stage_ms[3]) * 1e3
-        conv_tf = 2.0 * mac_launch[1] / (conv_us * 1e-6) / 1e12 if conv_us > 0 else 0.0
-        conv_peak = FP32_MFMA_PEAK_TF if engine == "f32" else BF16_MFMA_PEAK_TF / nprod
-        roofline_conv = {"bound": "mfma", "kernel": "k_conv* (stages B and D, mean of the two launches)", "us": conv_us,
-                         "achieved": conv_tf, "peak": conv_peak, "unit": "TFLOP/s", "frac": conv_tf / conv_peak,
-                         "mfma_util_pmc": pmc_field("k_conv", "mfma_util"),
-                         "mfma_util_source": "SQ_VALU_MFMA_BUSY_CYCLES / (SIMDs x kernel cycles), profiles/pmc_latest.json",
-                         "traffic": pmc_bytes(["k_conv"])}
-        sel_bytes = 4.0 * B * L * C
-        # S1-S5 as timed below (standalone selector: plain k_finalize, not the fused finalize + stage-A launch)
-        sel_counter = pmc_bytes(["k_spectrum", "k_colsum", "k_finalize("])
         out = {
             "metric": "TimesBlock-forward series/sec (B=256 L=336 N=512)",
             "value": value, "unit": "series/s", "n_gpus": dist_world if use_dist else 1, "steps": args.steps,
-            "warmup": args.warmup, "run_in_steps": RUN_IN_STEPS, "stage_events_every": events_every,
+            "warmup": args.warmup, "run_in_steps": RUN_IN_STEPS,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": {"f32": "f32", "bf16x3": "f32 via bf16x3 split", "f16x2": "f32 via f16x2 split", "bf16": "bf16"}[engine],
             "data": "synthetic",
@@ -540,26 +503,10 @@ def run_rank(args) -> None:
                                        f"{', REHEARSAL: ranks share GPUs' if os.environ.get('FTN_BENCH_SHARE_GPU') == '1' else ''}): one "
                                        "exchange of [F] fp64 partial sums per step, outputs stay sharded"
                                        if use_dist else "single")},
-            "roofline": {"bound": "mfma", "kernel": STAGES[dom], "achieved": achieved, "peak": peak_tf,
-                         "unit": "TFLOP/s", "frac": achieved / peak_tf, "traffic": traffic, "traffic_source": traffic_source,
-                         "definition": "achieved = executed (folded, unpadded) fp32 multiply-adds x2 per launch / avg "
-                                       "launch time (HIP events in the timed region); peak = dense 16-bit MFMA peak / "
-                                       "products per fp32 multiply (3 for f16x2, 6 for bf16x3); fp32 MFMA peak for f32",
-                         "frac_algorithmic": achieved / peak_tf, "frac_pipe": frac_pipe,
-                         "flops_per_launch": flops_alg, "avg_launch_ms": stage_ms[dom],
-                         "stage_ms": dict(zip(STAGES, [round(v, 4) for v in stage_ms])),
-                         "stage_note": "stage A (a = W_in1 x + b) runs inside the selector's finalize launch "
-                                       "(k_finalize_pw), so A_pw_in only brackets two event marks",
-                         "conv_path_ms": conv_ms,
-                         "block_executed_tflops": executed / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
-                         "block_nominal_tflops": nominal / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
-                         "block_frac_algorithmic": (executed / (conv_ms * 1e-3) / 1e12 / peak_tf) if conv_ms > 0 else 0.0},
-            "roofline_conv": roofline_conv,
-            "roofline_selector": {"bound": "hbm", "bytes": sel_bytes, "counter_bytes": sel_counter, "us": sel_us,
-                                  "GB/s": sel_bytes / (sel_us * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
-                                  "frac_hbm": sel_bytes / (sel_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                                  "what": "FFTPeriodSelector + PeriodGrouper + softmax weights (S1-S5), x read once"},
         }
+        if args.full:
+            out["stage_events_every"] = events_every
+            out.update(roofline_fields(pkg, engine, B, L, C, F, ks, ratio, periods, ms_sum, ncalls.value, sel_us))
         if ms_gather is not None:
             out["ms_per_step_with_output_allgather"] = ms_gather
         if ms_graph is not None:
@@ -573,12 +520,12 @@ def run_rank(args) -> None:
             out["batch_sweep"] = batch_sweep
         if torch_rocm is not None:
             out["torch_rocm_baseline"] = torch_rocm
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out["lrtc"] = lrtc_bench(pkg, dev, B, L, NS)
             out["model_forward"] = model_bench(pkg, dev, B, L, NS, C, ks, ratio, K)
             out["model_forward_c4_shard"] = model_bench(pkg, dev, 64, 720, 4096, 128, ks, ratio, K, iters=5,
                                                         note="BASELINE configs[4] per-GPU shard (B=64 of 512)")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0's host cores; at N > 1 a shorter sample (the other ranks wait at the closing barrier)
             cb = cpu_baseline(pkg, params, ks, x_host, K, L, NS, short=world > 1)
             out["cpu_baseline"] = cb
@@ -592,6 +539,116 @@ def run_rank(args) -> None:
             exchange.close()
         dist.barrier()
         dist.destroy_process_group()
+
+
+def roofline_fields(pkg, engine, B, L, C, F, ks, ratio, periods, ms_sum, ncalls, sel_us):
+    """(--full) The roofline objects of the line: the dominant stage launch and the conv launches from the stage
+    events of the timed region, the selector from its own timing; HBM traffic from profiles/pmc_latest.json."""
+    import numpy as np
+
+    # pixels one launch processes: B * sum_g (L + pad_g)
+    pads = [(-L) % p for p in sorted(set(periods))]
+    px = B * sum(L + pd for pd in pads)
+    stage_ms = [ms_sum[i] / max(1, ncalls) for i in range(6)]
+    macs = stage_macs(C, F, ks, ratio)
+    dom = int(np.argmax(stage_ms))
+    # executed multiply-adds per launch.  Stage A runs once per window position; so do two of stage C's four
+    # products in its position-major form (k_mlp_pos, the d_model-64 split-engine shape: res1 and res2 once per
+    # (b, t), W_out1 / W_in2 per grid pixel) - FTN_MLP_POS=0 or another shape keeps all four per grid pixel
+    from math import ceil
+    nk, mid = len(ks), max(1, int(ceil(min(C, F) / ratio)))
+    pos_major = (os.environ.get("FTN_MLP_POS", "1") != "0" and engine != "f32" and C == 64 and nk * 16 == 48
+                 and mid <= 16)
+    mac_launch = [macs[0] * B * L, macs[1] * px,
+                  (2 * C * F * B * L + 2 * nk * mid * F * px) if pos_major else macs[2] * px,
+                  macs[3] * px, macs[4] * px, 0]
+    # ALGORITHMIC work of the dominant launch: executed (folded, unpadded) multiply-adds, each an fp32
+    # product.  Peak: the dense MFMA peak of the pipe the stage runs on - fp32 MFMA for engine f32; for
+    # bf16x3 every fp32 product costs six bf16 partial products, so the ceiling of fp32-equivalent work on
+    # the bf16 pipe is 2500/6; plain bf16 (one product) 2500.  `frac_pipe` is the pipe-occupancy view of the
+    # same launch (all six products and the K padding counted against 2500).
+    flops_alg = 2.0 * mac_launch[dom]
+    nprod = {"f32": 1, "bf16x3": 6, "f16x2": 3, "bf16": 1}[engine]
+    on_mfma = dom in (1, 2, 3)
+    peak_tf = FP32_MFMA_PEAK_TF if (engine == "f32" or not on_mfma) else BF16_MFMA_PEAK_TF / nprod
+    achieved = flops_alg / (stage_ms[dom] * 1e-3) / 1e12 if stage_ms[dom] > 0 else 0.0
+    frac_pipe = None
+    if engine != "f32" and on_mfma:
+        mid2 = macs[1] // sum(kh * kw for kh, kw in ks)          # mid*mid
+        if dom == 2:
+            kpad = lambda v: (v + 31) // 32 * 32
+            nbm = len(ks) * int(round(mid2 ** 0.5))
+            if pos_major:                                  # per launch: K padded to 32, per-position and per-pixel parts
+                mac_pad_launch = (kpad(C) * F + F * C) * B * L + (kpad(nbm) * F + F * nbm) * px
+            else:
+                mac_pad_launch = (kpad(nbm) * F + kpad(C) * F + F * (nbm + C)) * px
+        else:
+            mac_pad_launch = mid2 * sum((kh * kw + 1) // 2 * 2 for kh, kw in ks) * px
+        frac_pipe = 2.0 * mac_pad_launch * nprod / (stage_ms[dom] * 1e-3) / 1e12 / BF16_MFMA_PEAK_TF
+    nominal = 2.0 * pkg.pack.macs_per_pixel(C, F, ks, ratio) * px
+    executed = 2.0 * sum(mac_launch)
+    conv_ms = sum(stage_ms)
+    # HBM traffic per launch from the committed rocprofv3 PMC passes of this same command (tools/profile2.sh:
+    # FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, separate --pmc runs); keys are kernel names, matched by prefix
+    pmc_k = {}
+    pmc = ROOT / "profiles" / "pmc_latest.json"
+    if pmc.exists():
+        try:
+            pmc_k = json.loads(pmc.read_text())["kernels"]
+        except Exception:
+            pmc_k = {}
+
+    def pmc_bytes(prefixes):
+        tot = 0.0
+        for k, v in pmc_k.items():
+            if any((k + "(").startswith(pf) for pf in prefixes) and v.get("hbm_bytes") is not None:
+                tot += float(v["hbm_bytes"])
+        return tot or None
+
+    kname = STAGES[dom].split("(")[-1].rstrip(")")
+    traffic = pmc_bytes([kname])
+    traffic_source = ("profiles/pmc_latest.json (committed rocprofv3 --pmc passes of this command on another run, "
+                      "FETCH_SIZE x2 + WRITE_SIZE per launch; not measured in this run)" if traffic else None)
+
+    def pmc_field(prefix, field):
+        for k, v in pmc_k.items():
+            if (k + "(").startswith(prefix) and v.get(field) is not None:
+                return float(v[field])
+        return None
+
+    # the two conv launches (stages B and D): north_star's "MFMA utilisation on the conv against chip peak"
+    conv_us = 0.5 * (stage_ms[1] + stage_ms[3]) * 1e3
+    conv_tf = 2.0 * mac_launch[1] / (conv_us * 1e-6) / 1e12 if conv_us > 0 else 0.0
+    conv_peak = FP32_MFMA_PEAK_TF if engine == "f32" else BF16_MFMA_PEAK_TF / nprod
+    roofline_conv = {"bound": "mfma", "kernel": "k_conv* (stages B and D, mean of the two launches)", "us": conv_us,
+                     "achieved": conv_tf, "peak": conv_peak, "unit": "TFLOP/s", "frac": conv_tf / conv_peak,
+                     "mfma_util_pmc": pmc_field("k_conv", "mfma_util"),
+                     "mfma_util_source": "SQ_VALU_MFMA_BUSY_CYCLES / (SIMDs x kernel cycles), profiles/pmc_latest.json",
+                     "traffic": pmc_bytes(["k_conv"])}
+    sel_bytes = 4.0 * B * L * C
+    # S1-S5 as timed below (standalone selector: plain k_finalize, not the fused finalize + stage-A launch)
+    sel_counter = pmc_bytes(["k_spectrum", "k_colsum", "k_finalize("])
+    return {
+        "roofline": {"bound": "mfma", "kernel": STAGES[dom], "achieved": achieved, "peak": peak_tf,
+                     "unit": "TFLOP/s", "frac": achieved / peak_tf, "traffic": traffic, "traffic_source": traffic_source,
+                     "definition": "achieved = executed (folded, unpadded) fp32 multiply-adds x2 per launch / avg "
+                                   "launch time (HIP events in the timed region); peak = dense 16-bit MFMA peak / "
+                                   "products per fp32 multiply (3 for f16x2, 6 for bf16x3); fp32 MFMA peak for f32",
+                     "frac_algorithmic": achieved / peak_tf, "frac_pipe": frac_pipe,
+                     "flops_per_launch": flops_alg, "avg_launch_ms": stage_ms[dom],
+                     "stage_ms": dict(zip(STAGES, [round(v, 4) for v in stage_ms])),
+                     "stage_note": "stage A (a = W_in1 x + b) runs inside the selector's finalize launch "
+                                   "(k_finalize_pw), so A_pw_in only brackets two event marks",
+                     "conv_path_ms": conv_ms,
+                     "block_executed_tflops": executed / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
+                     "block_nominal_tflops": nominal / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0,
+                     "block_frac_algorithmic": (executed / (conv_ms * 1e-3) / 1e12 / peak_tf) if conv_ms > 0 else 0.0},
+        "roofline_conv": roofline_conv,
+        "roofline_selector": {"bound": "hbm", "bytes": sel_bytes, "counter_bytes": sel_counter, "us": sel_us,
+                              "GB/s": sel_bytes / (sel_us * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
+                              "frac_hbm": sel_bytes / (sel_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                              "what": "FFTPeriodSelector + PeriodGrouper + softmax weights (S1-S5), x read once"},
+    }
 
 
 def lrtc_bench(pkg, dev, B, L, N, R=16, iters=20):

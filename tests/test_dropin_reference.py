@@ -1,30 +1,23 @@
-"""Drop-in check against the reference's OWN model shell (build container only: skipped
-when /root/reference is absent, e.g. on the GPU box).  The mirrors replace
-``FFTPeriodSelector`` / ``TimesBlock`` / ``LowRankTemporalContext`` inside the reference's
-``timesnet_forecast.models.timesnet`` module; the reference ``TimesNet`` is then built,
-loaded with ``load_state_dict(strict=True)`` from an unpatched twin (checkpoint ABI,
-reference predict.py:687-722) and must produce the same ``[B,T,N] -> [B,H,N]`` outputs."""
-import importlib
-import sys
-from pathlib import Path
-
+"""Drop-in check against the reference's OWN model shell, pinned by fixtures the reference wrote
+(tests/golden/make_golden_dropin.py: the reference ``TimesNet`` built on each config below with ``torch.manual_seed(0)``,
+its zero-initialised heads woken up, its ``state_dict``, the inputs it was called on and what it returned).  The mirror
+shell, assembled from the mirror ``FFTPeriodSelector`` / ``TimesBlock`` / ``LowRankTemporalContext``, must take that
+checkpoint with ``load_state_dict(strict=True)`` (checkpoint ABI, reference predict.py:687-722) and produce the same
+``[B,T,N] -> [B,H,N]`` outputs and periods."""
+import numpy as np
 import pytest
 import torch
 
-REF = Path("/root/reference/src")
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="reference checkout not present")
+from conftest import GOLDEN
 
 
-def _ref_module():
-    if str(REF) not in sys.path:
-        sys.path.insert(0, str(REF))
-    return importlib.import_module("timesnet_forecast.models.timesnet")
+def _fixture(name):
+    with np.load(GOLDEN / f"dropin_{name}.npz") as z:
+        return {k: z[k] for k in z.files}
 
 
-def _build(mod, cfg):
-    torch.manual_seed(0)
-    model = mod.TimesNet(**cfg)
-    return model
+def _part(z, prefix):
+    return {k[len(prefix):]: torch.from_numpy(np.array(v)) for k, v in z.items() if k.startswith(prefix)}
 
 
 CFG = dict(input_len=48, pred_len=12, d_model=16, d_ff=32, n_layers=2, k_periods=3,
@@ -33,41 +26,26 @@ CFG = dict(input_len=48, pred_len=12, d_model=16, d_ff=32, n_layers=2, k_periods
            use_zero_mean_context=True, context_rank=4, context_scale=0.05)
 
 
-def test_mirrors_drop_into_reference_timesnet(ftn, monkeypatch):
-    ref = _ref_module()
+def test_mirrors_drop_into_reference_timesnet(ftn):
     T = ftn.models.timesnet
-    B, L, N = 3, 48, 5
-    g = torch.Generator().manual_seed(1)
-    t = torch.arange(L, dtype=torch.float32).view(1, L, 1)
-    x = torch.randn(B, L, N, generator=g) + 2.0 * torch.sin(2 * torch.pi * t / 12.0) + torch.sin(2 * torch.pi * t / 8.0)
-    static = torch.randn(N, 6, generator=g)
-    ids = torch.arange(N)
-
+    z = _fixture("drop_in")
+    x, kw = torch.from_numpy(z["x"]), _part(z, "kw:")
+    want = _part(z, "sd:")
     with torch.no_grad():
-        orig = _build(ref, CFG).eval()
-        orig(x, series_static=static, series_ids=ids)          # materialise lazy layers
-        # non-zero heads, otherwise context/head paths are dead
-        for p in orig.parameters():
-            if float(p.detach().abs().sum()) == 0.0:
-                p.copy_(0.05 * torch.randn(p.shape, generator=g))
-        want_rate, want_disp = orig(x, series_static=static, series_ids=ids)
-        want_periods = orig.period_selector.last_selected_periods.tolist()
-
-        monkeypatch.setattr(ref, "FFTPeriodSelector", T.FFTPeriodSelector)
-        monkeypatch.setattr(ref, "TimesBlock", T.TimesBlock)
-        monkeypatch.setattr(ref, "LowRankTemporalContext", T.LowRankTemporalContext)
-        swapped = _build(ref, CFG).eval()
-        swapped(x, series_static=static, series_ids=ids)
-        assert type(swapped.blocks[0]) is T.TimesBlock and type(swapped.period_selector) is T.FFTPeriodSelector
+        torch.manual_seed(0)
+        swapped = ftn.models.TimesNet(**CFG).eval()
+        swapped(x, **kw)                                       # materialise lazy layers
+        assert all(type(b) is T.TimesBlock for b in swapped.blocks)
+        assert type(swapped.period_selector) is T.FFTPeriodSelector
         assert type(swapped.temporal_context) is T.LowRankTemporalContext
-        assert set(swapped.state_dict().keys()) == set(orig.state_dict().keys())
-        swapped.load_state_dict(orig.state_dict(), strict=True)
-        rate, disp = swapped(x, series_static=static, series_ids=ids)
+        assert set(swapped.state_dict().keys()) == set(want)
+        swapped.load_state_dict(want, strict=True)
+        rate, disp = swapped(x, **kw)
 
-    assert swapped.period_selector.last_selected_periods.tolist() == want_periods
+    assert swapped.period_selector.last_selected_periods.tolist() == z["periods"].tolist()
     assert all(b._period_calls >= 1 and b._last_backend == "torch" for b in swapped.blocks)
-    torch.testing.assert_close(rate, want_rate, rtol=1e-5, atol=1e-6)
-    torch.testing.assert_close(disp, want_disp, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(rate, torch.from_numpy(z["rate"]), rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(disp, torch.from_numpy(z["disp"]), rtol=1e-5, atol=1e-6)
 
 
 # ---- the full model shell mirror (flow-timesnet_amd/models/shell.py) vs the reference TimesNet ----
@@ -92,9 +70,15 @@ SHELL_CASES = {
 }
 
 
-@pytest.mark.parametrize("name", list(SHELL_CASES))
-def test_timesnet_shell_mirror_matches_reference(name, ftn):
-    ref = _ref_module()
+def case_inputs(name):
+    """The inputs a case's fixture was made on, and the generator that then woke the reference's zero heads."""
+    if name == "drop_in":
+        B, L, N = 3, 48, 5
+        g = torch.Generator().manual_seed(1)
+        t = torch.arange(L, dtype=torch.float32).view(1, L, 1)
+        x = torch.randn(B, L, N, generator=g) + 2.0 * torch.sin(2 * torch.pi * t / 12.0) + \
+            torch.sin(2 * torch.pi * t / 8.0)
+        return x, {"series_static": torch.randn(N, 6, generator=g), "series_ids": torch.arange(N)}, g
     cfg, opt = SHELL_CASES[name]
     N = opt.get("n", 5)
     L = cfg["input_len"] + opt.get("longer", 0)
@@ -112,34 +96,38 @@ def test_timesnet_shell_mirror_matches_reference(name, ftn):
     if opt.get("per_sample"):
         kw["series_static"] = torch.randn(B, N, 3, generator=g)
         kw["series_ids"] = torch.stack([torch.tensor([4, 0, 2, 7, 1][:N])] * B)
+    return x, kw, g
+
+
+# every fixture tests/golden/make_golden_dropin.py writes: config, and the scale of the heads it woke up
+CASES = {"drop_in": (CFG, 0.05), **{k: (v[0], 0.1) for k, v in SHELL_CASES.items()}}
+
+
+@pytest.mark.parametrize("name", list(SHELL_CASES))
+def test_timesnet_shell_mirror_matches_reference(name, ftn):
+    cfg, _ = SHELL_CASES[name]
+    z = _fixture(name)
+    x, kw = torch.from_numpy(z["x"]), _part(z, "kw:")
+    want = _part(z, "sd:")
+    rate_w, disp_w = torch.from_numpy(z["rate"]), torch.from_numpy(z["disp"])
     with torch.no_grad():
-        torch.manual_seed(0)
-        want = ref.TimesNet(**cfg).eval()
-        want(x, **kw)
-        for p in want.parameters():                      # wake up the zero-initialised heads
-            if float(p.detach().abs().sum()) == 0.0:
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-        rate_w, disp_w = want(x, **kw)
         torch.manual_seed(1)
         mine = ftn.models.TimesNet(**cfg).eval()
         mine(x, **kw)
-        assert set(mine.state_dict().keys()) == set(want.state_dict().keys())
+        assert set(mine.state_dict().keys()) == set(want.keys())
         assert {k: tuple(v.shape) for k, v in mine.state_dict().items()} == \
-               {k: tuple(v.shape) for k, v in want.state_dict().items()}
-        mine.load_state_dict(want.state_dict(), strict=True)
+               {k: tuple(v.shape) for k, v in want.items()}
+        mine.load_state_dict(want, strict=True)
         rate, disp = mine(x, **kw)
-    assert mine.period_selector.last_selected_periods.tolist() == want.period_selector.last_selected_periods.tolist()
+    assert mine.period_selector.last_selected_periods.tolist() == z["periods"].tolist()
     torch.testing.assert_close(rate, rate_w, rtol=1e-5, atol=1e-6)
     torch.testing.assert_close(disp, disp_w, rtol=1e-5, atol=1e-6)
     # the freshly built mirror starts in the reference's initial state too (zero heads, gate values)
     torch.manual_seed(0)
-    a = ref.TimesNet(**cfg).eval()
-    torch.manual_seed(0)
     b = ftn.models.TimesNet(**cfg).eval()
     with torch.no_grad():
-        ra, da = a(x, **kw)
         b(x, **kw)
-        b.load_state_dict(a.state_dict(), strict=True)
+        b.load_state_dict(_part(z, "init_sd:"), strict=True)
         rb, db = b(x, **kw)
-    torch.testing.assert_close(rb, ra, rtol=1e-5, atol=1e-6)
-    torch.testing.assert_close(db, da, rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(rb, torch.from_numpy(z["rate_init"]), rtol=1e-5, atol=1e-6)
+    torch.testing.assert_close(db, torch.from_numpy(z["disp_init"]), rtol=1e-5, atol=1e-6)

@@ -1,5 +1,6 @@
-"""The driver parses ONE JSON line from `python bench.py --gpus N --steps K --warmup W`: this test runs the bench on
-the GPU with a tiny K and checks the line's shape (fields the task contract names, their types, the roofline object)."""
+"""The driver parses ONE JSON line from `python bench.py --gpus N --steps K --warmup W`: these tests run the bench on
+the GPU with a tiny K and check the line's shape (fields the task contract names, their types; with --full the
+roofline objects and the extras), and what --dump-outputs writes."""
 import json
 import subprocess
 import sys
@@ -13,7 +14,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 def test_bench_prints_one_contract_line():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+                        "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, f"expected one line on stdout, got {len(lines)}"
@@ -47,7 +48,7 @@ def test_bench_strong_scaling_and_extras():
     """--scaling strong at one rank is the same batch; the N = 1 extras carry the batch sweep a strong-scaling rank
     sees, the stock PyTorch-ROCm composition on the same tensor, and the CPU baseline at its faster thread count."""
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
-                        "--scaling", "strong"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+                        "--full", "--scaling", "strong"], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -63,3 +64,29 @@ def test_bench_strong_scaling_and_extras():
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] >= cb["threads8"]["value"] * 0.999
     assert abs(d["vs_cpu_baseline"] - d["value"] / cb["value"]) / d["vs_cpu_baseline"] < 1e-9
+
+
+def test_plain_bench_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline fields and none of the --full measurements; --dump-outputs writes the last
+    timed step's TimesBlock output."""
+    import numpy as np
+
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600,
+                       cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, f"expected one line on stdout, got {len(lines)}"
+    d = json.loads(lines[0])
+    for key, typ in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float),
+                     ("higher_is_better", bool), ("dtype", str)):
+        assert key in d and isinstance(d[key], typ), key
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1
+    assert abs(d["value"] - 256 * 512 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for key in ("roofline", "roofline_conv", "roofline_selector", "batch_sweep", "torch_rocm_baseline",
+                "ms_per_step_hip_graph", "lrtc", "model_forward", "cpu_baseline"):
+        assert key not in d, key
+    assert d["config"]["other_engine_ms_per_step"] == {}
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["timesblock_out.npy"]
+    y = np.load(tmp_path / "out" / "timesblock_out.npy")
+    assert y.dtype == np.float32 and y.shape == (256, 336, 64) and np.isfinite(y).all() and np.abs(y).max() > 0

@@ -459,3 +459,20 @@ def test_every_environment_switch_is_documented():
         names |= set(re.findall(r'environ\.get\("((?:FTN|FLOWTIMES)_[A-Z0-9_]+)"', text))
     docs = (root / "README.md").read_text() + (root / "DESIGN.md").read_text()
     assert names and not sorted(n for n in names if n not in docs)
+
+
+def test_bench_dump_outputs_caps_size_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy per output; above the byte cap every output keeps the same seeded rows."""
+    import bench
+
+    y = torch.arange(40 * 3 * 2, dtype=torch.float64).reshape(40, 3, 2)
+    bench.dump_outputs(tmp_path / "all", {"y": y})
+    got = np.load(tmp_path / "all" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * 3 * 2 * 4)
+    bench.dump_outputs(tmp_path / "a", {"y": y})
+    bench.dump_outputs(tmp_path / "b", {"y": y})
+    a, b = np.load(tmp_path / "a" / "y.npy"), np.load(tmp_path / "b" / "y.npy")
+    assert a.shape == (10, 3, 2) and a.nbytes <= bench.DUMP_LIMIT_BYTES and np.array_equal(a, b)
+    rows = a[:, 0, 0] / 6
+    assert np.array_equal(rows, np.sort(rows)) and len(set(rows.tolist())) == 10

@@ -3,6 +3,7 @@
 #   tools/abench.sh OUTTAG ROUNDS "ENV=1" "ENV=2 OTHER=3" ...      ("-" = no switch)
 # prints ms/step and the stage times of every run; JSON lines land in gpurun_out/OUTTAG/.
 TAG=$1; ROUNDS=$2; shift 2
+BENCH_ARGS="--full ${BENCH_ARGS:-}"     # the stage times come with --full
 mkdir -p gpurun_out/$TAG
 for r in $(seq 1 $ROUNDS); do
   i=0
