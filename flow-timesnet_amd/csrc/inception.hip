@@ -2701,6 +2701,77 @@ static int launch_mlp_bf(const MlpBfArgs& ma, bool xvec, long long Nmax, hipStre
   return launch_mlp_bf_t<ACT, false, 8, false, NS>(ma, Nmax, st);
 }
 
+// The kernel form of every stage of forward_t (FtnForms, include/flowtimes.h): forward_t dispatches on exactly what this
+// returns, and ftn_timesblock_forms reports it.  bfg_out (may be NULL): the split conv engine's LDS plan.
+static FtnForms block_forms(const FtnPlan* pl, int L, int act_dtype, bool x_aligned, bool y_aligned, ConvBfGeom* bfg_out) {
+  FtnForms f = {};
+  const int C = pl->C, CP = pl->CP;
+  f.mode = pl->mode; f.act = pl->act == 1 ? 1 : 0;
+  f.xvec = (C % 4 == 0) && x_aligned;
+  f.yvec = y_aligned;
+  f.half_round = act_dtype != 0;
+  if (pl->mode != 0) {
+    f.stage_a_epi = -1; f.conv = FTN_FORM_CONV_FP32; f.stage_c = FTN_FORM_C_MLP; f.stage_e = FTN_FORM_E_OUT_MERGED;
+    return f;
+  }
+  const int CA = pl->nbr * pl->MP;
+  // conv engine: exact fp32 MFMA, or the bf16 matrix pipe (3 pieces = fp32-equivalent, 1 = plain bf16)
+  // activation pieces: 3 = bf16x3, 2 = f16x2, 1 = plain bf16
+  const int nsplit = pl->engine == 2 ? 1 : (pl->engine == 3 ? 2 : 3);
+  ConvBfGeom bfg = {0, 0, 0, 0, 0, 0};
+  if (pl->engine != 0) bfg = conv_bf_geom(L, pl->nbr, pl->kh, pl->kw, pl->MP, nsplit);
+  if (bfg_out) *bfg_out = bfg;
+  // (a kernel set whose weights do not fit the split engines' LDS plan runs on the exact fp32 MFMA kernels)
+  const bool use_bf = pl->engine != 0 && bfg.NCO > 0;
+  f.nsplit = use_bf ? nsplit : 0;
+  f.stage_a_epi = !use_bf ? 0 : (pl->engine == 3 ? 3 : 2);
+  f.conv = !use_bf ? FTN_FORM_CONV_FP32 : (bfg.fast ? FTN_FORM_CONV_BF_FAST : FTN_FORM_CONV_BF);
+  f.conv_n = !use_bf ? 0 : (bfg.fast ? pl->MP / 16 : bfg.NCO);
+  // stage C on the bf16 pipe too when the plan carries its fragments and the shapes fit
+  const int n_ot_c = CA / 16 + (pl->res2 ? CP / 16 : 0);
+  const bool mlp_bf = use_bf && pl->cfragbf_per_chunk > 0 && pl->res1 && pl->res2 && CA > 32 && CA <= 64 && CP > 32 && CP <= 64 &&
+                      n_ot_c <= 8 && (size_t)pl->cfragbf_per_chunk * 3 * 1024 * 2 <= 160 * 1024;
+  // the default pipeline shape (d_model 128, three kernels, mid 32): k_mlp_bf_c128
+  const bool mlp_bf128 = use_bf && !mlp_bf && pl->res1 && pl->res2 && CA == 96 && CP == 128 && n_ot_c == 14 &&
+                         pl->cfragbf_per_chunk == 28 &&
+                         (size_t)28 * 3 * 1024 + (size_t)pl->n_hchunks * 32 * 2 * sizeof(float) <= 160 * 1024;
+  // the u1 stage C of the d_model-64 shape with the FAST k_out behind it and fp32 activations: R keeps its x
+  // (OutArgs.r_keeps_x); every other combination subtracts x in stage C as the reference's delta does
+  const bool r_keeps_x = mlp_bf && g_mlp_u1 && g_r_keeps_x && act_dtype == 0 && (CA + 31) / 32 == 2 && (CP + 31) / 32 == 2 &&
+                         n_ot_c == 7 && CA <= 48 && CP <= 64;
+  // stage E on the 16-bit pipe (k_out_h): the second conv then leaves m' as activation pieces
+  const bool out_h = (mlp_bf || mlp_bf128) && ftn_out_h_enabled() != 0 && pl->w_out2fb != 0 && nsplit >= 2 && act_dtype == 0 &&
+                     ((CA <= 64 && CP <= 64) || (CA <= 96 && CP <= 128));
+  // position-major stage C (k_mlp_pos) for the same shape: res1 / res2 once per window position, R group-summed
+  const bool mlp_pos64 = mlp_bf && g_mlp_u1 && ftn_mlp_pos_enabled() != 0 && act_dtype == 0 && (CA + 31) / 32 == 2 && (CP + 31) / 32 == 2 &&
+                         n_ot_c == 7 && CA == 48 && CP == 64;
+  // the d_model-128 shape (f16x2): two groups per pass, one 8-wave workgroup per CU (stagec_pos.hip)
+  // (its group-summed R is only understood by k_out_h at this width)
+  const bool mlp_pos128 = mlp_bf128 && out_h && g_mlp_u1 && ftn_mlp_pos_enabled() != 0 && act_dtype == 0 && nsplit == 2;
+  const bool mlp_pos = mlp_pos64 || mlp_pos128;
+  if (mlp_bf128 && !mlp_pos128) f.stage_c = FTN_FORM_C_MLP_BF_C128;
+  else if (mlp_pos) f.stage_c = mlp_pos128 ? FTN_FORM_C_MLP_POS128 : FTN_FORM_C_MLP_POS64;
+  else if (mlp_bf && g_mlp_u1 && (CA + 31) / 32 == 2 && (CP + 31) / 32 == 2 && n_ot_c == 7) f.stage_c = FTN_FORM_C_MLP_BF_U1;
+  else if (mlp_bf) f.stage_c = FTN_FORM_C_MLP_BF;
+  else if (stagec_generic(pl)) f.stage_c = FTN_FORM_C_GENERIC;
+  else f.stage_c = FTN_FORM_C_MLP;
+  f.r_keeps_x = (r_keeps_x || mlp_pos) ? 1 : 0;
+  f.r_summed = mlp_pos ? 1 : 0;
+  f.stage_e = out_h ? FTN_FORM_E_OUT_H : (CA <= 48 && CP <= 64 ? FTN_FORM_E_OUT_FAST : FTN_FORM_E_OUT);
+  return f;
+}
+
+extern "C" int ftn_timesblock_forms(const FtnPlan* plan, int B, int L, int act_dtype, int x_misalign, FtnForms* forms_out) {
+  FTN_CHECK_ARG(plan && forms_out, "ftn_timesblock_forms: null pointer");
+  FTN_CHECK_ARG(B >= 1 && B <= 65535 && L >= 2, "ftn_timesblock_forms: bad shape B=%d L=%d", B, L);
+  FTN_CHECK_ARG(act_dtype >= 0 && act_dtype <= 2 && x_misalign >= 0 && x_misalign < 16,
+                "ftn_timesblock_forms: act_dtype=%d x_misalign=%d", act_dtype, x_misalign);
+  FTN_CHECK_ARG(plan->nbr >= 1 && plan->nbr <= FTN_MAXBR && (plan->mode == 1 || (plan->MP % 16 == 0 && plan->MP > 0)),
+                "ftn_timesblock_forms: bad plan");
+  *forms_out = block_forms(plan, L, act_dtype, x_misalign == 0, true, nullptr);
+  return 0;
+}
+
 template <int ACT>
 static int forward_t(const float* x, float* y, int B, int L, const FtnPlan* pl, const float* wb, const FtnDesc* desc_in,
                      const float* wts, int max_groups, int px_bound, char* ws, hipStream_t st, const float* ln_g,
@@ -2714,7 +2785,9 @@ static int forward_t(const float* x, float* y, int B, int L, const FtnPlan* pl, 
   float* bufR = (float*)(ws + wl.off2);
   float* bufG = (float*)(ws + wl.off3);
   const int C = pl->C, CP = pl->CP, FP = pl->FP;
-  const bool xvec = (C % 4 == 0) && (((uintptr_t)x & 15) == 0);
+  ConvBfGeom bfg = {0, 0, 0, 0, 0, 0};
+  const FtnForms fm = block_forms(pl, L, act_dtype, ((uintptr_t)x & 15) == 0, ((uintptr_t)y & 15) == 0, &bfg);
+  const bool xvec = fm.xvec != 0;
   const long long Nmax = (long long)B * px_row;
   int tiles_row;
   worst_tiles(L, max_groups, &tiles_row);
@@ -2722,20 +2795,15 @@ static int forward_t(const float* x, float* y, int B, int L, const FtnPlan* pl, 
   const int rows_est = (int)((long long)B * max_groups * ((L + FTN_TILE_PX - 1) / FTN_TILE_PX) < (1 << 20) ? B * max_groups * ((L + FTN_TILE_PX - 1) / FTN_TILE_PX) : 0);
   const int nblk_pw = (int)(((long long)B * L + 1 + 16 * NPXU * 4 - 1) / (16 * NPXU * 4));   // stage A: window rows + pad row
   const int nblk_ew = 2048;
-  const bool yvec = ((uintptr_t)y & 15) == 0;
+  const bool yvec = fm.yvec != 0;
   const int nblk_out = (int)(((long long)B * L + 127) / 128);
   int rc;
   prof_mark(0, st);
   if (pl->mode == 0) {
     const int CA = pl->nbr * pl->MP;
-    // conv engine: exact fp32 MFMA, or the bf16 matrix pipe (3 pieces = fp32-equivalent, 1 = plain bf16)
-    // activation pieces: 3 = bf16x3, 2 = f16x2, 1 = plain bf16
     const int nsplit = pl->engine == 2 ? 1 : (pl->engine == 3 ? 2 : 3);
-    ConvBfGeom bfg = {0, 0, 0, 0, 0, 0};
-    if (pl->engine != 0) bfg = conv_bf_geom(L, pl->nbr, pl->kh, pl->kw, pl->MP, nsplit);
-    const bool use_bf = pl->engine != 0 && bfg.NCO > 0;
+    const bool use_bf = fm.nsplit != 0;
     const bool h2 = use_bf && pl->engine == 3;
-    // (a kernel set whose weights do not fit the split engines' LDS plan runs on the exact fp32 MFMA kernels)
     // A: a = W_in1 x + b
     PwArgs pa = {};
     pa.x = x; pa.W = wb + pl->w_in1; pa.bias = wb + pl->b_in1; pa.out = bufA; pa.desc = desc;
@@ -2749,28 +2817,13 @@ static int forward_t(const float* x, float* y, int B, int L, const FtnPlan* pl, 
     else if ((rc = launch_pw<ACT, 1, 0>(pa, xvec, nblk_pw, st))) return rc;
     prof_mark(1, st);
     ConvBfArgs cb = {};
-    // stage C on the bf16 pipe too when the plan carries its fragments and the shapes fit
     const int n_ot_c = CA / 16 + (pl->res2 ? CP / 16 : 0);
-    const bool mlp_bf = use_bf && pl->cfragbf_per_chunk > 0 && pl->res1 && pl->res2 && CA > 32 && CA <= 64 && CP > 32 && CP <= 64 &&
-                        n_ot_c <= 8 && (size_t)pl->cfragbf_per_chunk * 3 * 1024 * 2 <= 160 * 1024;
-    // the default pipeline shape (d_model 128, three kernels, mid 32): k_mlp_bf_c128
-    const bool mlp_bf128 = use_bf && !mlp_bf && pl->res1 && pl->res2 && CA == 96 && CP == 128 && n_ot_c == 14 &&
-                           pl->cfragbf_per_chunk == 28 &&
-                           (size_t)28 * 3 * 1024 + (size_t)pl->n_hchunks * 32 * 2 * sizeof(float) <= 160 * 1024;
-    // the u1 stage C of the d_model-64 shape with the FAST k_out behind it and fp32 activations: R keeps its x
-    // (OutArgs.r_keeps_x); every other combination subtracts x in stage C as the reference's delta does
-    const bool r_keeps_x = mlp_bf && g_mlp_u1 && g_r_keeps_x && act_dtype == 0 && (CA + 31) / 32 == 2 && (CP + 31) / 32 == 2 &&
-                           n_ot_c == 7 && CA <= 48 && CP <= 64;
-    // stage E on the 16-bit pipe (k_out_h): the second conv then leaves m' as activation pieces
-    const bool out_h = (mlp_bf || mlp_bf128) && ftn_out_h_enabled() != 0 && pl->w_out2fb != 0 && nsplit >= 2 && act_dtype == 0 &&
-                       ((CA <= 64 && CP <= 64) || (CA <= 96 && CP <= 128));
-    // position-major stage C (k_mlp_pos) for the same shape: res1 / res2 once per window position, R group-summed
-    const bool mlp_pos64 = mlp_bf && g_mlp_u1 && ftn_mlp_pos_enabled() != 0 && act_dtype == 0 && (CA + 31) / 32 == 2 && (CP + 31) / 32 == 2 &&
-                           n_ot_c == 7 && CA == 48 && CP == 64;
-    // the d_model-128 shape (f16x2): two groups per pass, one 8-wave workgroup per CU (stagec_pos.hip)
-    // (its group-summed R is only understood by k_out_h at this width)
-    const bool mlp_pos128 = mlp_bf128 && out_h && g_mlp_u1 && ftn_mlp_pos_enabled() != 0 && act_dtype == 0 && nsplit == 2;
-    const bool mlp_pos = mlp_pos64 || mlp_pos128;
+    const bool mlp_pos128 = fm.stage_c == FTN_FORM_C_MLP_POS128;
+    const bool mlp_pos = mlp_pos128 || fm.stage_c == FTN_FORM_C_MLP_POS64;
+    const bool mlp_bf128 = mlp_pos128 || fm.stage_c == FTN_FORM_C_MLP_BF_C128;
+    const bool mlp_bf = !mlp_bf128 && (mlp_pos || fm.stage_c == FTN_FORM_C_MLP_BF_U1 || fm.stage_c == FTN_FORM_C_MLP_BF);
+    const bool r_keeps_x = !mlp_pos && fm.r_keeps_x;
+    const bool out_h = fm.stage_e == FTN_FORM_E_OUT_H;
     if (use_bf) {
       cb.range_flag = range_flag;
       cb.in = (const __bf16*)bufA; cb.bt_L = L; cb.out = buf1; cb.out_p3 = (mlp_bf || mlp_bf128) ? 1 : 0; cb.bias = wb + (h2 ? pl->b_conv1s : pl->b_conv1); cb.desc = desc;
@@ -2799,7 +2852,7 @@ static int forward_t(const float* x, float* y, int B, int L, const FtnPlan* pl, 
     ma.n_hchunks = pl->n_hchunks; ma.cfrag_per_chunk = pl->cfrag_per_chunk;
     ma.n_oa = CA / 16; ma.res2_ident = pl->res2 ? 0 : 1; ma.n_ot = ma.n_oa + (pl->res2 ? CP / 16 : 0);
     ma.outA_p3 = use_bf ? (h2 ? 2 : 1) : 0;
-    const bool generic_c = !(mlp_bf || mlp_bf128) && stagec_generic(pl);
+    const bool generic_c = fm.stage_c == FTN_FORM_C_GENERIC;
     if (!generic_c && !(mlp_bf || mlp_bf128) && ma.cfrag_per_chunk != MLP_HT * (ma.nKM + ma.nCP + ma.n_ot)) { ftn_set_error("plan/cfrag layout mismatch"); return -1; }
     if (generic_c) {
       // wide blocks: the chain as pointwise launches with the hidden tensor g in the workspace
@@ -2858,7 +2911,7 @@ static int forward_t(const float* x, float* y, int B, int L, const FtnPlan* pl, 
         const int tub = tail_units > (1 << 24) ? (1 << 24) : (int)tail_units;
         if (mlp_pos128) { if ((rc = ftn_launch_mlp_pos128(mp, ACT, xvec, tub, st))) return rc; }
         else if ((rc = ftn_launch_mlp_pos64(mp, ACT, nsplit, xvec, tub, st))) return rc;
-      } else if (g_mlp_u1 && mb.nsKM == 2 && mb.nsCP == 2 && mb.n_ot == 7) {
+      } else if (fm.stage_c == FTN_FORM_C_MLP_BF_U1) {
         // one 16-pixel unit per wave, four waves per SIMD (see k_mlp_bf_u1)
         if (nsplit == 3) { if ((rc = launch_mlp_bf_u1<ACT, 3, 2, 2, 7>(mb, xvec, Nmax, st))) return rc; }
         else if (nsplit == 2) { if ((rc = launch_mlp_bf_u1<ACT, 2, 2, 2, 7>(mb, xvec, Nmax, st))) return rc; }
@@ -2881,10 +2934,10 @@ static int forward_t(const float* x, float* y, int B, int L, const FtnPlan* pl, 
     OutArgs oa = {};
     oa.x = x; oa.y = y; oa.m = buf1; oa.R = bufR; oa.W = wb + pl->w_out2; oa.bias = wb + pl->b_out2; oa.wts = wts;
     oa.desc = desc; oa.B = B; oa.L = L; oa.C = C; oa.CP = CP; oa.KM = CA; oa.act_dtype = act_dtype;
-    oa.r_keeps_x = (r_keeps_x || mlp_pos) ? 1 : 0;
-    oa.r_summed = mlp_pos ? 1 : 0;
+    oa.r_keeps_x = fm.r_keeps_x;
+    oa.r_summed = fm.r_summed;
     oa.range_flag = range_flag;
-    const bool fast = CA <= 48 && CP <= 64;
+    const bool fast = fm.stage_e == FTN_FORM_E_OUT_FAST;
     if (fast || out_h) { oa.ln_g = ln_g; oa.ln_b = ln_b; oa.ln_eps = ln_eps; ln_g = nullptr; }   // fused epilogue
     // FAST path: 16 pixels per wave (3 waves/SIMD; with 32 the kernel needs > 256 registers -> 1 wave/SIMD)
     const unsigned nblk_fast = (unsigned)(((long long)B * L + 63) / 64);
@@ -3038,11 +3091,8 @@ extern "C" int ftn_period_finalize_stage_a(const double* psum_dev, int nparts, i
   FTN_CHECK_ARG(lds <= 48 * 1024, "ftn_period_finalize_stage_a: L=%d too long", L);
   const WsLayout wl = ws_layout(plan, B, L, max_groups, px_bound);
   const int CA = plan->nbr * plan->MP;
-  const int nsplit = plan->engine == 2 ? 1 : (plan->engine == 3 ? 2 : 3);
-  ConvBfGeom bfg = {0, 0, 0, 0, 0, 0};
-  if (plan->engine != 0) bfg = conv_bf_geom(L, plan->nbr, plan->kh, plan->kw, plan->MP, nsplit);
-  const bool use_bf = plan->engine != 0 && bfg.NCO > 0;
-  const int epi = !use_bf ? 0 : (plan->engine == 3 ? 3 : 2);
+  const FtnForms fm = block_forms(plan, L, act_dtype, x_dev != nullptr && ((uintptr_t)x_dev & 15) == 0, true, nullptr);
+  const int epi = fm.stage_a_epi;
   FinalizeArgs fa = {psum_dev, nparts, Btotal, med_dev, B, L, F, k_periods, pmax, min_period_threshold, desc_dev,
                      amps_dev, weights_dev, act_dtype, max_unique > 0 ? max_unique : 0, log_base > 1.0 ? (float)log(log_base) : 0.f};
   if (xch != nullptr) ftn_xch_fill(xch, F, &fa);
@@ -3053,7 +3103,7 @@ extern "C" int ftn_period_finalize_stage_a(const double* psum_dev, int nparts, i
   pa.guard_src = desc_dev; pa.guard_dst = (FtnDesc*)ws_dev; pa.guard_groups = max_groups;
   pa.guard_px = worst_px_per_row(L, max_groups, px_bound);
   pa.range_flag = epi == 3 ? range_flag_dev : nullptr;
-  const bool xvec = (plan->C % 4 == 0) && (((uintptr_t)x_dev & 15) == 0);
+  const bool xvec = fm.xvec != 0;
   const int nblk_pw = (int)(((long long)B * L + 1 + 16 * NPXU * 4 - 1) / (16 * NPXU * 4));
   const int part = do_fin && do_a ? 0 : (do_a ? 1 : 2);
   if (plan->act == 1) return finalize_stage_a_t<1>(fa, pa, epi, xvec, nblk_pw, lds, part, (hipStream_t)stream);

@@ -908,6 +908,34 @@ extern "C" size_t ftn_period_spectrum_scratch_bytes(int B, int L, int C) {
   return (size_t)B * (L / 2 + 1) * C * sizeof(float);
 }
 
+// The form ftn_period_spectrum takes (ftn_period_spectrum_form): 0 k_spectrum, 1 k_spectrum_row, 2 k_spectrum_rowq,
+// 3 channel-tiled k_spectrum_rowq + k_median_rows.  Row-resident forms where the folded row and its amplitude tile fit
+// LDS and there are rows enough to fill the chip; FTN_SEL_ROW: 0 = k_spectrum, 1 = k_spectrum_row, 2 = k_spectrum_rowq,
+// unset = fastest form that fits (the kernels are bit-identical, tests compare them).
+static int spectrum_form(int B, int L, int C, bool scratch) {
+  static const int row_mode = [] { const char* e = getenv("FTN_SEL_ROW"); return e == nullptr ? -1 : atoi(e); }();
+  const int FPAD = fpad_of(L), nfb = FPAD / 32;
+  const int KT = L / 2 + 1, KTP = (KT + 1) & ~1, nct = (C + 31) / 32;
+  const size_t lds_row = (size_t)KTP * nct * 32 * 8 + (size_t)FPAD * (C + 1) * sizeof(float);
+  const bool row_fits = C <= 64 && nfb * nct <= 16 && lds_row <= 160 * 1024 && L >= 3;
+  const int QP = qfold_qp(L), FQ = qfold_fq(L);
+  const int amp_rows = ((2 * FQ > FPAD ? 2 * FQ : FPAD) + 7) & ~7;
+  const size_t lds_q = (size_t)4 * QP * nct * 32 * sizeof(float) + (size_t)amp_rows * (C + 1) * sizeof(float);
+  const bool q_fits = qfold_ok(L) && C <= 64 && 2 * (FQ / 32) * nct <= 16 && lds_q <= 160 * 1024;
+  if (scratch && B <= 65535 && qtile_fits(L, C) && row_mode != 0 && row_mode != 1) return 3;
+  if (q_fits && (row_mode == 2 || (row_mode < 0 && B >= 64))) return 2;
+  if (row_fits && (row_mode == 1 || (row_mode < 0 && B >= 64))) return 1;
+  return 0;
+}
+
+extern "C" int ftn_period_spectrum_form(int B, int L, int C, int x_misalign, int scratch) {
+  FTN_CHECK_ARG(B >= 1 && L >= 2 && C >= 1 && x_misalign >= 0 && x_misalign < 16 && x_misalign % 4 == 0,
+                "ftn_period_spectrum_form: bad shape B=%d L=%d C=%d misalign=%d", B, L, C, x_misalign);
+  const int form = spectrum_form(B, L, C, scratch != 0 && ftn_period_spectrum_scratch_bytes(B, L, C) > 0);
+  // k_spectrum has only scalar loads; the row forms read float4 when C % 4 == 0 and x is 16-byte aligned
+  return form + (form != 0 && (C & 3) == 0 && x_misalign == 0 ? 4 : 0);
+}
+
 extern "C" int ftn_period_spectrum(const float* x_dev, int B, int L, int C, const void* table_dev,
                                    float* med_dev, double* psum_dev, void* stream, const FtnExchange* xch,
                                    void* scratch_dev) {
@@ -926,18 +954,13 @@ extern "C" int ftn_period_spectrum(const float* x_dev, int B, int L, int C, cons
     if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute: %s", hipGetErrorString(e)); return (int)e; }
   }
   const int nfb = FPAD / 32;
-  // row-resident form where the folded row and its amplitude tile fit LDS and there are rows enough to fill the chip
-  // (FTN_SEL_ROW=1 / 0 forces / forbids it: the two kernels are bit-identical, tests compare them)
   const int KT = L / 2 + 1, KTP = (KT + 1) & ~1, nct = (C + 31) / 32;
   const size_t lds_row = (size_t)KTP * nct * 32 * 8 + (size_t)FPAD * (C + 1) * sizeof(float);
-  // FTN_SEL_ROW: 0 = k_spectrum, 1 = k_spectrum_row, 2 = k_spectrum_rowq, unset = fastest form that fits
-  static const int row_mode = [] { const char* e = getenv("FTN_SEL_ROW"); return e == nullptr ? -1 : atoi(e); }();
-  const bool row_fits = C <= 64 && nfb * nct <= 16 && lds_row <= 160 * 1024 && L >= 3;
   const int QP = qfold_qp(L), FQ = qfold_fq(L);
   const int amp_rows = ((2 * FQ > FPAD ? 2 * FQ : FPAD) + 7) & ~7;
   const size_t lds_q = (size_t)4 * QP * nct * 32 * sizeof(float) + (size_t)amp_rows * (C + 1) * sizeof(float);
-  const bool q_fits = qfold_ok(L) && C <= 64 && 2 * (FQ / 32) * nct <= 16 && lds_q <= 160 * 1024;
-  if (scratch_dev != nullptr && B <= 65535 && qtile_fits(L, C) && row_mode != 0 && row_mode != 1) {
+  const int form = spectrum_form(B, L, C, scratch_dev != nullptr);
+  if (form == 3) {
     // d_model > 64: (row, 32-channel tile) workgroups, amplitudes through the caller's scratch, medians in a second launch
     const size_t lds_t = (size_t)4 * QP * 32 * sizeof(float);
     hipError_t e = hipFuncSetAttribute((const void*)k_spectrum_rowq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t);
@@ -948,12 +971,12 @@ extern "C" int ftn_period_spectrum(const float* x_dev, int B, int L, int C, cons
     const long long rows = (long long)B * F;
     hipLaunchKernelGGL(k_median_rows, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
                        (const float*)scratch_dev, rows, C, med_dev);
-  } else if (q_fits && (row_mode == 2 || (row_mode < 0 && B >= 64))) {
+  } else if (form == 2) {
     hipError_t e = hipFuncSetAttribute((const void*)k_spectrum_rowq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
     if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute(k_spectrum_rowq): %s", hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(k_spectrum_rowq, dim3((unsigned)B), dim3(64 * 2 * (FQ / 32) * nct), lds_q, (hipStream_t)stream, x_dev, B, L,
                        C, (const float*)table_dev + (size_t)2 * L * FPAD, F, QP, FQ, amp_rows, med_dev, C, (float*)nullptr);
-  } else if (row_fits && (row_mode == 1 || (row_mode < 0 && B >= 64))) {
+  } else if (form == 1) {
     hipError_t e = hipFuncSetAttribute((const void*)k_spectrum_row, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row);
     if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute(k_spectrum_row): %s", hipGetErrorString(e)); return (int)e; }
     hipLaunchKernelGGL(k_spectrum_row, dim3((unsigned)B), dim3(64 * nfb * nct), lds_row, (hipStream_t)stream, x_dev, B, L, C,

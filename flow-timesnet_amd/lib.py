@@ -13,7 +13,7 @@ from typing import Optional
 
 FTN_KMAX = 16
 FTN_MAXBR = 8
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "csrc" / "libflowtimes_hip.so"
@@ -79,6 +79,14 @@ class FtnPlan(C.Structure):
     ]
 
 
+class FtnForms(C.Structure):
+    """Mirror of ``struct FtnForms`` (include/flowtimes.h): the kernel form each stage of a block call takes."""
+
+    _fields_ = [(n, C.c_int32) for n in ("mode", "act", "nsplit", "xvec", "yvec", "stage_a_epi", "conv", "conv_n",
+                                         "stage_c", "r_keeps_x", "r_summed", "stage_e", "half_round")] + [
+        ("reserved", C.c_int32 * 3)]
+
+
 class FtnInceptionBlockWeights(C.Structure):
     """Mirror of ``struct FtnInceptionBlockWeights`` (include/flowtimes.h): raw host pointers to the reference
     ``state_dict`` tensors of one InceptionBlock."""
@@ -123,6 +131,8 @@ _SIGNATURES = {
                                               C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, C.POINTER(FtnPlan), _P,
                                               C.c_int, C.c_int, _P, C.c_size_t, _P, _P, C.POINTER(FtnExchange)]),
     "ftn_residual_layernorm": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, _P, _P, C.c_float, _P]),
+    "ftn_timesblock_forms": (C.c_int, [C.POINTER(FtnPlan), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(FtnForms)]),
+    "ftn_period_spectrum_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_head_forward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_longlong,
                                    C.c_int, _P, C.c_longlong, _P, C.c_float, _P, _P, _P, _P]),
     "ftn_embed_forward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong,
@@ -196,6 +206,11 @@ def load() -> C.CDLL:
 
                 warnings.warn(f"`make` failed but {path.name} is newer than all of its sources - using it.\n{build_log[-500:]}",
                               RuntimeWarning, stacklevel=2)
+    # torch first: its bundled HIP runtime carries the soname the library links against, so the library binds to
+    # that runtime.  Loaded before torch, the library would pull in a second HIP runtime from the ROCm install, and
+    # the device pointers and streams torch hands over belong to the first one.
+    import torch  # noqa: F401
+
     if not path.exists():
         raise FlowTimesLibraryError(
             f"{path} not found: build it with `make -C {_HERE / 'csrc'}` "

@@ -322,6 +322,7 @@ class TimesBlock(nn.Module):
         self._last_group_count = 0
         self._last_loop_iterations = 0
         self._last_backend: Optional[str] = None
+        self._last_forms: Optional[dict] = None      # kernel forms of the last HIP call (_forms)
         self._hip_calls = 0
         self._lazy_sel = None
         self._pack_key = None
@@ -491,6 +492,23 @@ class TimesBlock(nn.Module):
             new = _layer_norm_fp32(post_norm, x + (new - x))
         return new
 
+    def _forms(self, plan, B: int, L: int, adt: int, xf: torch.Tensor, native: bool, fused_a: bool) -> dict:
+        """The kernel forms of this call (``runtime.timesblock_forms``; host-only, cached per shape: the library reads
+        its switches once per process).  ``A`` names ``k_finalize_pw`` when stage A rode in the selector's launch;
+        ``spectrum`` is the native selector's form (None for a host-side selector)."""
+        from .. import runtime
+
+        key = (bytes(plan), B, L, adt, xf.data_ptr() % 16, native, fused_a)
+        cache = self.__dict__.setdefault("_forms_cache", {})
+        forms = cache.get(key)
+        if forms is None:
+            forms = runtime.timesblock_forms(plan, B, L, adt, xf.data_ptr() % 16)
+            if fused_a:
+                forms["A"] = forms["A"].replace("k_pw<1,", "k_finalize_pw<")
+            forms["spectrum"] = runtime.spectrum_form(B, L, xf.shape[-1], xf.data_ptr() % 16) if native else None
+            cache[key] = forms
+        return dict(forms)
+
     def _within_native_limits(self) -> bool:
         """The HIP kernels hold at most FTN_KMAX period candidates and FTN_MAXBR kernels per InceptionBlock; the
         reference has no such limits (:55-62, :622-633), so anything beyond them runs on the torch backend."""
@@ -584,6 +602,7 @@ class TimesBlock(nn.Module):
             if int(dh.n_groups) != grp.periods.numel():
                 raise RuntimeError("host grouping and descriptor disagree")
             sel = runtime.selection_from_host(dh, w, x.device)
+        self._last_forms = self._forms(plan, B, L, adt, xf, native, getattr(sel, "stage_a", None) is not None)
         y = runtime.timesblock_forward(xf, plan, wblob, sel, norm, adt, range_flag)
         if y.dtype != x.dtype:
             y = y.to(x.dtype)

@@ -213,6 +213,45 @@ def selection_from_host(desc_host: FtnDesc, weights: torch.Tensor, device: torch
     return sel
 
 
+# ------------------------------------------------------------------ kernel forms
+_SPECTRUM_FORMS = ("k_spectrum", "k_spectrum_row", "k_spectrum_rowq", "k_spectrum_rowq_tiled")
+
+
+def spectrum_form(B: int, L: int, C: int, x_misalign: int = 0, scratch: bool = True) -> Tuple[str, bool]:
+    """The kernel ``ftn_period_spectrum`` runs for this shape (host-only query; ``scratch``: the caller passes the
+    scratch buffer, as ``spectrum`` does) and whether it reads x with 16-byte vector loads."""
+    lib = _lib.load()
+    f = lib.ftn_period_spectrum_form(int(B), int(L), int(C), int(x_misalign), int(bool(scratch)))
+    if f < 0:
+        check(f, "ftn_period_spectrum_form")
+    return _SPECTRUM_FORMS[f & 3], bool(f & 4)
+
+
+_STAGE_C = {0: "k_mlp", 1: "k_pw_chain", 2: "k_mlp_bf<{ns}>", 3: "k_mlp_bf_u1<{ns}>", 4: "k_mlp_bf_c128<{ns}>",
+            5: "k_mlp_pos64<{ns}>", 6: "k_mlp_pos128<{ns}>"}
+_STAGE_E = {0: "k_out", 1: "k_out_fast", 2: "k_out_h<{ns}>", 3: "k_out_merged"}
+
+
+def timesblock_forms(plan: FtnPlan, B: int, L: int, act_dtype: int = 0, x_misalign: int = 0) -> Dict[str, object]:
+    """The kernel form each stage of ``timesblock_forward`` takes (``ftn_timesblock_forms``, host-only): the
+    library dispatches through the same function, so this is what runs.  Stage names carry the template arguments
+    that vary (activation pieces ``NS``, conv tiles); ``act`` is the ``ACT`` argument every stage shares."""
+    lib = _lib.load()
+    f = _lib.FtnForms()
+    check(lib.ftn_timesblock_forms(C.byref(plan), int(B), int(L), int(act_dtype), int(x_misalign), C.byref(f)),
+          "ftn_timesblock_forms")
+    ns = f.nsplit
+    if f.mode != 0:
+        stage_a = "k_embed"
+        conv = "k_conv"
+    else:
+        stage_a = f"k_pw<1,{f.stage_a_epi}>"
+        conv = ("k_conv", f"k_conv_bf<{f.conv_n},{ns}>", f"k_conv_bf_fast<{ns},{f.conv_n}>")[f.conv]
+    return {"act": "relu" if f.act == 1 else "gelu", "xvec": bool(f.xvec), "yvec": bool(f.yvec), "A": stage_a,
+            "conv": conv, "C": _STAGE_C[f.stage_c].format(ns=ns), "r_keeps_x": bool(f.r_keeps_x),
+            "r_summed": bool(f.r_summed), "E": _STAGE_E[f.stage_e].format(ns=ns), "half_round": bool(f.half_round)}
+
+
 # ------------------------------------------------------------------ conv path
 def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel: Selection,
                        norm=None, act_dtype: int = 0, range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:

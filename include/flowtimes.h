@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define FTN_ABI_VERSION 10
+#define FTN_ABI_VERSION 11
 #define FTN_KMAX 16      /* max period candidates / groups per block call        */
 #define FTN_MAXBR 8      /* max kernels in kernel_set                             */
 
@@ -268,6 +268,49 @@ int ftn_timesblock_forward_norm(const float* x_dev, float* y_dev, int B, int L, 
  * allowed: out == new).  Used when a block returns x unchanged (no valid period, :796-797). */
 int ftn_residual_layernorm(const float* x_dev, const float* new_dev, float* out_dev, long long rows, int C,
                            const float* ln_gamma_dev, const float* ln_beta_dev, float ln_eps, void* stream);
+
+/* ---- kernel forms (ABI 11, host-only) -------------------------------------------- */
+/* Which kernel form each stage of ftn_timesblock_forward takes for a plan, shape, activation dtype and input
+ * alignment.  ftn_timesblock_forward makes its choice through the same host function, so the report is what runs;
+ * the environment switches the library reads (FTN_MLP_POS, FTN_OUT_H, FTN_MLP_U1, FTN_R_KEEPS_X,
+ * FTN_CONV_GENERIC) are reflected.  y is taken to be 16-byte aligned (callers allocate it). */
+#define FTN_FORM_CONV_FP32 0          /* k_conv (exact fp32 MFMA)                                        */
+#define FTN_FORM_CONV_BF 1            /* k_conv_bf<conv_n, nsplit>                                        */
+#define FTN_FORM_CONV_BF_FAST 2       /* k_conv_bf_fast<nsplit, conv_n>                                   */
+#define FTN_FORM_C_MLP 0              /* k_mlp (fp32)                                                     */
+#define FTN_FORM_C_GENERIC 1          /* the chain as generic pointwise launches (k_pw / k_ew_ident)      */
+#define FTN_FORM_C_MLP_BF 2           /* k_mlp_bf<nsplit>                                                 */
+#define FTN_FORM_C_MLP_BF_U1 3        /* k_mlp_bf_u1<nsplit> (one 16-pixel unit per wave)                 */
+#define FTN_FORM_C_MLP_BF_C128 4      /* k_mlp_bf_c128<nsplit> (d_model 128, three kernels, mid 32)       */
+#define FTN_FORM_C_MLP_POS64 5        /* k_mlp_pos, d_model-64 shape (position-major, R group-summed)     */
+#define FTN_FORM_C_MLP_POS128 6       /* k_mlp_pos, d_model-128 shape                                     */
+#define FTN_FORM_E_OUT 0              /* k_out, general form                                              */
+#define FTN_FORM_E_OUT_FAST 1         /* k_out, FAST form (16 pixels per wave)                            */
+#define FTN_FORM_E_OUT_H 2            /* k_out_h (stage E on the 16-bit pipe)                             */
+#define FTN_FORM_E_OUT_MERGED 3       /* k_out of a merged-conv (mode 1) plan                             */
+typedef struct FtnForms {
+  int32_t mode;        /* plan mode: 0 bottleneck branches, 1 one merged conv                               */
+  int32_t act;         /* ACT template argument: 0 GELU, 1 ReLU                                             */
+  int32_t nsplit;      /* activation pieces of the split conv engine: 3 bf16x3, 2 f16x2, 1 bf16; 0 fp32      */
+  int32_t xvec;        /* x is read with 16-byte vector loads (C % 4 == 0 and x 16-byte aligned)            */
+  int32_t yvec;        /* y is written with 16-byte vector stores                                           */
+  int32_t stage_a_epi; /* epilogue of stage A (k_pw / k_finalize_pw): 0 fp32, 2 bf16 pieces, 3 f16x2 pieces;
+                          -1 for mode 1 (k_embed)                                                           */
+  int32_t conv;        /* FTN_FORM_CONV_*                                                                   */
+  int32_t conv_n;      /* k_conv_bf: output tiles per workgroup (NCO); k_conv_bf_fast: input groups (NCI)   */
+  int32_t stage_c;     /* FTN_FORM_C_*                                                                      */
+  int32_t r_keeps_x;   /* stage C leaves x inside R (stage E does not add it again)                         */
+  int32_t r_summed;    /* R is already summed over the groups with their weights                            */
+  int32_t stage_e;     /* FTN_FORM_E_*                                                                      */
+  int32_t half_round;  /* act_dtype != 0: stage E rounds every per-group term to the half dtype             */
+  int32_t reserved[3];
+} FtnForms;
+/* x_misalign: byte offset of x from a 16-byte boundary (0 = aligned).  Returns 0, or < 0 on a bad argument. */
+int ftn_timesblock_forms(const FtnPlan* plan, int B, int L, int act_dtype, int x_misalign, FtnForms* forms_out);
+/* The form ftn_period_spectrum takes (scratch: whether the caller passes the scratch buffer):
+ * 0 k_spectrum, 1 k_spectrum_row, 2 k_spectrum_rowq, 3 channel-tiled k_spectrum_rowq + k_median_rows;
+ * plus 4 when x is read with 16-byte vector loads.  < 0 on a bad argument. */
+int ftn_period_spectrum_form(int B, int L, int C, int x_misalign, int scratch);
 
 /* ---- LowRankTemporalContext (:1340-1371) -------------------------------------- */
 /* basis buffer: (L+1)*R floats = basis[l][r] (DCT-II columns r=1..R, centred over l,
