@@ -29,18 +29,28 @@ struct FinalizeArgs {
   FtnDesc* desc; float* amps; float* wts;
   int act_dtype, max_unique; float log_den;   // log_den = (float)log(base) of TIMES_PERIOD_BINNING, evaluated in double on the host (0 = off)
   // multi-GPU exchange (FtnExchange): the nparts partial sums are peer-written slots; ready[p * ready_n + i] turns
-  // ready_seq when block i of rank p's k_colsum has stored its columns.  psum rows are psum_stride doubles apart.
+  // the call's seq when block i of rank p's k_colsum has stored its columns.  psum rows are psum_stride doubles apart.
+  // psum and ready point into half 0 of this rank's buffer; the call's half is (seq & 1) * xhalf bytes further on.
+  // seq = ready_seq (mode 0), or *xctr + 1 (mode 1: the buffer's call counter, set to seq here once the slots are summed).
   const unsigned long long* ready; unsigned long long ready_seq; int ready_n, psum_stride; int* xerr;
+  unsigned long long* xctr; size_t xhalf;
   unsigned long long* dbg;   // diagnostic s_memtime stamps of the finalize workgroup's phases (ftn_debug_stamps which & 8), 8 words
 };
 
 // exchange buffer of one rank: two halves (seq parity); per half [world][F_cap] doubles, then [world][FTN_XCHG_NBLK]
-// sequence words; one error word at the very end
+// sequence words; then one 256-byte line: the error word (int32 at +0) and the mode-1 call counter (uint64 at +8)
 #define FTN_XCHG_NBLK 32
 __host__ __device__ inline size_t ftn_xchg_half_bytes(int world, int F_cap) {
   return ((size_t)world * ((size_t)F_cap * 8 + FTN_XCHG_NBLK * 8) + 255) & ~(size_t)255;
 }
 __host__ __device__ inline size_t ftn_xchg_flags_off(int world, int F_cap) { return (size_t)world * F_cap * 8; }
+__host__ __device__ inline size_t ftn_xchg_counter_off(int world, int F_cap) { return 2 * ftn_xchg_half_bytes(world, F_cap) + 8; }
+
+// mode-1 call counter: read and written only by the GPU that owns the buffer, in stream order (k_colsum of call n+1
+// starts after the finalize of call n has stored it), so agent scope is enough; the peer words stay at system scope
+__device__ __forceinline__ unsigned long long ftn_xchg_seq(const unsigned long long* ctr, unsigned long long seq) {
+  return ctr != nullptr ? __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 : seq;
+}
 
 // One 256-thread workgroup.  Dynamic LDS: F rounded up to a multiple of 16 floats (scores) + as many 64-bit keys
 // (ftn_finalize_lds_bytes).
@@ -69,7 +79,12 @@ __device__ __forceinline__ void finalize_body(const FinalizeArgs& fa) {
 
   const int pstride = fa.psum_stride > 0 ? fa.psum_stride : F;
   __shared__ int peers_late;
+  const unsigned long long seq = fa.ready != nullptr ? ftn_xchg_seq(fa.xctr, fa.ready_seq) : 0ull;
+  const unsigned long long* ready = fa.ready;
   if (fa.ready != nullptr) {
+    const size_t hoff = (size_t)(seq & 1) * fa.xhalf;
+    psum = (const double*)((const char*)psum + hoff);
+    ready = (const unsigned long long*)((const char*)ready + hoff);
     // every (rank, column block) sequence word must have turned ready_seq.  Bounded wait: s_memrealtime ticks at
     // 100 MHz, 2 s = 2e8 ticks - a peer that died must not hang this GPU.  System-scope loads: the words and the
     // slots are written by other GPUs (or, in a rehearsal, other processes) and must not come from a stale cache line.
@@ -78,8 +93,8 @@ __device__ __forceinline__ void finalize_body(const FinalizeArgs& fa) {
     const int nflag = nparts * fa.ready_n;
     for (int i = tid; i < nflag; i += 256) {
       const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      while (__hip_atomic_load(fa.ready + (size_t)(i / fa.ready_n) * FTN_XCHG_NBLK + (i % fa.ready_n), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_SYSTEM) != fa.ready_seq) {
+      while (__hip_atomic_load(ready + (size_t)(i / fa.ready_n) * FTN_XCHG_NBLK + (i % fa.ready_n), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM) != seq) {
         if (__builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) { peers_late = 1; break; }
         __builtin_amdgcn_s_sleep(32);
       }
@@ -103,6 +118,8 @@ __device__ __forceinline__ void finalize_body(const FinalizeArgs& fa) {
     score[f] = (f == 0) ? -INFINITY : sc;
   }
   __syncthreads();
+  // every thread has read the counter (above) and the slots: this call is done with the buffer
+  if (fa.xctr != nullptr && tid == 0) __hip_atomic_store(fa.xctr, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   fstamp(1);
   int k = kcfg < F - 1 ? kcfg : F - 1;                            // :122-123
   if (k > FTN_KMAX) k = FTN_KMAX;

@@ -273,6 +273,7 @@ __global__ __launch_bounds__(256) void k_pw(PwArgs a) { pw_body<ACT, XIN, XVEC, 
 // disappear behind the selector's tail (ftn_period_finalize_stage_a).
 #include "ftn_finalize.h"
 void ftn_xch_fill(const FtnExchange* x, int F, FinalizeArgs* fa);   // selector.hip
+bool ftn_xch_ok(const FtnExchange* x, int F);                       // selector.hip
 // part: 0 = both (workgroup 0 finalizes, the others run stage A), 1 = stage A only (a sharded batch runs it while
 // the partial sums are exchanged), 2 = finalize + descriptor copy only (one workgroup, after that exchange)
 template <int ACT, bool XVEC, int EPI>
@@ -3063,9 +3064,7 @@ extern "C" int ftn_period_finalize_stage_a(const double* psum_dev, int nparts, i
   // psum_dev == NULL: stage A only;  x_dev == NULL: finalize + descriptor copy only (stage A is in the workspace)
   const bool do_fin = psum_dev != nullptr || xch != nullptr, do_a = x_dev != nullptr;
   if (xch != nullptr) {
-    FTN_CHECK_ARG(xch->world >= 1 && xch->world <= FTN_XCHG_MAXWORLD && xch->rank >= 0 && xch->rank < xch->world &&
-                  xch->seq > 0 && L / 2 + 1 <= xch->F_cap && xch->slots[xch->rank] != nullptr,
-                  "ftn_period_finalize_stage_a: bad exchange (world / rank / seq / F_cap)");
+    FTN_CHECK_ARG(ftn_xch_ok(xch, L / 2 + 1), "ftn_period_finalize_stage_a: bad exchange (world / rank / seq / mode / F_cap)");
     nparts = xch->world;
   }
   FTN_CHECK_ARG(do_fin || do_a, "ftn_period_finalize_stage_a: nothing to do (psum and x both null)");

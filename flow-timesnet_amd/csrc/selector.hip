@@ -778,8 +778,11 @@ __global__ __launch_bounds__(256) void k_median_rows(const float* __restrict__ a
 // With an exchange (XchArgs.world > 0) block i also stores its 32 columns into slot `rank` of every rank's exchange
 // buffer (peer device memory, mapped through hipIpcOpenMemHandle) and then turns that slot's sequence word i: plain
 // stores, a system-scope fence, a system-scope store of the word - the consumer is ftn_finalize.h's bounded wait.
+// The call's half, seq & 1, is chosen here: seq is the launch argument (mode 0) or this rank's call counter + 1 (mode 1).
 struct XchArgs {
-  char* half[FTN_XCHG_MAXWORLD];     // this call's half of every rank's buffer
+  char* base[FTN_XCHG_MAXWORLD];     // every rank's buffer (half 0)
+  size_t half_bytes;
+  const unsigned long long* ctr;     // mode 1: this rank's call counter; nullptr in mode 0
   int world, rank, F_cap;
   unsigned long long seq;
 };
@@ -794,20 +797,23 @@ __global__ __launch_bounds__(1024) void k_colsum(const float* __restrict__ med, 
     for (int b = bl; b < B; b += 32) s += (double)med[(size_t)b * F + f];
   part[bl][fl] = s;
   __syncthreads();
-  if (bl == 0 && f < F) {
+  if (bl != 0) return;                                          // wave 0 of the block holds all 32 storing lanes
+  const unsigned long long seq = xa.world > 0 ? ftn_xchg_seq(xa.ctr, xa.seq) : 0ull;
+  const size_t hoff = (size_t)(seq & 1) * xa.half_bytes;
+  if (f < F) {
     double t = 0.0;
 #pragma unroll
     for (int k = 0; k < 32; ++k) t += part[k][fl];
     psum[f] = t;
-    for (int r = 0; r < xa.world; ++r) ((double*)xa.half[r])[(size_t)xa.rank * xa.F_cap + f] = t;
+    for (int r = 0; r < xa.world; ++r) ((double*)(xa.base[r] + hoff))[(size_t)xa.rank * xa.F_cap + f] = t;
   }
-  if (xa.world > 0 && bl == 0) {                                // wave 0 of the block holds all 32 storing lanes
+  if (xa.world > 0) {
     __threadfence_system();
     if (fl == 0)
       for (int r = 0; r < xa.world; ++r)
-        __hip_atomic_store((unsigned long long*)(xa.half[r] + ftn_xchg_flags_off(xa.world, xa.F_cap)) +
+        __hip_atomic_store((unsigned long long*)(xa.base[r] + hoff + ftn_xchg_flags_off(xa.world, xa.F_cap)) +
                                (size_t)xa.rank * FTN_XCHG_NBLK + blockIdx.x,
-                           xa.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                           seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 
@@ -816,24 +822,27 @@ extern "C" size_t ftn_exchange_bytes(int world, int F_cap) {
   return 2 * ftn_xchg_half_bytes(world, F_cap) + 256;           // two halves + the error word's line
 }
 
-static bool xch_ok(const FtnExchange* x, int F) {
-  return x->world >= 1 && x->world <= FTN_XCHG_MAXWORLD && x->rank >= 0 && x->rank < x->world && x->seq > 0 &&
-         F <= x->F_cap && x->F_cap <= 32 * FTN_XCHG_NBLK && x->slots[x->rank] != nullptr;
+// mode 0 needs the host's sequence number (> 0); mode 1 keeps it in the buffer's call counter
+bool ftn_xch_ok(const FtnExchange* x, int F) {
+  return x->world >= 1 && x->world <= FTN_XCHG_MAXWORLD && x->rank >= 0 && x->rank < x->world &&
+         (x->mode == 1 || (x->mode == 0 && x->seq > 0)) && F <= x->F_cap && x->F_cap <= 32 * FTN_XCHG_NBLK &&
+         x->slots[x->rank] != nullptr;
 }
 static bool xch_mapped(const FtnExchange* x) {
   for (int r = 0; r < x->world; ++r)
     if (x->slots[r] == nullptr) return false;
   return true;
 }
-static char* xch_half(const FtnExchange* x, int r) {
-  return (char*)x->slots[r] + (size_t)(x->seq & 1) * ftn_xchg_half_bytes(x->world, x->F_cap);
-}
 int* ftn_xch_err_word(const FtnExchange* x) {
   return (int*)((char*)x->slots[x->rank] + 2 * ftn_xchg_half_bytes(x->world, x->F_cap));
 }
-// the finalize side of an exchange: psum rows = the world slots of this rank's own buffer
+static unsigned long long* xch_counter(const FtnExchange* x) {
+  return x->mode == 1 ? (unsigned long long*)((char*)x->slots[x->rank] + ftn_xchg_counter_off(x->world, x->F_cap))
+                      : nullptr;
+}
+// the finalize side of an exchange: psum rows = the world slots of this rank's own buffer (the kernel picks the half)
 void ftn_xch_fill(const FtnExchange* x, int F, FinalizeArgs* fa) {
-  char* mine = xch_half(x, x->rank);
+  char* mine = (char*)x->slots[x->rank];
   fa->psum = (const double*)mine;
   fa->nparts = x->world;
   fa->psum_stride = x->F_cap;
@@ -841,6 +850,8 @@ void ftn_xch_fill(const FtnExchange* x, int F, FinalizeArgs* fa) {
   fa->ready_seq = x->seq;
   fa->ready_n = (F + 31) / 32;
   fa->xerr = ftn_xch_err_word(x);
+  fa->xctr = xch_counter(x);
+  fa->xhalf = ftn_xchg_half_bytes(x->world, x->F_cap);
 }
 
 // One rank's exchange buffer: allocated and zeroed here (hipMalloc: its own allocation, which is what an IPC handle
@@ -883,6 +894,20 @@ extern "C" int ftn_exchange_free(void* buf) {
   hipError_t e = buf ? hipFree(buf) : hipSuccess;
   if (e != hipSuccess) { ftn_set_error("hipFree: %s", hipGetErrorString(e)); return (int)e; }
   return 0;
+}
+
+extern "C" size_t ftn_exchange_counter_offset(int world, int F_cap) {
+  return ftn_exchange_bytes(world, F_cap) > 0 ? ftn_xchg_counter_off(world, F_cap) : 0;
+}
+
+extern "C" int64_t ftn_exchange_calls(const FtnExchange* xch, void* stream) {
+  FTN_CHECK_ARG(xch && xch->world >= 1 && xch->world <= FTN_XCHG_MAXWORLD && xch->rank >= 0 && xch->rank < xch->world &&
+                xch->slots[xch->rank] && xch->mode == 1, "ftn_exchange_calls: bad exchange (or not mode 1)");
+  unsigned long long v = 0;
+  hipError_t e = hipMemcpyAsync(&v, xch_counter(xch), sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess) { ftn_set_error("ftn_exchange_calls: %s", hipGetErrorString(e)); return -1; }
+  return (int64_t)v;
 }
 
 extern "C" int ftn_exchange_error(const FtnExchange* xch, void* stream) {
@@ -940,7 +965,7 @@ extern "C" int ftn_period_spectrum(const float* x_dev, int B, int L, int C, cons
                                    float* med_dev, double* psum_dev, void* stream, const FtnExchange* xch,
                                    void* scratch_dev) {
   FTN_CHECK_ARG(x_dev && table_dev && med_dev && psum_dev, "ftn_period_spectrum: null pointer");
-  FTN_CHECK_ARG(xch == nullptr || xch_ok(xch, L / 2 + 1), "ftn_period_spectrum: bad exchange (world / rank / seq / F_cap)");
+  FTN_CHECK_ARG(xch == nullptr || ftn_xch_ok(xch, L / 2 + 1), "ftn_period_spectrum: bad exchange (world / rank / seq / mode / F_cap)");
   FTN_CHECK_ARG(xch == nullptr || xch_mapped(xch), "ftn_period_spectrum: an exchange slot is not mapped");
   FTN_CHECK_ARG(B >= 1 && L >= 2 && C >= 1, "ftn_period_spectrum: bad shape B=%d L=%d C=%d", B, L, C);
   FTN_CHECK_ARG((long long)(B + 7) * (fpad_of(L) / 32) < 0x7fffffffLL, "ftn_period_spectrum: B=%d too large", B);
@@ -988,7 +1013,9 @@ extern "C" int ftn_period_spectrum(const float* x_dev, int B, int L, int C, cons
   FTN_CHECK_LAUNCH();
   XchArgs xa = {};
   if (xch != nullptr) {
-    for (int r = 0; r < xch->world; ++r) xa.half[r] = xch_half(xch, r);
+    for (int r = 0; r < xch->world; ++r) xa.base[r] = (char*)xch->slots[r];
+    xa.half_bytes = ftn_xchg_half_bytes(xch->world, xch->F_cap);
+    xa.ctr = xch_counter(xch);
     xa.world = xch->world; xa.rank = xch->rank; xa.F_cap = xch->F_cap; xa.seq = xch->seq;
   }
   hipLaunchKernelGGL(k_colsum, dim3(ftn_cdiv(F, 32)), dim3(1024), 0, (hipStream_t)stream, med_dev, B, F, psum_dev, xa);
@@ -1004,7 +1031,7 @@ extern "C" int ftn_period_finalize(const double* psum_dev, int nparts, int Btota
                                    int max_unique, double log_base, FtnDesc* desc_dev, float* amps_dev,
                                    float* weights_dev, void* stream, const FtnExchange* xch) {
   FTN_CHECK_ARG((psum_dev || xch) && med_dev && desc_dev && amps_dev && weights_dev, "ftn_period_finalize: null pointer");
-  FTN_CHECK_ARG(xch == nullptr || xch_ok(xch, L / 2 + 1), "ftn_period_finalize: bad exchange (world / rank / seq / F_cap)");
+  FTN_CHECK_ARG(xch == nullptr || ftn_xch_ok(xch, L / 2 + 1), "ftn_period_finalize: bad exchange (world / rank / seq / mode / F_cap)");
   if (xch != nullptr) nparts = xch->world;
   FTN_CHECK_ARG((((uintptr_t)amps_dev | (uintptr_t)weights_dev) & 15) == 0, "ftn_period_finalize: amps / weights must be 16-byte aligned");
   FTN_CHECK_ARG(B >= 1 && L >= 2 && nparts >= 1 && Btotal >= B, "ftn_period_finalize: bad shape");

@@ -36,16 +36,39 @@ def _refuse_flagged_grouping(block_index=None) -> None:
                                   "selector: unset them or run unsharded")
 
 
+def _refuse_capture(sharded: bool, x: torch.Tensor, exchange, gather) -> None:
+    """A sharded call captured into a HIP graph may use neither a collective (the ``torch.distributed`` all-gather of
+    the partial sums, ``gather=True`` / ``"async"``) nor a host-side sequence number (a mode-0 ``IpcExchange``, whose
+    captured ``seq`` a replay would reuse: the finalize would read the peers' words of an earlier call).  Raise before
+    anything is enqueued instead of capturing a graph that races or hangs."""
+    if not sharded or not x.is_cuda or not torch.cuda.is_current_stream_capturing():
+        return
+    if exchange is None:
+        raise RuntimeError("a sharded forward cannot be captured with the torch.distributed exchange (exchange=None): "
+                           "use dist.IpcExchange(..., capturable=True)")
+    if not exchange.capturable:
+        raise RuntimeError("a sharded forward cannot be captured with an IpcExchange built with capturable=False "
+                           "(its sequence number is a launch argument): build it with capturable=True")
+    if gather:
+        raise RuntimeError("a sharded forward cannot be captured with gather=True / 'async' (a collective): capture "
+                           "with gather=False and call dist.gather_batch on the outputs after the replay")
+
+
 class IpcExchange:
     """SURVEY section 8e step 2 without a collective: every rank owns one exchange buffer in its GPU's memory, maps the
     other ranks' buffers once (``hipIpcGetMemHandle`` / ``hipIpcOpenMemHandle``, handles traded through the process
     group), and from then on each block call's partial sums are plain stores into the peers' buffers issued by the
     selector's own kernel, with a sequence word behind them (``include/flowtimes.h``, ``FtnExchange``).  Attach it with
-    ``ShardedTimesBlock(block, group, exchange=IpcExchange(group, device))``; ranks must call in lockstep."""
+    ``ShardedTimesBlock(block, group, exchange=IpcExchange(group, device))``; ranks must call in lockstep.
+
+    ``capturable=True`` (``FtnExchange.mode`` 1): the sequence number is not a launch argument but a call counter in
+    this rank's own buffer, read and advanced by the kernels, so the sharded forward can be captured in a HIP graph
+    (``graph.GraphedForward`` with ``gather=False``) and eager calls and replays can be mixed on one exchange.
+    ``calls()`` returns that counter."""
 
     _IPC_HANDLE_BYTES = 64
 
-    def __init__(self, group, device: torch.device, f_cap: int = 1024) -> None:
+    def __init__(self, group, device: torch.device, f_cap: int = 1024, capturable: bool = False) -> None:
         import ctypes as C
 
         from . import lib as _lib
@@ -70,6 +93,8 @@ class IpcExchange:
         self._own, self._mapped = own, []
         self.x = _lib.FtnExchange()
         self.x.world, self.x.rank, self.x.F_cap, self.x.seq = self.world, self.rank, int(f_cap), 0
+        self.capturable = bool(capturable)
+        self.x.mode = 1 if self.capturable else 0
         for r, raw in enumerate(handles):
             if r == self.rank:
                 self.x.slots[r] = own.value
@@ -82,11 +107,26 @@ class IpcExchange:
         dist.barrier(group=self.group)                          # every rank has zeroed and mapped before the first call
 
     def next_call(self, F: int):
-        """The struct pointer for one exchange (bumps the sequence number: every rank must make the same calls)."""
+        """The struct pointer for one exchange (every rank must make the same calls).  Bumps the host sequence number;
+        with ``capturable=True`` the device counter is the only one, so nothing changes on the host."""
         if F > self.x.F_cap:
             raise ValueError(f"IpcExchange: F={F} exceeds F_cap={self.x.F_cap}")
-        self.x.seq += 1
+        if not self.capturable:
+            self.x.seq += 1
         return self._C.byref(self.x)
+
+    def calls(self) -> int:
+        """Synchronises; the number of exchanges this rank has completed (``capturable=True`` only): eager calls and
+        graph replays alike.  Equal on every rank that called in lockstep."""
+        from . import lib as _lib
+        from . import runtime
+
+        if not self.capturable:
+            raise RuntimeError("IpcExchange.calls() needs capturable=True (mode 0 counts on the host: x.seq)")
+        n = _lib.load().ftn_exchange_calls(self._C.byref(self.x), runtime._stream(self.device))
+        if n < 0:
+            raise RuntimeError(f"ftn_exchange_calls failed: {_lib.load().ftn_last_error().decode(errors='replace')}")
+        return int(n)
 
     def check(self) -> None:
         """Synchronises; raises if a peer's sums did not arrive within the kernel's bounded wait."""
@@ -152,8 +192,10 @@ class ShardedTimesBlock(nn.Module):
         grp = self.group if self.group is not None else dist.group.WORLD
         if dist.get_world_size(grp) > 1:
             _refuse_flagged_grouping(getattr(self.block, "block_index", None))
+        sharded = dist.get_world_size(grp) > 1 or os.environ.get("FTN_BENCH_FORCE_DIST") == "1"
+        _refuse_capture(sharded, x_local, self.exchange, gather)
         prev, prev_x = sel.shard_group, sel.shard_exchange
-        sel.shard_group = grp if (dist.get_world_size(grp) > 1 or os.environ.get("FTN_BENCH_FORCE_DIST") == "1") else None
+        sel.shard_group = grp if sharded else None
         sel.shard_exchange = self.exchange if (self.exchange is not None and x_local.is_cuda) else None
         try:
             y = self.block(x_local)
@@ -168,14 +210,38 @@ class ShardedTimesNet(nn.Module):
     """Batch-sharded whole model (P2): the model's blocks share one ``FFTPeriodSelector``, so
     pointing its ``shard_group`` at the process group makes every block exchange its ``[F]`` partial sums;
     everything else in ``TimesNet.forward`` is row-wise or per-series and needs no communication.
-    ``forward`` returns this rank's ``(rate, dispersion)`` rows, or the all-gathered ones with ``gather=True``."""
+    ``forward`` returns this rank's ``(rate, dispersion)`` rows, or the all-gathered ones with ``gather=True``.
+    ``exchange``: as in ``ShardedTimesBlock``; with ``IpcExchange(..., capturable=True)`` the wrapper can be captured
+    by ``graph.GraphedForward(wrapper, x_local, gather=False)``, which runs the model's deferred output checks through
+    the three attributes forwarded below."""
 
-    def __init__(self, model: nn.Module, group=None) -> None:
+    def __init__(self, model: nn.Module, group=None, exchange: Optional[IpcExchange] = None) -> None:
         super().__init__()
         self.model = model
         self.group = group
+        self.exchange = exchange                                 # None: all-gather through torch.distributed (RCCL / gloo)
         if not hasattr(model.period_selector, "shard_group"):
             raise ValueError("ShardedTimesNet needs the mirror TimesNet (native FFTPeriodSelector)")
+
+    # graph.GraphedForward defers the model's output checks during capture and runs them after every replay
+    @property
+    def _defer_checks(self) -> bool:
+        return self.model._defer_checks
+
+    @_defer_checks.setter
+    def _defer_checks(self, v: bool) -> None:
+        self.model._defer_checks = v
+
+    @property
+    def _pending_bad(self):
+        return self.model._pending_bad
+
+    @_pending_bad.setter
+    def _pending_bad(self, v) -> None:
+        self.model._pending_bad = v
+
+    def check_outputs(self) -> None:
+        self.model.check_outputs()
 
     def forward(self, x_local: torch.Tensor, gather: bool = False, **kwargs):
         sel = self.model.period_selector
@@ -183,12 +249,15 @@ class ShardedTimesNet(nn.Module):
         if dist.get_world_size(grp) > 1:
             for blk in self.model.blocks:
                 _refuse_flagged_grouping(getattr(blk, "block_index", None))
-        prev = sel.shard_group
-        sel.shard_group = grp if (dist.get_world_size(grp) > 1 or os.environ.get("FTN_BENCH_FORCE_DIST") == "1") else None
+        sharded = dist.get_world_size(grp) > 1 or os.environ.get("FTN_BENCH_FORCE_DIST") == "1"
+        _refuse_capture(sharded, x_local, self.exchange, gather)
+        prev, prev_x = sel.shard_group, sel.shard_exchange
+        sel.shard_group = grp if sharded else None
+        sel.shard_exchange = self.exchange if (self.exchange is not None and x_local.is_cuda) else None
         try:
             rate, disp = self.model(x_local, **kwargs)
         finally:
-            sel.shard_group = prev
+            sel.shard_group, sel.shard_exchange = prev, prev_x
         if gather:
             return gather_batch(rate, grp), gather_batch(disp, grp)
         return rate, disp

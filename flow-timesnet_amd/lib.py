@@ -13,7 +13,7 @@ from typing import Optional
 
 FTN_KMAX = 16
 FTN_MAXBR = 8
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "csrc" / "libflowtimes_hip.so"
@@ -30,7 +30,7 @@ class FtnExchange(C.Structure):
     """Mirror of ``struct FtnExchange`` (include/flowtimes.h): the peer-mapped exchange buffers of a batch-sharded run."""
 
     _fields_ = [("slots", C.c_void_p * FTN_XCHG_MAXWORLD), ("world", C.c_int32), ("rank", C.c_int32),
-                ("F_cap", C.c_int32), ("seq", C.c_uint64)]
+                ("F_cap", C.c_int32), ("seq", C.c_uint64), ("mode", C.c_int32)]
 
 
 class FtnDesc(C.Structure):
@@ -113,6 +113,8 @@ _SIGNATURES = {
     "ftn_period_spectrum": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(FtnExchange), _P]),
     "ftn_exchange_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_exchange_error": (C.c_int, [C.POINTER(FtnExchange), _P]),
+    "ftn_exchange_counter_offset": (C.c_size_t, [C.c_int, C.c_int]),
+    "ftn_exchange_calls": (C.c_int64, [C.POINTER(FtnExchange), _P]),
     "ftn_exchange_alloc": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_void_p), _P]),
     "ftn_exchange_open": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "ftn_exchange_close": (C.c_int, [_P]),

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define FTN_ABI_VERSION 11
+#define FTN_ABI_VERSION 12
 #define FTN_KMAX 16      /* max period candidates / groups per block call        */
 #define FTN_MAXBR 8      /* max kernels in kernel_set                             */
 
@@ -150,15 +150,28 @@ int ftn_inception_pack_weights(const FtnInceptionBlockWeights* block0, const Ftn
  * passing this struct; no collective; deterministic.
  *   slots[r]  rank r's exchange buffer as mapped into THIS process (slots[rank] = this rank's own hipMalloc'ed
  *             buffer of ftn_exchange_bytes(world, F_cap) bytes, zeroed once before the first call)
- *   seq       this call's sequence number: identical on every rank, starts at 1, +1 per exchange (the two halves of
- *             the buffer alternate by seq & 1, so a rank one call ahead never overwrites what a peer still reads)
+ *   seq       mode 0: this call's sequence number: identical on every rank, starts at 1, +1 per exchange (the two
+ *             halves of the buffer alternate by seq & 1).  Ignored in mode 1.
+ *   mode      (ABI 12) 0 = seq is a launch argument, set by the host before every call: the launches cannot be
+ *             captured in a HIP graph (a replay would reuse the captured seq and read the peers' words of an earlier
+ *             call: a silent race).  1 = capturable: seq = counter + 1, where counter is a 64-bit call counter in this rank's own
+ *             buffer (byte offset ftn_exchange_counter_offset, in the line of the error word; zeroed by
+ *             ftn_exchange_alloc).  k_colsum and the finalize workgroup read it, the finalize workgroup stores
+ *             counter = seq once the slots are summed (or its wait timed out); nothing else writes it.  A zeroed
+ *             struct is mode 0.  Other values are refused.
+ * Two halves suffice, in either mode: a rank's k_colsum of call n+1 runs after its own finalize of call n, which waited
+ * for every peer's k_colsum of call n, which each peer ran after its finalize of call n-1 - so a rank is at most one
+ * call ahead of any peer, and what it stores into half (n+1) & 1 is no longer read.  In mode 1 the same stream order
+ * gives each call on a rank one counter value: every rank that made the same calls uses the same seq, whether a call
+ * was enqueued eagerly or replayed from a graph.
  * A rank that does not hear from a peer within ~2 s writes an empty descriptor (the block becomes the identity) and
- * sets the buffer's error word (ftn_exchange_error).  Not capturable in a HIP graph (seq is a launch argument). */
+ * sets the buffer's error word (ftn_exchange_error). */
 #define FTN_XCHG_MAXWORLD 16
 typedef struct FtnExchange {
   void* slots[FTN_XCHG_MAXWORLD];
   int32_t world, rank, F_cap;
   uint64_t seq;
+  int32_t mode;
 } FtnExchange;
 size_t ftn_exchange_bytes(int world, int F_cap);
 /* this rank's buffer on the current device (hipMalloc + zero) and its 64-byte hipIpcMemHandle_t, to be sent to the
@@ -169,6 +182,10 @@ int ftn_exchange_close(void* mapped);
 int ftn_exchange_free(void* buf);
 /* host-side read of the error word of this rank's own buffer (synchronises the stream): 0 = ok, 1 = a peer timed out */
 int ftn_exchange_error(const FtnExchange* xch, void* stream);
+/* byte offset of the mode-1 call counter (uint64) in a rank's buffer: 8 bytes past the error word, in its 256-byte line */
+size_t ftn_exchange_counter_offset(int world, int F_cap);
+/* host-side read of the mode-1 call counter of this rank's own buffer (synchronises the stream); -1 on a bad argument */
+int64_t ftn_exchange_calls(const FtnExchange* xch, void* stream);
 
 /* ---- period selector: FFTPeriodSelector.forward (:64-159) ------------------- */
 /* bytes of the DFT twiddle table for window length L */
@@ -205,7 +222,7 @@ int ftn_period_finalize(const double* psum_dev, int nparts, int Btotal, const fl
                         int max_unique, double log_base, FtnDesc* desc_dev, float* amps_dev, float* weights_dev,
                         void* stream, const FtnExchange* xch);
 /* (xch != NULL: psum_dev / nparts are ignored - the partial sums are the world slots of this rank's exchange buffer
- *  for sequence number xch->seq, which the kernel waits for) */
+ *  for this call's sequence number - xch->seq, or in mode 1 the device counter + 1 - which the kernel waits for) */
 /* Host-only: PeriodGrouper.group (:513-557, env flags unset) + conv tiling for
  * periods that come from somewhere else (stub selectors in the reference tests).
  * `periods` is a host array; `desc_host` is filled on the host. */
