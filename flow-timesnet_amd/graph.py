@@ -53,6 +53,8 @@ class GraphedForward:
         # the captured launches have the packed weight blobs' addresses baked in: keep them alive even if a block
         # repacks later (new weights need a new capture)
         self._packs = [m._pack for m in module.modules() if getattr(m, "_pack", None) is not None]
+        # likewise the series-sharded weight slices (TimesNet.series_slices)
+        self._slices = [m.__dict__["_series_slice_cache"] for m in module.modules() if "_series_slice_cache" in m.__dict__]
 
     @staticmethod
     def _refill(dst: Any, src: Any) -> None:

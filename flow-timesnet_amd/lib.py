@@ -13,7 +13,7 @@ from typing import Optional
 
 FTN_KMAX = 16
 FTN_MAXBR = 8
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "csrc" / "libflowtimes_hip.so"
@@ -31,6 +31,17 @@ class FtnExchange(C.Structure):
 
     _fields_ = [("slots", C.c_void_p * FTN_XCHG_MAXWORLD), ("world", C.c_int32), ("rank", C.c_int32),
                 ("F_cap", C.c_int32), ("seq", C.c_uint64), ("mode", C.c_int32)]
+
+
+FTN_ROWX_CHUNK = 16384
+
+
+class FtnRowExchange(C.Structure):
+    """Mirror of ``struct FtnRowExchange`` (include/flowtimes.h): the peer-mapped row buffers of a series-sharded run
+    (``kind`` 0 = reduce-scatter, 1 = all-gather)."""
+
+    _fields_ = [("slots", C.c_void_p * FTN_XCHG_MAXWORLD), ("world", C.c_int32), ("rank", C.c_int32),
+                ("rows_per_rank", C.c_int32), ("width", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32)]
 
 
 class FtnDesc(C.Structure):
@@ -119,6 +130,17 @@ _SIGNATURES = {
     "ftn_exchange_open": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
     "ftn_exchange_close": (C.c_int, [_P]),
     "ftn_exchange_free": (C.c_int, [_P]),
+    "ftn_rowx_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ftn_rowx_alloc": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p), _P]),
+    "ftn_rowx_open": (C.c_int, [_P, C.POINTER(C.c_void_p)]),
+    "ftn_rowx_close": (C.c_int, [_P]),
+    "ftn_rowx_free": (C.c_int, [_P]),
+    "ftn_rowx_error": (C.c_int, [C.POINTER(FtnRowExchange), _P]),
+    "ftn_rowx_calls": (C.c_int64, [C.POINTER(FtnRowExchange), _P]),
+    "ftn_rowx_push": (C.c_int, [_P, C.POINTER(FtnRowExchange), _P]),
+    "ftn_rowx_reduce": (C.c_int, [C.POINTER(FtnRowExchange), C.c_int, C.c_int, _P, C.c_longlong, _P, _P, C.c_float,
+                                  _P, _P]),
+    "ftn_rowx_gather": (C.c_int, [C.POINTER(FtnRowExchange), _P, _P]),
     "ftn_period_finalize": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_double, _P, _P, _P, _P, C.POINTER(FtnExchange)]),
     "ftn_desc_from_periods": (C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_int, C.c_int, C.c_int,

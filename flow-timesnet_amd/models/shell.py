@@ -613,6 +613,144 @@ class TimesNet(nn.Module):
             if flag & bit:
                 raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
 
+    # ---- series-sharded pieces (dist.SeriesShardedTimesNet): this rank owns series [offset, offset + n) ----------
+    # Only the value embedding mixes series (a contraction over N); everything else below is per series, so a rank
+    # computes a partial embedding over its own series, the partials are summed across ranks, and the heads run on
+    # the rank's own rows of mu_head / sigma_head.  Nothing here changes the model's state.
+    def series_slices(self, offset: int, n: int, device: torch.device) -> dict:
+        """This rank's weight slices: ``value_embedding.weight[:, S]``, the ``mu_head`` / ``sigma_head`` rows and
+        ``min_sigma_vector[S]``.  Cached and keyed on the parameters' storage pointers and version counters (as
+        TimesBlock's pack cache), so ``load_state_dict`` or an optimiser step invalidates them."""
+        emb = self.embedding
+        floor = self.min_sigma_vector
+        has_floor = isinstance(floor, torch.Tensor) and floor.numel() > 0
+        params = [emb.value_embedding.weight, self.mu_head.weight, self.mu_head.bias, self.sigma_head.weight,
+                  self.sigma_head.bias] + ([floor] if has_floor else [])
+        key = (int(offset), int(n), str(device)) + tuple(
+            (p.data_ptr(), -1 if p.is_inference() else p._version) for p in params)
+        cache = self.__dict__.get("_series_slice_cache")
+        if cache is not None and cache[0] == key:
+            return cache[1]
+        sl = slice(int(offset), int(offset) + int(n))
+        take = lambda t: t.detach()[sl].to(device=device, dtype=torch.float32).contiguous()
+        out = {"w_emb": emb.value_embedding.weight.detach()[:, sl].to(device=device, dtype=torch.float32).contiguous(),
+               "w_mu": take(self.mu_head.weight), "b_mu": take(self.mu_head.bias),
+               "w_sigma": take(self.sigma_head.weight), "b_sigma": take(self.sigma_head.bias),
+               "floor": take(floor.reshape(-1)) if has_floor else None}
+        self.__dict__["_series_slice_cache"] = (key, out)
+        return out
+
+    def series_context_rows(self, window, series_static, series_ids, offset: int) -> Optional[torch.Tensor]:
+        """``_context_rows`` for this rank's series without touching the remembered ids: the static features and ids
+        are the rank's slices, and missing ids default to the GLOBAL ``arange(offset, offset + n)``."""
+        B, _, N = window.shape
+        if series_ids is None and self.series_embedding is not None and self.id_embed_dim > 0:
+            series_ids = torch.arange(int(offset), int(offset) + N, device=window.device)
+        shared = ((series_static is None or series_static.ndim == 2)
+                  and (series_ids is None or series_ids.ndim == 1 or series_ids.size(0) == 1))
+        Bc = 1 if shared else B
+        cols = []
+        if self.static_proj is not None and series_static is not None:
+            if series_static.shape[-2] != N or (series_static.ndim == 3 and series_static.size(0) != B):
+                raise ValueError("series_static must be [n_local, F] or [B, n_local, F] for this rank's series")
+            st = series_static if series_static.ndim == 3 else series_static.unsqueeze(0).expand(Bc, -1, -1)
+            proj = self.static_proj(st.to(device=window.device, dtype=window.dtype, non_blocking=window.is_cuda))
+            cols.append(proj if self.static_norm is None else _norm(self.static_norm, proj))
+        if self.series_embedding is not None and self.id_embed_dim > 0:
+            ids = series_ids.view(1, -1) if series_ids.ndim == 1 else series_ids
+            if ids.size(0) not in (1, B) or ids.size(1) != N:
+                raise ValueError("series_ids must be [n_local] or [B, n_local] for this rank's series")
+            ids = ids.to(device=window.device, dtype=torch.long)
+            cols.append(self.series_embedding(ids.expand(Bc, -1) if ids.size(0) != Bc else ids))
+        if not cols:
+            return None
+        rows = cols[0] if len(cols) == 1 else torch.cat(cols, dim=-1)
+        return rows if self.context_norm is None else _norm(self.context_norm, rows)
+
+    def series_partial_embedding(self, window, rows, w_emb: torch.Tensor) -> torch.Tensor:
+        """This rank's share of the value embedding, ``[B, L, D]``: ``x_r W_r^T + (context terms of S_r) W_r^T`` -
+        no bias, no positional / time-feature term, no norm (those are added once, after the sum over ranks)."""
+        coeff = bias = None
+        if rows is not None:
+            if self.context_coeff is not None and self.temporal_context is not None and self.use_zero_mean_context:
+                coeff = self.context_coeff(rows.to(self.context_coeff.weight.dtype))
+            if self.context_proj is not None and self.use_constant_context_bias:
+                bias = self.context_proj(rows.to(self.context_proj.weight.dtype)).squeeze(-1)
+        L = window.size(1)
+        if window.is_cuda:
+            from .. import runtime
+
+            add = None
+            if coeff is not None:
+                add = self.temporal_context.project(coeff.detach().float(), L, w_emb)
+            if bias is not None:
+                cb = (bias.detach().float() @ w_emb.t()).unsqueeze(1)
+                add = cb if add is None else add + cb
+            return runtime.embed_forward(window, w_emb, None if add is None else add.contiguous(), None)
+        feats = window
+        if coeff is not None:
+            feats = feats + self.temporal_context(coeff, L).to(feats.dtype)
+        if bias is not None:
+            feats = feats + bias.to(feats.dtype).unsqueeze(1)
+        return F.linear(feats, w_emb.to(feats.dtype))
+
+    def series_embedding_epilogue(self, window, mark) -> Tuple[torch.Tensor, Optional[tuple]]:
+        """What the summed partials still need: ``add`` = value bias + positional (+ time-feature) term, gated and
+        normalised in the "decoupled" mode, ``[1 or B_local, L, D]`` fp32; and ``(gamma, beta, eps)`` of the "layer"
+        mode's LayerNorm (None otherwise)."""
+        emb = self.embedding
+        add = (emb.aux_term(window[:1], mark) + emb.value_embedding.bias.detach()).detach().float().contiguous()
+        ln = None
+        if emb.embed_norm_mode == "layer":
+            ln = (emb.norm.weight.detach().float().contiguous(), emb.norm.bias.detach().float().contiguous(),
+                  emb.norm.eps)
+        return add, ln
+
+    def series_hidden(self, seq: torch.Tensor, steps: int) -> torch.Tensor:
+        """``forecast_time_proj`` of the local rows: ``[B_local, steps, d_model]`` (as ``_heads``)."""
+        wt, bt = self.forecast_time_proj.weight, self.forecast_time_proj.bias
+        if steps != self.pred_len:
+            wt, bt = wt[-steps:], bt[-steps:]
+        if seq.is_cuda:
+            return torch.baddbmm(bt.detach().view(1, -1, 1), wt.detach().unsqueeze(0).expand(seq.size(0), -1, -1),
+                                 seq.detach()).contiguous()
+        return torch.matmul(wt, seq) + bt.view(1, -1, 1)
+
+    def series_heads(self, hidden, window, rows, sl: dict, steps: int):
+        """Rate / dispersion of this rank's series from the gathered ``hidden [B, steps, D]``: ``(rate, dispersion,
+        bad)`` with ``bad`` the HIP head's device flag (None on the torch path, which raises itself)."""
+        B, L, N = window.shape
+        hist = min(steps, L)
+        late = None
+        if (rows is not None and self.late_bias_head is not None and self.late_bias_norm is not None
+                and isinstance(self.late_bias_gate, nn.Parameter)):
+            head = self.late_bias_head
+            lb = head(_norm(self.late_bias_norm, rows.to(device=head.weight.device, dtype=head.weight.dtype)))
+            late = self.late_bias_gate.to(lb) * lb.transpose(1, 2)                          # [Bc, steps, n_local]
+        if hidden.is_cuda:
+            from .. import runtime
+
+            return runtime.head_forward(hidden, sl["w_mu"], sl["b_mu"], sl["w_sigma"], sl["b_sigma"],
+                                        window[:, -hist:, :], hist,
+                                        None if late is None else late.detach().float().contiguous(), sl["floor"],
+                                        self.min_sigma)
+        last = window[:, -hist:, :]
+        if hist < steps:
+            last = torch.cat([last, last[:, -1:, :].expand(-1, steps - hist, -1)], dim=1)
+        pre = F.linear(hidden, sl["w_mu"], sl["b_mu"]) + last.to(window.dtype)
+        if late is not None:
+            pre = pre + late.to(pre.dtype)
+        soft = lambda t: F.softplus(t.float(), beta=1.0, threshold=20).to(t.dtype)
+        rate = soft(pre) + 1e-6
+        spread = soft(F.linear(hidden, sl["w_sigma"], sl["b_sigma"]))
+        floor = (sl["floor"].to(spread.dtype).view(1, 1, -1).expand_as(spread) if sl["floor"] is not None
+                 else torch.full_like(spread, self.min_sigma))
+        dispersion = spread + floor + 1e-6
+        for name, val in (("rate", rate), ("dispersion", dispersion)):
+            if not bool((torch.isfinite(val) & (val > 0)).all()):
+                raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
+        return rate, dispersion, None
+
     # ---- forward ------------------------------------------------------------------
     def forward(self, x: torch.Tensor, x_mark: Optional[torch.Tensor] = None,
                 series_static: Optional[torch.Tensor] = None,

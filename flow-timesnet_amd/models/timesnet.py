@@ -337,6 +337,9 @@ class TimesBlock(nn.Module):
         self._range_slots: list = []          # free (flag, event) pairs
         self._range_pending: list = []        # calls in flight: (flag, event, x, y, post_norm)
         self._range_dev_flag = None           # device-memory flag used while a HIP graph is being captured
+        # opt-in: use that device flag in eager calls too, and never repeat a call on the host's own initiative - the
+        # caller reads _range_dev_flag after the forward (dist.SeriesShardedTimesNet repairs collectively)
+        self.range_flag_on_device = False
         self._last_engine_used: Optional[str] = None
         self._range_fallbacks = 0
 
@@ -527,7 +530,7 @@ class TimesBlock(nn.Module):
         guarded = engine == "f16x2" and os.getenv("FTN_RANGE_GUARD", "1") != "0"
         range_flag = slot_ev = None
         if guarded:
-            if torch.cuda.is_current_stream_capturing():
+            if torch.cuda.is_current_stream_capturing() or getattr(self, "range_flag_on_device", False):
                 # a captured forward cannot record host events: it sets a device word (zeroed by a captured fill at
                 # every replay) that check_range() / TimesNet.check_outputs() read after the replay
                 self._range_dev_flag = range_flag = torch.zeros(1, dtype=torch.int32, device=x.device)

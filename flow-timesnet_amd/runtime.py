@@ -351,6 +351,37 @@ def embed_forward(window: torch.Tensor, weight: torch.Tensor, add, norm=None) ->
     return out
 
 
+# ------------------------------------------------------------------ row exchange (series-sharded forward)
+def rowx_push(src: torch.Tensor, xch) -> None:
+    """Store this rank's rows into every destination's buffer (``xch``: ``C.byref`` of an ``FtnRowExchange``).
+    ``src`` contiguous fp32: ``[W*R, width]`` for a reduce-scatter, ``[R, width]`` for an all-gather."""
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("rowx_push: src must be contiguous fp32")
+    check(_lib.load().ftn_rowx_push(_ptr(src), xch, _stream(src.device)), "ftn_rowx_push")
+
+
+def rowx_reduce(xch, rows: int, L: int, D: int, device: torch.device, add=None, norm=None) -> torch.Tensor:
+    """This rank's ``[rows, L, D]`` of the rank-order sum of every rank's pushed partials, ``+ add`` (None, or contiguous
+    ``[1|rows, L, D]``), then the LayerNorm ``norm = (gamma, beta, eps)`` over D (optional)."""
+    out = torch.empty(rows, L, D, dtype=torch.float32, device=device)
+    add_bs = 0
+    if add is not None:
+        if add.shape[-2:] != (L, D) or not add.is_contiguous() or add.dtype != torch.float32:
+            raise ValueError("rowx_reduce: add must be contiguous fp32 [1|rows, L, D]")
+        add_bs = L * D if add.dim() == 3 and add.shape[0] == rows and rows > 1 else 0
+    g, b, eps = norm if norm is not None else (None, None, 0.0)
+    check(_lib.load().ftn_rowx_reduce(xch, int(L), int(D), _ptr_or_null(add), add_bs, _ptr_or_null(g), _ptr_or_null(b),
+                                      float(eps), _ptr(out), _stream(device)), "ftn_rowx_reduce")
+    return out
+
+
+def rowx_gather(xch, shape, device: torch.device) -> torch.Tensor:
+    """Every rank's pushed rows, row block s from rank s, as a new fp32 tensor of ``shape`` (``[W*R, ...]``)."""
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    check(_lib.load().ftn_rowx_gather(xch, _ptr(out), _stream(device)), "ftn_rowx_gather")
+    return out
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_forward(coeff: torch.Tensor, L: int, scale: torch.Tensor, x: torch.Tensor | None) -> torch.Tensor:
     lib = _lib.load()

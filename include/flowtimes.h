@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define FTN_ABI_VERSION 12
+#define FTN_ABI_VERSION 13
 #define FTN_KMAX 16      /* max period candidates / groups per block call        */
 #define FTN_MAXBR 8      /* max kernels in kernel_set                             */
 
@@ -186,6 +186,60 @@ int ftn_exchange_error(const FtnExchange* xch, void* stream);
 size_t ftn_exchange_counter_offset(int world, int F_cap);
 /* host-side read of the mode-1 call counter of this rank's own buffer (synchronises the stream); -1 on a bad argument */
 int64_t ftn_exchange_calls(const FtnExchange* xch, void* stream);
+
+/* ---- multi-GPU row exchange of a series-sharded forward (ABI 13) ---------------------------------------------
+ * A series-sharded TimesNet (dist.SeriesShardedTimesNet) moves fp32 rows between ranks twice per forward: the
+ * partial value embeddings [B, L, D] are reduce-scattered along B (rank q receives rows q*B/W .. (q+1)*B/W - 1 of
+ * every rank's partial and sums them in rank order), and the hidden rows [B/W, H, D] are all-gathered along B.  Both
+ * are peer stores into IPC-mapped buffers, driven by a device call counter as FtnExchange mode 1 (there is no mode 0).
+ *   slots[r]       rank r's row buffer as mapped into THIS process (slots[rank] = this rank's own buffer)
+ *   rows_per_rank  R: rows each rank receives from each source (B/W)
+ *   width          floats per row (L*D or H*D), a multiple of 4
+ *   kind           0 = reduce-scatter: ftn_rowx_push sends source rows q*R .. q*R+R-1 to rank q (src is [W*R][width]),
+ *                  ftn_rowx_reduce consumes; 1 = all-gather: ftn_rowx_push sends the same R rows to every rank (src
+ *                  is [R][width]), ftn_rowx_gather consumes.  Other values are refused.
+ * Buffer of one rank (ftn_rowx_bytes): two halves, each [W][R*width] floats (slot s = the rows rank s sent here) and,
+ * 256-byte aligned behind them, [W][nblk] 64-bit sequence words (nblk = ceil(R*width / FTN_ROWX_CHUNK)); then one
+ * 256-byte line: error word (int32 at +0), call counter (uint64 at +8), workgroup ticket (uint32 at +16).
+ * Protocol, per call: seq = counter + 1, read on the device; half = seq & 1.  Every push workgroup copies one chunk of
+ * FTN_ROWX_CHUNK floats into slot `rank` of one destination, releases at system scope and stores seq into the
+ * destination's word [rank][chunk].  The consumer waits (bounded) for the words its chunks need, reads the slots, and
+ * its last workgroup stores counter = seq.  A consumer that does not see a word within ~2 s sets the error word and
+ * writes NaN rows (the heads' finite check then raises), so a lost peer never becomes plausible numbers.
+ * Two halves suffice: on every rank the consumer of call n-1 runs before the push of call n (stream order).  A rank's
+ * push of call n+1 into half (n+1) & 1 = (n-1) & 1 of rank q therefore follows its own consumer of call n, which
+ * waited for rank q's push of call n, which rank q enqueued after its consumer of call n-1 - the last reader of that
+ * half.  Every rank that made the same calls, eagerly or replayed from a graph, uses the same seq. */
+#define FTN_ROWX_CHUNK 16384
+typedef struct FtnRowExchange {
+  void* slots[FTN_XCHG_MAXWORLD];
+  int32_t world, rank;
+  int32_t rows_per_rank, width;
+  int32_t kind;
+  int32_t reserved;
+} FtnRowExchange;
+/* bytes of one rank's row buffer; 0 on a bad argument (world 1..16, rows_per_rank >= 1, width >= 4 and % 4 == 0,
+ * rows_per_rank * width <= 2^28) */
+size_t ftn_rowx_bytes(int world, int rows_per_rank, int width);
+/* this rank's buffer on the current device: uncached device memory, zeroed; an error (not plain hipMalloc) when the
+ * runtime cannot allocate it.  handle64_out: its 64-byte hipIpcMemHandle_t for the other ranks' ftn_rowx_open. */
+int ftn_rowx_alloc(int world, int rows_per_rank, int width, void** buf_out, void* handle64_out);
+int ftn_rowx_open(const void* handle64, void** mapped_out);
+int ftn_rowx_close(void* mapped);
+int ftn_rowx_free(void* buf);
+/* host-side reads (synchronise the stream): the error word (0 = ok, 1 = a peer timed out) and the call counter */
+int ftn_rowx_error(const FtnRowExchange* xch, void* stream);
+int64_t ftn_rowx_calls(const FtnRowExchange* xch, void* stream);
+/* push this rank's rows (src_dev fp32, 16-byte aligned; [W*R][width] for kind 0, [R][width] for kind 1) */
+int ftn_rowx_push(const float* src_dev, const FtnRowExchange* xch, void* stream);
+/* kind 0 consumer: out[R][L][D] = sum over ranks s = 0..W-1 (in that order) of slot s, + add (optional: [L][D] with
+ * add_bstride 0 or [R][L][D] with add_bstride L*D), then LayerNorm over D when ln_gamma / ln_beta are given.
+ * width must be L*D; D a multiple of 4, <= 128; out / add / gamma / beta 16-byte aligned. */
+int ftn_rowx_reduce(const FtnRowExchange* xch, int L, int D, const float* add_dev_or_null, long long add_bstride,
+                    const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null, float ln_eps, float* out_dev,
+                    void* stream);
+/* kind 1 consumer: out[W*R][width], row block s = the rows rank s pushed (16-byte aligned) */
+int ftn_rowx_gather(const FtnRowExchange* xch, float* out_dev, void* stream);
 
 /* ---- period selector: FFTPeriodSelector.forward (:64-159) ------------------- */
 /* bytes of the DFT twiddle table for window length L */
