@@ -102,7 +102,6 @@ struct MlpPosArgs {
   const float* wts;      // [B][FTN_KMAX] softmax group weights w[b,g] (finalize kernel)
   float* outRs;          // [B*L][CP]: sum_g w[b,g] (res2(g_g) + b_res2)   (x NOT subtracted: OutArgs.r_summed)
   int n_main, n_tail;    // blocks [0, n_main) own window positions, [n_main, n_main + n_tail) the tail pixels
-  int abl;               // timing ablations (FTN_MLP_POS_ABL; results wrong): 1 = no weight refill / chunk barriers after chunk 0
 };
 
 // position-major stage C of the d_model-64 shape (stagec_pos.hip); act 0 GELU / 1 ReLU, nsplit = activation pieces

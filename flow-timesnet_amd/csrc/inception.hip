@@ -41,9 +41,6 @@ static int g_stamp_which = 0;  // 1: k_conv, 2: k_mlp
 static const bool g_conv_generic = [] { const char* e = getenv("FTN_CONV_GENERIC"); return e != nullptr && e[0] == '1'; }();  // experiment switch
 static const bool g_mlp_split = [] { const char* e = getenv("FTN_MLP_SPLIT"); return e == nullptr || e[0] != '0'; }();   // split refill (default on)
 static const bool g_r_keeps_x = [] { const char* e = getenv("FTN_R_KEEPS_X"); return e == nullptr || e[0] != '0'; }();   // stage C leaves x inside R (default on)
-static const bool g_mlp_pfd2 = [] { const char* e = getenv("FTN_MLP_PFD"); return e != nullptr && e[0] == '2'; }();   // experiment: fragment reads two steps ahead
-static const bool g_mlp_w16 = [] { const char* e = getenv("FTN_MLP_W16"); return e != nullptr && e[0] == '1'; }();   // experiment: 16-wave double-buffered k_mlp_bf_u1
-static const bool g_mlp_w4 = [] { const char* e = getenv("FTN_MLP_W4"); return e != nullptr && e[0] == '1'; }();     // experiment: 4-wave workgroups, three per CU
 static const bool g_mlp_u1 = [] { const char* e = getenv("FTN_MLP_U1"); return e == nullptr || e[0] != '0'; }();    // 0: the two-unit k_mlp_bf
 __device__ __forceinline__ void stamp(unsigned long long* buf, size_t cap, size_t wg, int slot) {
   if (buf != nullptr && threadIdx.x == 0 && (wg * 8 + slot) < cap) buf[wg * 8 + slot] = __builtin_amdgcn_s_memtime();
@@ -587,15 +584,14 @@ __global__ __launch_bounds__(256, (NPX >= 3 ? 2 : 1)) void k_mlp(MlpArgs a) {
 // (m: P3 rows written by the conv; x: split on load) are preloaded once; after the two
 // GELUs the fp32 hidden accumulators of a 32-channel chunk (two row tiles) are split into
 // pieces in registers and become the B operand of the output projection (the host packs
-// the projection's K order to match the accumulator lane map).  512-thread workgroups
-// (256 pixels) share each chunk's weight fragments, DMA-staged and double-buffered.
-// NW = waves per workgroup.  NW = 8: one 256-pixel workgroup per CU, chunk weights double-buffered.
-// NW = 4: 128-pixel workgroups with a single weight buffer (2 x 66 KB would not fit twice), two per CU:
+// the projection's K order to match the accumulator lane map).  The waves of a workgroup share
+// each chunk's weight fragments, DMA-staged into LDS.
+// 4-wave 128-pixel workgroups with a single weight buffer (2 x 66 KB would not fit twice), two per CU:
 // VALU and MFMA work of a SIMD serialise on gfx950 (tools/ubench/mfma_valu.hip), so what a second
 // workgroup buys is cover for the first one's prologue loads, chunk barriers, DMA waits and stores.
-template <int ACT, bool XVEC, int OTM, bool EXACT, int NS, int NW>
-__global__ __launch_bounds__(NW * 64, 2) void k_mlp_bf(MlpBfArgs a) {
-  constexpr int NPX = 2;
+template <int ACT, bool XVEC, int OTM, bool EXACT, int NS>
+__global__ __launch_bounds__(256, 2) void k_mlp_bf(MlpBfArgs a) {
+  constexpr int NW = 4, NPX = 2;
   extern __shared__ __attribute__((aligned(16))) char wlb[];
   const FtnDesc* __restrict__ d = a.desc;
   const int N = a.B * d->total_px;
@@ -606,15 +602,14 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mlp_bf(MlpBfArgs a) {
   const int n0 = (blockIdx.x * NW + wave) * (16 * NPX);
   const bool active = n0 < N;
   const int bufsz = a.per_chunk * 3 * 1024;
-  // fragments [f_lo, f_hi) of chunk hc -> the same slots of buffer `buf`
-  auto dma_frags = [&](int hc, int buf, int f_lo, int f_hi) {
+  // the fragments of chunk hc -> the weight buffer
+  auto dma_chunk = [&](int hc) {
     const __bf16* __restrict__ src = a.cfrag + (size_t)hc * a.per_chunk * 3 * 512;
-    for (int piece = 3 * f_lo + wv; piece < 3 * f_hi; piece += NW)
+    for (int piece = wv; piece < 3 * a.per_chunk; piece += NW)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)piece * 512 + lane * 8),
-                                       (__attribute__((address_space(3))) void*)(wlb + (size_t)buf * bufsz + (size_t)piece * 1024),
+                                       (__attribute__((address_space(3))) void*)(wlb + (size_t)piece * 1024),
                                        16, 0, 0);
   };
-  auto dma_chunk = [&](int hc, int buf) { dma_frags(hc, buf, 0, a.per_chunk); };
   // Prologue order matters: vmcnt retires in order, so whatever is issued before the pixel loads is
   // waited for with them.  Decode first (scalar loads only), then this wave's m / x rows, and only then
   // the chunk-0 weight DMA and the bias staging, which are not needed before the first barrier.
@@ -643,11 +638,10 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mlp_bf(MlpBfArgs a) {
     }
   }
   __builtin_amdgcn_sched_barrier(0);
-  dma_chunk(0, 0);
+  dma_chunk(0);
   // biases of both hidden layers, zero-padded to whole chunks, in LDS behind the weight buffers
   const int FPc = a.n_hchunks * 32;
-  constexpr int NBUF = NW == 8 ? 2 : 1;
-  float* __restrict__ bias_l = (float*)(wlb + NBUF * (size_t)bufsz);
+  float* __restrict__ bias_l = (float*)(wlb + (size_t)bufsz);
   for (int i = threadIdx.x; i < 2 * FPc; i += NW * 64) {
     const int c = i < FPc ? i : i - FPc;
     bias_l[i] = c < a.FP ? (i < FPc ? a.bo[c] : a.br[c]) : 0.f;
@@ -685,11 +679,8 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mlp_bf(MlpBfArgs a) {
   stamp(a.dbg, a.dbg_cap, blockIdx.x, 1);
   for (int hc = 0; hc < a.n_hchunks; ++hc) {
     if (hc == 1) stamp(a.dbg, a.dbg_cap, blockIdx.x, 2);
-    const char* __restrict__ wl = wlb + (size_t)(NBUF == 2 ? (hc & 1) : 0) * bufsz + lane * 16;
-    // request the next chunk right away: its buffer was last read before the barrier that
-    // opened this chunk, and nothing below waits on vmcnt until the closing barrier.  The
-    // biases come from LDS (staged once in the prologue), not from global memory.
-    if (NBUF == 2 && hc + 1 < a.n_hchunks) dma_chunk(hc + 1, (hc + 1) & 1);
+    const char* __restrict__ wl = wlb + lane * 16;
+    // the biases come from LDS (staged once in the prologue), not from global memory
     f4 bo_t[2], br_t[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -796,10 +787,10 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mlp_bf(MlpBfArgs a) {
     if (hc == 1 && a.dbg) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp(a.dbg, a.dbg_cap, blockIdx.x, 5); }
     __syncthreads();
     if (hc == 1) stamp(a.dbg, a.dbg_cap, blockIdx.x, 4);
-    if (NBUF == 1 && hc + 1 < a.n_hchunks) {
+    if (hc + 1 < a.n_hchunks) {
       // single buffer: refill once every wave has left the chunk.  (Refilling in halves behind a
       // mid-chunk barrier hides the DMA but costs more in barrier skew than it saves: measured +5 %.)
-      dma_chunk(hc + 1, 0);
+      dma_chunk(hc + 1);
       __syncthreads();
     }
     if (hc == 1) stamp(a.dbg, a.dbg_cap, blockIdx.x, 6);
@@ -838,18 +829,12 @@ __global__ __launch_bounds__(NW * 64, 2) void k_mlp_bf(MlpBfArgs a) {
 // SKM / SCP = K=32 slabs of layer 1 / of the residual, OTM = output tiles: <3, 4, 14> is that shape; <2, 2, 7> is
 // d_model 64 with three kernels of mid 16 (48 -> 64 K padding), where the smaller register footprint lets two
 // 8-wave workgroups = four waves per SIMD share a CU (the two-unit k_mlp_bf above runs two).
-// NWV = 8 (default): two single-buffered 128-pixel workgroups per CU.  The other launch shapes are kept as measured
-// experiments: NWV = 16 (FTN_MLP_W16=1) = one 256-pixel workgroup per CU with the chunk weights
-// DOUBLE-buffered - half the L2 -> LDS weight stream (1.2 GB per launch at the bench shape otherwise) and no exposed
-// refill, yet slower (276 vs 248 us: sixteen waves coupled by one barrier run their MFMA and GELU phases in step);
-// NWV = 4 (FTN_MLP_W4=1) = three 64-pixel workgroups per CU, twice the weight stream, the same time.
-// PFD = fragment reads issued PFD steps ahead of their MFMAs (FTN_MLP_PFD=2: no gain - the waves do not wait on LDS).
-template <int ACT, bool XVEC, int NS, int SKM, int SCP, int OTM, int NWV, int PFD = 1, bool SPLIT = false>
-__global__ __launch_bounds__(NWV * 64, NWV == 16 ? 1 : (NWV == 4 ? 3 : 2)) void k_mlp_bf_u1(MlpBfArgs a) {
+// Two single-buffered 128-pixel workgroups per CU (other launch shapes measured slower: DESIGN.md section 4).
+template <int ACT, bool XVEC, int NS, int SKM, int SCP, int OTM, bool SPLIT = false>
+__global__ __launch_bounds__(512, 2) void k_mlp_bf_u1(MlpBfArgs a) {
+  constexpr int NWV = 8;
   constexpr int NFR = 2 * SKM + 2 * SCP + OTM;
   constexpr int NL1 = 2 * SKM + 2 * SCP;        // fragments of layer 1 (+ residual); the other OTM are layer 2's
-  constexpr int NBUF = NWV == 16 ? 2 : 1;
-  static_assert(!SPLIT || (NBUF == 1 && PFD == 1), "SPLIT is the single-buffer, one-ahead form");
   extern __shared__ __attribute__((aligned(16))) char wlb[];
   const FtnDesc* __restrict__ d = a.desc;
   const int N = a.B * d->total_px;
@@ -861,10 +846,9 @@ __global__ __launch_bounds__(NWV * 64, NWV == 16 ? 1 : (NWV == 4 ? 3 : 2)) void 
   const int bufsz = NFR * 3 * 1024;
   auto dma_chunk = [&](int hc) {
     const __bf16* __restrict__ src = a.cfrag + (size_t)hc * NFR * 3 * 512;
-    char* dst = wlb + (size_t)(NBUF == 2 ? (hc & 1) : 0) * bufsz;
     for (int piece = wv; piece < NFR * 3; piece += NWV)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)piece * 512 + lane * 8),
-                                       (__attribute__((address_space(3))) void*)(dst + (size_t)piece * 1024), 16, 0, 0);
+                                       (__attribute__((address_space(3))) void*)(wlb + (size_t)piece * 1024), 16, 0, 0);
   };
   // SPLIT: LDS = [layer-1 fragments, two buffers][layer-2 fragments, one buffer][biases].  A chunk's layer-2 fragments
   // and the NEXT chunk's layer-1 fragments are requested at the top of the chunk and land while layer 1 runs; the
@@ -910,7 +894,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 16 ? 1 : (NWV == 4 ? 3 : 2)) void 
   if (SPLIT) dma_l1(0, 0);
   else dma_chunk(0);
   const int FPc = a.n_hchunks * 32;
-  float* __restrict__ bias_l = (float*)(wlb + (SPLIT ? (size_t)(2 * l1sz + l2sz) : (size_t)NBUF * bufsz));
+  float* __restrict__ bias_l = (float*)(wlb + (SPLIT ? (size_t)(2 * l1sz + l2sz) : (size_t)bufsz));
   for (int i = threadIdx.x; i < 2 * FPc; i += NWV * 64) {
     const int c = i < FPc ? i : i - FPc;
     bias_l[i] = c < a.FP ? (i < FPc ? a.bo[c] : a.br[c]) : 0.f;
@@ -996,9 +980,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 16 ? 1 : (NWV == 4 ? 3 : 2)) void 
     }
   } else
   for (int hc = 0; hc < a.n_hchunks; ++hc) {
-    const char* __restrict__ wl = wlb + (size_t)(NBUF == 2 ? (hc & 1) : 0) * bufsz + lane * 16;
-    // double-buffered: the other buffer was last read in chunk hc - 1, which every wave left at the barrier
-    if (NBUF == 2 && hc + 1 < a.n_hchunks) dma_chunk(hc + 1);
+    const char* __restrict__ wl = wlb + lane * 16;
     f4 bo_t[2], br_t[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -1008,21 +990,17 @@ __global__ __launch_bounds__(NWV * 64, NWV == 16 ? 1 : (NWV == 4 ? 3 : 2)) void 
     if (active) {
       f4 h[2] = {bo_t[0], bo_t[1]};
       bf8 hp[NS];
-      // fragment reads run PFD steps ahead of their MFMAs in a ring of PFD + 1 register sets (PFD = 2 where the
-      // registers allow): one step (3 MFMAs + its share of the GELUs) is shorter than an LDS read's latency when
-      // sixteen waves stream fragments at once
-      bf8 fr[PFD + 1][NWP];
+      bf8 fr[2][NWP];                                  // fragment reads run one step ahead of their MFMAs
       auto ldfrag = [&](int f, bf8 (&ap)[NWP]) {
 #pragma unroll
         for (int pz = 0; pz < NWP; ++pz) ap[pz] = *(const bf8*)(wl + (size_t)(f * 3 + pz) * 1024);
       };
-#pragma unroll
-      for (int f = 0; f < PFD; ++f) ldfrag(f, fr[f]);
+      ldfrag(0, fr[0]);
 #pragma unroll
       for (int f = 0; f < NFR; ++f) {
-        if (f + PFD < NFR) ldfrag(f + PFD, fr[(f + PFD) % (PFD + 1)]);
+        if (f + 1 < NFR) ldfrag(f + 1, fr[(f + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
-        const bf8 (&cur)[NWP] = fr[f % (PFD + 1)];
+        const bf8 (&cur)[NWP] = fr[f & 1];
         if (f < SKM) h[0] = chain_bf<NS>(cur, mp[f], h[0]);                         // layer 1, hidden tile 0
         else if (f < 2 * SKM) h[1] = chain_bf<NS>(cur, mp[f - SKM], h[1]);          // layer 1, hidden tile 1
         else if (f < 2 * SKM + SCP) h[0] = chain_bf<NS>(cur, xp[f - 2 * SKM], h[0]);               // + res1(x)
@@ -1043,7 +1021,7 @@ __global__ __launch_bounds__(NWV * 64, NWV == 16 ? 1 : (NWV == 4 ? 3 : 2)) void 
       }
     }
     __syncthreads();
-    if (NBUF == 1 && hc + 1 < a.n_hchunks) {
+    if (hc + 1 < a.n_hchunks) {
       dma_chunk(hc + 1);
       __syncthreads();
     }
@@ -1067,37 +1045,29 @@ __global__ __launch_bounds__(NWV * 64, NWV == 16 ? 1 : (NWV == 4 ? 3 : 2)) void 
   }
 }
 
-template <int ACT, int NS, int SKM, int SCP, int OTM, int NWV, int PFD = 1, bool SPLIT = false>
+template <int ACT, int NS, int SKM, int SCP, int OTM, bool SPLIT = false>
 static int launch_mlp_bf_u1w(MlpBfArgs ma, bool xvec, long long Nmax, hipStream_t st) {
   ma.dbg = nullptr; ma.dbg_cap = 0;
   const size_t lds = (SPLIT ? (size_t)(2 * (2 * SKM + 2 * SCP) + OTM) * 3 * 1024
-                            : (size_t)ma.per_chunk * 3 * 1024 * (NWV == 16 ? 2 : 1)) + (size_t)ma.n_hchunks * 32 * 2 * sizeof(float);
+                            : (size_t)ma.per_chunk * 3 * 1024) + (size_t)ma.n_hchunks * 32 * 2 * sizeof(float);
   if (lds > 160 * 1024) { ftn_set_error("stage C needs %zu B of LDS", lds); return -1; }
-  const int nblk = (int)((Nmax + NWV * 16 - 1) / (NWV * 16));
-  hipError_t e = xvec ? hipFuncSetAttribute((const void*)k_mlp_bf_u1<ACT, true, NS, SKM, SCP, OTM, NWV, PFD, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                      : hipFuncSetAttribute((const void*)k_mlp_bf_u1<ACT, false, NS, SKM, SCP, OTM, NWV, PFD, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  const int nblk = (int)((Nmax + 8 * 16 - 1) / (8 * 16));
+  hipError_t e = xvec ? hipFuncSetAttribute((const void*)k_mlp_bf_u1<ACT, true, NS, SKM, SCP, OTM, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                      : hipFuncSetAttribute((const void*)k_mlp_bf_u1<ACT, false, NS, SKM, SCP, OTM, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute(k_mlp_bf_u1): %s", hipGetErrorString(e)); return (int)e; }
-  if (xvec) hipLaunchKernelGGL((k_mlp_bf_u1<ACT, true, NS, SKM, SCP, OTM, NWV, PFD, SPLIT>), dim3(nblk), dim3(NWV * 64), lds, st, ma);
-  else hipLaunchKernelGGL((k_mlp_bf_u1<ACT, false, NS, SKM, SCP, OTM, NWV, PFD, SPLIT>), dim3(nblk), dim3(NWV * 64), lds, st, ma);
+  if (xvec) hipLaunchKernelGGL((k_mlp_bf_u1<ACT, true, NS, SKM, SCP, OTM, SPLIT>), dim3(nblk), dim3(512), lds, st, ma);
+  else hipLaunchKernelGGL((k_mlp_bf_u1<ACT, false, NS, SKM, SCP, OTM, SPLIT>), dim3(nblk), dim3(512), lds, st, ma);
   FTN_CHECK_LAUNCH();
   return 0;
 }
 
 template <int ACT, int NS, int SKM, int SCP, int OTM>
 static int launch_mlp_bf_u1(const MlpBfArgs& ma, bool xvec, long long Nmax, hipStream_t st) {
-  // 16-wave double-buffered form where two chunk buffers fit LDS (d_model 64: 2 x 45 KB) unless FTN_MLP_W16=0
-  if (g_mlp_w16 && (size_t)ma.per_chunk * 3 * 1024 * 2 + (size_t)ma.n_hchunks * 256 <= 160 * 1024)
-    return launch_mlp_bf_u1w<ACT, NS, SKM, SCP, OTM, 16>(ma, xvec, Nmax, st);
-  if (g_mlp_w4 && ((size_t)ma.per_chunk * 3 * 1024 + (size_t)ma.n_hchunks * 256) * 3 <= 160 * 1024)
-    return launch_mlp_bf_u1w<ACT, NS, SKM, SCP, OTM, 4>(ma, xvec, Nmax, st);
-  if constexpr (NS == 2 && OTM <= 7) {
-    if (g_mlp_pfd2) return launch_mlp_bf_u1w<ACT, NS, SKM, SCP, OTM, 8, 2>(ma, xvec, Nmax, st);
-  }
-  // default: split refill where two workgroups' LDS still fit a CU (or, for the d_model-128 shape, one does)
+  // split refill where two workgroups' LDS still fit a CU (or, for the d_model-128 shape, one does)
   if (g_mlp_split && ma.per_chunk == 2 * SKM + 2 * SCP + OTM &&
       (size_t)(2 * (2 * SKM + 2 * SCP) + OTM) * 3 * 1024 + (size_t)ma.n_hchunks * 256 <= (OTM <= 7 ? 80 : 160) * 1024)
-    return launch_mlp_bf_u1w<ACT, NS, SKM, SCP, OTM, 8, 1, true>(ma, xvec, Nmax, st);
-  return launch_mlp_bf_u1w<ACT, NS, SKM, SCP, OTM, 8>(ma, xvec, Nmax, st);
+    return launch_mlp_bf_u1w<ACT, NS, SKM, SCP, OTM, true>(ma, xvec, Nmax, st);
+  return launch_mlp_bf_u1w<ACT, NS, SKM, SCP, OTM>(ma, xvec, Nmax, st);
 }
 
 template <int ACT, int NS>
@@ -1368,8 +1338,6 @@ struct ConvBfArgs {
   int wg_off[2 * FTN_MAXBR + 1];   // k_conv_bf_fast: workgroups [wg_off[v], wg_off[v+1]) serve virtual branch v = branch * (cout / 16) + output tile
   int nvb;               // virtual branches of the fast path: nbr * (cout / 16)
   int* range_flag;       // f16x2 piece output (out_p3): set when an output leaves the fp16 range; may be null
-  int abl;               // timing ablations of k_conv_bf_fast (FTN_CONV_ABL; results wrong): 1 no output stores, 2 no region
-                         // DMA after a tile's first row, 4 no barrier after a tile's first row, 8 no MFMA work
   unsigned long long* dbg; size_t dbg_cap;
 };
 
@@ -1901,28 +1869,24 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
       // (rolled: one copy of the unrolled slab loops)
 #pragma unroll 1
       for (int gi = 0; gi < NCI; ++gi) {
-        if (!((a.abl & 4) && (b > b_begin || gi > 0))) barrier_keep_vm(keep);   // this item (and, the first time, the weights) have landed
+        barrier_keep_vm(keep);                                // this item (and, the first time, the weights) have landed
         keep = gi == NCI - 1 ? __builtin_amdgcn_readfirstlane(nst_row) : 0;   // stores only follow a row's last group
         if (gi == 0) {
           if (b == b_begin) stamp(a.dbg, a.dbg_cap, wgid, 1);
           if (b == b_begin + 1) stamp(a.dbg, a.dbg_cap, wgid, 2);
         }
-        if (!(a.abl & 2)) {
-          if (gi + 1 < NCI) dma_region(b, gi + 1, (it + 1) & 1);
-          else if (b + 1 < b_end) dma_region(b + 1, 0, (it + 1) & 1);
-        }
-        const char* __restrict__ reg = rbuf0 + (size_t)((a.abl & 2) ? 0 : (it & 1)) * a.region_bytes;
+        if (gi + 1 < NCI) dma_region(b, gi + 1, (it + 1) & 1);
+        else if (b + 1 < b_end) dma_region(b + 1, 0, (it + 1) & 1);
+        const char* __restrict__ reg = rbuf0 + (size_t)(it & 1) * a.region_bytes;
         ++it;
         const char* __restrict__ wg_ = wlane + (size_t)gi * S * WSTR * 1024;
-        if (a.abl & 8) {}
-        else if (kw == 7) conv_fast_row<NS, 7, 7>(acc, reg, wg_, ld, vmask, RW * CBF_PX_BYTES, h1 != 0);
+        if (kw == 7) conv_fast_row<NS, 7, 7>(acc, reg, wg_, ld, vmask, RW * CBF_PX_BYTES, h1 != 0);
         else if (kw == 5) conv_fast_row<NS, 5, 5>(acc, reg, wg_, ld, vmask, RW * CBF_PX_BYTES, h1 != 0);
         else conv_fast_row<NS, 3, 3>(acc, reg, wg_, ld, vmask, RW * CBF_PX_BYTES, h1 != 0);
       }
       // uniform row base + per-lane offsets fixed for the tile (ooff)
       const size_t nimg = img0 + (size_t)b * P;
-      if ((a.abl & 1) && acc[0][0] != 12345.678f) {}
-      else if (a.out_p3) {
+      if (a.out_p3) {
         __bf16* __restrict__ ob = (__bf16*)a.out + nimg * (size_t)(a.OUTC >> 4) * PXE;
 #pragma unroll
         for (int u = 0; u < CBF_NU; ++u)
@@ -2542,8 +2506,6 @@ static int launch_conv_bf(ConvBfArgs& ca, const ConvBfGeom& gm, int B, int grid_
   ca.wbytes = gm.wbytes;
   ca.sgroup = gm.sgroup;
   ca.dbg = ((g_stamp_which & 1) && (!(g_stamp_which & 4) || ca.bt_L > 0)) ? g_stamp_buf : nullptr; ca.dbg_cap = g_stamp_cap;   // which & 4: stage B only
-  static const int conv_abl = [] { const char* e = getenv("FTN_CONV_ABL"); return e ? atoi(e) : 0; }();
-  ca.abl = conv_abl;
   // batch rows per (persistent) workgroup: as many as still leave ~2 workgroups per CU in the launch - each
   // staging of a tile's weights and pixel bookkeeping is shared by the rows (8 rows: -3 % against 4 at B = 256)
   ca.bpw = 1;
@@ -2671,25 +2633,19 @@ static int launch_mlp(const MlpArgs& ma, bool xvec, long long Nmax, hipStream_t 
   return xvec ? launch_mlp_x<ACT, true>(ma, Nmax, st) : launch_mlp_x<ACT, false>(ma, Nmax, st);
 }
 
-template <int ACT, bool XVEC, int OTM, bool EXACT, int NS, int NW>
-static int launch_mlp_bf_w(MlpBfArgs ma, long long Nmax, hipStream_t st) {
+template <int ACT, bool XVEC, int OTM, bool EXACT, int NS>
+static int launch_mlp_bf_t(MlpBfArgs ma, long long Nmax, hipStream_t st) {
+  // 4-wave workgroups, two per CU (an 8-wave double-buffered form measured 425 us against 360 us at the bench shape)
   ma.dbg = (g_stamp_which & 2) ? g_stamp_buf : nullptr; ma.dbg_cap = g_stamp_cap;
-  const size_t lds = (size_t)ma.per_chunk * 3 * 1024 * (NW == 8 ? 2 : 1) + (size_t)ma.n_hchunks * 32 * 2 * sizeof(float);
-  hipError_t e = hipFuncSetAttribute((const void*)k_mlp_bf<ACT, XVEC, OTM, EXACT, NS, NW>,
+  const size_t lds = (size_t)ma.per_chunk * 3 * 1024 + (size_t)ma.n_hchunks * 32 * 2 * sizeof(float);
+  hipError_t e = hipFuncSetAttribute((const void*)k_mlp_bf<ACT, XVEC, OTM, EXACT, NS>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute(k_mlp_bf): %s", hipGetErrorString(e)); return (int)e; }
-  const int px_wg = NW * 32;
+  const int px_wg = 4 * 32;
   const int nblk = (int)((Nmax + px_wg - 1) / px_wg);
-  hipLaunchKernelGGL((k_mlp_bf<ACT, XVEC, OTM, EXACT, NS, NW>), dim3(nblk), dim3(NW * 64), lds, st, ma);
+  hipLaunchKernelGGL((k_mlp_bf<ACT, XVEC, OTM, EXACT, NS>), dim3(nblk), dim3(256), lds, st, ma);
   FTN_CHECK_LAUNCH();
   return 0;
-}
-
-template <int ACT, bool XVEC, int OTM, bool EXACT, int NS>
-static int launch_mlp_bf_t(const MlpBfArgs& ma, long long Nmax, hipStream_t st) {
-  // 4-wave workgroups, two per CU (the 8-wave double-buffered form is kept in the kernel template:
-  // 425 us against 360 us at the bench shape)
-  return launch_mlp_bf_w<ACT, XVEC, OTM, EXACT, NS, 4>(ma, Nmax, st);
 }
 
 template <int ACT, int NS>

@@ -253,7 +253,7 @@ __device__ __forceinline__ void wave_lower_median_rows(const float* __restrict__
 
 __global__ __launch_bounds__(256) void k_spectrum(const float* __restrict__ x, int B, int L, int C,
                                                   const float* __restrict__ tab, int F, int FPAD,
-                                                  float* __restrict__ med, int flat) {
+                                                  float* __restrict__ med) {
   extern __shared__ __attribute__((aligned(16))) float amp[];  // [32][CS]
   const int CS = C + 1;
   // Workgroup -> (batch row, 32-bin block).  Workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8),
@@ -262,9 +262,9 @@ __global__ __launch_bounds__(256) void k_spectrum(const float* __restrict__ x, i
   // XCDs and fetched it six times).  Speed only: any mapping is correct.
   const int nfb = FPAD >> 5;
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int b = flat ? (int)blockIdx.x / nfb : (slot / nfb) * 8 + xcd;
+  const int b = (slot / nfb) * 8 + xcd;
   if (b >= B) return;
-  const int f0 = (flat ? (int)blockIdx.x % nfb : slot % nfb) * 32;
+  const int f0 = (slot % nfb) * 32;
   const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int i = lane & 31, h = lane >> 5;
   const float* __restrict__ xb = x + (size_t)b * L * C;
@@ -1008,7 +1008,7 @@ extern "C" int ftn_period_spectrum(const float* x_dev, int B, int L, int C, cons
                        (const float*)table_dev, F, FPAD, med_dev);
   } else {
     hipLaunchKernelGGL(k_spectrum, dim3((unsigned)(ftn_cdiv(B, 8) * 8 * nfb)), dim3(64 * nw), lds, (hipStream_t)stream, x_dev,
-                       B, L, C, (const float*)table_dev, F, FPAD, med_dev, getenv("FTN_SEL_FLAT") != nullptr ? 1 : 0);
+                       B, L, C, (const float*)table_dev, F, FPAD, med_dev);
   }
   FTN_CHECK_LAUNCH();
   XchArgs xa = {};

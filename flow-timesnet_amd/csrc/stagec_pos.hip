@@ -23,7 +23,7 @@ __device__ __forceinline__ void wait_vm_keep(int n) {
 // PF: every weight fragment is requested from LDS one fragment ahead of its use (two fragment buffers) and the res2
 // accumulators wait in a wave-private LDS slab between chunks, which is where the second buffer's registers come from.
 // Without it hipcc, at 254 registers, emits read -> wait -> 3 MFMAs per fragment: 43 exposed LDS round trips per chunk.
-template <int ACT, bool XVEC, int NS, int SKM, int SCP, int NOA, int NOR, int NWV, int GB, int NBUF, int PF>
+template <int ACT, bool XVEC, int NS, int SKM, int SCP, int NOA, int NOR, int NWV, int GB, int PF>
 __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
   const MlpBfArgs& a = pa.c;
   constexpr int NL1 = 2 * SKM + 2 * SCP, NFR = NL1 + NOA + NOR;
@@ -53,19 +53,18 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
   const bool ok_m = active_m && t0m + j < L;
   const int tcm = t0m + j < L ? t0m + j : L - 1;
 
-  auto dma_chunk = [&](int hc, int buf) {
+  auto dma_chunk = [&](int hc) {
     const __bf16* __restrict__ src = a.cfrag + (size_t)hc * NFR * 3 * 512;
-    char* dst = wlb + (size_t)buf * bufsz;
     for (int piece = wv; piece < NFR * 3; piece += NWV)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)piece * 512 + lane * 8),
-                                       (__attribute__((address_space(3))) void*)(dst + (size_t)piece * 1024), 16, 0, 0);
+                                       (__attribute__((address_space(3))) void*)(wlb + (size_t)piece * 1024), 16, 0, 0);
   };
   // ---- prologue, ordered for latency (it was 13 % of a workgroup's life as load -> wait -> store chains): every
   // global load is issued before anything waits - x rows, this batch row's group weights as one fixed-trip batch
   // (selects instead of a data-dependent loop), then LDS is filled.  The hidden-layer biases are not staged at all:
   // a chunk reads its 2 x 2 bias tiles straight from L2 while it waits for its weights.
   const int kmg = a.KM >> 4;
-  char* __restrict__ xl = wlb + (size_t)NBUF * bufsz + (size_t)wave * (SCP * NS * 1024) + lane * 16;
+  char* __restrict__ xl = wlb + (size_t)bufsz + (size_t)wave * (SCP * NS * 1024) + lane * 16;
   bool range_bad = false;                                       // f16x2: a value left the fp16 range (ftn_common.h)
   f4 xr[SCP][2];
   {
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
   }
   f4 racc[NOR];
   // (PF: the accumulators live in this wave's LDS slab, [NOR][64 lanes] f4, between their once-per-chunk updates)
-  char* __restrict__ rl = wlb + (size_t)NBUF * bufsz + (size_t)NWV * (SCP * NS * 1024) + (size_t)wave * (NOR * 1024) + lane * 16;
+  char* __restrict__ rl = wlb + (size_t)bufsz + (size_t)NWV * (SCP * NS * 1024) + (size_t)wave * (NOR * 1024) + lane * 16;
 #pragma unroll
   for (int o = 0; o < NOR; ++o) {
     racc[o] = *(const f4*)(a.bc + 16 * (NOA + o) + 4 * qa) * wsum;
@@ -153,7 +152,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
 #pragma unroll
       for (int o = 0; o < NOA; ++o) aacc[i][o] = *(const f4*)(a.bc + 16 * o + 4 * qa);
     __builtin_amdgcn_sched_barrier(0);
-    dma_chunk(0, 0);                                            // the previous pass's closing barrier freed the buffer
+    dma_chunk(0);                                               // the previous pass's closing barrier freed the buffer
     __builtin_amdgcn_sched_barrier(0);
     bf8 mp[GB][SKM][NS];
 #pragma unroll
@@ -176,7 +175,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
     }
     __builtin_amdgcn_sched_barrier(0);
     for (int hc = 0; hc < a.n_hchunks; ++hc) {
-      const bool sync = !((pa.abl & 1) && hc > 0);
       const bool st = it == 0 && hc == 1;
       if (it == 0 && hc == 0) stamp(a.dbg, a.dbg_cap, blockIdx.x, 1);
       if (st) stamp(a.dbg, a.dbg_cap, blockIdx.x, 2);
@@ -188,19 +186,16 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
         res1[t] = tile ? *(const f4*)(a.br + 16 * (hc * 2 + t) + 4 * qa) : f4{0.f, 0.f, 0.f, 0.f};
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (NBUF == 1 && sync && hc > 0) dma_chunk(hc, 0);
-      if (sync) {
-        // chunk 0's fragments were requested BEFORE this pass's m rows (vmcnt retires in order): wait for them and
-        // leave the rows in flight - 80 KB per workgroup at ~11 B/clk/CU is 7.5 k cycles, which the first chunk's
-        // res1 and first groups now cover
-        if (hc == 0) wait_vm_keep<SKM * NS, GB * SKM * NS>(gcnt * SKM * NS);
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // (a raw barrier: __syncthreads() would drain vmcnt to zero again)
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // chunk hc has landed; every wave has left chunk hc - 1
-      }
+      if (hc > 0) dma_chunk(hc);
+      // chunk 0's fragments were requested BEFORE this pass's m rows (vmcnt retires in order): wait for them and
+      // leave the rows in flight - 80 KB per workgroup at ~11 B/clk/CU is 7.5 k cycles, which the first chunk's
+      // res1 and first groups now cover
+      if (hc == 0) wait_vm_keep<SKM * NS, GB * SKM * NS>(gcnt * SKM * NS);
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      // (a raw barrier: __syncthreads() would drain vmcnt to zero again)
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // chunk hc has landed; every wave has left chunk hc - 1
       if (st) stamp(a.dbg, a.dbg_cap, blockIdx.x, 3);
-      if (NBUF == 2 && hc + 1 < a.n_hchunks) dma_chunk(hc + 1, (hc + 1) & 1);
-      unsigned wl_off = (unsigned)((NBUF == 2 ? (hc & 1) : 0) * bufsz + lane * 16);
+      unsigned wl_off = (unsigned)(lane * 16);
       // every group re-reads the fragments from LDS: laundering the offset keeps hipcc from holding all 7 group-shared
       // fragments (84 registers) across the unrolled group loop, which spills
       auto ldfrag = [&](int f, bf8 (&ap)[NWP]) {
@@ -344,10 +339,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
         }
       }
       if (st) stamp(a.dbg, a.dbg_cap, blockIdx.x, 4);
-      if (NBUF == 1 && !((pa.abl & 1) && hc + 1 < a.n_hchunks)) __syncthreads();   // every wave is done with the single buffer
+      __syncthreads();                                           // every wave is done with the single buffer
       if (st) stamp(a.dbg, a.dbg_cap, blockIdx.x, 5);
     }
-    if (NBUF == 2) __syncthreads();                             // the next pass refills buffer 0
     if (it == 0) stamp(a.dbg, a.dbg_cap, blockIdx.x, 6);
     // ---- a'_g of this pass
     if (ok) {
@@ -376,23 +370,18 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
 }
 
 static const int g_mlp_pos = [] { const char* e = getenv("FTN_MLP_POS"); return e ? atoi(e) : 1; }();      // 0: pixel-major k_mlp_bf_u1
-static const int g_mlp_pos_nwv = [] { const char* e = getenv("FTN_MLP_POS_NWV"); return e ? atoi(e) : 0; }();   // experiment: waves per workgroup
-static const int g_mlp_pos_abl = [] { const char* e = getenv("FTN_MLP_POS_ABL"); return e ? atoi(e) : 0; }();   // timing ablations
-static const int g_mlp_pos_pf = [] { const char* e = getenv("FTN_MLP_POS_PF"); return e ? atoi(e) : 1; }();     // 0: no fragment prefetch
-static const int g_mlp_pos_gb = [] { const char* e = getenv("FTN_MLP_POS_GB"); return e ? atoi(e) : 0; }();     // experiment: groups per pass
 
-template <int ACT, bool XVEC, int NS, int SKM, int SCP, int NOA, int NOR, int NWV, int GB, int NBUF, int PF>
+template <int ACT, bool XVEC, int NS, int SKM, int SCP, int NOA, int NOR, int NWV, int GB, int PF>
 static int launch_mlp_pos_t(MlpPosArgs pa, int tail_units_bound, hipStream_t st) {
   constexpr int NFR = 2 * SKM + 2 * SCP + NOA + NOR;
-  const size_t lds = (size_t)NBUF * NFR * 3 * 1024 + (size_t)NWV * SCP * NS * 1024 + (PF == 1 ? (size_t)NWV * NOR * 1024 : 0);
+  const size_t lds = (size_t)NFR * 3 * 1024 + (size_t)NWV * SCP * NS * 1024 + (PF == 1 ? (size_t)NWV * NOR * 1024 : 0);
   if (lds > 160 * 1024) { ftn_set_error("position-major stage C needs %zu B of LDS", lds); return -1; }
   const long long units = (long long)pa.c.B * ((pa.c.L + 15) / 16);
   pa.n_main = (int)((units + NWV - 1) / NWV);
   // the tail pixels are few (pad_g < period): a fixed set of workgroups strides over them
   const int tail_wg = (tail_units_bound + NWV - 1) / NWV;
   pa.n_tail = tail_wg < 512 ? tail_wg : 512;
-  pa.abl = g_mlp_pos_abl;
-  auto kfn = k_mlp_pos<ACT, XVEC, NS, SKM, SCP, NOA, NOR, NWV, GB, NBUF, PF>;
+  auto kfn = k_mlp_pos<ACT, XVEC, NS, SKM, SCP, NOA, NOR, NWV, GB, PF>;
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute(k_mlp_pos): %s", hipGetErrorString(e)); return (int)e; }
   hipLaunchKernelGGL(kfn, dim3(pa.n_main + pa.n_tail), dim3(NWV * 64), lds, st, pa);
@@ -401,47 +390,25 @@ static int launch_mlp_pos_t(MlpPosArgs pa, int tail_units_bound, hipStream_t st)
 }
 
 // d_model-64 shape (two K slabs each, 3 + 4 output tiles).  Launch shape: two 4-wave workgroups per CU with a single
-// weight buffer each (a workgroup's exposed refill is covered by its neighbour), or for small batches 2-wave
-// workgroups so that the grid still covers the chip.
-// d_model-64 shape (two K slabs each, 3 + 4 output tiles).  Launch shape: two 4-wave workgroups per CU with a single
 // weight buffer each (a workgroup's exposed refill is covered by its neighbour); an 8-wave workgroup with two weight
-// buffers (FTN_MLP_POS_NWV=8, f16x2 only) measured 5 % slower, 2-wave workgroups 55 % slower.
+// buffers measured 5 % slower, 2-wave workgroups 55 % slower.  Groups per pass = what 256 registers hold: 5 with two
+// activation pieces (f16x2) or one (bf16), 4 with three (bf16x3).  The fragment prefetch (PF) is the f16x2 form.
 template <int ACT, int NS>
 static int launch_mlp_pos64(const MlpPosArgs& pa, bool xvec, int tail_units_bound, hipStream_t st) {
-  const int nwv = g_mlp_pos_nwv ? g_mlp_pos_nwv : 4;
-  // groups per pass = what 256 registers hold: 5 with two activation pieces (f16x2) or one (bf16), 4 with three (bf16x3)
-  constexpr int GBD = NS == 3 ? 4 : 5;
-  const int gb = g_mlp_pos_gb ? g_mlp_pos_gb : GBD;
-#define FTN_POS_CASE(W, GBV, NB, PFV)                                                                                         \
-  if (nwv == W && gb == GBV && pf == PFV)                                                                                     \
-    return xvec ? launch_mlp_pos_t<ACT, true, NS, 2, 2, 3, 4, W, GBV, NB, PFV>(pa, tail_units_bound, st)                     \
-                : launch_mlp_pos_t<ACT, false, NS, 2, 2, 3, 4, W, GBV, NB, PFV>(pa, tail_units_bound, st);
-  // fragment prefetch (template PF): the f16x2 default; FTN_MLP_POS_PF=0 the form without it
-  const int pf = (NS == 2 && nwv == 4 && gb == GBD) ? (g_mlp_pos_pf ? 1 : 0) : 0;
-  if constexpr (NS == 2) { FTN_POS_CASE(4, GBD, 1, 1) }
-  FTN_POS_CASE(4, GBD, 1, 0)
-  if constexpr (NS == 2) {
-    FTN_POS_CASE(8, GBD, 2, 0)
-    FTN_POS_CASE(4, 4, 1, 0)
-  }
-#undef FTN_POS_CASE
-  ftn_set_error("position-major stage C: no build for FTN_MLP_POS_NWV=%d FTN_MLP_POS_GB=%d", nwv, gb);
-  return -1;
+  constexpr int GB = NS == 3 ? 4 : 5, PF = NS == 2 ? 1 : 0;
+  return xvec ? launch_mlp_pos_t<ACT, true, NS, 2, 2, 3, 4, 4, GB, PF>(pa, tail_units_bound, st)
+              : launch_mlp_pos_t<ACT, false, NS, 2, 2, 3, 4, 4, GB, PF>(pa, tail_units_bound, st);
 }
 
 // d_model-128 shape (three 32-channel branches: K = 96 = three slabs, C = 128 = four slabs, 6 + 8 output tiles; f16x2).
 // 48 registers per group (m pieces 24, a' accumulators 24) + 32 for R: three groups per pass at 256 registers with 42
 // spilled (two fit without spills, but then five groups are three passes: 530 us on the c4 shard against 490 with
 // three and 500 for the pixel-major k_mlp_bf_u1); a chunk's 28 fragments are 84 KB, so ONE 8-wave workgroup per CU
-// (84 KB + 8 x 8 KB of x pieces).  FTN_MLP_POS_GB=2 selects the spill-free form.
+// (84 KB + 8 x 8 KB of x pieces).
 template <int ACT>
 static int launch_mlp_pos128(const MlpPosArgs& pa, bool xvec, int tail_units_bound, hipStream_t st) {
-  const int gb = g_mlp_pos_gb == 2 ? 2 : 3;
-  if (gb == 3)
-    return xvec ? launch_mlp_pos_t<ACT, true, 2, 3, 4, 6, 8, 8, 3, 1, 0>(pa, tail_units_bound, st)
-                : launch_mlp_pos_t<ACT, false, 2, 3, 4, 6, 8, 8, 3, 1, 0>(pa, tail_units_bound, st);
-  return xvec ? launch_mlp_pos_t<ACT, true, 2, 3, 4, 6, 8, 8, 2, 1, 0>(pa, tail_units_bound, st)
-              : launch_mlp_pos_t<ACT, false, 2, 3, 4, 6, 8, 8, 2, 1, 0>(pa, tail_units_bound, st);
+  return xvec ? launch_mlp_pos_t<ACT, true, 2, 3, 4, 6, 8, 8, 3, 0>(pa, tail_units_bound, st)
+              : launch_mlp_pos_t<ACT, false, 2, 3, 4, 6, 8, 8, 3, 0>(pa, tail_units_bound, st);
 }
 
 int ftn_launch_mlp_pos128(const MlpPosArgs& pa, int act, bool xvec, int tail_units_bound, hipStream_t st) {

@@ -15,9 +15,8 @@ SLICE = ("test_block_matches_reference and (b_c1_pipe-f16x2 or b_c2_pipe_k5-f16x
 
 
 @pytest.mark.parametrize("switch", ["FTN_MLP_SPLIT=0", "FTN_R_KEEPS_X=0", "FTN_FUSE_STAGE_A=0", "FTN_CONV_QUANT=0",
-                                    "FTN_MLP_U1=0", "FTN_MLP_W16=1", "FTN_MLP_W4=1", "FTN_MLP_PFD=2",
-                                    "FTN_CONV_GENERIC=1", "FTN_SEL_ROW=0", "FTN_SEL_ROW=1", "FTN_SEL_FLAT=1",
-                                    "FTN_MLP_POS=0", "FTN_MLP_POS_NWV=8", "FTN_MLP_POS_GB=4", "FTN_OUT_H=0", "FTN_MLP_POS_PF=0"])
+                                    "FTN_MLP_U1=0", "FTN_CONV_GENERIC=1", "FTN_SEL_ROW=0", "FTN_SEL_ROW=1",
+                                    "FTN_MLP_POS=0", "FTN_OUT_H=0"])
 def test_parity_slice_under_switch(switch):
     name, value = switch.split("=")
     env = dict(os.environ, **{name: value})
@@ -32,10 +31,10 @@ SLICE_128 = ("test_block_matches_oracle_seeded and 720-128 and f16x2 or "
              "test_awkward_geometries_match_oracle and 250-128 and f16x2")
 
 
-@pytest.mark.parametrize("switch", ["FTN_MLP_POS=0", "FTN_OUT_H=0", "FTN_CONV_GENERIC=1", "FTN_MLP_POS_GB=2", "FTN_SEL_ROW=0"])
+@pytest.mark.parametrize("switch", ["FTN_MLP_POS=0", "FTN_OUT_H=0", "FTN_CONV_GENERIC=1", "FTN_SEL_ROW=0"])
 def test_d_model_128_slice_under_switch(switch):
     """The d_model-128 forms added late in round 3 - channel-tiled selector, fast conv path for mid 32, position-major
-    stage C (three or two groups per pass), k_out_h with eight output tiles - each against the form it replaced."""
+    stage C, k_out_h with eight output tiles - each against the form it replaced."""
     name, value = switch.split("=")
     env = dict(os.environ, **{name: value})
     r = subprocess.run([sys.executable, "-m", "pytest", str(ROOT / "tests" / "test_gpu_parity.py"), "-m", "gpu", "-x", "-q",
