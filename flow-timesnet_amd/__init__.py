@@ -9,6 +9,7 @@ Sub-modules
 ``models.timesnet``  drop-in mirrors of the reference modules
 ``models.shell``     mirror of the TimesNet model shell; HIP embedding / head kernels around the blocks
 ``dist``             batch-sharded multi-GPU forward (RCCL via torch.distributed)
+``forecast``         recursive forecasting with the window state on the device (eager or one HIP graph)
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401
@@ -17,6 +18,6 @@ from . import synth  # noqa: F401
 def __getattr__(name):  # lazy: keeps `import flow_timesnet_amd.synth` torch-free
     import importlib
 
-    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph"):
+    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

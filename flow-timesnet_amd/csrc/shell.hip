@@ -1,6 +1,7 @@
 // Model-shell kernels either side of the TimesBlock stack:
 //   k_head   rate / dispersion heads of TimesNet.forward (reference models/timesnet.py:2066-2102)
 //   k_embed_in  value embedding GEMM with the low-rank temporal context folded in (:1958-1996, :1283-1325)
+//   k_embed_ring  the embedding of a sliding window from a ring of stored x W^T rows (recursive forecasting)
 // HBM-bound: each reads its input once and writes its outputs once; the small GEMMs run on the exact
 // fp32 MFMA (v_mfma_f32_16x16x4_f32) so no precision is traded.
 #include <stdlib.h>
@@ -348,55 +349,65 @@ struct EmbedArgs {
   const float* add;      // optional
   const float* ln_g;     // optional LayerNorm epilogue ("layer" mode)
   const float* ln_b;
-  float* out;            // [B][L][D]
-  long long x_bs, add_bs;
+  float* out;            // row (b, l) at out + b * out_bs + l * D
+  long long x_bs, add_bs, out_bs;
   int B, L, N, D;
   float ln_eps;
 };
+
+// + add, optional LayerNorm over one row held by the four q-lanes of a 16-row tile: lane (j, q) holds columns
+// 16*o + 4*q .. +3 of row j in v[o].  Shared by the GEMM epilogue and the ring epilogue (k_embed_ring), so that a row
+// assembled from stored x W^T plus `add` comes out bit-identical to the one-pass embedding.
+template <int NO>
+__device__ __forceinline__ void embed_row_finish(f4 (&v)[NO], const float* __restrict__ ap, const float* ln_g,
+                                                 const float* ln_b, float ln_eps, int D, int q) {
+  const float invD = 1.0f / (float)D;
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    const int cb = 16 * o + 4 * q;
+    if (ap && cb < D) v[o] = v[o] + *(const f4*)(ap + cb);      // D % 4 == 0
+  }
+  if (ln_g) {
+    float s = 0.f;
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+      if (16 * o + 4 * q < D) s += (v[o][0] + v[o][1]) + (v[o][2] + v[o][3]);
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    const float mean = s * invD;
+    float ss = 0.f;
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+      if (16 * o + 4 * q < D) {
+        const f4 dv = v[o] - mean;
+        ss += (dv[0] * dv[0] + dv[1] * dv[1]) + (dv[2] * dv[2] + dv[3] * dv[3]);
+      }
+    ss += __shfl_xor(ss, 16);
+    ss += __shfl_xor(ss, 32);
+    const float rstd = 1.0f / sqrtf(ss * invD + ln_eps);
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      const int cb = 16 * o + 4 * q;
+      if (cb < D) v[o] = (v[o] - mean) * rstd * *(const f4*)(ln_g + cb) + *(const f4*)(ln_b + cb);
+    }
+  }
+}
 
 // + add, optional LayerNorm, store.  Lane (j = row, q) holds columns cb(o) .. cb(o)+3 of its rows
 template <int RT, int NO>
 __device__ __forceinline__ void embed_epilogue(const EmbedArgs& a, f4 (&acc)[RT][NO], const long long (&rr)[RT],
                                                const bool (&rok)[RT], int q) {
-  const float invD = 1.0f / (float)a.D;
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
-    const long long b = rr[t] / a.L;
-    const float* __restrict__ ap = a.add ? a.add + b * a.add_bs + (rr[t] - b * a.L) * a.D : nullptr;
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-      const int cb = 16 * o + 4 * q;
-      if (ap && cb < a.D) acc[t][o] = acc[t][o] + *(const f4*)(ap + cb);      // D % 4 == 0
-    }
-    if (a.ln_g) {
-      float s = 0.f;
-#pragma unroll
-      for (int o = 0; o < NO; ++o)
-        if (16 * o + 4 * q < a.D) s += (acc[t][o][0] + acc[t][o][1]) + (acc[t][o][2] + acc[t][o][3]);
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      const float mean = s * invD;
-      float ss = 0.f;
-#pragma unroll
-      for (int o = 0; o < NO; ++o)
-        if (16 * o + 4 * q < a.D) {
-          const f4 dv = acc[t][o] - mean;
-          ss += (dv[0] * dv[0] + dv[1] * dv[1]) + (dv[2] * dv[2] + dv[3] * dv[3]);
-        }
-      ss += __shfl_xor(ss, 16);
-      ss += __shfl_xor(ss, 32);
-      const float rstd = 1.0f / sqrtf(ss * invD + a.ln_eps);
-#pragma unroll
-      for (int o = 0; o < NO; ++o) {
-        const int cb = 16 * o + 4 * q;
-        if (cb < a.D) acc[t][o] = (acc[t][o] - mean) * rstd * *(const f4*)(a.ln_g + cb) + *(const f4*)(a.ln_b + cb);
-      }
-    }
+    const long long b = rr[t] / a.L, l = rr[t] - b * a.L;
+    const float* __restrict__ ap = a.add ? a.add + b * a.add_bs + l * a.D : nullptr;
+    embed_row_finish<NO>(acc[t], ap, a.ln_g, a.ln_b, a.ln_eps, a.D, q);
     if (!rok[t]) continue;
+    float* __restrict__ op = a.out + b * a.out_bs + l * a.D;
 #pragma unroll
     for (int o = 0; o < NO; ++o) {
       const int cb = 16 * o + 4 * q;
-      if (cb < a.D) *(f4*)(a.out + rr[t] * a.D + cb) = acc[t][o];
+      if (cb < a.D) *(f4*)(op + cb) = acc[t][o];
     }
   }
 }
@@ -628,6 +639,12 @@ static int launch_embed(const EmbedArgs& a, bool vec, hipStream_t st) {
   return 0;
 }
 
+static int embed_launch(EmbedArgs& a, hipStream_t st) {
+  const bool vec = a.N % 4 == 0 && a.x_bs % 4 == 0 && (((uintptr_t)a.x | (uintptr_t)a.W) & 15) == 0;
+  if (a.D <= 64) return launch_embed<4>(a, vec, st);
+  return launch_embed<8>(a, vec, st);
+}
+
 extern "C" int ftn_embed_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
                                  int D, const float* add_dev_or_null, long long add_bstride,
                                  const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null, float ln_eps,
@@ -642,9 +659,99 @@ extern "C" int ftn_embed_forward(const float* x_dev, long long x_bstride, int B,
                 "ftn_embed_forward: out / add / LayerNorm parameters must be 16-byte aligned");
   EmbedArgs a;
   a.x = x_dev; a.W = w_dev; a.add = add_dev_or_null; a.ln_g = ln_gamma_dev_or_null; a.ln_b = ln_beta_dev_or_null;
-  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = ln_eps;
-  const bool vec = N % 4 == 0 && x_bstride % 4 == 0 && (((uintptr_t)x_dev | (uintptr_t)w_dev) & 15) == 0;
+  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.out_bs = (long long)L * D;
+  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = ln_eps;
+  return embed_launch(a, (hipStream_t)stream);
+}
+
+// The value-embedding GEMM alone (no add, no LayerNorm) into rows of a larger buffer: row (b, l) of x W^T lands at
+// out + b * out_bstride + l * D.  Same kernels, same form selection and same K order as ftn_embed_forward, so a row
+// comes out bit-identical to what the full-window call computes for it before its epilogue.  The recursive forecaster
+// (forecast.py) appends each step's B new rows (L = 1) to its ring of embedded rows with it.
+extern "C" int ftn_embed_rows_strided(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
+                                      int D, float* out_dev, long long out_bstride, void* stream) {
+  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "ftn_embed_rows_strided: null pointer");
+  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "ftn_embed_rows_strided: bad shape B=%d L=%d N=%d", B, L, N);
+  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "ftn_embed_rows_strided: d_model=%d must be a multiple of 4, <= 128",
+                D);
+  FTN_CHECK_ARG(B == 1 || out_bstride >= (long long)L * D, "ftn_embed_rows_strided: out_bstride=%lld < L*D=%lld",
+                out_bstride, (long long)L * D);
+  FTN_CHECK_ARG(((uintptr_t)out_dev & 15) == 0 && out_bstride % 4 == 0,
+                "ftn_embed_rows_strided: out must be 16-byte aligned, out_bstride a multiple of 4");
+  EmbedArgs a;
+  a.x = x_dev; a.W = w_dev; a.add = nullptr; a.ln_g = nullptr; a.ln_b = nullptr;
+  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = 0; a.out_bs = out_bstride;
+  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = 0.f;
+  return embed_launch(a, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ring epilogue: out[b][t][:] = finish(V[b][(head + t) mod L][:] + add[b?][t][:])   (+ LayerNorm)
+// ---------------------------------------------------------------------------------------------
+// V holds value-embedded rows x W^T (no bias, add or norm) of a sliding window as a ring: the oldest row sits in
+// slot `head`.  One memory-bound pass: reads V and add, writes the window's embedding in time order.  Lane layout,
+// add and LayerNorm are the GEMM epilogue's (embed_row_finish): 16 rows per wave, four lanes per row.
+struct RingArgs {
+  const float* V;        // [B][L][D]
+  const float* add;      // optional, row (b, t) at add + b * add_bs + t * D
+  const float* ln_g;
+  const float* ln_b;
+  float* out;            // [B][L][D]
+  long long add_bs;
+  int B, L, D, head;
+  float ln_eps;
+};
+
+template <int NO>
+__global__ __launch_bounds__(256) void k_embed_ring(RingArgs a) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+  const long long M = (long long)a.B * a.L;
+  const long long row = ((long long)blockIdx.x * 4 + wave) * 16 + j;
+  const bool ok = row < M;
+  const long long r = ok ? row : M - 1;            // rows past the end still take part in the row shuffles
+  const long long b = r / a.L;
+  const int t = (int)(r - b * a.L);
+  int slot = a.head + t;
+  if (slot >= a.L) slot -= a.L;
+  const float* __restrict__ vp = a.V + (b * a.L + slot) * a.D;
+  f4 v[NO];
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    const int cb = 16 * o + 4 * q;
+    v[o] = cb < a.D ? *(const f4*)(vp + cb) : f4{0.f, 0.f, 0.f, 0.f};
+  }
+  const float* __restrict__ ap = a.add ? a.add + b * a.add_bs + (long long)t * a.D : nullptr;
+  embed_row_finish<NO>(v, ap, a.ln_g, a.ln_b, a.ln_eps, a.D, q);
+  if (!ok) return;
+  float* __restrict__ op = a.out + r * a.D;
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    const int cb = 16 * o + 4 * q;
+    if (cb < a.D) *(f4*)(op + cb) = v[o];
+  }
+}
+
+extern "C" int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                              long long add_bstride, const float* ln_gamma_dev_or_null,
+                              const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream) {
+  FTN_CHECK_ARG(v_dev && out_dev, "ftn_embed_ring: null pointer");
+  FTN_CHECK_ARG(B >= 1 && L >= 1, "ftn_embed_ring: bad shape B=%d L=%d", B, L);
+  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "ftn_embed_ring: d_model=%d must be a multiple of 4, <= 128", D);
+  FTN_CHECK_ARG(head >= 0 && head < L, "ftn_embed_ring: head=%d outside [0, L=%d)", head, L);
+  FTN_CHECK_ARG((ln_gamma_dev_or_null == nullptr) == (ln_beta_dev_or_null == nullptr),
+                "ftn_embed_ring: LayerNorm needs both gamma and beta");
+  FTN_CHECK_ARG((((uintptr_t)v_dev | (uintptr_t)out_dev | (uintptr_t)add_dev_or_null |
+                  (uintptr_t)ln_gamma_dev_or_null | (uintptr_t)ln_beta_dev_or_null) & 15) == 0 &&
+                add_bstride % 4 == 0 && add_bstride >= 0,
+                "ftn_embed_ring: V / out / add / LayerNorm parameters must be 16-byte aligned");
+  RingArgs a;
+  a.V = v_dev; a.add = add_dev_or_null; a.ln_g = ln_gamma_dev_or_null; a.ln_b = ln_beta_dev_or_null; a.out = out_dev;
+  a.add_bs = add_bstride; a.B = B; a.L = L; a.D = D; a.head = head; a.ln_eps = ln_eps;
+  const long long M = (long long)B * L;
+  const dim3 grid((unsigned)((M + 63) / 64));
   hipStream_t st = (hipStream_t)stream;
-  if (D <= 64) return launch_embed<4>(a, vec, st);
-  return launch_embed<8>(a, vec, st);
+  if (D <= 64) hipLaunchKernelGGL(k_embed_ring<4>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_embed_ring<8>, grid, dim3(256), 0, st, a);
+  FTN_CHECK_LAUNCH();
+  return 0;
 }

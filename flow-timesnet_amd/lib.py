@@ -161,6 +161,10 @@ _SIGNATURES = {
                                    C.c_int, _P, C.c_longlong, _P, C.c_float, _P, _P, _P, _P]),
     "ftn_embed_forward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong,
                                     _P, _P, C.c_float, _P, _P]),
+    "ftn_embed_rows_strided": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong,
+                                         _P]),
+    "ftn_embed_ring": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, _P, C.c_float, _P,
+                                 _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

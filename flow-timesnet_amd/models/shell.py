@@ -476,31 +476,44 @@ class TimesNet(nn.Module):
                 and self.d_model % 4 == 0 and self.d_model <= 128
                 and window.stride(2) == 1 and window.stride(1) == window.size(2))
 
-    def _embed(self, window, mark, rows) -> torch.Tensor:
-        """``embedding(window + temporal context + constant bias)`` (:1958-2020).  On the HIP path the two context
-        terms are pushed through the value embedding's weight instead (``x W^T + (basis coeff^T + cb) W^T``): one pass
-        over the window (``ftn_embed_forward``) and the [B, L, N] context tensor is never formed."""
+    def _context_terms(self, rows):
+        """The temporal-context coefficients and the constant context bias of the series rows (None when unused)."""
         coeff = bias = None
         if rows is not None:
             if self.context_coeff is not None and self.temporal_context is not None and self.use_zero_mean_context:
                 coeff = self.context_coeff(rows.to(self.context_coeff.weight.dtype))
             if self.context_proj is not None and self.use_constant_context_bias:
                 bias = self.context_proj(rows.to(self.context_proj.weight.dtype)).squeeze(-1)
+        return coeff, bias
+
+    def _hip_embed_terms(self, window, mark, coeff, bias):
+        """What the HIP embedding adds to ``x W^T``: ``(w, add, ln)`` with ``w`` the value weight [D, N], ``add`` the
+        bias + positional (+ time-feature) term + the two context terms pushed through ``w``, contiguous fp32
+        ``[1|B, L, D]``, and ``ln = (gamma, beta, eps)`` of the "layer" mode (None otherwise).  Shared by ``_embed``
+        and the recursive forecaster (``forecast.py``), which embeds its window row by row."""
+        emb, L = self.embedding, window.size(1)
+        w = emb.value_embedding.weight.detach()
+        add = emb.aux_term(window[:1], mark) + emb.value_embedding.bias.detach()
+        if coeff is not None:
+            add = add + self.temporal_context.project(coeff.detach().float(), L, w)
+        if bias is not None:
+            add = add + (bias.detach().float() @ w.t()).unsqueeze(1)
+        ln = None
+        if emb.embed_norm_mode == "layer":
+            ln = (emb.norm.weight.detach().float().contiguous(), emb.norm.bias.detach().float().contiguous(), emb.norm.eps)
+        return w, add.detach().float().contiguous(), ln
+
+    def _embed(self, window, mark, rows) -> torch.Tensor:
+        """``embedding(window + temporal context + constant bias)`` (:1958-2020).  On the HIP path the two context
+        terms are pushed through the value embedding's weight instead (``x W^T + (basis coeff^T + cb) W^T``): one pass
+        over the window (``ftn_embed_forward``) and the [B, L, N] context tensor is never formed."""
+        coeff, bias = self._context_terms(rows)
         if self._hip_embed_ok(window):
             from .. import runtime
 
-            emb, L = self.embedding, window.size(1)
-            w = emb.value_embedding.weight.detach()
-            add = emb.aux_term(window[:1], mark) + emb.value_embedding.bias.detach()
-            if coeff is not None:
-                add = add + self.temporal_context.project(coeff.detach().float(), L, w)
-            if bias is not None:
-                add = add + (bias.detach().float() @ w.t()).unsqueeze(1)
-            ln = None
-            if emb.embed_norm_mode == "layer":
-                ln = (emb.norm.weight.detach().float().contiguous(), emb.norm.bias.detach().float().contiguous(), emb.norm.eps)
+            w, add, ln = self._hip_embed_terms(window, mark, coeff, bias)
             self._last_embed_backend = "hip"
-            seq = runtime.embed_forward(window, w, add.detach().float().contiguous(), ln)
+            seq = runtime.embed_forward(window, w, add, ln)
         else:
             feats = window
             if coeff is not None:

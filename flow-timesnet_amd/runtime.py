@@ -351,6 +351,41 @@ def embed_forward(window: torch.Tensor, weight: torch.Tensor, add, norm=None) ->
     return out
 
 
+def embed_rows_strided(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor, slot: int) -> None:
+    """``x W^T`` of ``x`` [B,L,N] (fp32 view with contiguous rows) into rows ``slot .. slot+L-1`` of ``out``
+    [B,Lr,D] (contiguous fp32), no add, no norm: the GEMM of ``embed_forward`` row for row."""
+    lib = _lib.load()
+    B, L, N = x.shape
+    D = weight.shape[0]
+    if x.stride(2) != 1 or x.stride(1) != N:
+        raise ValueError("x rows must be contiguous")
+    if (out.dim() != 3 or out.shape[0] != B or out.shape[2] != D or not out.is_contiguous()
+            or out.dtype != torch.float32 or not 0 <= slot <= out.shape[1] - L):
+        raise ValueError("out must be contiguous fp32 [B, Lr, D] with room for L rows from slot")
+    check(lib.ftn_embed_rows_strided(_ptr(x), x.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
+                                     _ptr(out) + 4 * slot * D, out.stride(0), _stream(x.device)),
+          "ftn_embed_rows_strided")
+
+
+def embed_ring(V: torch.Tensor, head: int, add, norm=None) -> torch.Tensor:
+    """``out[b, t] = V[b, (head + t) % L] + add[b?, t]`` (+ LayerNorm ``norm = (gamma, beta, eps)``) with
+    ``embed_forward``'s epilogue arithmetic.  ``V`` contiguous fp32 [B,L,D]; ``add`` None or contiguous [1|B,L,D]."""
+    lib = _lib.load()
+    B, L, D = V.shape
+    if not V.is_contiguous() or V.dtype != torch.float32:
+        raise ValueError("V must be contiguous fp32 [B, L, D]")
+    add_bs = 0
+    if add is not None:
+        if add.dim() != 3 or add.shape[-2:] != (L, D) or add.shape[0] not in (1, B) or not add.is_contiguous():
+            raise ValueError("add must be contiguous [1|B, L, D]")
+        add_bs = L * D if add.shape[0] == B and B > 1 else 0
+    out = torch.empty(B, L, D, dtype=torch.float32, device=V.device)
+    g, b, eps = norm if norm is not None else (None, None, 0.0)
+    check(lib.ftn_embed_ring(_ptr(V), B, L, D, int(head), _ptr_or_null(add), add_bs, _ptr_or_null(g), _ptr_or_null(b),
+                             float(eps), _ptr(out), _stream(V.device)), "ftn_embed_ring")
+    return out
+
+
 # ------------------------------------------------------------------ row exchange (series-sharded forward)
 def rowx_push(src: torch.Tensor, xch) -> None:
     """Store this rank's rows into every destination's buffer (``xch``: ``C.byref`` of an ``FtnRowExchange``).

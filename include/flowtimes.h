@@ -421,6 +421,21 @@ int ftn_embed_forward(const float* x_dev, long long x_bstride, int B, int L, int
                       const float* add_dev_or_null, long long add_bstride, const float* ln_gamma_dev_or_null,
                       const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream);
 
+/* The GEMM of ftn_embed_forward alone (no add, no LayerNorm), row (b, l) of x W^T stored at
+ * out + b * out_bstride + l * D: same kernels, form selection and K order, so each row is bit-identical to
+ * the one ftn_embed_forward computes before its epilogue.  The recursive forecaster appends a step's B new
+ * rows (L = 1) to its ring of embedded rows with it.  out 16-byte aligned, out_bstride % 4 == 0. */
+int ftn_embed_rows_strided(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev, int D,
+                           float* out_dev, long long out_bstride, void* stream);
+
+/* Embedding of a sliding window from a ring of stored x W^T rows V [B][L][D] whose oldest row is slot `head`:
+ *   out[b][t][:] = V[b][(head + t) mod L][:] + add[b?][t][:]      (+ LayerNorm over D when gamma/beta are given)
+ * with ftn_embed_forward's epilogue arithmetic (bit-identical to it on the equivalent window).  add optional
+ * ([L][D] with add_bstride 0, or [B][L][D]); every pointer 16-byte aligned; D a multiple of 4, <= 128. */
+int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                   long long add_bstride, const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null,
+                   float ln_eps, float* out_dev, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
