@@ -16,12 +16,15 @@ Everything else (top-k, grouping, convs, aggregation) is rank-local.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional
 
 import torch
 import torch.distributed as dist
 from torch import nn
+
+from . import range_guard
 
 
 def _refuse_flagged_grouping(block_index=None) -> None:
@@ -52,6 +55,18 @@ def _refuse_capture(sharded: bool, x: torch.Tensor, exchange, gather) -> None:
     if gather:
         raise RuntimeError("a sharded forward cannot be captured with gather=True / 'async' (a collective): capture "
                            "with gather=False and call dist.gather_batch on the outputs after the replay")
+
+
+@contextlib.contextmanager
+def _sharded_selector(sel, group, exchange, sharded: bool, x: torch.Tensor):
+    """Point the shared selector at the process group (and the IPC exchange, on the device) for one call."""
+    prev = sel.shard_group, sel.shard_exchange
+    sel.shard_group = group if sharded else None
+    sel.shard_exchange = exchange if (exchange is not None and x.is_cuda) else None
+    try:
+        yield
+    finally:
+        sel.shard_group, sel.shard_exchange = prev
 
 
 class IpcExchange:
@@ -173,6 +188,10 @@ class ShardedTimesBlock(nn.Module):
 
     ``forward(x_local)`` returns this rank's rows (``gather=False``) or the
     re-assembled global batch (``gather=True``).  Shards must be equally sized.
+
+    f16x2 range guard: the block repairs a flagged call on its own rank (``check_range()``, its next call), on the
+    selection the call made, so no exchange is repeated and the ranks stay in lockstep.  With ``gather=True`` /
+    ``"async"`` the all-gather is enqueued before that repair, so the gathered copy can hold the unrepaired rows.
     """
 
     def __init__(self, block: nn.Module, group=None, exchange: Optional[IpcExchange] = None) -> None:
@@ -194,36 +213,17 @@ class ShardedTimesBlock(nn.Module):
             _refuse_flagged_grouping(getattr(self.block, "block_index", None))
         sharded = dist.get_world_size(grp) > 1 or os.environ.get("FTN_BENCH_FORCE_DIST") == "1"
         _refuse_capture(sharded, x_local, self.exchange, gather)
-        prev, prev_x = sel.shard_group, sel.shard_exchange
-        sel.shard_group = grp if sharded else None
-        sel.shard_exchange = self.exchange if (self.exchange is not None and x_local.is_cuda) else None
-        try:
+        with _sharded_selector(sel, grp, self.exchange, sharded, x_local):
             y = self.block(x_local)
-        finally:
-            sel.shard_group, sel.shard_exchange = prev, prev_x
         if gather == "async":
             return gather_batch(y, grp, async_op=True)
         return gather_batch(y, grp) if gather else y
 
 
-class ShardedTimesNet(nn.Module):
-    """Batch-sharded whole model (P2, SURVEY §8e): the model's blocks share one ``FFTPeriodSelector``, so
-    pointing its ``shard_group`` at the process group makes every block exchange its ``[F]`` partial sums;
-    everything else in ``TimesNet.forward`` is row-wise or per-series and needs no communication.
-    ``forward`` returns this rank's ``(rate, dispersion)`` rows, or the all-gathered ones with ``gather=True``.
-    ``exchange``: as in ``ShardedTimesBlock``; with ``IpcExchange(..., capturable=True)`` the wrapper can be captured
-    by ``graph.GraphedForward(wrapper, x_local, gather=False)``, which runs the model's deferred output checks through
-    the three attributes forwarded below."""
+class _ShardedModel(nn.Module):
+    """What both whole-model wrappers share: ``graph.GraphedForward`` defers the model's output checks during capture
+    and runs them after every replay, through the three attributes forwarded here."""
 
-    def __init__(self, model: nn.Module, group=None, exchange: Optional[IpcExchange] = None) -> None:
-        super().__init__()
-        self.model = model
-        self.group = group
-        self.exchange = exchange                                 # None: all-gather through torch.distributed (RCCL / gloo)
-        if not hasattr(model.period_selector, "shard_group"):
-            raise ValueError("ShardedTimesNet needs the mirror TimesNet (native FFTPeriodSelector)")
-
-    # graph.GraphedForward defers the model's output checks during capture and runs them after every replay
     @property
     def _defer_checks(self) -> bool:
         return self.model._defer_checks
@@ -243,21 +243,44 @@ class ShardedTimesNet(nn.Module):
     def check_outputs(self) -> None:
         self.model.check_outputs()
 
+
+class ShardedTimesNet(_ShardedModel):
+    """Batch-sharded whole model (P2, SURVEY §8e): the model's blocks share one ``FFTPeriodSelector``, so
+    pointing its ``shard_group`` at the process group makes every block exchange its ``[F]`` partial sums;
+    everything else in ``TimesNet.forward`` is row-wise or per-series and needs no communication.
+    ``forward`` returns this rank's ``(rate, dispersion)`` rows, or the all-gathered ones with ``gather=True``.
+    ``exchange``: as in ``ShardedTimesBlock``; with ``IpcExchange(..., capturable=True)`` the wrapper can be captured
+    by ``graph.GraphedForward(wrapper, x_local, gather=False)``, which runs the model's deferred output checks through
+    the three attributes forwarded by ``_ShardedModel``.
+
+    f16x2 range guard: after an eager forward the blocks' flags are all-reduced (MAX) over the group and, if any rank
+    tripped, every rank switches its blocks to ``bf16x3`` and repeats the forward, so the ranks stay in lockstep.  In a
+    captured forward ``check_outputs()`` raises instead."""
+
+    def __init__(self, model: nn.Module, group=None, exchange: Optional[IpcExchange] = None) -> None:
+        super().__init__()
+        self.model = model
+        self.group = group
+        self.exchange = exchange                                 # None: all-gather through torch.distributed (RCCL / gloo)
+        if not hasattr(model.period_selector, "shard_group"):
+            raise ValueError("ShardedTimesNet needs the mirror TimesNet (native FFTPeriodSelector)")
+
     def forward(self, x_local: torch.Tensor, gather: bool = False, **kwargs):
-        sel = self.model.period_selector
+        m = self.model
         grp = self.group if self.group is not None else dist.group.WORLD
         if dist.get_world_size(grp) > 1:
-            for blk in self.model.blocks:
+            for blk in m.blocks:
                 _refuse_flagged_grouping(getattr(blk, "block_index", None))
         sharded = dist.get_world_size(grp) > 1 or os.environ.get("FTN_BENCH_FORCE_DIST") == "1"
         _refuse_capture(sharded, x_local, self.exchange, gather)
-        prev, prev_x = sel.shard_group, sel.shard_exchange
-        sel.shard_group = grp if sharded else None
-        sel.shard_exchange = self.exchange if (self.exchange is not None and x_local.is_cuda) else None
-        try:
-            rate, disp = self.model(x_local, **kwargs)
-        finally:
-            sel.shard_group, sel.shard_exchange = prev, prev_x
+        with _sharded_selector(m.period_selector, grp, self.exchange, sharded, x_local):
+            # the model's single pass under this wrapper's collective decision (never the model's rank-local one)
+            rate, disp = range_guard.repeat_on_trip(
+                m.blocks, lambda: m._forward_once(x_local, **kwargs), group=grp if sharded else None,
+                message="ShardedTimesNet: a value left the fp16 range of engine f16x2 on some rank; every rank repeats "
+                        "the forward on engine bf16x3")
+        if not m._defer_checks:
+            m.check_outputs()
         if gather:
             return gather_batch(rate, grp), gather_batch(disp, grp)
         return rate, disp
@@ -370,7 +393,7 @@ def series_row_exchanges(model: nn.Module, batch: int, group=None, device=None):
             IpcRowExchange(grp, device, batch // world, steps * D, "all_gather"))
 
 
-class SeriesShardedTimesNet(nn.Module):
+class SeriesShardedTimesNet(_ShardedModel):
     """Series-sharded (channel-sharded) whole model: every rank holds ``[B, T, N_r]``, a contiguous slice of the series
     in rank order (slices may be uneven), and gets ``(rate, dispersion)`` of its own series, ``[B, H, N_r]``.
 
@@ -409,26 +432,6 @@ class SeriesShardedTimesNet(nn.Module):
         if self.row_exchange is not None and len(self.row_exchange) != 2:
             raise ValueError("row_exchange must be the (reduce_scatter, all_gather) pair of series_row_exchanges")
         self._sizes = None
-
-    # graph.GraphedForward defers the model's output checks during capture and runs them after every replay
-    @property
-    def _defer_checks(self) -> bool:
-        return self.model._defer_checks
-
-    @_defer_checks.setter
-    def _defer_checks(self, v: bool) -> None:
-        self.model._defer_checks = v
-
-    @property
-    def _pending_bad(self):
-        return self.model._pending_bad
-
-    @_pending_bad.setter
-    def _pending_bad(self, v) -> None:
-        self.model._pending_bad = v
-
-    def check_outputs(self) -> None:
-        self.model.check_outputs()
 
     def series_sizes(self, n_local: int, grp):
         """Every rank's series count (one collective at the first call; never during a capture)."""
@@ -496,31 +499,12 @@ class SeriesShardedTimesNet(nn.Module):
         window = x_local.narrow(1, T - L, L)
         mark = None if x_mark is None else x_mark.narrow(1, T - L, L)
         sl = m.series_slices(offset, n_local, x_local.device)
-        eager_hip = hip and not torch.cuda.is_current_stream_capturing()
-        blocks = list(m.blocks)
-        prev_flag = [getattr(b, "range_flag_on_device", False) for b in blocks]
-        for b in blocks:
-            b.range_flag_on_device = hip
-        try:
-            out = self._forward_once(window, mark, series_static, series_ids, sl, offset, grp, world, rank, sharded)
-            if eager_hip and self._range_tripped(grp):
-                import warnings
-
-                warnings.warn("SeriesShardedTimesNet: a value left the fp16 range of engine f16x2 on some rank; every "
-                              "rank repeats the forward on engine bf16x3", RuntimeWarning, stacklevel=2)
-                for b in blocks:
-                    b.engine = "bf16x3"
-                    b._range_dev_flag = None
-                    b._range_fallbacks += 1
-                out = self._forward_once(window, mark, series_static, series_ids, sl, offset, grp, world, rank,
-                                         sharded)
-            if eager_hip:
-                for b in blocks:                                # resolved collectively above
-                    b._range_dev_flag = None
-        finally:
-            for b, v in zip(blocks, prev_flag):
-                b.range_flag_on_device = v
-        rate, disp, bad = out
+        rate, disp, bad = range_guard.repeat_on_trip(
+            m.blocks, lambda: self._forward_once(window, mark, series_static, series_ids, sl, offset, grp, world, rank,
+                                                 sharded),
+            group=grp if sharded else None,
+            message="SeriesShardedTimesNet: a value left the fp16 range of engine f16x2 on some rank; every rank "
+                    "repeats the forward on engine bf16x3")
         if bad is not None:
             m._pending_bad = bad
             if not m._defer_checks:
@@ -528,17 +512,6 @@ class SeriesShardedTimesNet(nn.Module):
         if gather:
             return self.gather_series(rate, grp), self.gather_series(disp, grp)
         return rate, disp
-
-    def _range_tripped(self, grp) -> bool:
-        """All-reduce (MAX) of the blocks' f16x2 range flags of the forward just enqueued (synchronises)."""
-        flags = [b._range_dev_flag for b in self.model.blocks if getattr(b, "_range_dev_flag", None) is not None]
-        dev = next(self.model.parameters()).device
-        v = torch.stack(flags).max().reshape(1) if flags else torch.zeros(1, dtype=torch.int32, device=dev)
-        v = v.to(torch.int32)
-        if dist.get_backend(grp) == "gloo":
-            v = v.cpu()
-        dist.all_reduce(v, op=dist.ReduceOp.MAX, group=grp)
-        return int(v.item()) != 0
 
     def _forward_once(self, window, mark, series_static, series_ids, sl, offset, grp, world, rank, sharded):
         m = self.model
@@ -563,14 +536,8 @@ class SeriesShardedTimesNet(nn.Module):
                 seq = torch.nn.functional.layer_norm(seq, (D,), ln[0], ln[1], ln[2])
             elif m.embedding.norm is not None:                   # rms (torch path only)
                 seq = m.embedding.norm(seq)
-        sel = m.period_selector
-        prev, prev_x = sel.shard_group, sel.shard_exchange
-        sel.shard_group = grp if sharded else None
-        sel.shard_exchange = self.exchange if (self.exchange is not None and window.is_cuda) else None
-        try:
+        with _sharded_selector(m.period_selector, grp, self.exchange, sharded, window):
             seq = m._stack(seq)
-        finally:
-            sel.shard_group, sel.shard_exchange = prev, prev_x
         steps = m._out_steps
         hidden_q = m.series_hidden(seq, steps)                                       # [B/W, steps, D]
         if rx is not None:

@@ -24,11 +24,13 @@ model - runs the reference's loop unchanged (``forecast_recursive_batch_loop``).
 """
 from __future__ import annotations
 
+import contextlib
 import os
-import warnings
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
+
+from . import range_guard
 
 _MISSING_Y_MARK = "Temporal features provided for history but missing future marks during recursive forecast"
 _SHORT_Y_MARK = "y_mark does not provide enough future steps for recursive forecasting"
@@ -152,7 +154,7 @@ def _mark_window(x_mark, y_mark, L: int, s: int) -> torch.Tensor:
 
 def _enqueue(model, last_seq, H, x_mark, y_mark, series_static, series_ids, rate_out, disp_out):
     """Enqueue the H steps (no host synchronisation).  Writes step s into ``[:, s]`` of the outputs; returns the heads'
-    finite-positive flags (one per step) and the blocks' f16x2 range flags (every step, every block)."""
+    finite-positive flags (one per step)."""
     from . import runtime
 
     L = model.input_len
@@ -167,58 +169,33 @@ def _enqueue(model, last_seq, H, x_mark, y_mark, series_static, series_ids, rate
     V = torch.empty(B, L, D, dtype=torch.float32, device=window.device)
     runtime.embed_rows_strided(window, w, V, 0)
     tail = last_seq[:, -1:, :]
-    bads, flags = [], []
+    bads = []
     for s in range(H):
         if s > 0:
             runtime.embed_rows_strided(tail, w, V, (s - 1) % L)
             if x_mark is not None:
                 _, add, _ = model._hip_embed_terms(window, _mark_window(x_mark, y_mark, L, s), coeff, bias)
         seq = model._stack(runtime.embed_ring(V, s % L, add, ln))
-        flags.extend(blk._range_dev_flag for blk in model.blocks if getattr(blk, "_range_dev_flag", None) is not None)
         rate, disp = model._heads(seq, tail, rows, 1)
         bads.append(model._pending_bad)
         rate_out[:, s].copy_(rate[:, 0])
         disp_out[:, s].copy_(disp[:, 0])
         tail = rate
     model._last_embed_backend = "hip"
-    return bads, flags
+    return bads
 
 
-class _Guards:
-    """Deferred checks for the length of one forecast: the model's finite-positive check and the blocks' range flags
-    in device memory.  Restores both on exit."""
-
-    def __init__(self, model) -> None:
-        self.model = model
-
-    def __enter__(self):
-        self.saved = (self.model._defer_checks, [blk.range_flag_on_device for blk in self.model.blocks])
-        self.model._defer_checks = True
-        for blk in self.model.blocks:
-            blk.range_flag_on_device = True
-            blk._range_dev_flag = None
-        return self
-
-    def __exit__(self, *exc) -> None:
-        self.model._defer_checks, on = self.saved
-        for blk, v in zip(self.model.blocks, on):
-            blk.range_flag_on_device = v
-        self.model._pending_bad = None
-
-
-def _range_tripped(model, flags) -> bool:
-    """Read every range flag of a forecast (one synchronisation).  If any is set, warn and put every block on bf16x3:
-    the caller then runs the forecast again."""
-    for blk in model.blocks:
-        blk._range_dev_flag = None               # read here; a stale flag must not trip a later check_range()
-    if not flags or not bool(torch.stack([f.reshape(()) for f in flags]).any()):
-        return False
-    warnings.warn(_RANGE_WARNING, RuntimeWarning, stacklevel=3)
-    for blk in model.blocks:
-        if blk._engine_name() == "f16x2":
-            blk._range_fallbacks = getattr(blk, "_range_fallbacks", 0) + 1
-        blk.engine = "bf16x3"
-    return True
+@contextlib.contextmanager
+def _deferred_checks(model):
+    """The model's finite-positive check is left to the caller for the length of one forecast (and its ids check,
+    which reads the device, is skipped, as in a capture)."""
+    saved = model._defer_checks
+    model._defer_checks = True
+    try:
+        yield
+    finally:
+        model._defer_checks = saved
+        model._pending_bad = None
 
 
 def _raise_if_bad(bads) -> None:
@@ -234,14 +211,15 @@ def _raise_if_bad(bads) -> None:
 
 
 def _forecast_device(model, last_seq, H, x_mark, y_mark, series_static, series_ids):
-    B, N = last_seq.size(0), last_seq.size(2)
-    while True:
-        rate = torch.empty(B, H, N, dtype=torch.float32, device=last_seq.device)
+    """The blocks' f16x2 range flags of all H steps are read once, after the forecast (``range_guard``)."""
+    def run():
+        rate = torch.empty(last_seq.size(0), H, last_seq.size(2), dtype=torch.float32, device=last_seq.device)
         disp = torch.empty_like(rate)
-        with _Guards(model):
-            bads, flags = _enqueue(model, last_seq, H, x_mark, y_mark, series_static, series_ids, rate, disp)
-        if not _range_tripped(model, flags):
-            break
+        bads = _enqueue(model, last_seq, H, x_mark, y_mark, series_static, series_ids, rate, disp)
+        return rate, disp, bads
+
+    with _deferred_checks(model):
+        rate, disp, bads = range_guard.repeat_on_trip(model.blocks, run, message=_RANGE_WARNING)
     _raise_if_bad(bads)
     return rate, disp
 
@@ -295,10 +273,9 @@ class RecursiveForecaster:
         with torch.inference_mode():
             self._rate = torch.empty(B, self.H, N, dtype=torch.float32, device=dev)
             self._disp = torch.empty_like(self._rate)
-            with _Guards(model), torch.cuda.graph(self.graph):
-                self._bads, self._flags = _enqueue(model, seq, self.H, xm, ym, st, ids, self._rate, self._disp)
-        for blk in model.blocks:
-            blk._range_dev_flag = None
+            with _deferred_checks(model), range_guard.device_flags(model.blocks) as self._flags, \
+                    torch.cuda.graph(self.graph):
+                self._bads = _enqueue(model, seq, self.H, xm, ym, st, ids, self._rate, self._disp)
         self._sel = model.period_selector._pending          # the last step's period selection (device descriptor)
         # the captured launches have the packed weight blobs' addresses baked in: keep them alive
         self._packs = [m._pack for m in model.modules() if getattr(m, "_pack", None) is not None]
@@ -312,8 +289,9 @@ class RecursiveForecaster:
     def replay(self) -> Tuple[torch.Tensor, torch.Tensor]:
         while True:
             self.graph.replay()
-            if not _range_tripped(self.model, self._flags):
+            if not range_guard.tripped(self._flags):
                 break
+            range_guard.fall_back(self.model.blocks, _RANGE_WARNING)
             self._capture()                               # every block is on bf16x3 now
         _raise_if_bad(self._bads)
         if self._sel is not None:

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.utils.checkpoint import checkpoint
 
+from .. import range_guard
 from .timesnet import FFTPeriodSelector, LowRankTemporalContext, TimesBlock
 
 _HALF = (torch.float16, torch.bfloat16)
@@ -579,9 +580,9 @@ class TimesNet(nn.Module):
                 self.sigma_head.weight.detach(), self.sigma_head.bias.detach(), window[:, -hist:, :], hist,
                 None if late is None else late.detach().float().contiguous(), floor_vec, self.min_sigma)
             self._last_head_backend = "hip"
-            self._pending_bad = bad
-            if not self._defer_checks:
-                self.check_outputs()
+            # the forward's one synchronisation (range_guard.tripped then reads the blocks' pinned words behind it);
+            # deferred, check_outputs() reads the device word after a replay
+            self._pending_bad = bad if self._defer_checks else bad.cpu()
             return rate, dispersion
         hidden = torch.matmul(wt, seq) + bt.view(1, -1, 1)                                  # [B, steps, d_model]
         last = window[:, -hist:, :]
@@ -604,20 +605,11 @@ class TimesNet(nn.Module):
     def check_outputs(self) -> None:
         """Raise the reference's RuntimeError (:2095-2098) if the last HIP head call produced a rate or
         dispersion that is not finite and > 0.  Reads one int32 from the device (synchronises); called by
-        ``forward`` itself unless ``_defer_checks`` is set (HIP-graph capture, ``graph.GraphedForward``)."""
-        # f16x2 range guard of the blocks (TimesBlock.check_range): a block that had to repeat its call on bf16x3 has
-        # repaired its own output, but the layers behind it have consumed the old one - forward() then runs again
-        # with every block on bf16x3 (which stays selected)
-        seen = sum(getattr(blk, "_range_fallbacks", 0) for blk in self.blocks)
+        ``forward`` itself unless ``_defer_checks`` is set (HIP-graph capture, ``graph.GraphedForward``).  Before that,
+        a block whose f16x2 range flag tripped inside a captured forward raises ``FloatingPointError``
+        (``TimesBlock.check_range``; an eager forward has already repeated itself on bf16x3)."""
         for blk in self.blocks:
-            if getattr(blk, "_range_dev_flag", None) is not None or getattr(blk, "_range_pending", None):
-                blk.check_range()
-        if sum(getattr(blk, "_range_fallbacks", 0) for blk in self.blocks) != seen:
-            for blk in self.blocks:
-                blk.engine = "bf16x3"
-            self._range_retry = True
-            self._pending_bad = None
-            return
+            blk.check_range()
         bad, self._pending_bad = self._pending_bad, None
         if bad is None:
             return
@@ -768,13 +760,15 @@ class TimesNet(nn.Module):
     def forward(self, x: torch.Tensor, x_mark: Optional[torch.Tensor] = None,
                 series_static: Optional[torch.Tensor] = None,
                 series_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        out = self._forward_once(x, x_mark, series_static, series_ids)
-        if getattr(self, "_range_retry", False):                # check_outputs(): a block left the f16x2 range
-            self._range_retry = False
-            out = self._forward_once(x, x_mark, series_static, series_ids)
+        out = range_guard.repeat_on_trip(self.blocks, lambda: self._forward_once(x, x_mark, series_static, series_ids),
+                                         message="TimesNet: " + range_guard.MESSAGE)
+        if not self._defer_checks:
+            self.check_outputs()
         return out
 
-    def _forward_once(self, x, x_mark, series_static, series_ids) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _forward_once(self, x, x_mark=None, series_static=None, series_ids=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One pass, without the checks: ``forward`` and the batch-sharded wrapper (``dist.ShardedTimesNet``) decide
+        on the f16x2 range around it and call ``check_outputs``."""
         L = self.input_len
         if x.dim() != 3:
             raise ValueError("TimesNet expects input shaped [B, T, N]")

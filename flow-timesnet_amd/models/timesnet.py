@@ -331,14 +331,16 @@ class TimesBlock(nn.Module):
         # conv arithmetic of the HIP backend: None = pack.default_engine() ("f16x2" unless FLOWTIMES_ENGINE says
         # otherwise); "bf16x3" = three bf16 pieces, full fp32 exponent range; "f32" = exact fp32 MFMA; "bf16" = plain bf16
         self.engine: Optional[str] = None
-        # f16x2 range guard (include/flowtimes.h, ABI 9): the kernels flag values that do not fit fp16 pieces; the
-        # flag of a call is looked at once its completion event has fired - at the next call of this block, by
-        # check_range(), or when _last_engine is read - and a flagged call is repeated on bf16x3 INTO THE SAME output
+        # f16x2 range guard (include/flowtimes.h, ABI 9; words armed by range_guard.arm): the kernels flag values that
+        # do not fit fp16 pieces; the flag of an eager call is looked at once its completion event has fired - at the
+        # next call of this block, by check_range(), or when _last_engine is read - and a flagged call is repeated on
+        # bf16x3 with its own selection INTO THE SAME output
         self._range_slots: list = []          # free (flag, event) pairs
-        self._range_pending: list = []        # calls in flight: (flag, event, x, y, post_norm)
-        self._range_dev_flag = None           # device-memory flag used while a HIP graph is being captured
-        # opt-in: use that device flag in eager calls too, and never repeat a call on the host's own initiative - the
-        # caller reads _range_dev_flag after the forward (dist.SeriesShardedTimesNet repairs collectively)
+        self._range_pending: list = []        # calls in flight: (flag, event, xf, y, norm, selection)
+        self._range_dev_flag = None           # word of a captured call, or of device-flag mode
+        self._range_word = None               # this block's reusable word for eager device-flag mode
+        # device-flag mode (range_guard.device_flags): the block never reads its words itself - the composite
+        # forward around it does, and repeats itself on bf16x3 (range_guard.repeat_on_trip)
         self.range_flag_on_device = False
         self._last_engine_used: Optional[str] = None
         self._range_fallbacks = 0
@@ -422,12 +424,13 @@ class TimesBlock(nn.Module):
 
         return getattr(self, "engine", None) or pack.default_engine()
 
-    def _resolve_range(self, block: bool) -> None:
-        """Look at the range flags of finished f16x2 calls (all pending calls when ``block``); a flagged call is
-        repeated on the bf16x3 engine into the output tensor it returned."""
+    def _resolve_range(self, wait: bool) -> None:
+        """Look at the range flags of finished eager f16x2 calls (all pending calls when ``wait``).  A flagged call is
+        repeated on the bf16x3 engine with the selection it made, into the output tensor it returned: no selector
+        runs and nothing is exchanged, so the repair is rank-local even in a batch-sharded call."""
         while self._range_pending:
-            flag, ev, x, y, post_norm = self._range_pending[0]
-            if block:
+            flag, ev, xf, y, norm, sel = self._range_pending[0]
+            if wait:
                 ev.synchronize()
             elif not ev.query():
                 return
@@ -443,15 +446,16 @@ class TimesBlock(nn.Module):
                 warnings.warn("TimesBlock: a value left the fp16 range of engine f16x2 (|v| >= 65504 or not finite); "
                               "the call was repeated on engine bf16x3", RuntimeWarning, stacklevel=3)
                 self._range_fallbacks += 1
-                y2 = self._forward_hip(x, post_norm, engine="bf16x3")
-                y.copy_(y2 if y2.dtype == y.dtype else y2.to(y.dtype))
+                y.copy_(self._run(xf, y.dtype, sel, self._packed(xf.device, "bf16x3"), norm))
                 self._last_engine_used = "bf16x3"
 
     def check_range(self) -> Optional[str]:
         """Wait for this block's outstanding HIP calls and repair any whose values left the f16x2 engine's fp16
         range (see ``_resolve_range``); returns the engine the last call finally ran on."""
-        self._resolve_range(block=True)
+        self._resolve_range(wait=True)
         flag = self._range_dev_flag
+        if flag is not None and not flag.is_cuda:                # a pinned word of device-flag mode: written by the device
+            torch.cuda.current_stream().synchronize()
         if flag is not None and int(flag.item()) != 0:           # set during a captured / deferred forward
             raise FloatingPointError("TimesBlock: a value left the fp16 range of engine f16x2 inside a captured "
                                      "forward; set block.engine = 'bf16x3' and capture again")
@@ -521,98 +525,46 @@ class TimesBlock(nn.Module):
         k = getattr(sel, "k", None) if type(sel) is FFTPeriodSelector else None
         return len(self._kernel_spec) <= FTN_MAXBR and (k is None or int(k) <= FTN_KMAX)
 
-    # ---- HIP backend -----------------------------------------------------------
-    def _forward_hip(self, x: torch.Tensor, post_norm: Optional[nn.LayerNorm] = None,
-                     engine: Optional[str] = None) -> torch.Tensor:
-        from .. import lib, runtime
+    # ---- HIP backend: select, then run stages A-F on the selection ---------------------
+    def _forward_hip(self, x: torch.Tensor, post_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
+        from .. import range_guard, runtime
 
-        engine = engine or self._engine_name()
-        guarded = engine == "f16x2" and os.getenv("FTN_RANGE_GUARD", "1") != "0"
-        range_flag = slot_ev = None
-        if guarded:
-            if torch.cuda.is_current_stream_capturing() or getattr(self, "range_flag_on_device", False):
-                # a captured forward cannot record host events: it sets a device word (zeroed by a captured fill at
-                # every replay) that check_range() / TimesNet.check_outputs() read after the replay
-                self._range_dev_flag = range_flag = torch.zeros(1, dtype=torch.int32, device=x.device)
-            else:
-                self._range_dev_flag = None
-                self._resolve_range(block=False)
+        engine = self._engine_name()
+        flag = ev = None
+        if engine == "f16x2" and os.getenv("FTN_RANGE_GUARD", "1") != "0":
+            flag, ev = range_guard.arm(self, x.device)
+            if ev is not None:                                  # an eager call this block looks at itself
+                self._resolve_range(wait=False)
                 if len(self._range_pending) >= 8:              # the host runs far ahead: wait for the oldest call only
                     self._range_pending[0][1].synchronize()
-                    self._resolve_range(block=False)
-                range_flag, slot_ev = self._range_slots.pop() if self._range_slots else (
-                    runtime.new_range_flag(x.device), torch.cuda.Event())
-
-        norm = None
-        if post_norm is not None:
-            norm = (post_norm.weight.detach().float().contiguous(), post_norm.bias.detach().float().contiguous(),
-                    post_norm.eps)
-
-        def unchanged():
-            # the reference returns x itself (:796-797); the shell then normalises x + (x - x)
-            if slot_ev is not None:
-                self._range_slots.append((range_flag, slot_ev))
-            if norm is None:
-                return x
-            xc = x.detach().float().contiguous()
-            y = runtime.residual_layernorm(xc, xc, *norm)
-            return y if y.dtype == x.dtype else y.to(x.dtype)
-
-        B, L, _ = x.shape
-        sel_mod = self.period_selector
-        native = type(sel_mod) is FFTPeriodSelector
-        # TIMES_PERIOD_MAX_UNIQ / TIMES_PERIOD_BINNING (per-depth schedules resolved here, :320-325) are grouping
-        # variants of the device finalize kernel: no host round trip on the native path
-        from ..grouping import _resolve_log_binning_base, _resolve_scheduled_int
-        max_unique = _resolve_scheduled_int(os.getenv("TIMES_PERIOD_MAX_UNIQ"), self.block_index)
-        log_base = _resolve_log_binning_base(os.getenv("TIMES_PERIOD_BINNING"), self.block_index)
+                    self._resolve_range(wait=False)
         xf = x.detach()
         if xf.dtype != torch.float32:
             xf = xf.float()
         xf = xf.contiguous()
         adt = runtime.ACT_DTYPE.get(x.dtype, 0)
-        if adt != 0:
-            norm = None                        # half inputs: the shell's LayerNorm runs outside (see forward)
+        norm = None
+        if post_norm is not None and adt == 0:     # half inputs: the shell's LayerNorm runs outside (see forward)
+            norm = (post_norm.weight.detach().float().contiguous(), post_norm.bias.detach().float().contiguous(),
+                    post_norm.eps)
         wblob, plan = self._packed(x.device, engine)
-        if native:
-            sel = sel_mod.select_device(xf, act_dtype=x.dtype, max_unique=max_unique, log_base=log_base,
-                                        stage_a=(plan, wblob, range_flag))
-            if sel is None:                                            # reference :796-797
-                self._last_raw_period_count = self._last_valid_period_count = self._last_group_count = 0
-                return unchanged()
-            self._lazy_sel = sel                                       # counters resolve on access
-        else:
-            # foreign selector (reference tests inject stubs, :711-713) or env-flag
-            # grouping: group on the host, upload descriptor + weights
-            periods, amps = sel_mod(x)
-            if periods.numel() == 0:
-                return unchanged()
-            if periods.numel() > FTN_KMAX:
-                raise ValueError(f"{periods.numel()} period candidates exceed FTN_KMAX={FTN_KMAX}")
-            grp = PeriodGrouper(periods.detach().to("cpu", torch.long), amps.detach().float().cpu(), seq_len=L,
-                                min_period=getattr(sel_mod, "min_period_threshold", None),
-                                max_period=getattr(sel_mod, "pmax", None), block_index=self.block_index,
-                                freq_indices=getattr(sel_mod, "last_frequency_indices", None)).group()
-            self._lazy_sel = None
-            self._last_raw_period_count = int(periods.numel())
-            self._last_valid_period_count = int(grp.valid_mask.sum().item())
-            self._last_group_count = int(grp.periods.numel())
-            if grp.periods.numel() == 0:
-                return unchanged()
-            # softmax in fp32, rounded to the amplitudes' dtype and scatter-added in it, as the reference (:1000-1009)
-            w = _group_weights(amps.detach().cpu(), grp.mapping, grp.periods.numel(), B).float()
-            dh = lib.desc_from_periods(grp.periods.tolist(), L, 1, 2 ** 30)
-            if int(dh.n_groups) != grp.periods.numel():
-                raise RuntimeError("host grouping and descriptor disagree")
-            sel = runtime.selection_from_host(dh, w, x.device)
-        self._last_forms = self._forms(plan, B, L, adt, xf, native, getattr(sel, "stage_a", None) is not None)
-        y = runtime.timesblock_forward(xf, plan, wblob, sel, norm, adt, range_flag)
-        if y.dtype != x.dtype:
-            y = y.to(x.dtype)
-        if slot_ev is not None:
-            slot_ev.record()
-            self._range_pending.append((range_flag, slot_ev, x, y, post_norm))
-        elif not guarded:
+        sel = self._select(x, xf, plan, wblob, flag)
+        if sel is None:
+            # the reference returns x itself (:796-797); the shell then normalises x + (x - x)
+            if ev is not None:
+                self._range_slots.append((flag, ev))
+            if norm is None:
+                return x
+            y = runtime.residual_layernorm(xf, xf, *norm)
+            return y if y.dtype == x.dtype else y.to(x.dtype)
+        native = type(self.period_selector) is FFTPeriodSelector
+        self._last_forms = self._forms(plan, B=x.shape[0], L=x.shape[1], adt=adt, xf=xf, native=native,
+                                       fused_a=getattr(sel, "stage_a", None) is not None)
+        y = self._run(xf, x.dtype, sel, (wblob, plan), norm, flag)
+        if ev is not None:
+            ev.record()
+            self._range_pending.append((flag, ev, xf, y, norm, sel))
+        elif flag is None:
             self._last_engine_used = engine
         if _env_on("TIMESBLOCK_VEC_DISABLE"):
             # same kernels either way (the two reference paths are the same math, :866-953);
@@ -622,6 +574,60 @@ class TimesBlock(nn.Module):
             self._vec_calls += 1
             self._last_loop_iterations = 0
         return y
+
+    def _select(self, x: torch.Tensor, xf: torch.Tensor, plan, wblob: torch.Tensor, flag):
+        """This call's ``runtime.Selection``, or None when the block returns its input unchanged.  The native selector
+        runs on the device, and its finalize launch also runs stage A when it can (storing into ``flag``); any other
+        selector, or the env-flag grouping, groups on the host."""
+        from .. import lib, runtime
+
+        B, L, _ = x.shape
+        sel_mod = self.period_selector
+        if type(sel_mod) is FFTPeriodSelector:
+            # TIMES_PERIOD_MAX_UNIQ / TIMES_PERIOD_BINNING (per-depth schedules resolved here, :320-325) are grouping
+            # variants of the device finalize kernel: no host round trip on the native path
+            from ..grouping import _resolve_log_binning_base, _resolve_scheduled_int
+            max_unique = _resolve_scheduled_int(os.getenv("TIMES_PERIOD_MAX_UNIQ"), self.block_index)
+            log_base = _resolve_log_binning_base(os.getenv("TIMES_PERIOD_BINNING"), self.block_index)
+            sel = sel_mod.select_device(xf, act_dtype=x.dtype, max_unique=max_unique, log_base=log_base,
+                                        stage_a=(plan, wblob, flag))
+            if sel is None:                                            # reference :796-797
+                self._last_raw_period_count = self._last_valid_period_count = self._last_group_count = 0
+            else:
+                self._lazy_sel = sel                                   # counters resolve on access
+            return sel
+        # foreign selector (reference tests inject stubs, :711-713) or env-flag
+        # grouping: group on the host, upload descriptor + weights
+        periods, amps = sel_mod(x)
+        if periods.numel() == 0:
+            return None
+        if periods.numel() > FTN_KMAX:
+            raise ValueError(f"{periods.numel()} period candidates exceed FTN_KMAX={FTN_KMAX}")
+        grp = PeriodGrouper(periods.detach().to("cpu", torch.long), amps.detach().float().cpu(), seq_len=L,
+                            min_period=getattr(sel_mod, "min_period_threshold", None),
+                            max_period=getattr(sel_mod, "pmax", None), block_index=self.block_index,
+                            freq_indices=getattr(sel_mod, "last_frequency_indices", None)).group()
+        self._lazy_sel = None
+        self._last_raw_period_count = int(periods.numel())
+        self._last_valid_period_count = int(grp.valid_mask.sum().item())
+        self._last_group_count = int(grp.periods.numel())
+        if grp.periods.numel() == 0:
+            return None
+        # softmax in fp32, rounded to the amplitudes' dtype and scatter-added in it, as the reference (:1000-1009)
+        w = _group_weights(amps.detach().cpu(), grp.mapping, grp.periods.numel(), B).float()
+        dh = lib.desc_from_periods(grp.periods.tolist(), L, 1, 2 ** 30)
+        if int(dh.n_groups) != grp.periods.numel():
+            raise RuntimeError("host grouping and descriptor disagree")
+        return runtime.selection_from_host(dh, w, x.device)
+
+    def _run(self, xf: torch.Tensor, dtype: torch.dtype, sel, pack, norm=None, flag=None) -> torch.Tensor:
+        """Stages A-F of one call on a given selection and an engine's ``pack`` = ``(wblob, plan)`` (``_packed``): a
+        selection does not depend on the engine."""
+        from .. import runtime
+
+        wblob, plan = pack
+        y = runtime.timesblock_forward(xf, plan, wblob, sel, norm, runtime.ACT_DTYPE.get(dtype, 0), flag)
+        return y if y.dtype == dtype else y.to(dtype)
 
     # ---- torch backend (generic: any inception module, autograd, CPU) ----------
     def _forward_torch(self, x: torch.Tensor) -> torch.Tensor:

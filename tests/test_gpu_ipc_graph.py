@@ -194,3 +194,78 @@ def test_sharded_model_graph_two_ranks_on_one_gpu(tmp_path):
             got0, got1 = np.load(tmp_path / f"{name}{i}_0.npy"), np.load(tmp_path / f"{name}{i}_1.npy")
             assert np.array_equal(got0, got1)
             np.testing.assert_allclose(got0, np.load(tmp_path / f"want_{name}{i}.npy"), rtol=1e-4, atol=2e-5)
+
+
+# ---- f16x2 range repair with only rank 0's rows out of range -------------------------------------------------------
+def _range_worker(rank, world, port, out_dir):
+    import warnings
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    sys.path.insert(0, str(ROOT))
+    import torch.distributed as dist
+
+    import __graft_entry__ as ge
+    pkg = ge.load_package()
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=120))
+    try:
+        dev = torch.device("cuda:0")
+        xch = pkg.dist.IpcExchange(None, dev, f_cap=ML // 2 + 1, capturable=True)
+        # the bare block: rank 0 repairs its rows on its own, on the selection of the full batch
+        blk = _block(pkg, dev)
+        x = torch.from_numpy(np.load(os.path.join(out_dir, "x.npy"))).chunk(world, dim=0)[rank].to(dev)
+        runner = pkg.dist.ShardedTimesBlock(blk, exchange=xch)
+        with torch.inference_mode(), warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            y = runner(x, gather=False)
+            blk.check_range()
+        assert sum("fp16 range" in str(w.message) for w in seen) == (1 if rank == 0 else 0)
+        np.save(os.path.join(out_dir, f"y_{rank}.npy"), y.cpu().numpy())
+        np.save(os.path.join(out_dir, f"p_{rank}.npy"), np.asarray(blk.period_selector.last_selected_periods.tolist()))
+        block_calls = xch.calls()
+        # the whole model: every rank repeats the forward when one rank trips
+        model, xs = _model(pkg, dev)
+        xm = xs[0].clone()
+        xm[:MB // world] *= 1e6                                    # rank 0's rows
+        runner = pkg.dist.ShardedTimesNet(model, exchange=xch)
+        with torch.inference_mode(), warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            rate, disp = runner(xm.chunk(world, dim=0)[rank].contiguous(), gather=False)
+        assert sum("fp16 range" in str(w.message) for w in seen) == 1, [str(w.message) for w in seen]
+        assert all(b.engine == "bf16x3" for b in model.blocks)
+        with torch.inference_mode():
+            want = model(xm)                                       # unsharded, on bf16x3 now
+        for got, w in ((rate, want[0]), (disp, want[1])):
+            torch.testing.assert_close(got, w.chunk(world, dim=0)[rank], rtol=1e-4, atol=2e-5)
+        np.save(os.path.join(out_dir, f"calls_{rank}.npy"), np.asarray([block_calls, xch.calls()]))
+        xch.check()
+        xch.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_range_repair_two_ranks_on_one_gpu(ftn, tmp_path):
+    """Only rank 0's rows leave the fp16 range.  ShardedTimesBlock: check_range() repairs rank 0's rows without a second
+    exchange (the exchange counts stay equal), both ranks keep the full batch's periods, and the rows are the
+    reference's.  ShardedTimesNet: both ranks warn and run the forward twice, and match the unsharded bf16x3 model."""
+    from oracle import timesblock_oracle as orc
+    from test_gpu_range import _close
+
+    world = 2
+    x = ftn.synth.make_input(B, L, C, seed=6, planted=(24, 12, 8))
+    x = (x / np.abs(x).max()).astype(np.float32)
+    x[:B // world] *= np.float32(1e5)
+    np.save(tmp_path / "x.npy", x)
+    mp.spawn(_range_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    c0, c1 = np.load(tmp_path / "calls_0.npy").tolist(), np.load(tmp_path / "calls_1.npy").tolist()
+    assert c0 == c1 == [1, 1 + 2 * 3], (c0, c1)                   # one block call; two forwards of three blocks
+    sd = ftn.synth.make_inception_params(C, 4 * C, KS, 4.0, 3)
+    y_ref, aux = orc.timesblock_forward(torch.from_numpy(x), {k: torch.from_numpy(v) for k, v in sd.items()}, KS,
+                                        "gelu", K, L)
+    for r in range(world):
+        assert np.load(tmp_path / f"p_{r}.npy").tolist() == aux.sel.periods
+        rows = slice(r * B // world, (r + 1) * B // world)
+        y = np.load(tmp_path / f"y_{r}.npy")
+        assert np.isfinite(y).all()
+        err, tol = _close(y, y_ref.numpy()[rows], x[rows])
+        assert err <= tol, (r, err, tol)

@@ -170,3 +170,80 @@ def test_nan_row_stays_nan(ftn, dev):
     y = y.cpu().numpy()
     assert np.isnan(y[2]).all()
     assert np.isfinite(np.delete(y, 2, axis=0)).all()
+
+
+def test_repair_reuses_the_call_selection(ftn, dev, monkeypatch):
+    """Call 1 out of range, call 2 in range with other periods, then check_range(): call 1 is repeated on bf16x3 with
+    the selection it made.  The selector runs once per call and never for the repair, so the periods it reports are
+    still call 2's."""
+    from oracle import timesblock_oracle as orc
+
+    B, L, C, K = 3, 96, 64, 3
+    blk, _ = _block(ftn, dev, C, K, L)
+    safe, _ = _block(ftn, dev, C, K, L, engine="bf16x3")
+    plain, _ = _block(ftn, dev, C, K, L)
+    x1 = torch.from_numpy(_unit_input(ftn, B, L, C, 6) * np.float32(1e5))
+    base = ftn.synth.make_input(B, L, C, seed=7, planted=(16, 6, 32))
+    x2 = torch.from_numpy((base / np.abs(base).max()).astype(np.float32))
+    p1, p2 = orc.period_select(x1, K, L).periods, orc.period_select(x2, K, L).periods
+    assert p1 != p2
+    sel = blk.period_selector
+    calls = []
+    select = sel.select_device
+    monkeypatch.setattr(sel, "select_device", lambda *a, **k: calls.append(1) or select(*a, **k))
+    with torch.inference_mode():
+        want1, want2 = safe(x1.to(dev)), plain(x2.to(dev))
+        with pytest.warns(RuntimeWarning, match="fp16 range"):
+            y1 = blk(x1.to(dev))
+            y2 = blk(x2.to(dev))
+            assert blk.check_range() == "f16x2"                   # the last call ran on f16x2
+        assert blk._range_fallbacks == 1 and len(calls) == 2
+        assert sel.last_selected_periods.tolist() == p2
+        assert torch.equal(y1, want1) and torch.equal(y2, want2)
+
+
+def _model(ftn, dev, scale_block0=False, seed=0):
+    """A small direct-mode TimesNet with every zero-initialised layer randomised; ``scale_block0`` scales the first 1x1
+    of every branch of block 0 by 3e5 (as in test_gpu_recursive.py): its hidden values leave the fp16 range."""
+    cfg = dict(input_len=96, pred_len=8, d_model=64, d_ff=256, n_layers=2, k_periods=3, kernel_set=KS, dropout=0.0,
+               activation="gelu", mode="direct", bottleneck_ratio=4.0)
+    torch.manual_seed(seed)
+    model = ftn.models.TimesNet(**cfg).eval().to(dev)
+    x = (torch.from_numpy(ftn.synth.make_input(4, 96, 16, seed=seed + 3)).abs() + 0.5).to(dev)
+    g = torch.Generator().manual_seed(seed + 1)
+    with torch.no_grad():
+        model(x[:2])                                              # lazy build, on the device
+        for name, p in model.named_parameters():
+            if float(p.abs().sum()) == 0.0:
+                p.copy_(0.05 * torch.randn(p.shape, generator=g).to(p.device))
+            if scale_block0 and name.startswith("blocks.0.inception.0.paths.") and name.endswith("branch.0.weight"):
+                p.mul_(3e5)
+    return model, x
+
+
+def test_model_forward_is_repeated_on_bf16x3(ftn, dev):
+    """Eager TimesNet: one warning, every block on bf16x3, the outputs of a bf16x3 twin.  A captured forward does not
+    repeat itself: the replay that trips raises FloatingPointError from check_outputs()."""
+    model, x = _model(ftn, dev, scale_block0=True)
+    safe, _ = _model(ftn, dev, scale_block0=True)
+    for b in safe.blocks:
+        b.engine = "bf16x3"
+    with torch.inference_mode():
+        want = safe(x)
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            got = model(x)
+    hits = [w for w in seen if issubclass(w.category, RuntimeWarning) and "fp16 range" in str(w.message)]
+    assert len(hits) == 1, [str(w.message) for w in seen]
+    assert all(b.engine == "bf16x3" for b in model.blocks)
+    assert [b._range_fallbacks for b in model.blocks] == [1, 1]
+    assert all(not b.range_flag_on_device for b in model.blocks)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+
+    plain, x = _model(ftn, dev)                                   # in range: the warm-up calls stay on f16x2
+    g = ftn.graph.GraphedForward(plain, x)
+    g(x)
+    assert all(b._engine_name() == "f16x2" for b in plain.blocks)
+    with pytest.raises(FloatingPointError, match="captured"):
+        g(x * 1e6)
+    assert all(b._engine_name() == "f16x2" for b in plain.blocks)
