@@ -9,13 +9,23 @@
 #include "ftn_mlp.h"
 
 // softplus(beta=1, threshold=20) as torch evaluates it (x > 20 -> x, else log1p(exp(x))), in the
-// overflow-free form max(x,0) + log1p(exp(-|x|)).  exp2/log2 are the raw hardware ops (1 ulp);
-// below 2^-6 the series replaces log(1+e), whose argument rounding would cost relative accuracy.
+// overflow-free form max(x,0) + log1p(exp(-|x|)).  exp2/log2 are the raw hardware ops (1 ulp).  Two roundings would
+// each cost more than those: t = -|x| log2(e) rounded to fp32 is a relative error of |x| 2^-24 in e (5 ulp of the
+// result at x = -10), so t is carried as hi + lo and the lo part applied to e; and 1 + e rounded is a relative error
+// of 2^-24 / e in log(1 + e) (32 ulp just above e = 2^-6), so the rounding error of the sum is handed back through
+// log(u + d) = log(u) + d / u.  Below 2^-6 the series replaces the logarithm.  |x| is clamped at 128 (e = 0 in fp32
+// from |x| = 104 on) so that an infinite x does not meet inf - inf in the lo part; a NaN stays a NaN.
 __device__ __forceinline__ float softplus20(float x) {
   if (x > 20.f) return x;
-  const float e = __builtin_amdgcn_exp2f(-fabsf(x) * 1.44269504088896341f);
+  const float ax = fabsf(x);
+  const float a = ax > 128.f ? -128.f : -ax;
+  const float th = a * 1.44269504088896341f;
+  const float tl = fmaf(a, 1.44269504088896341f, -th) + a * 1.925963033500011e-8f;
+  float e = __builtin_amdgcn_exp2f(th);
+  e = fmaf(e, tl * 0.69314718055994531f, e);
   const float series = e * (1.f - e * (0.5f - e * (0.33333333333f - 0.25f * e)));
-  const float lg = __builtin_amdgcn_logf(1.f + e) * 0.69314718055994531f;
+  const float u = 1.f + e;
+  const float lg = fmaf(__builtin_amdgcn_logf(u), 0.69314718055994531f, (e - (u - 1.f)) * __builtin_amdgcn_rcpf(u));
   return fmaxf(x, 0.f) + (e < 0.015625f ? series : lg);
 }
 
@@ -269,12 +279,38 @@ __global__ __launch_bounds__(256, 3) void k_head_bf(HeadArgs a) {
   if (badbits) atomicOr(a.bad, badbits);
 }
 
+static const int g_head_f32 = [] { const char* e = getenv("FTN_HEAD_F32"); return e ? atoi(e) : 0; }();   // 1: the fp32-MFMA form
+
+// The form ftn_head_forward takes (include/flowtimes.h, FTN_SHELL_*): the one place the choice is made - the launch
+// below dispatches on this value and ftn_head_form exports it.  misalign: the OR of the byte offsets of tail, late,
+// rate and disp from a 16-byte boundary.  The cap on gridDim.y keeps three (16-bit forms) / four (fp32 forms)
+// workgroups per CU in flight; beyond 64 * cap rows a workgroup walks several row tiles.
+static int head_form(int N, int D, long long tail_bs, long long late_bs, unsigned misalign) {
+  const bool vec = N % 4 == 0 && tail_bs % 4 == 0 && late_bs % 4 == 0 && (misalign & 15) == 0;
+  if (vec && !g_head_f32) {
+    const int nt = D <= 64 ? 4 : 2, ns32 = D <= 32 ? 1 : D <= 64 ? 2 : 4;
+    const int ntile = (N + 16 * nt - 1) / (16 * nt);
+    const int cap = (3 * 256 + ntile - 1) / ntile;            // three workgroups per CU in flight
+    return FTN_SHELL_BF | FTN_SHELL_VEC | nt << 4 | ns32 << 8 | cap << 16;
+  }
+  const int ns = D <= 16 ? 1 : D <= 32 ? 2 : D <= 64 ? 4 : 8;
+  const int ntile = (N + 63) / 64;
+  const int cap = (4 * 256 + ntile - 1) / ntile;              // ~4 workgroups per CU in flight
+  return (vec ? FTN_SHELL_VEC : 0) | ns << 4 | cap << 16;
+}
+
+extern "C" int ftn_head_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or) {
+  FTN_CHECK_ARG(N >= 1 && D >= 4 && D % 4 == 0 && D <= 128 && misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0,
+                "ftn_head_form: N=%d d_model=%d misalign=%d", N, D, misalign_or);
+  return head_form(N, D, tail_bstride, late_bstride, (unsigned)misalign_or);
+}
+
 template <int NT, int NS32>
-static int launch_head_bf(const HeadArgs& a, hipStream_t st) {
+static int launch_head_bf(const HeadArgs& a, int form, hipStream_t st) {
   const int ntile = (a.N + 16 * NT - 1) / (16 * NT);
   const long long rtiles = (a.rows + 15) / 16;
   long long gy = (rtiles + 3) / 4;
-  const long long want = (3 * 256 + ntile - 1) / ntile;       // three workgroups per CU in flight
+  const long long want = form >> 16;
   if (gy > want) gy = want;
   const size_t lds = (size_t)2 * NT * NS32 * 3 * 1024 + 3 * 16 * NT * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)k_head_bf<NT, NS32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -284,17 +320,15 @@ static int launch_head_bf(const HeadArgs& a, hipStream_t st) {
   return 0;
 }
 
-static const int g_head_f32 = [] { const char* e = getenv("FTN_HEAD_F32"); return e ? atoi(e) : 0; }();   // 1: the fp32-MFMA form
-
 template <int NS>
-static int launch_head(const HeadArgs& a, bool vec, hipStream_t st) {
+static int launch_head(const HeadArgs& a, int form, hipStream_t st) {
   const int ntile = (a.N + 63) / 64;
   const long long rtiles = (a.rows + 15) / 16;
   long long gy = (rtiles + 3) / 4;
-  const long long want = (4 * 256 + ntile - 1) / ntile;       // ~4 workgroups per CU in flight
+  const long long want = form >> 16;
   if (gy > want) gy = want;
   const size_t lds = (size_t)2 * 4 * NS * 64 * sizeof(f4) + 192 * sizeof(float);
-  if (vec) hipLaunchKernelGGL((k_head<NS, true>), dim3(ntile, (unsigned)gy), dim3(256), lds, st, a);
+  if (form & FTN_SHELL_VEC) hipLaunchKernelGGL((k_head<NS, true>), dim3(ntile, (unsigned)gy), dim3(256), lds, st, a);
   else hipLaunchKernelGGL((k_head<NS, false>), dim3(ntile, (unsigned)gy), dim3(256), lds, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
@@ -320,18 +354,20 @@ extern "C" int ftn_head_forward(const float* hidden_dev, long long rows, int S, 
   a.rate = rate_dev; a.disp = disp_dev; a.bad = bad_flag_dev;
   a.rows = rows; a.tail_bs = tail_bstride; a.late_bs = late_bstride;
   a.S = S; a.D = D; a.N = N; a.hist = hist; a.floor_s = floor_scalar;
-  const bool vec = N % 4 == 0 && tail_bstride % 4 == 0 && late_bstride % 4 == 0 &&
-                   (((uintptr_t)tail_dev | (uintptr_t)late_dev_or_null | (uintptr_t)rate_dev | (uintptr_t)disp_dev) & 15) == 0;
+  const int form = head_form(N, D, tail_bstride, late_bstride,
+                             (unsigned)(((uintptr_t)tail_dev | (uintptr_t)late_dev_or_null | (uintptr_t)rate_dev |
+                                         (uintptr_t)disp_dev) & 15));
   hipStream_t st = (hipStream_t)stream;
-  if (vec && !g_head_f32) {
-    if (D <= 32) return launch_head_bf<4, 1>(a, st);
-    if (D <= 64) return launch_head_bf<4, 2>(a, st);
-    return launch_head_bf<2, 4>(a, st);
+  const int p0 = (form >> 4) & 15, p1 = (form >> 8) & 15;     // NT, NS32 (16-bit forms) | NS (fp32 forms)
+  if (form & FTN_SHELL_BF) {
+    if (p0 == 4 && p1 == 1) return launch_head_bf<4, 1>(a, form, st);
+    if (p0 == 4 && p1 == 2) return launch_head_bf<4, 2>(a, form, st);
+    return launch_head_bf<2, 4>(a, form, st);
   }
-  if (D <= 16) return launch_head<1>(a, vec, st);
-  if (D <= 32) return launch_head<2>(a, vec, st);
-  if (D <= 64) return launch_head<4>(a, vec, st);
-  return launch_head<8>(a, vec, st);
+  if (p0 == 1) return launch_head<1>(a, form, st);
+  if (p0 == 2) return launch_head<2>(a, form, st);
+  if (p0 == 4) return launch_head<4>(a, form, st);
+  return launch_head<8>(a, form, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -621,18 +657,38 @@ __global__ __launch_bounds__(256, RT == 1 ? (NO <= 4 ? 4 : 3) : (NO <= 4 ? 3 : 2
 }
 
 static const int g_embed_f32 = [] { const char* e = getenv("FTN_EMBED_F32"); return e ? atoi(e) : 0; }();   // 1: the fp32-MFMA form
+static const int g_embed_rt = [] { const char* e = getenv("FTN_EMBED_RT"); return e ? atoi(e) : 0; }();     // 1|2: RT of the 16-bit form
+
+// The form the embedding entry points take (include/flowtimes.h, FTN_SHELL_*): the one place the choice is made -
+// embed_launch dispatches on this value and ftn_embed_form exports it.  misalign: the OR of the byte offsets of x and
+// W from a 16-byte boundary.
+// d_model 128: one 16-row tile per wave - at 32 rows a wave the c4 shard (46 080 rows) is 1 440 waves for 1 024 SIMDs,
+// two on some, one on others, and the launch lasts as long as the SIMDs with two (350 vs 296 us); d_model <= 64: two
+// tiles per wave share every W fragment read (51 vs 61 us at the bench shape).  FTN_EMBED_RT=1|2 forces one.
+static int embed_form(int N, int D, long long x_bs, unsigned misalign) {
+  const bool vec = N % 4 == 0 && x_bs % 4 == 0 && (misalign & 15) == 0;
+  const int no = D <= 64 ? 4 : 8;
+  if (vec && !g_embed_f32) {
+    const int rt = g_embed_rt ? g_embed_rt : (no > 4 ? 1 : 2);
+    return FTN_SHELL_BF | FTN_SHELL_VEC | no << 4 | (rt == 1 ? 1 : 2) << 8;
+  }
+  return (vec ? FTN_SHELL_VEC : 0) | no << 4 | 2 << 8;        // k_embed_in: two row tiles per wave
+}
+
+extern "C" int ftn_embed_form(int N, int D, long long x_bstride, int x_misalign, int w_misalign) {
+  FTN_CHECK_ARG(N >= 1 && D >= 4 && D % 4 == 0 && D <= 128 && x_misalign >= 0 && x_misalign < 16 && x_misalign % 4 == 0 &&
+                    w_misalign >= 0 && w_misalign < 16 && w_misalign % 4 == 0,
+                "ftn_embed_form: N=%d d_model=%d misalign=%d/%d", N, D, x_misalign, w_misalign);
+  return embed_form(N, D, x_bstride, (unsigned)(x_misalign | w_misalign));
+}
 
 template <int NO>
-static int launch_embed(const EmbedArgs& a, bool vec, hipStream_t st) {
+static int launch_embed(const EmbedArgs& a, int form, hipStream_t st) {
   const long long M = (long long)a.B * a.L;
   const unsigned nblk = (unsigned)((M + 127) / 128);
-  // d_model 128: one 16-row tile per wave - at 32 rows a wave the c4 shard (46 080 rows) is 1 440 waves for 1 024 SIMDs,
-  // two on some, one on others, and the launch lasts as long as the SIMDs with two (350 vs 296 us); d_model <= 64: two
-  // tiles per wave share every W fragment read (51 vs 61 us at the bench shape).  FTN_EMBED_RT=1|2 forces one.
-  static const int rt_env = [] { const char* e = getenv("FTN_EMBED_RT"); return e ? atoi(e) : 0; }();
-  const int rt = rt_env ? rt_env : (NO > 4 ? 1 : 2);
-  if (vec && !g_embed_f32 && rt == 1) hipLaunchKernelGGL((k_embed_in_bf<NO, 1>), dim3((unsigned)((M + 63) / 64)), dim3(256), 0, st, a);
-  else if (vec && !g_embed_f32) hipLaunchKernelGGL((k_embed_in_bf<NO, 2>), dim3(nblk), dim3(256), 0, st, a);
+  const bool bf = form & FTN_SHELL_BF, vec = form & FTN_SHELL_VEC;
+  if (bf && ((form >> 8) & 15) == 1) hipLaunchKernelGGL((k_embed_in_bf<NO, 1>), dim3((unsigned)((M + 63) / 64)), dim3(256), 0, st, a);
+  else if (bf) hipLaunchKernelGGL((k_embed_in_bf<NO, 2>), dim3(nblk), dim3(256), 0, st, a);
   else if (vec) hipLaunchKernelGGL((k_embed_in<NO, true>), dim3(nblk), dim3(256), 0, st, a);
   else hipLaunchKernelGGL((k_embed_in<NO, false>), dim3(nblk), dim3(256), 0, st, a);
   FTN_CHECK_LAUNCH();
@@ -640,9 +696,9 @@ static int launch_embed(const EmbedArgs& a, bool vec, hipStream_t st) {
 }
 
 static int embed_launch(EmbedArgs& a, hipStream_t st) {
-  const bool vec = a.N % 4 == 0 && a.x_bs % 4 == 0 && (((uintptr_t)a.x | (uintptr_t)a.W) & 15) == 0;
-  if (a.D <= 64) return launch_embed<4>(a, vec, st);
-  return launch_embed<8>(a, vec, st);
+  const int form = embed_form(a.N, a.D, a.x_bs, (unsigned)(((uintptr_t)a.x | (uintptr_t)a.W) & 15));
+  if (((form >> 4) & 15) == 4) return launch_embed<4>(a, form, st);
+  return launch_embed<8>(a, form, st);
 }
 
 extern "C" int ftn_embed_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,

@@ -20,12 +20,13 @@ the whole unrolled H-step forecast as one HIP graph (every ring slot is a Python
 counter is needed).  Both are bit-identical to the reference loop driven over the same model on the same device.
 
 Anything else - CPU tensors, a ``direct``-mode model, autograd, ``embed_norm_mode="rms"``, d_model > 128, a foreign
-model - runs the reference's loop unchanged (``forecast_recursive_batch_loop``).
+model, a ``last_seq`` whose window takes another embedding kernel than the loop's later windows (a view that is not
+16-byte aligned, or whose batch stride is not a multiple of 4, with N % 4 == 0), ``embed_norm_mode="layer"`` at a
+d_model that is not a multiple of 16 - runs the reference's loop unchanged (``forecast_recursive_batch_loop``).
 """
 from __future__ import annotations
 
 import contextlib
-import os
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
@@ -36,6 +37,12 @@ _MISSING_Y_MARK = "Temporal features provided for history but missing future mar
 _SHORT_Y_MARK = "y_mark does not provide enough future steps for recursive forecasting"
 _RANGE_WARNING = ("TimesBlock: a value left the fp16 range of engine f16x2 (|v| >= 65504 or not finite) during a "
                   "recursive forecast; the forecast was repeated with every block on engine bf16x3")
+
+
+# embedding forms whose LayerNorm epilogue is bit-identical to k_embed_ring's at d_model % 16 == 0: the default forms
+# bar the fp32-MFMA one of d_model > 64 (k_embed_in<8, *>); the forms behind FTN_EMBED_F32 / FTN_EMBED_RT are not
+# (k_embed_in_bf<8,2> differs in the last bit) or not established
+RING_EXACT_LAYER_FORMS = frozenset({"k_embed_in_bf<4,2>", "k_embed_in_bf<8,1>", "k_embed_in<4,false>"})
 
 
 def _invoke_model(model, xb, x_mark=None, series_static=None, series_ids=None):
@@ -130,11 +137,24 @@ def _prepare(model, last_seq, x_mark, series_static, series_ids):
     tail = last_seq[:, -1:, :]
     if not (model._hip_embed_ok(window) and model._hip_heads_ok(tail, tail)):
         return False
-    # "layer" mode at d_model > 64 on the fp32-MFMA embedding form (N % 4 != 0, or FTN_EMBED_F32=1): the compiler
-    # contracts that kernel's LayerNorm epilogue into FMAs differently from k_embed_ring's, so the ring would not be
-    # bit-identical to the loop there: the loop runs instead
-    fp32_form = last_seq.size(2) % 4 != 0 or int(os.getenv("FTN_EMBED_F32", "0") or 0) != 0
-    return not (model.embedding.embed_norm_mode == "layer" and model.d_model > 64 and fp32_form)
+    # The ring holds the step-0 rows as the first window's kernel form computed them, while the loop re-embeds them at
+    # every step from a fresh torch.cat - an aligned view with batch stride T * N.  The forms differ when the first
+    # window is not 16-byte aligned or has a batch stride that is not a multiple of 4 while N % 4 == 0 (fp32 MFMA
+    # first, bf16x3 afterwards): not bit-identical, so the loop runs.  The library's own rule decides (embed_form).
+    from . import runtime
+
+    w = model.embedding.value_embedding.weight.detach()
+    B, T, N = last_seq.shape
+    form = runtime.embed_form(window, w)
+    if form != runtime.embed_form_of(N, w.size(0), T * N if B > 1 else 0, 0, w.data_ptr() & 15):
+        return False
+    # "layer" mode: the compiler contracts the LayerNorm epilogue of the GEMM kernels into FMAs differently from
+    # k_embed_ring's on some forms, and on every form at a d_model that is not a multiple of 16 (partly masked column
+    # tiles).  The ring is then equal to the loop up to rounding only, so it is used for the forms
+    # whose bit-identity the GPU suite establishes and the loop runs for the rest
+    if model.embedding.embed_norm_mode != "layer":
+        return True
+    return model.d_model % 16 == 0 and form in RING_EXACT_LAYER_FORMS
 
 
 def _device_ok(model, last_seq, H, x_mark, y_mark, series_static, series_ids) -> bool:

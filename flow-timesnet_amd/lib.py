@@ -13,7 +13,7 @@ from typing import Optional
 
 FTN_KMAX = 16
 FTN_MAXBR = 8
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "csrc" / "libflowtimes_hip.so"
@@ -165,6 +165,8 @@ _SIGNATURES = {
                                          _P]),
     "ftn_embed_ring": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, _P, C.c_float, _P,
                                  _P]),
+    "ftn_embed_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]),
+    "ftn_head_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

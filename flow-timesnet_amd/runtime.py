@@ -252,6 +252,47 @@ def timesblock_forms(plan: FtnPlan, B: int, L: int, act_dtype: int = 0, x_misali
             "r_summed": bool(f.r_summed), "E": _STAGE_E[f.stage_e].format(ns=ns), "half_round": bool(f.half_round)}
 
 
+def _embed_form_name(f: int) -> str:
+    no, rt = (f >> 4) & 15, (f >> 8) & 15
+    return f"k_embed_in_bf<{no},{rt}>" if f & 1 else f"k_embed_in<{no},{'true' if f & 2 else 'false'}>"
+
+
+def embed_form_of(N: int, D: int, x_bstride: int = 0, x_misalign: int = 0, w_misalign: int = 0) -> str:
+    """The kernel ``ftn_embed_forward`` / ``ftn_embed_rows_strided`` run for a window of N series into d_model D with
+    this batch stride (elements) and these byte offsets of x and W from a 16-byte boundary (``ftn_embed_form``,
+    host-only: the launch dispatches through the same function, switches included)."""
+    f = _lib.load().ftn_embed_form(int(N), int(D), int(x_bstride), int(x_misalign), int(w_misalign))
+    if f < 0:
+        check(f, "ftn_embed_form")
+    return _embed_form_name(f)
+
+
+def embed_form(window: torch.Tensor, weight: torch.Tensor) -> str:
+    """The kernel ``embed_forward(window, weight, ...)`` / ``embed_rows_strided(window, weight, ...)`` runs."""
+    B, _, N = window.shape
+    return embed_form_of(N, weight.shape[0], window.stride(0) if B > 1 else 0, _ptr(window) & 15, _ptr(weight) & 15)
+
+
+def head_form_of(N: int, D: int, tail_bstride: int = 0, late_bstride: int = 0, misalign_or: int = 0) -> Tuple[str, int]:
+    """The kernel ``ftn_head_forward`` runs (``ftn_head_form``, host-only) and the cap on its ``gridDim.y``: the
+    row loop of a workgroup iterates when ``rows > 64 * cap``."""
+    f = _lib.load().ftn_head_form(int(N), int(D), int(tail_bstride), int(late_bstride), int(misalign_or))
+    if f < 0:
+        check(f, "ftn_head_form")
+    p0, p1, cap = (f >> 4) & 15, (f >> 8) & 15, f >> 16
+    return (f"k_head_bf<{p0},{p1}>" if f & 1 else f"k_head<{p0},{'true' if f & 2 else 'false'}>"), cap
+
+
+def head_form(hidden: torch.Tensor, w_mu: torch.Tensor, tail: torch.Tensor, late=None) -> Tuple[str, int]:
+    """``head_form_of`` for the tensors ``head_forward`` would be given (its outputs are fresh, aligned tensors)."""
+    B = hidden.shape[0]
+    late_bs = 0
+    if late is not None and late.shape[0] == B and B > 1:
+        late_bs = late.shape[-2] * late.shape[-1]
+    mis = (_ptr(tail) | (_ptr(late) if late is not None else 0)) & 15
+    return head_form_of(w_mu.shape[0], hidden.shape[2], tail.stride(0) if B > 1 else 0, late_bs, mis)
+
+
 # ------------------------------------------------------------------ conv path
 def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel: Selection,
                        norm=None, act_dtype: int = 0, range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -291,11 +332,14 @@ def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel:
 
 
 def residual_layernorm(x: torch.Tensor, new: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
-                       eps: float) -> torch.Tensor:
-    """LayerNorm over the last axis of ``x + (new - x)`` (fp32, contiguous)."""
+                       eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """LayerNorm over the last axis of ``x + (new - x)`` (fp32, contiguous).  ``out`` may be ``new`` (in place)."""
     lib = _lib.load()
     Cc = x.shape[-1]
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be contiguous fp32 of x's shape")
     check(lib.ftn_residual_layernorm(_ptr(x), _ptr(new), _ptr(out), x.numel() // Cc, Cc, _ptr(gamma), _ptr(beta),
                                      float(eps), _stream(x.device)), "ftn_residual_layernorm")
     return out

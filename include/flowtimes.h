@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define FTN_ABI_VERSION 13
+#define FTN_ABI_VERSION 14
 #define FTN_KMAX 16      /* max period candidates / groups per block call        */
 #define FTN_MAXBR 8      /* max kernels in kernel_set                             */
 
@@ -435,6 +435,24 @@ int ftn_embed_rows_strided(const float* x_dev, long long x_bstride, int B, int L
 int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
                    long long add_bstride, const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null,
                    float ln_eps, float* out_dev, void* stream);
+
+/* ---- kernel forms of the model shell (ABI 14, host-only) ------------------------------------------------------
+ * Which kernel the embedding entry points (ftn_embed_forward, ftn_embed_rows_strided) and ftn_head_forward run.
+ * The launches dispatch through the same host functions, so the report is what runs; the environment switches the
+ * library reads (FTN_EMBED_F32, FTN_EMBED_RT, FTN_HEAD_F32) are reflected.  Encoding (both functions):
+ *   bit 0      FTN_SHELL_BF   1 = bf16x3 on the 16-bit matrix pipe (k_embed_in_bf / k_head_bf), 0 = exact fp32 MFMA
+ *   bit 1      FTN_SHELL_VEC  16-byte vector loads / stores (always set with FTN_SHELL_BF)
+ *   bits 4-7   first template argument:  NO (embedding: 4 | 8), NT (k_head_bf: 4 | 2), NS (k_head: 1 | 2 | 4 | 8)
+ *   bits 8-11  second template argument: RT (embedding: 16-row tiles per wave), NS32 (k_head_bf), 0 for k_head
+ *   bits 16-27 heads only: the cap on gridDim.y; a workgroup walks more than one 64-row group of `hidden` when
+ *              rows > 64 * cap
+ * *_misalign: byte offset of the pointer from a 16-byte boundary (0, 4, 8 or 12); for the heads the OR of the
+ * offsets of tail, late, rate and disp (hidden and the weights must be aligned).  Strides in elements, as the entry
+ * points take them.  Returns < 0 on a bad argument. */
+#define FTN_SHELL_BF 1
+#define FTN_SHELL_VEC 2
+int ftn_embed_form(int N, int D, long long x_bstride, int x_misalign, int w_misalign);
+int ftn_head_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or);
 
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,

@@ -42,3 +42,16 @@ def test_d_model_128_slice_under_switch(switch):
     tail = (r.stdout + r.stderr)[-1500:]
     assert r.returncode == 0, tail
     assert " passed" in r.stdout and "failed" not in r.stdout, tail
+
+
+@pytest.mark.parametrize("switch", ["FTN_EMBED_F32=1", "FTN_HEAD_F32=1", "FTN_EMBED_RT=1", "FTN_EMBED_RT=2"])
+def test_shell_forms_under_switch(switch):
+    """The model-shell kernels' other forms (fp32-MFMA vector embedding and heads, the embedding's other row tiling):
+    the form and edge cases of test_gpu_shell.py, whose expected forms follow the switch, without the 50 000-row ones."""
+    name, value = switch.split("=")
+    env = dict(os.environ, **{name: value})
+    r = subprocess.run([sys.executable, "-m", "pytest", str(ROOT / "tests" / "test_gpu_shell.py"), "-m", "gpu", "-x", "-q",
+                        "-k", "not row_loop"], env=env, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+    tail = (r.stdout + r.stderr)[-1500:]
+    assert r.returncode == 0, tail
+    assert " passed" in r.stdout and "failed" not in r.stdout, tail

@@ -33,7 +33,7 @@ def test_ctypes_row_exchange_matches_header(ftn):
     assert X.slots.offset == 0 and X.world.offset == 128 and X.rank.offset == 132
     assert X.rows_per_rank.offset == 136 and X.width.offset == 140 and X.kind.offset == 144 and C.sizeof(X) == 152
     assert int(re.search(r"FTN_ROWX_CHUNK (\d+)", _header()).group(1)) == ftn.lib.FTN_ROWX_CHUNK == CHUNK
-    assert ftn.lib.load().ftn_abi_version() == 13
+    assert ftn.lib.load().ftn_abi_version() == 14
 
 
 def test_exchange_layout_unchanged(ftn):
