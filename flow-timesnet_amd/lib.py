@@ -167,6 +167,8 @@ _SIGNATURES = {
                                  _P]),
     "ftn_embed_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]),
     "ftn_head_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_timeproj_forward": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "ftn_timeproj_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -319,6 +319,7 @@ class TimesNet(nn.Module):
         self._series_id_vocab: Optional[int] = None
         self._series_id_reference: Optional[torch.Tensor] = None
         self._last_head_backend = "torch"
+        self._last_timeproj_backend = "torch"
         self._last_embed_backend = "torch"
         self._defer_checks = False
         self._pending_bad = None
@@ -569,8 +570,9 @@ class TimesNet(nn.Module):
         if self._hip_heads_ok(seq, window):
             from .. import runtime
 
-            # one batched GEMM straight into [B, steps, d_model] (no permute copies), then ftn_head_forward
-            hidden = torch.baddbmm(bt.detach().view(1, -1, 1), wt.detach().unsqueeze(0).expand(B, -1, -1), seq.detach())
+            # ftn_timeproj_forward straight into [B, steps, d_model] (no permute copies), then ftn_head_forward
+            hidden = runtime.timeproj_forward(seq.detach().contiguous(), wt.detach(), bt.detach())
+            self._last_timeproj_backend = "hip"
             floor = self.min_sigma_vector
             floor_vec = None
             if isinstance(floor, torch.Tensor) and floor.numel() > 0:
@@ -584,6 +586,7 @@ class TimesNet(nn.Module):
             # deferred, check_outputs() reads the device word after a replay
             self._pending_bad = bad if self._defer_checks else bad.cpu()
             return rate, dispersion
+        self._last_timeproj_backend = "torch"
         hidden = torch.matmul(wt, seq) + bt.view(1, -1, 1)                                  # [B, steps, d_model]
         last = window[:, -hist:, :]
         if hist < steps:                                       # recursive mode / short windows: repeat the last step
@@ -716,6 +719,12 @@ class TimesNet(nn.Module):
         wt, bt = self.forecast_time_proj.weight, self.forecast_time_proj.bias
         if steps != self.pred_len:
             wt, bt = wt[-steps:], bt[-steps:]
+        if seq.is_cuda and seq.dtype == torch.float32 and self.d_model % 4 == 0 and self.d_model <= 128:
+            from .. import runtime
+
+            self._last_timeproj_backend = "hip"
+            return runtime.timeproj_forward(seq.detach().contiguous(), wt.detach(), bt.detach())
+        self._last_timeproj_backend = "torch"
         if seq.is_cuda:
             return torch.baddbmm(bt.detach().view(1, -1, 1), wt.detach().unsqueeze(0).expand(seq.size(0), -1, -1),
                                  seq.detach()).contiguous()

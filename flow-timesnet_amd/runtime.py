@@ -293,6 +293,21 @@ def head_form(hidden: torch.Tensor, w_mu: torch.Tensor, tail: torch.Tensor, late
     return head_form_of(w_mu.shape[0], hidden.shape[2], tail.stride(0) if B > 1 else 0, late_bs, mis)
 
 
+def timeproj_form_of(L: int, S: int, D: int, wt_misalign: int = 0) -> str:
+    """The kernel ``ftn_timeproj_forward`` runs for an ``L -> S`` projection at d_model D with W_t at this byte
+    offset from a 16-byte boundary (``ftn_timeproj_form``, host-only: the launch dispatches through the same
+    function): ``k_timeproj_row`` for S == 1, else ``k_timeproj_bf<NST,WV>``."""
+    f = _lib.load().ftn_timeproj_form(int(L), int(S), int(D), int(wt_misalign))
+    if f < 0:
+        check(f, "ftn_timeproj_form")
+    return f"k_timeproj_bf<{(f >> 4) & 15},{'true' if f & 2 else 'false'}>" if f & 1 else "k_timeproj_row"
+
+
+def timeproj_form(seq: torch.Tensor, wt: torch.Tensor) -> str:
+    """The kernel ``timeproj_forward(seq, wt, bt)`` runs."""
+    return timeproj_form_of(seq.shape[1], wt.shape[0], seq.shape[2], _ptr(wt) & 15)
+
+
 # ------------------------------------------------------------------ conv path
 def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel: Selection,
                        norm=None, act_dtype: int = 0, range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -371,6 +386,28 @@ def head_forward(hidden: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor, w
                                _ptr(floor_vec) if floor_vec is not None else None, float(floor_scalar),
                                _ptr(rate), _ptr(disp), _ptr(bad), _stream(dev)), "ftn_head_forward")
     return rate, disp, bad
+
+
+def timeproj_forward(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> torch.Tensor:
+    """``hidden[b] = wt @ seq[b] + bt[:, None]``: ``seq`` [B,L,D] contiguous fp32, ``wt`` [S,L] with contiguous rows
+    (a row slice of a taller weight is fine), ``bt`` [S].  Returns [B,S,D].  Row b of the result does not depend on
+    B or on which rows share the call."""
+    lib = _lib.load()
+    if seq.dim() != 3 or wt.dim() != 2 or bt.dim() != 1:
+        raise ValueError("timeproj_forward takes seq [B, L, D], wt [S, L] and bt [S]")
+    B, L, D = seq.shape
+    S = wt.shape[0]
+    if wt.shape[1] != L or bt.shape[0] != S:
+        raise ValueError(f"wt {tuple(wt.shape)} / bt {tuple(bt.shape)} do not project seq {tuple(seq.shape)}")
+    if any(t.dtype != torch.float32 or not t.is_cuda for t in (seq, wt, bt)):
+        raise ValueError("timeproj_forward takes fp32 device tensors")
+    if not seq.is_contiguous() or (S > 1 and wt.stride(0) != L) or (L > 1 and wt.stride(1) != 1) or \
+            (S > 1 and bt.stride(0) != 1):
+        raise ValueError("seq must be contiguous, wt rows contiguous with stride L, bt contiguous")
+    hidden = torch.empty(B, S, D, dtype=torch.float32, device=seq.device)
+    check(lib.ftn_timeproj_forward(_ptr(seq), B, L, D, _ptr(wt), _ptr(bt), S, _ptr(hidden), _stream(seq.device)),
+          "ftn_timeproj_forward")
+    return hidden
 
 
 def embed_forward(window: torch.Tensor, weight: torch.Tensor, add, norm=None) -> torch.Tensor:

@@ -454,6 +454,22 @@ int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const floa
 int ftn_embed_form(int N, int D, long long x_bstride, int x_misalign, int w_misalign);
 int ftn_head_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or);
 
+/* Time projection between the block stack and the heads (forecast_time_proj, :2063-2066):
+ *   hidden[b][s][:] = b_t[s] + sum_l W_t[s][l] seq[b][l][:]
+ * seq [B][L][D] and hidden [B][S][D] contiguous fp32, 16-byte aligned; W_t [S][L] with row stride L and b_t [S]
+ * need only 4-byte alignment (they may be the row slice weight[-S:]).  D a multiple of 4, <= 128; any B, L, S >= 1.
+ * The order in which the L terms of an output element are added depends on (L, S, D) alone: row b comes out
+ * bit-identical whatever B is and whichever rows share the call.  One launch, no workspace.
+ * ftn_timeproj_form (host-only; the launch dispatches through the same function): 0 = k_timeproj_row (S == 1, fp32
+ * FMA on the VALU); otherwise FTN_SHELL_BF (bf16x3 on the 16-bit matrix pipe, k_timeproj_bf<NST, WV>) with
+ *   bit 1      FTN_SHELL_VEC  WV: W_t is read with 16-byte loads (L % 4 == 0 and wt_misalign == 0)
+ *   bits 4-7   NST: 16-step tiles of S a wave accumulates (1 | 2 | 4 | 6); gridDim.y = ceil(S / (16 NST))
+ *   bits 8-11  waves of a workgroup, which share the K-32 slabs of L (8)
+ * Returns < 0 on a bad argument. */
+int ftn_timeproj_forward(const float* seq_dev, int B, int L, int D, const float* wt_dev, const float* bt_dev, int S,
+                         float* hidden_dev, void* stream);
+int ftn_timeproj_form(int L, int S, int D, int wt_misalign);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
