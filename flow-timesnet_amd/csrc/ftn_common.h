@@ -8,6 +8,8 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 
 void ftn_set_error(const char* fmt, ...);
+// the diagnostic stamp buffer (ftn_debug_stamps, block.hip) when `which_bit` of its selection is set, else null
+unsigned long long* ftn_stamp_buf(int which_bit, size_t* cap);
 
 #define FTN_CHECK_ARG(cond, ...)        \
   do {                                  \
@@ -124,6 +126,28 @@ __host__ __device__ inline void ftn_build_groups(const int* periods, int K, int 
 }
 
 #ifdef __HIPCC__
+// diagnostic cycle stamps (ftn_debug_stamps): thread 0 of a workgroup, 8 words per workgroup
+__device__ __forceinline__ void stamp(unsigned long long* buf, size_t cap, size_t wg, int slot) {
+  if (buf != nullptr && threadIdx.x == 0 && (wg * 8 + slot) < cap) buf[wg * 8 + slot] = __builtin_amdgcn_s_memtime();
+}
+
+// Workgroup barrier that waits only until at most `keep` of this wave's vector-memory operations are still in
+// flight (vmcnt retires in issue order on gfx9, loads and stores alike): the conv row loop issues
+//   LDS-DMA of row b+1 | compute row b | output stores of row b
+// and the next barrier needs the DMA, not the stores - a plain __syncthreads() waits vmcnt(0), i.e. one HBM write
+// round trip per batch row.  `keep` is wave-uniform.
+__device__ __forceinline__ void barrier_keep_vm(int keep) {
+  switch (keep) {
+    case 1: asm volatile("s_waitcnt vmcnt(1) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    case 2: asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    case 3: asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    case 4: asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    case 5: asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    case 6: asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+    default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); break;
+  }
+}
+
 // v_mfma_f32_16x16x4_f32: lane l supplies A[i=l&15][k=l>>4], B[k=l>>4][j=l&15];
 // result register r of lane l is D[i=4*(l>>4)+r][j=l&15]  (cdna_hip_programming.md §3).
 __device__ __forceinline__ f4 mfma16(float a, float b, f4 c) {

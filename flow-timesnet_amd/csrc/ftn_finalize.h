@@ -1,5 +1,5 @@
 // S3-S5 of the period selector as a device function (one 256-thread workgroup), shared by selector.hip's k_finalize
-// and by the fused finalize + stage-A launch of inception.hip (ftn_period_finalize_stage_a).
+// and by the fused finalize + stage-A launch of stage_a.hip (k_finalize_pw, ftn_period_finalize_stage_a).
 #pragma once
 #include <math.h>
 #include "ftn_common.h"

@@ -1,5 +1,6 @@
-// Shared between inception.hip and stagec_pos.hip: the split-engine stage-C argument block, the piece-product
-// chain, the in-register piece split and the guarded x loads (gfx950 only).
+// Shared by the stage-C units (stagec_px.hip, stagec_pos.hip), the block driver and every unit that runs the split
+// engines: the stage-C argument blocks and launch entries, the piece-product chain, the in-register piece split and
+// the guarded x loads (gfx950 only).
 #pragma once
 #include "ftn_common.h"
 
@@ -18,6 +19,27 @@ __device__ __forceinline__ f4 load_x4(const float* __restrict__ xrow, int c, int
   return v;
 }
 
+struct MlpArgs {
+  const float* x;
+  const float* m;        // [N][KM] conv output of block 1
+  const float* cfrag;    // [n_hchunks][cfrag_per_chunk][256]
+  const float* bo;       // [FP] bias of W_out1 (null when z = m)
+  const float* br;       // [FP] bias of W_res1 (null when res = x)
+  const float* bc;       // [16*n_ot]
+  float* outA;           // [N][AC]: first n_oa output tiles (a'), may be null
+  float* outG;           // [N][FP]: hidden store (single-conv mode), may be null
+  float* outR;           // [N][CP]: r = res2(g) - x
+  const FtnDesc* desc;
+  int B, L, C, CP, FP, KM, AC;
+  int nKM;               // K chunks of layer 1 (KM/16), 0: z = m (KM == FP)
+  int nCP;               // K chunks of the residual (CP/16), 0: res = x (FP == CP)
+  int n_oa;              // output tiles that go to outA
+  int n_ot;              // total output tiles (n_oa + CP/16 when res2 is a conv)
+  int res2_ident;        // 1: r = g - x  (FP == CP), taken from the hidden tiles
+  int n_hchunks, cfrag_per_chunk;
+  int outA_p3;           // 1: write a' as three bf16 pieces (bf16x3 conv engine), 2: two fp16 pieces (f16x2)
+  unsigned long long* dbg; size_t dbg_cap;
+};
 
 struct MlpBfArgs {
   const float* x;
@@ -82,7 +104,6 @@ __device__ __forceinline__ void split_pieces(const float (&v)[8], bf8 (&out)[NS]
   }
 }
 
-
 // ---------------------------------------------------------------- stage C, position-major (split engines, fp32 activations)
 // For t < L grid pixel t of EVERY period group is window position (b, t), and two of stage C's four
 // matrix products do not depend on the group at all:
@@ -104,6 +125,9 @@ struct MlpPosArgs {
   int n_main, n_tail;    // blocks [0, n_main) own window positions, [n_main, n_main + n_tail) the tail pixels
 };
 
+// pixel-major stage C (stagec_px.hip); act 0 GELU / 1 ReLU, nsplit = activation pieces, form = FTN_FORM_C_MLP_BF*
+int ftn_launch_mlp(const MlpArgs& ma, int act, bool xvec, long long Nmax, hipStream_t st);
+int ftn_launch_mlp_bf(const MlpBfArgs& mb, int form, int act, int nsplit, bool xvec, long long Nmax, hipStream_t st);
 // position-major stage C of the d_model-64 shape (stagec_pos.hip); act 0 GELU / 1 ReLU, nsplit = activation pieces
 int ftn_launch_mlp_pos64(const MlpPosArgs& pa, int act, int nsplit, bool xvec, int tail_units_bound, hipStream_t st);
 // the same for the d_model-128 shape (f16x2 only)

@@ -1,4 +1,4 @@
-// Stage E + F argument block and the pieces both of its kernels use (k_out in inception.hip, k_out_h in
+// Stage E + F argument block and the pieces both of its kernels use (k_out and k_out_h,
 // stage_out.hip); gfx950 only.
 #pragma once
 #include "ftn_common.h"
@@ -77,7 +77,8 @@ __device__ __forceinline__ void ln_tiles(f4 (&v)[NO][NPX], int n_ot, int C, int 
   }
 }
 
-
+// stage E + F on the exact fp32 MFMA (k_out); ident: merged-conv plan (z = m'), fast: FTN_FORM_E_OUT_FAST
+int ftn_launch_out(const OutArgs& oa, int act, bool xvec, bool ident, bool fast, hipStream_t st);
 // stage E + F with W_out2 m' on the 16-bit matrix pipe (stage_out.hip); act 0 GELU / 1 ReLU, nsplit 2 (f16x2) / 3 (bf16x3)
 int ftn_launch_out_h(const OutArgs& oa, int act, int nsplit, bool xvec, hipStream_t st);
 int ftn_out_h_enabled();

@@ -167,7 +167,7 @@ void frag_split(const Mat* W, int R, const int* cols, bool h2, uint16_t* dst) {
       }
 }
 
-#define CHUNK_TILES 2     // hidden row tiles per fp32 stage-C chunk (MLP_HT in inception.hip)
+#define CHUNK_TILES 2     // hidden row tiles per fp32 stage-C chunk (MLP_HT in stagec_px.hip)
 
 struct BlockFold {        // one InceptionBlock, bottleneck mode
   Mat W_in, W_out;        // [CA][cinP], [coutP][CA]
@@ -298,7 +298,7 @@ static int pack_impl(const FtnInceptionBlockWeights* blk0, const FtnInceptionBlo
     const int per = CHUNK_TILES * (nKM + nCP + n_ot);
     plan->n_hchunks = (FP + 16 * CHUNK_TILES - 1) / (16 * CHUNK_TILES);
     if (n_ot > 16 || (size_t)per * 1024 * 2 > 160 * 1024) {
-      plan->w_cfrag = 0; plan->cfrag_per_chunk = 0;             // generic stage C (inception.hip stagec_generic)
+      plan->w_cfrag = 0; plan->cfrag_per_chunk = 0;             // generic stage C (block.hip stagec_generic)
     } else {
       dvec cf((size_t)plan->n_hchunks * per * 256, 0.0);
       for (int hc = 0; hc < plan->n_hchunks; ++hc) {

@@ -2,7 +2,7 @@
 //   y = x + sum_g w[b,g] * ( act(W_out2 m'_g + b) + r_g )[:L]
 // (reference models/timesnet.py :1063-1069 delta, :1075-1092 weighted sum in group order, :818 residual).
 //
-// k_out (inception.hip) multiplies fp32 m' rows by fp32 fragments with v_mfma_f32_16x16x4_f32: 48 issues of 32
+// k_out (below) multiplies fp32 m' rows by fp32 fragments with v_mfma_f32_16x16x4_f32: 48 issues of 32
 // cycles per (16 positions, group).  Here the second conv leaves m' as the engine's activation pieces (the same
 // bytes per pixel for f16x2) and W_out2 arrives as K=32 fragments of three pieces (FtnPlan.w_out2fb): 24 issues of
 // 16 cycles.  The fragments (24 KB at d_model 64) sit in LDS, filled once per workgroup; a wave then strides over
@@ -14,6 +14,279 @@
 #include "ftn_mlp.h"
 #include "ftn_out.h"
 
+// ---------------------------------------------------------------- stages E + F, exact fp32 MFMA
+// One wave owns 2 units of 16 consecutive (b,t) positions and walks the groups in
+// ascending order (same summation order as the reference; deterministic, no
+// atomics); the tail pixels t >= L of every grid are never touched.  HBM/L2-bound:
+// reads m' and r once, x once, writes y once.
+// Fast path (FAST): K <= 48 and <= 4 output tiles (d_model <= 64, nbr*mid <= 48): the 12
+// weight fragments are group-independent and live in registers; per group the wave only
+// streams its m' and r rows, with the next group's m' rows requested one group ahead.
+template <int ACT, bool XVEC, bool IDENT, bool FAST, int NPX = 2>
+__global__ __launch_bounds__(256, NPX == 1 ? 3 : 2) void k_out(OutArgs a) {
+  const FtnDesc* __restrict__ d = a.desc;
+  const int total = a.B * a.L;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+  const int n0 = (blockIdx.x * 4 + wave) * (16 * NPX);
+  if (n0 >= total) return;
+  int bb[NPX], tt[NPX];
+  bool ok[NPX];
+#pragma unroll
+  for (int u = 0; u < NPX; ++u) {
+    int n = n0 + 16 * u + j;
+    ok[u] = n < total;
+    if (!ok[u]) n = total - 1;
+    bb[u] = n / a.L;
+    tt[u] = n - bb[u] * a.L;
+  }
+  const int G = d->n_groups, KM = a.KM, CP = a.CP, n_ot = CP >> 4;
+  if (FAST) {
+    const int nKM = KM >> 4;
+    f4 aw[4][3], bias[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      bias[o] = o < n_ot ? *(const f4*)(a.bias + 16 * o + 4 * q) : f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 3; ++s)
+        aw[o][s] = (o < n_ot && s < nKM) ? *(const f4*)(a.W + (size_t)(16 * o + j) * KM + 16 * s + 4 * q)
+                                         : f4{0.f, 0.f, 0.f, 0.f};
+    }
+    f4 yacc[4][NPX], mc[3][NPX];
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int u = 0; u < NPX; ++u) yacc[o][u] = f4{0.f, 0.f, 0.f, 0.f};
+    auto pix = [&](int g, int u) -> size_t {
+      const int P = d->g_px_off[g + 1] - d->g_px_off[g];
+      return (size_t)a.B * d->g_px_off[g] + (size_t)bb[u] * P + tt[u];
+    };
+    auto load_m = [&](int g, f4 (&dst)[3][NPX]) {
+#pragma unroll
+      for (int u = 0; u < NPX; ++u) {
+        const float* __restrict__ row = a.m + pix(g, u) * KM + 4 * q;
+#pragma unroll
+        for (int s = 0; s < 3; ++s) dst[s][u] = s < nKM ? *(const f4*)(row + 16 * s) : f4{0.f, 0.f, 0.f, 0.f};
+      }
+    };
+    if (G > 0) load_m(0, mc);
+    float wsum[NPX];
+#pragma unroll
+    for (int u = 0; u < NPX; ++u) wsum[u] = 0.f;
+    for (int g = 0; g < G; ++g) {
+      f4 rr[4][NPX], mn[3][NPX];
+      float w[NPX];
+#pragma unroll
+      for (int u = 0; u < NPX; ++u) {
+        if (!a.r_summed) {
+          const float* __restrict__ row = a.R + pix(g, u) * CP + 4 * q;
+#pragma unroll
+          for (int o = 0; o < 4; ++o) rr[o][u] = o < n_ot ? *(const f4*)(row + 16 * o) : f4{0.f, 0.f, 0.f, 0.f};
+        } else {
+#pragma unroll
+          for (int o = 0; o < 4; ++o) rr[o][u] = f4{0.f, 0.f, 0.f, 0.f};
+        }
+        w[u] = a.wts[(size_t)bb[u] * FTN_KMAX + g];
+        wsum[u] += w[u];
+      }
+      load_m(g + 1 < G ? g + 1 : g, mn);
+      f4 z[4][NPX];
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+#pragma unroll
+        for (int u = 0; u < NPX; ++u) z[o][u] = bias[o];
+#pragma unroll
+      for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int o = 0; o < 4; ++o)
+#pragma unroll
+            for (int u = 0; u < NPX; ++u) z[o][u] = mfma16(aw[o][s][e], mc[s][u][e], z[o][u]);
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+#pragma unroll
+        for (int u = 0; u < NPX; ++u) {
+          if (a.act_dtype == 0) yacc[o][u] += (act4<ACT>(z[o][u]) + rr[o][u]) * w[u];
+          else yacc[o][u] += rnd_act4(rnd_act4(act4<ACT>(z[o][u]) + rr[o][u], a.act_dtype) * w[u], a.act_dtype);
+        }
+#pragma unroll
+      for (int s = 0; s < 3; ++s)
+#pragma unroll
+        for (int u = 0; u < NPX; ++u) mc[s][u] = mn[s][u];
+    }
+    const bool ln = a.ln_g != nullptr;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      if (o < n_ot) {
+#pragma unroll
+        for (int u = 0; u < NPX; ++u) {
+          const int ch = 16 * o + 4 * q;
+          const size_t e0 = ((size_t)bb[u] * a.L + tt[u]) * a.C + ch;
+          f4 xv = {0.f, 0.f, 0.f, 0.f};
+          if (XVEC) {
+            if (ch < a.C) xv = *(const f4*)(a.x + e0);
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (ch + r < a.C) xv[r] = a.x[e0 + r];
+          }
+          if (a.r_summed && ch < CP)                                     // the group-summed residual of k_mlp_pos
+            yacc[o][u] += *(const f4*)(a.R + ((size_t)bb[u] * a.L + tt[u]) * CP + ch);
+          if (a.r_keeps_x) yacc[o][u] = yacc[o][u] - xv * wsum[u];      // the x that stage C left inside every R_g
+          const f4 nv = a.act_dtype == 0 ? xv + yacc[o][u] : rnd_act4(xv + rnd_act4(yacc[o][u], a.act_dtype), a.act_dtype);
+          yacc[o][u] = ln ? xv + (nv - xv) : nv;
+        }
+      }
+    }
+    if (ln) ln_tiles<4, NPX>(yacc, n_ot, a.C, q, a.ln_g, a.ln_b, a.ln_eps);
+    if (a.range_flag != nullptr) {
+      bool bad = false;
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+#pragma unroll
+        for (int u = 0; u < NPX; ++u)
+          if (o < n_ot && ok[u]) bad |= not_finite4(yacc[o][u]);
+      raise_range_flag(a.range_flag, bad);
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      if (o < n_ot) {
+#pragma unroll
+        for (int u = 0; u < NPX; ++u) {
+          if (!ok[u]) continue;
+          const int ch = 16 * o + 4 * q;
+          const size_t e0 = ((size_t)bb[u] * a.L + tt[u]) * a.C + ch;
+          if (XVEC) {
+            if (ch < a.C) *(f4*)(a.y + e0) = yacc[o][u];
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (ch + r < a.C) a.y[e0 + r] = yacc[o][u][r];
+          }
+        }
+      }
+    }
+    return;
+  }
+  for (int og = 0; og < n_ot; og += 4) {
+    f4 yacc[4][NPX];
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+      for (int u = 0; u < NPX; ++u) yacc[o][u] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int g = 0; g < G; ++g) {
+      const int P = d->g_px_off[g + 1] - d->g_px_off[g];
+      size_t pn[NPX];
+      float w[NPX];
+#pragma unroll
+      for (int u = 0; u < NPX; ++u) {
+        pn[u] = (size_t)a.B * d->g_px_off[g] + (size_t)bb[u] * P + tt[u];
+        w[u] = a.wts[(size_t)bb[u] * FTN_KMAX + g];
+      }
+      f4 z[4][NPX];
+      if (IDENT) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+#pragma unroll
+          for (int u = 0; u < NPX; ++u) {
+            f4 v = {0.f, 0.f, 0.f, 0.f};
+            if (og + o < n_ot) v = *(const f4*)(a.m + pn[u] * KM + 16 * (og + o) + 4 * q);
+            z[o][u] = v;
+          }
+      } else {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          f4 bv = {0.f, 0.f, 0.f, 0.f};
+          if (og + o < n_ot) bv = *(const f4*)(a.bias + 16 * (og + o) + 4 * q);
+#pragma unroll
+          for (int u = 0; u < NPX; ++u) z[o][u] = bv;
+        }
+        for (int s = 0; s < KM; s += 16) {
+          f4 bf[NPX];
+#pragma unroll
+          for (int u = 0; u < NPX; ++u) bf[u] = *(const f4*)(a.m + pn[u] * KM + s + 4 * q);
+#pragma unroll
+          for (int o = 0; o < 4; ++o) {
+            if (og + o < n_ot) {
+              const f4 af = *(const f4*)(a.W + (size_t)(16 * (og + o) + j) * KM + s + 4 * q);
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int u = 0; u < NPX; ++u) z[o][u] = mfma16(af[e], bf[u][e], z[o][u]);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int o = 0; o < 4; ++o) {
+        if (og + o < n_ot) {
+#pragma unroll
+          for (int u = 0; u < NPX; ++u) {
+            const f4 r = *(const f4*)(a.R + pn[u] * CP + 16 * (og + o) + 4 * q);
+            const f4 dl = act4<ACT>(z[o][u]) + r;
+            if (a.act_dtype == 0) yacc[o][u] += dl * w[u];
+            else yacc[o][u] += rnd_act4(rnd_act4(dl, a.act_dtype) * w[u], a.act_dtype);
+          }
+        }
+      }
+    }
+    if (a.range_flag != nullptr) {
+      bool bad = false;
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+#pragma unroll
+        for (int u = 0; u < NPX; ++u)
+          if (og + o < n_ot && ok[u]) bad |= not_finite4(yacc[o][u]);
+      raise_range_flag(a.range_flag, bad);
+    }
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      if (og + o < n_ot) {
+#pragma unroll
+        for (int u = 0; u < NPX; ++u) {
+          if (!ok[u]) continue;
+          const int ch = 16 * (og + o) + 4 * q;
+          const size_t e0 = ((size_t)bb[u] * a.L + tt[u]) * a.C + ch;
+          if (XVEC) {
+            if (ch < a.C) {
+              const f4 xv = *(const f4*)(a.x + e0);
+              *(f4*)(a.y + e0) = a.act_dtype == 0 ? xv + yacc[o][u] : rnd_act4(xv + rnd_act4(yacc[o][u], a.act_dtype), a.act_dtype);
+            }
+          } else {
+            const f4 sr = rnd_act4(yacc[o][u], a.act_dtype);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (ch + r < a.C) {
+                const float t = a.x[e0 + r] + sr[r];
+                a.y[e0 + r] = a.act_dtype == 1 ? (float)(__bf16)t : (a.act_dtype == 2 ? (float)(_Float16)t : t);
+              }
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int ACT>
+static int launch_out_t(const OutArgs& oa, bool xvec, bool ident, bool fast, hipStream_t st) {
+  const dim3 nblk((unsigned)(((long long)oa.B * oa.L + 127) / 128)), blk(256);
+  // FAST path: 16 pixels per wave (3 waves/SIMD; with 32 the kernel needs > 256 registers -> 1 wave/SIMD)
+  const dim3 nblk_fast((unsigned)(((long long)oa.B * oa.L + 63) / 64));
+  if (ident && xvec) hipLaunchKernelGGL((k_out<ACT, true, true, false>), nblk, blk, 0, st, oa);
+  else if (ident) hipLaunchKernelGGL((k_out<ACT, false, true, false>), nblk, blk, 0, st, oa);
+  else if (xvec && fast) hipLaunchKernelGGL((k_out<ACT, true, false, true, 1>), nblk_fast, blk, 0, st, oa);
+  else if (xvec) hipLaunchKernelGGL((k_out<ACT, true, false, false>), nblk, blk, 0, st, oa);
+  else if (fast) hipLaunchKernelGGL((k_out<ACT, false, false, true, 1>), nblk_fast, blk, 0, st, oa);
+  else hipLaunchKernelGGL((k_out<ACT, false, false, false>), nblk, blk, 0, st, oa);
+  FTN_CHECK_LAUNCH();
+  return 0;
+}
+
+int ftn_launch_out(const OutArgs& oa, int act, bool xvec, bool ident, bool fast, hipStream_t st) {
+  return act == 1 ? launch_out_t<1>(oa, xvec, ident, fast, st) : launch_out_t<0>(oa, xvec, ident, fast, st);
+}
+
+// ---------------------------------------------------------------- stages E + F, 16-bit matrix pipe
 template <int ACT, bool XVEC, int NS, bool RSUM, int NOT, int NSK>
 __global__ __launch_bounds__(256, NOT <= 4 ? 3 : 2) void k_out_h(OutArgs a) {
   constexpr int NWP = PxFmt<NS>::NW, PXE = PxFmt<NS>::ELEMS;

@@ -4,11 +4,6 @@
 #include <stdlib.h>
 #include "ftn_mlp.h"
 
-// diagnostic cycle stamps (ftn_debug_stamps, tools/stamps_pos.py): thread 0 of a workgroup, 8 words per workgroup
-__device__ __forceinline__ void stamp(unsigned long long* buf, size_t cap, size_t wg, int slot) {
-  if (buf != nullptr && threadIdx.x == 0 && (wg * 8 + slot) < cap) buf[wg * 8 + slot] = __builtin_amdgcn_s_memtime();
-}
-
 // s_waitcnt vmcnt(n) for a wave-uniform n that is a multiple of STEP (vmcnt takes an immediate)
 template <int STEP, int MAXN>
 __device__ __forceinline__ void wait_vm_keep(int n) {
@@ -378,6 +373,7 @@ static int launch_mlp_pos_t(MlpPosArgs pa, int tail_units_bound, hipStream_t st)
   if (lds > 160 * 1024) { ftn_set_error("position-major stage C needs %zu B of LDS", lds); return -1; }
   const long long units = (long long)pa.c.B * ((pa.c.L + 15) / 16);
   pa.n_main = (int)((units + NWV - 1) / NWV);
+  pa.c.dbg = ftn_stamp_buf(2, &pa.c.dbg_cap);                   // tools/stamps_pos.py
   // the tail pixels are few (pad_g < period): a fixed set of workgroups strides over them
   const int tail_wg = (tail_units_bound + NWV - 1) / NWV;
   pa.n_tail = tail_wg < 512 ? tail_wg : 512;

@@ -203,7 +203,7 @@ def _frag(W: np.ndarray, R: int, S: int) -> np.ndarray:
     return blk.reshape(16, 4, 4).transpose(1, 0, 2).reshape(-1)
 
 
-CHUNK_TILES = 2   # hidden row tiles (of 16 channels) per stage-C chunk; must match HT in csrc/inception.hip
+CHUNK_TILES = 2   # hidden row tiles (of 16 channels) per stage-C chunk; must match MLP_HT in csrc/stagec_px.hip
 
 
 def _pack_cfrag(W_out, W_res, W_c, FP: int, nKM: int, nCP: int, n_ot: int) -> np.ndarray:
@@ -456,7 +456,7 @@ def pack_inception_numpy(
         per = CHUNK_TILES * (nKM + nCP + n_ot)
         plan.n_hchunks = (FP + 16 * CHUNK_TILES - 1) // (16 * CHUNK_TILES)
         if n_ot > 16 or per * 1024 * 2 > 160 * 1024:
-            # beyond the fused stage-C kernels (csrc/inception.hip stagec_generic): the chain runs as generic
+            # beyond the fused stage-C kernels (csrc/block.hip stagec_generic): the chain runs as generic
             # pointwise launches on the row-major matrices, no fragments needed
             plan.w_cfrag, plan.cfrag_per_chunk = 0, 0
         else:

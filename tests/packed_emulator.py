@@ -1,5 +1,5 @@
 """numpy emulation of what the HIP kernels do with a packed weight blob
-(stages A-F of flow-timesnet_amd/csrc/inception.hip).  Test infrastructure: it
+(stages A-F of the forward in flow-timesnet_amd/csrc/block.hip).  Test infrastructure: it
 lets the CPU suite validate the host-side folding/packing (pack.py) and the stage
 algebra (live zero tail pixels, zero conv halo, r = res2 - x) against the oracle
 without a GPU."""

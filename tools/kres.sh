@@ -1,6 +1,6 @@
 #!/bin/bash
 # Compile one csrc/*.hip with the kernel-resource-usage remarks and print VGPRs / spills of kernels matching $2.
-# usage: tools/kres.sh inception k_mlp_pos
+# usage: tools/kres.sh stagec_pos k_mlp_pos     ($1 = the unit's file name without .hip, $2 = a kernel name pattern)
 set -e
 cd "$(dirname "$(readlink -f "$0")")/../flow-timesnet_amd/csrc"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wall -Wno-unused-function \
