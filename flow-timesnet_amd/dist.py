@@ -25,6 +25,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import range_guard
+from .models.shell import hip_width_ok
 
 
 def _refuse_flagged_grouping(block_index=None) -> None:
@@ -486,7 +487,7 @@ class SeriesShardedTimesNet(_ShardedModel):
         hip = x_local.is_cuda
         if hip:
             D = int(m.d_model)
-            if D % 4 or D > 128:
+            if not hip_width_ok(D):
                 raise ValueError(f"d_model={D} is outside the HIP kernels' limits (a multiple of 4, <= 128)")
             if x_local.dtype != torch.float32:
                 raise ValueError("SeriesShardedTimesNet takes fp32 inputs on the HIP path")

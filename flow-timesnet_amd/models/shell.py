@@ -6,8 +6,18 @@ constructor signatures, attribute names, error messages and ``state_dict`` keys 
 SURVEY section 8f ranks 1-2.  The structure is this package's own: the lazily built layers come from one declarative
 table (``_LAZY_TABLE``), and the forward is four stages - series context rows, embedding front end, block stack,
 heads - each of which calls the HIP entry point for its stage when the tensors live on a ROCm device
-(``ftn_embed_forward``, the TimesBlock kernels with the LayerNorm epilogue, ``ftn_head_forward``) and composes
-stock torch ops otherwise (CPU tensors, autograd, dropout in training).
+(``ftn_embed_forward``, the TimesBlock kernels with the LayerNorm epilogue, ``ftn_timeproj_forward``,
+``ftn_head_forward``) and composes stock torch ops otherwise (CPU tensors, autograd, dropout in training).
+
+Each stage has one body, and three callers compose them: the plain forward (``_forward_once``), the device recursive
+forecaster (``forecast.py``) and the series-sharded forward (``dist.SeriesShardedTimesNet``, through the thin
+``series_*`` entry points, which hand the same bodies this rank's slices):
+
+* context rows - ``_rows_of`` (``_context_rows`` / ``series_context_rows`` resolve the ids their own way);
+* embedding - ``_context_terms``, then ``_through_weight`` + ``_embed_epilogue`` (HIP) or ``_with_context`` (torch);
+* heads - ``_late_bias``, ``_time_projection``, ``_rate_dispersion``.
+
+``hip_width_ok`` is the one statement of the d_model these kernels take.
 """
 from __future__ import annotations
 
@@ -20,28 +30,19 @@ from torch import nn
 from torch.utils.checkpoint import checkpoint
 
 from .. import range_guard
-from .timesnet import FFTPeriodSelector, LowRankTemporalContext, TimesBlock
-
-_HALF = (torch.float16, torch.bfloat16)
-
-
-def _fp32_if_half(dtype: torch.dtype) -> torch.dtype:
-    return torch.float32 if dtype in _HALF else dtype
+from .timesnet import (FFTPeriodSelector, LowRankTemporalContext, TimesBlock, _layer_norm_fp32 as _norm, _ln_params,
+                       _param_key, _safe_param_dtype)
 
 
 def _place(module: nn.Module, ref: torch.Tensor) -> nn.Module:
     """Lazily built modules follow the input's device; parameters stay fp32 for
     half-precision inputs (reference :30-34)."""
-    return module.to(device=ref.device, dtype=_fp32_if_half(ref.dtype))
+    return module.to(device=ref.device, dtype=_safe_param_dtype(ref.dtype))
 
 
-def _norm(module: nn.Module, x: torch.Tensor) -> torch.Tensor:
-    """LayerNorm with fp32 statistics for half inputs; other modules as they are."""
-    if not isinstance(module, nn.LayerNorm):
-        return module(x)
-    cd = _fp32_if_half(x.dtype)
-    cast = lambda p: None if p is None else p.to(cd)
-    return F.layer_norm(x.to(cd), module.normalized_shape, cast(module.weight), cast(module.bias), module.eps).to(x.dtype)
+def hip_width_ok(d_model: int) -> bool:
+    """The d_model the shell's HIP kernels (embedding, time projection, heads) take."""
+    return d_model % 4 == 0 and d_model <= 128
 
 
 # -------------------------------------------------------------------------
@@ -84,7 +85,7 @@ class RMSNorm(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.size(-1) != self.weight.numel():
             raise ValueError("RMSNorm dimension mismatch")
-        cd = _fp32_if_half(x.dtype)
+        cd = _safe_param_dtype(x.dtype)
         v = x.to(cd)
         inv_rms = torch.rsqrt(v.square().mean(dim=-1, keepdim=True) + self.eps)
         return torch.addcmul(self.bias.to(cd), v * inv_rms, self.weight.to(cd)).to(x.dtype)
@@ -414,37 +415,31 @@ class TimesNet(nn.Module):
         self.pre_embedding_dropout.to(x.device)
         self.forecast_time_proj = _place(self.forecast_time_proj, x)
 
-        floor = self.min_sigma_vector
-        if isinstance(floor, torch.Tensor) and floor.numel() > 0:
+        floor = self._floor_vector()
+        if floor is not None:
             if int(floor.shape[-1]) < n_series:
                 raise ValueError("min_sigma_vector length does not match number of series")
             self.min_sigma_vector = floor[..., :n_series]
         self.embedding_time_features = time_dim
         self.output_dim = n_series
 
-    def _dispersion_floor_from_ref(self, ref: torch.Tensor) -> torch.Tensor:
+    def _floor_vector(self) -> Optional[torch.Tensor]:
+        """``min_sigma_vector`` when it is set (any shape, N elements), else None: the scalar ``min_sigma`` applies."""
         floor = self.min_sigma_vector
-        if isinstance(floor, torch.Tensor) and floor.numel() > 0:
-            return floor.to(device=ref.device, dtype=ref.dtype).expand_as(ref).clone()
-        return torch.full_like(ref, self.min_sigma)
+        return floor if isinstance(floor, torch.Tensor) and floor.numel() > 0 else None
+
+    def _uses_ids(self) -> bool:
+        return self.series_embedding is not None and self.id_embed_dim > 0
 
     # ---- series context: [Bc, N, ctx] rows the context / late-bias maps read ----------------
     def _context_rows(self, window, series_static, series_ids) -> Optional[torch.Tensor]:
-        """Static projection and id embedding side by side, through ``context_norm`` (:1883-1956).  Every op is
-        row-wise, so when the static features / ids are shared by the batch (2-D / 1-D inputs, the pipeline's
-        case) the rows are built once (Bc = 1) and broadcast by their consumers."""
+        """``_rows_of`` for the whole model: missing ids default to the remembered ones, given ids are remembered."""
         B, _, N = window.shape
-        shared = ((series_static is None or series_static.ndim == 2)
-                  and (series_ids is None or series_ids.ndim == 1 or series_ids.size(0) == 1))
-        Bc = 1 if shared else B
-        cols = []
-        if self.static_proj is not None and series_static is not None:
-            if series_static.ndim == 3 and series_static.size(0) != B:
-                raise ValueError("series_static batch dimension must match input batch size")
-            st = series_static if series_static.ndim == 3 else series_static.unsqueeze(0).expand(Bc, -1, -1)
-            proj = self.static_proj(st.to(device=window.device, dtype=window.dtype, non_blocking=window.is_cuda))
-            cols.append(proj if self.static_norm is None else _norm(self.static_norm, proj))
-        if self.series_embedding is not None and self.id_embed_dim > 0:
+        if (self.static_proj is not None and series_static is not None and series_static.ndim == 3
+                and series_static.size(0) != B):
+            raise ValueError("series_static batch dimension must match input batch size")
+        ids = series_ids
+        if self._uses_ids():
             if series_ids is not None:
                 ids = series_ids.view(1, -1) if series_ids.ndim == 1 else series_ids
                 if ids.size(0) not in (1, B):
@@ -458,6 +453,23 @@ class TimesNet(nn.Module):
                 if remembered is not None and remembered.numel() != N:
                     raise ValueError("Stored series identifiers do not match input dimension")
                 ids = (torch.arange(N, device=window.device) if remembered is None else remembered.to(window.device)).view(1, N)
+        return self._rows_of(window, series_static, ids)
+
+    def _rows_of(self, window, static, ids) -> Optional[torch.Tensor]:
+        """Static projection and id embedding side by side, through ``context_norm`` (:1883-1956), from checked
+        inputs: ``static`` None, [N, F] or [B, N, F]; ``ids`` long [1|B, N] on the window's device when the model
+        embeds ids (otherwise only their batch shape is looked at).  Every op is row-wise, so when the static
+        features / ids are shared by the batch (2-D / one-row inputs, the pipeline's case) the rows are built once
+        (Bc = 1) and broadcast by their consumers."""
+        B = window.size(0)
+        shared = (static is None or static.ndim == 2) and (ids is None or ids.ndim == 1 or ids.size(0) == 1)
+        Bc = 1 if shared else B
+        cols = []
+        if self.static_proj is not None and static is not None:
+            st = static if static.ndim == 3 else static.unsqueeze(0).expand(Bc, -1, -1)
+            proj = self.static_proj(st.to(device=window.device, dtype=window.dtype, non_blocking=window.is_cuda))
+            cols.append(proj if self.static_norm is None else _norm(self.static_norm, proj))
+        if self._uses_ids():
             cols.append(self.series_embedding(ids.expand(Bc, -1) if ids.size(0) != Bc else ids))
         if not cols:
             return None
@@ -474,8 +486,7 @@ class TimesNet(nn.Module):
             return False
         return (window.is_cuda and window.dtype == torch.float32
                 and not (torch.is_grad_enabled() and (window.requires_grad or emb.value_embedding.weight.requires_grad))
-                and not (self.training and self.dropout > 0.0)
-                and self.d_model % 4 == 0 and self.d_model <= 128
+                and not (self.training and self.dropout > 0.0) and hip_width_ok(self.d_model)
                 and window.stride(2) == 1 and window.stride(1) == window.size(2))
 
     def _context_terms(self, rows):
@@ -488,22 +499,46 @@ class TimesNet(nn.Module):
                 bias = self.context_proj(rows.to(self.context_proj.weight.dtype)).squeeze(-1)
         return coeff, bias
 
+    def _through_weight(self, add, coeff, bias, L: int, w):
+        """``add`` (None = nothing yet) plus the two context terms pushed through the value weight ``w`` [D, N] (or a
+        column slice of it): ``(add + project(coeff)) + bias @ w^T``, summed left to right - the recursive forecaster
+        and the graph tests rest on these bits.  None when there is nothing to add."""
+        terms = (None if coeff is None else self.temporal_context.project(coeff.detach().float(), L, w),
+                 None if bias is None else (bias.detach().float() @ w.t()).unsqueeze(1))
+        for term in terms:
+            if term is not None:
+                add = term if add is None else add + term
+        return add
+
+    def _embed_epilogue(self, window, mark):
+        """What is added to ``x W^T`` once, whatever the series: value bias + positional (+ time-feature) term, gated
+        and normalised in the "decoupled" mode, ``[1|B, L, D]``; and ``(gamma, beta, eps)`` of the "layer" mode's
+        LayerNorm (None otherwise)."""
+        emb = self.embedding
+        add = emb.aux_term(window[:1], mark) + emb.value_embedding.bias.detach()
+        return add, (_ln_params(emb.norm) if emb.embed_norm_mode == "layer" else None)
+
     def _hip_embed_terms(self, window, mark, coeff, bias):
         """What the HIP embedding adds to ``x W^T``: ``(w, add, ln)`` with ``w`` the value weight [D, N], ``add`` the
-        bias + positional (+ time-feature) term + the two context terms pushed through ``w``, contiguous fp32
-        ``[1|B, L, D]``, and ``ln = (gamma, beta, eps)`` of the "layer" mode (None otherwise).  Shared by ``_embed``
-        and the recursive forecaster (``forecast.py``), which embeds its window row by row."""
-        emb, L = self.embedding, window.size(1)
-        w = emb.value_embedding.weight.detach()
-        add = emb.aux_term(window[:1], mark) + emb.value_embedding.bias.detach()
-        if coeff is not None:
-            add = add + self.temporal_context.project(coeff.detach().float(), L, w)
-        if bias is not None:
-            add = add + (bias.detach().float() @ w.t()).unsqueeze(1)
-        ln = None
-        if emb.embed_norm_mode == "layer":
-            ln = (emb.norm.weight.detach().float().contiguous(), emb.norm.bias.detach().float().contiguous(), emb.norm.eps)
+        epilogue term + the two context terms pushed through ``w``, contiguous fp32 ``[1|B, L, D]``, and ``ln`` of
+        ``_embed_epilogue``.  Shared by ``_embed`` and the recursive forecaster (``forecast.py``), which embeds its
+        window row by row."""
+        w = self.embedding.value_embedding.weight.detach()
+        add, ln = self._embed_epilogue(window, mark)
+        add = self._through_weight(add, coeff, bias, window.size(1), w)
         return w, add.detach().float().contiguous(), ln
+
+    def _with_context(self, window, coeff, bias) -> torch.Tensor:
+        """``window + temporal context + constant bias`` as a [B, L, N] tensor (the torch path of the embedding)."""
+        feats = window
+        if coeff is not None:
+            signal = self.temporal_context(coeff, window.size(1))          # HIP LRTC kernel on ROCm tensors
+            if signal.ndim != 3 or signal.shape[1:] != window.shape[1:] or signal.size(0) not in (1, window.size(0)):
+                raise RuntimeError("Temporal context must align with the [B, L, N] input")
+            feats = feats + signal.to(feats.dtype)
+        if bias is not None:
+            feats = feats + bias.to(feats.dtype).unsqueeze(1)
+        return feats
 
     def _embed(self, window, mark, rows) -> torch.Tensor:
         """``embedding(window + temporal context + constant bias)`` (:1958-2020).  On the HIP path the two context
@@ -517,15 +552,7 @@ class TimesNet(nn.Module):
             self._last_embed_backend = "hip"
             seq = runtime.embed_forward(window, w, add, ln)
         else:
-            feats = window
-            if coeff is not None:
-                signal = self.temporal_context(coeff, window.size(1))          # HIP LRTC kernel on ROCm tensors
-                if signal.ndim != 3 or signal.shape[1:] != window.shape[1:] or signal.size(0) not in (1, window.size(0)):
-                    raise RuntimeError("Temporal context must align with the [B, L, N] input")
-                feats = feats + signal.to(feats.dtype)
-            if bias is not None:
-                feats = feats + bias.to(feats.dtype).unsqueeze(1)
-            seq = self.embedding(feats, mark)
+            seq = self.embedding(self._with_context(window, coeff, bias), mark)
         if seq.ndim != 3 or seq.size(1) != self.input_len or seq.size(-1) != self.d_model:
             raise RuntimeError("Embedding output must have shape [B, input_len, d_model]")
         return seq
@@ -550,58 +577,82 @@ class TimesNet(nn.Module):
         params = (self.forecast_time_proj.weight, self.mu_head.weight, self.sigma_head.weight)
         return (seq.is_cuda and seq.dtype == torch.float32 and window.dtype == torch.float32
                 and not (torch.is_grad_enabled() and (seq.requires_grad or any(p.requires_grad for p in params)))
-                and self.d_model % 4 == 0 and self.d_model <= 128
+                and hip_width_ok(self.d_model)
                 and window.stride(2) == 1 and window.stride(1) == window.size(2))
 
-    def _heads(self, seq, window, rows, steps: int):
-        """Time projection L -> steps, then ``rate = softplus(mu + last observed values (+ late bias)) + 1e-6`` and
-        ``dispersion = softplus(sigma) + floor + 1e-6`` (:2063-2102)."""
-        B, L, N = window.shape
-        hist = min(steps, L)
-        late = None
-        if (rows is not None and self.late_bias_head is not None and self.late_bias_norm is not None
-                and isinstance(self.late_bias_gate, nn.Parameter)):
-            head = self.late_bias_head
-            lb = head(_norm(self.late_bias_norm, rows.to(device=head.weight.device, dtype=head.weight.dtype)))
-            late = self.late_bias_gate.to(lb) * lb.transpose(1, 2)                          # [Bc, steps, N]
+    def _late_bias(self, rows) -> Optional[torch.Tensor]:
+        """The gated late-bias head of the series rows, ``[Bc, steps, N]`` (None when the model has none)."""
+        if (rows is None or self.late_bias_head is None or self.late_bias_norm is None
+                or not isinstance(self.late_bias_gate, nn.Parameter)):
+            return None
+        head = self.late_bias_head
+        lb = head(_norm(self.late_bias_norm, rows.to(device=head.weight.device, dtype=head.weight.dtype)))
+        return self.late_bias_gate.to(lb) * lb.transpose(1, 2)
+
+    def _time_projection(self, seq, steps: int, hip: bool) -> torch.Tensor:
+        """``forecast_time_proj`` L -> steps (its last ``steps`` rows), ``[B, steps, d_model]``: ``hip`` runs
+        ``ftn_timeproj_forward`` straight into that layout (no permute copies)."""
         wt, bt = self.forecast_time_proj.weight, self.forecast_time_proj.bias
         if steps != self.pred_len:
             wt, bt = wt[-steps:], bt[-steps:]
-        if self._hip_heads_ok(seq, window):
+        self._last_timeproj_backend = "hip" if hip else "torch"
+        if hip:
             from .. import runtime
 
-            # ftn_timeproj_forward straight into [B, steps, d_model] (no permute copies), then ftn_head_forward
-            hidden = runtime.timeproj_forward(seq.detach().contiguous(), wt.detach(), bt.detach())
-            self._last_timeproj_backend = "hip"
-            floor = self.min_sigma_vector
-            floor_vec = None
-            if isinstance(floor, torch.Tensor) and floor.numel() > 0:
-                floor_vec = floor.to(device=seq.device, dtype=torch.float32).reshape(-1).contiguous()
-            rate, dispersion, bad = runtime.head_forward(
-                hidden.contiguous(), self.mu_head.weight.detach(), self.mu_head.bias.detach(),
-                self.sigma_head.weight.detach(), self.sigma_head.bias.detach(), window[:, -hist:, :], hist,
-                None if late is None else late.detach().float().contiguous(), floor_vec, self.min_sigma)
-            self._last_head_backend = "hip"
-            # the forward's one synchronisation (range_guard.tripped then reads the blocks' pinned words behind it);
-            # deferred, check_outputs() reads the device word after a replay
-            self._pending_bad = bad if self._defer_checks else bad.cpu()
-            return rate, dispersion
-        self._last_timeproj_backend = "torch"
-        hidden = torch.matmul(wt, seq) + bt.view(1, -1, 1)                                  # [B, steps, d_model]
+            return runtime.timeproj_forward(seq.detach().contiguous(), wt.detach(), bt.detach())
+        return torch.matmul(wt, seq) + bt.view(1, -1, 1)
+
+    def _rate_dispersion(self, hidden, window, late, steps: int, heads, hip: bool):
+        """``rate = softplus(mu + last observed values (+ late bias)) + 1e-6`` and ``dispersion = softplus(sigma) +
+        floor + 1e-6`` (:2063-2102) of ``hidden [B, steps, D]`` for the series of ``heads = (w_mu, b_mu, w_sigma,
+        b_sigma, floor vector or None)``: ``(rate, dispersion, bad)`` with ``bad`` the HIP head's device flag (None on
+        the torch path, which raises itself).  The torch path applies the weights with ``F.linear``, not through
+        ``mu_head`` / ``sigma_head`` as modules: forward hooks on the heads do not run."""
+        w_mu, b_mu, w_sigma, b_sigma, floor = heads
+        hist = min(steps, window.size(1))
         last = window[:, -hist:, :]
+        if hip:
+            from .. import runtime
+
+            if floor is not None:
+                floor = floor.to(device=hidden.device, dtype=torch.float32).reshape(-1).contiguous()
+            return runtime.head_forward(hidden.contiguous(), w_mu.detach(), b_mu.detach(), w_sigma.detach(),
+                                        b_sigma.detach(), last, hist,
+                                        None if late is None else late.detach().float().contiguous(), floor,
+                                        self.min_sigma)
         if hist < steps:                                       # recursive mode / short windows: repeat the last step
             last = torch.cat([last, last[:, -1:, :].expand(-1, steps - hist, -1)], dim=1)
-        pre = self.mu_head(hidden) + last.to(window.dtype)
+        pre = F.linear(hidden, w_mu, b_mu) + last.to(window.dtype)
         if late is not None:
             pre = pre + late.to(pre.dtype)
         soft = lambda t: F.softplus(t.float(), beta=1.0, threshold=20).to(t.dtype)
         rate = soft(pre) + 1e-6
-        spread = soft(self.sigma_head(hidden))
-        dispersion = spread + self._dispersion_floor_from_ref(rate).to(spread.dtype) + 1e-6
+        spread = soft(F.linear(hidden, w_sigma, b_sigma))
+        if floor is None:
+            floor = torch.full_like(rate, self.min_sigma)
+        else:
+            floor = floor.to(device=rate.device, dtype=rate.dtype).reshape(1, 1, -1).expand_as(rate)
+        dispersion = spread + floor.to(spread.dtype) + 1e-6
         for name, val in (("rate", rate), ("dispersion", dispersion)):
             if not bool((torch.isfinite(val) & (val > 0)).all()):
                 raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
-        if rate.shape != (B, steps, N) or dispersion.shape != (B, steps, N):
+        return rate, dispersion, None
+
+    def _heads(self, seq, window, rows, steps: int):
+        """Late bias, time projection L -> steps, then the rate / dispersion heads of every series."""
+        B, _, N = window.shape
+        late = self._late_bias(rows)
+        hip = self._hip_heads_ok(seq, window)
+        hidden = self._time_projection(seq, steps, hip)
+        heads = (self.mu_head.weight, self.mu_head.bias, self.sigma_head.weight, self.sigma_head.bias,
+                 self._floor_vector())
+        rate, dispersion, bad = self._rate_dispersion(hidden, window, late, steps, heads, hip)
+        if hip:
+            self._last_head_backend = "hip"
+            # the forward's one synchronisation (range_guard.tripped then reads the blocks' pinned words behind it);
+            # deferred, check_outputs() reads the device word after a replay
+            self._pending_bad = bad if self._defer_checks else bad.cpu()
+        elif rate.shape != (B, steps, N) or dispersion.shape != (B, steps, N):
             raise RuntimeError("Predicted rate/dispersion have incorrect shape")
         return rate, dispersion
 
@@ -621,149 +672,70 @@ class TimesNet(nn.Module):
             if flag & bit:
                 raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
 
-    # ---- series-sharded pieces (dist.SeriesShardedTimesNet): this rank owns series [offset, offset + n) ----------
-    # Only the value embedding mixes series (a contraction over N); everything else below is per series, so a rank
-    # computes a partial embedding over its own series, the partials are summed across ranks, and the heads run on
-    # the rank's own rows of mu_head / sigma_head.  Nothing here changes the model's state.
+    # ---- series-sharded entry points (dist.SeriesShardedTimesNet): this rank owns series [offset, offset + n) -----
+    # Only the value embedding mixes series (a contraction over N); everything else is per series, so a rank computes
+    # a partial embedding over its own series, the partials are summed across ranks, and the heads run on the rank's
+    # own rows of mu_head / sigma_head.  Each is the stage body above on the rank's slices; none changes the model's
+    # state.
     def series_slices(self, offset: int, n: int, device: torch.device) -> dict:
-        """This rank's weight slices: ``value_embedding.weight[:, S]``, the ``mu_head`` / ``sigma_head`` rows and
-        ``min_sigma_vector[S]``.  Cached and keyed on the parameters' storage pointers and version counters (as
-        TimesBlock's pack cache), so ``load_state_dict`` or an optimiser step invalidates them."""
-        emb = self.embedding
-        floor = self.min_sigma_vector
-        has_floor = isinstance(floor, torch.Tensor) and floor.numel() > 0
-        params = [emb.value_embedding.weight, self.mu_head.weight, self.mu_head.bias, self.sigma_head.weight,
-                  self.sigma_head.bias] + ([floor] if has_floor else [])
-        key = (int(offset), int(n), str(device)) + tuple(
-            (p.data_ptr(), -1 if p.is_inference() else p._version) for p in params)
+        """This rank's weight slices: ``value_embedding.weight[:, S]`` and the ``heads`` tuple of
+        ``_rate_dispersion`` (``mu_head`` / ``sigma_head`` rows, ``min_sigma_vector[S]``).  Cached and keyed on the
+        parameters (``_param_key``, as TimesBlock's pack cache)."""
+        w_emb, floor = self.embedding.value_embedding.weight, self._floor_vector()
+        params = (self.mu_head.weight, self.mu_head.bias, self.sigma_head.weight, self.sigma_head.bias)
+        key = (int(offset), int(n), str(device)) + _param_key((w_emb,) + params + (() if floor is None else (floor,)))
         cache = self.__dict__.get("_series_slice_cache")
         if cache is not None and cache[0] == key:
             return cache[1]
         sl = slice(int(offset), int(offset) + int(n))
-        take = lambda t: t.detach()[sl].to(device=device, dtype=torch.float32).contiguous()
-        out = {"w_emb": emb.value_embedding.weight.detach()[:, sl].to(device=device, dtype=torch.float32).contiguous(),
-               "w_mu": take(self.mu_head.weight), "b_mu": take(self.mu_head.bias),
-               "w_sigma": take(self.sigma_head.weight), "b_sigma": take(self.sigma_head.bias),
-               "floor": take(floor.reshape(-1)) if has_floor else None}
+        own = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
+        heads = tuple(own(p.detach()[sl]) for p in params) + (None if floor is None else own(floor.reshape(-1)[sl]),)
+        out = {"w_emb": own(w_emb.detach()[:, sl]), "heads": heads}
         self.__dict__["_series_slice_cache"] = (key, out)
         return out
 
     def series_context_rows(self, window, series_static, series_ids, offset: int) -> Optional[torch.Tensor]:
-        """``_context_rows`` for this rank's series without touching the remembered ids: the static features and ids
+        """``_rows_of`` for this rank's series without touching the remembered ids: the static features and ids
         are the rank's slices, and missing ids default to the GLOBAL ``arange(offset, offset + n)``."""
         B, _, N = window.shape
-        if series_ids is None and self.series_embedding is not None and self.id_embed_dim > 0:
-            series_ids = torch.arange(int(offset), int(offset) + N, device=window.device)
-        shared = ((series_static is None or series_static.ndim == 2)
-                  and (series_ids is None or series_ids.ndim == 1 or series_ids.size(0) == 1))
-        Bc = 1 if shared else B
-        cols = []
-        if self.static_proj is not None and series_static is not None:
-            if series_static.shape[-2] != N or (series_static.ndim == 3 and series_static.size(0) != B):
-                raise ValueError("series_static must be [n_local, F] or [B, n_local, F] for this rank's series")
-            st = series_static if series_static.ndim == 3 else series_static.unsqueeze(0).expand(Bc, -1, -1)
-            proj = self.static_proj(st.to(device=window.device, dtype=window.dtype, non_blocking=window.is_cuda))
-            cols.append(proj if self.static_norm is None else _norm(self.static_norm, proj))
-        if self.series_embedding is not None and self.id_embed_dim > 0:
-            ids = series_ids.view(1, -1) if series_ids.ndim == 1 else series_ids
+        if self.static_proj is not None and series_static is not None and (
+                series_static.shape[-2] != N or (series_static.ndim == 3 and series_static.size(0) != B)):
+            raise ValueError("series_static must be [n_local, F] or [B, n_local, F] for this rank's series")
+        ids = series_ids
+        if self._uses_ids():
+            if ids is None:
+                ids = torch.arange(int(offset), int(offset) + N, device=window.device)
+            ids = ids.view(1, -1) if ids.ndim == 1 else ids
             if ids.size(0) not in (1, B) or ids.size(1) != N:
                 raise ValueError("series_ids must be [n_local] or [B, n_local] for this rank's series")
             ids = ids.to(device=window.device, dtype=torch.long)
-            cols.append(self.series_embedding(ids.expand(Bc, -1) if ids.size(0) != Bc else ids))
-        if not cols:
-            return None
-        rows = cols[0] if len(cols) == 1 else torch.cat(cols, dim=-1)
-        return rows if self.context_norm is None else _norm(self.context_norm, rows)
+        return self._rows_of(window, series_static, ids)
 
     def series_partial_embedding(self, window, rows, w_emb: torch.Tensor) -> torch.Tensor:
         """This rank's share of the value embedding, ``[B, L, D]``: ``x_r W_r^T + (context terms of S_r) W_r^T`` -
-        no bias, no positional / time-feature term, no norm (those are added once, after the sum over ranks)."""
-        coeff = bias = None
-        if rows is not None:
-            if self.context_coeff is not None and self.temporal_context is not None and self.use_zero_mean_context:
-                coeff = self.context_coeff(rows.to(self.context_coeff.weight.dtype))
-            if self.context_proj is not None and self.use_constant_context_bias:
-                bias = self.context_proj(rows.to(self.context_proj.weight.dtype)).squeeze(-1)
-        L = window.size(1)
+        no bias, no positional / time-feature term, no norm (``series_embedding_epilogue``: once, after the sum over
+        ranks)."""
+        coeff, bias = self._context_terms(rows)
         if window.is_cuda:
             from .. import runtime
 
-            add = None
-            if coeff is not None:
-                add = self.temporal_context.project(coeff.detach().float(), L, w_emb)
-            if bias is not None:
-                cb = (bias.detach().float() @ w_emb.t()).unsqueeze(1)
-                add = cb if add is None else add + cb
+            add = self._through_weight(None, coeff, bias, window.size(1), w_emb)
             return runtime.embed_forward(window, w_emb, None if add is None else add.contiguous(), None)
-        feats = window
-        if coeff is not None:
-            feats = feats + self.temporal_context(coeff, L).to(feats.dtype)
-        if bias is not None:
-            feats = feats + bias.to(feats.dtype).unsqueeze(1)
-        return F.linear(feats, w_emb.to(feats.dtype))
+        return F.linear(self._with_context(window, coeff, bias), w_emb.to(window.dtype))
 
     def series_embedding_epilogue(self, window, mark) -> Tuple[torch.Tensor, Optional[tuple]]:
-        """What the summed partials still need: ``add`` = value bias + positional (+ time-feature) term, gated and
-        normalised in the "decoupled" mode, ``[1 or B_local, L, D]`` fp32; and ``(gamma, beta, eps)`` of the "layer"
-        mode's LayerNorm (None otherwise)."""
-        emb = self.embedding
-        add = (emb.aux_term(window[:1], mark) + emb.value_embedding.bias.detach()).detach().float().contiguous()
-        ln = None
-        if emb.embed_norm_mode == "layer":
-            ln = (emb.norm.weight.detach().float().contiguous(), emb.norm.bias.detach().float().contiguous(),
-                  emb.norm.eps)
-        return add, ln
+        """What the summed partials still need: ``_embed_epilogue`` with ``add`` as contiguous fp32."""
+        add, ln = self._embed_epilogue(window, mark)
+        return add.detach().float().contiguous(), ln
 
     def series_hidden(self, seq: torch.Tensor, steps: int) -> torch.Tensor:
         """``forecast_time_proj`` of the local rows: ``[B_local, steps, d_model]`` (as ``_heads``)."""
-        wt, bt = self.forecast_time_proj.weight, self.forecast_time_proj.bias
-        if steps != self.pred_len:
-            wt, bt = wt[-steps:], bt[-steps:]
-        if seq.is_cuda and seq.dtype == torch.float32 and self.d_model % 4 == 0 and self.d_model <= 128:
-            from .. import runtime
-
-            self._last_timeproj_backend = "hip"
-            return runtime.timeproj_forward(seq.detach().contiguous(), wt.detach(), bt.detach())
-        self._last_timeproj_backend = "torch"
-        if seq.is_cuda:
-            return torch.baddbmm(bt.detach().view(1, -1, 1), wt.detach().unsqueeze(0).expand(seq.size(0), -1, -1),
-                                 seq.detach()).contiguous()
-        return torch.matmul(wt, seq) + bt.view(1, -1, 1)
+        return self._time_projection(seq, steps, seq.is_cuda and seq.dtype == torch.float32
+                                     and hip_width_ok(self.d_model))
 
     def series_heads(self, hidden, window, rows, sl: dict, steps: int):
-        """Rate / dispersion of this rank's series from the gathered ``hidden [B, steps, D]``: ``(rate, dispersion,
-        bad)`` with ``bad`` the HIP head's device flag (None on the torch path, which raises itself)."""
-        B, L, N = window.shape
-        hist = min(steps, L)
-        late = None
-        if (rows is not None and self.late_bias_head is not None and self.late_bias_norm is not None
-                and isinstance(self.late_bias_gate, nn.Parameter)):
-            head = self.late_bias_head
-            lb = head(_norm(self.late_bias_norm, rows.to(device=head.weight.device, dtype=head.weight.dtype)))
-            late = self.late_bias_gate.to(lb) * lb.transpose(1, 2)                          # [Bc, steps, n_local]
-        if hidden.is_cuda:
-            from .. import runtime
-
-            return runtime.head_forward(hidden, sl["w_mu"], sl["b_mu"], sl["w_sigma"], sl["b_sigma"],
-                                        window[:, -hist:, :], hist,
-                                        None if late is None else late.detach().float().contiguous(), sl["floor"],
-                                        self.min_sigma)
-        last = window[:, -hist:, :]
-        if hist < steps:
-            last = torch.cat([last, last[:, -1:, :].expand(-1, steps - hist, -1)], dim=1)
-        pre = F.linear(hidden, sl["w_mu"], sl["b_mu"]) + last.to(window.dtype)
-        if late is not None:
-            pre = pre + late.to(pre.dtype)
-        soft = lambda t: F.softplus(t.float(), beta=1.0, threshold=20).to(t.dtype)
-        rate = soft(pre) + 1e-6
-        spread = soft(F.linear(hidden, sl["w_sigma"], sl["b_sigma"]))
-        floor = (sl["floor"].to(spread.dtype).view(1, 1, -1).expand_as(spread) if sl["floor"] is not None
-                 else torch.full_like(spread, self.min_sigma))
-        dispersion = spread + floor + 1e-6
-        for name, val in (("rate", rate), ("dispersion", dispersion)):
-            if not bool((torch.isfinite(val) & (val > 0)).all()):
-                raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
-        return rate, dispersion, None
+        """``(rate, dispersion, bad)`` of this rank's series from the gathered ``hidden [B, steps, D]``."""
+        return self._rate_dispersion(hidden, window, self._late_bias(rows), steps, sl["heads"], hidden.is_cuda)
 
     # ---- forward ------------------------------------------------------------------
     def forward(self, x: torch.Tensor, x_mark: Optional[torch.Tensor] = None,

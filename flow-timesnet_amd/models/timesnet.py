@@ -35,6 +35,12 @@ def _safe_param_dtype(dtype: torch.dtype) -> torch.dtype:
     return torch.float32 if dtype in (torch.float16, torch.bfloat16) else dtype
 
 
+def _param_key(params) -> tuple:
+    """What a cache of derived weights is keyed on: storage pointer and version counter of every parameter, so
+    ``load_state_dict``, an optimiser step or ``.to()`` invalidates it (inference tensors carry no version counter)."""
+    return tuple((p.data_ptr(), -1 if p.is_inference() else p._version) for p in params)
+
+
 def _env_on(name: str) -> bool:
     v = os.getenv(name)
     return bool(v) and v.strip().lower() not in {"0", "false", "off"}
@@ -394,9 +400,7 @@ class TimesBlock(nn.Module):
 
         params = list(self.inception.parameters())
         engine = engine or getattr(self, "engine", None) or pack.default_engine()
-        # inference tensors (lazy build under torch.inference_mode) carry no version counter
-        key = (str(device),) + tuple(
-            (p.data_ptr(), -1 if p.is_inference() else p._version) for p in params)
+        key = (str(device),) + _param_key(params)
         if self._pack_key != key:                               # new weights / device: every engine's blob is stale
             self._packs = {}
             self._pack_key = key
@@ -543,10 +547,8 @@ class TimesBlock(nn.Module):
             xf = xf.float()
         xf = xf.contiguous()
         adt = runtime.ACT_DTYPE.get(x.dtype, 0)
-        norm = None
-        if post_norm is not None and adt == 0:     # half inputs: the shell's LayerNorm runs outside (see forward)
-            norm = (post_norm.weight.detach().float().contiguous(), post_norm.bias.detach().float().contiguous(),
-                    post_norm.eps)
+        # half inputs: the shell's LayerNorm runs outside (see forward)
+        norm = _ln_params(post_norm) if post_norm is not None and adt == 0 else None
         wblob, plan = self._packed(x.device, engine)
         sel = self._select(x, xf, plan, wblob, flag)
         if sel is None:
@@ -675,10 +677,16 @@ def _affine_layernorm(m, C: int) -> bool:
             and m.bias is not None)
 
 
+def _ln_params(ln: nn.LayerNorm) -> Tuple[torch.Tensor, torch.Tensor, float]:
+    """``(gamma, beta, eps)`` of an affine LayerNorm as the HIP epilogues take them (contiguous fp32)."""
+    return ln.weight.detach().float().contiguous(), ln.bias.detach().float().contiguous(), ln.eps
+
+
 def _layer_norm_fp32(module: nn.Module, x: torch.Tensor) -> torch.Tensor:
-    """LayerNorm with fp32 statistics and fp32 parameters for half inputs (reference :30-34)."""
+    """LayerNorm with fp32 statistics and fp32 parameters for half inputs (reference :30-34); other modules as they
+    are."""
     if isinstance(module, nn.LayerNorm):
-        cd = torch.float32 if x.dtype in (torch.float16, torch.bfloat16) else x.dtype
+        cd = _safe_param_dtype(x.dtype)
         w = None if module.weight is None else module.weight.to(cd)
         b = None if module.bias is None else module.bias.to(cd)
         return F.layer_norm(x.to(cd), module.normalized_shape, weight=w, bias=b, eps=module.eps).to(x.dtype)

@@ -30,6 +30,31 @@ def _ptr_or_null(t):
     return None if t is None else t.data_ptr()
 
 
+def _batch_stride(t, B: int) -> int:
+    """Elements between the batch rows of an optional contiguous ``[1|B, R, C]`` operand: 0 when one ``[R, C]`` block
+    serves every row of the batch (or there is no operand)."""
+    return t.shape[-2] * t.shape[-1] if t is not None and t.dim() == 3 and t.shape[0] == B and B > 1 else 0
+
+
+def _norm_args(norm):
+    """``(gamma pointer, beta pointer, eps)`` of an optional LayerNorm epilogue ``norm = (gamma, beta, eps)``."""
+    g, b, eps = norm if norm is not None else (None, None, 0.0)
+    return _ptr_or_null(g), _ptr_or_null(b), float(eps)
+
+
+def _workspace_bytes(lib, plan: FtnPlan, B: int, L: int, max_groups: int, px_bound: int) -> int:
+    need = lib.ftn_timesblock_workspace_bytes(C.byref(plan), B, L, max_groups, px_bound)
+    if need == 0:
+        raise ValueError(f"ftn_timesblock_workspace_bytes rejected the shape (B={B}, L={L})")
+    return need
+
+
+def _workspace(device, need: int) -> torch.Tensor:
+    """One TimesBlock workspace of ``_workspace_bytes`` per call, from the caching allocator: ordered on the calling
+    stream, private to a graph capture's pool, never shared between calls in flight (a process-wide buffer would be)."""
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
 class DeviceState:
     """Caches that live as long as the process, one instance per CUDA device."""
 
@@ -142,10 +167,7 @@ def stage_a_only(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, k: int, pm
     lib = _lib.load()
     B, L, _ = x.shape
     mg, pxb = _selector_bounds(lib, L, k, pmax, min_thr)
-    need = lib.ftn_timesblock_workspace_bytes(C.byref(plan), B, L, mg, pxb)
-    if need == 0:
-        raise ValueError(f"ftn_timesblock_workspace_bytes rejected the shape (B={B}, L={L})")
-    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ws = _workspace(x.device, _workspace_bytes(lib, plan, B, L, mg, pxb))
     check(lib.ftn_period_finalize_stage_a(None, 0, 0, None, B, L, int(k), int(pmax), int(min_thr), 0, 0, 0.0,
                                           None, None, None, _ptr(x), C.byref(plan), _ptr(wblob), mg, pxb, _ptr(ws),
                                           ws.numel(), _stream(x.device), _ptr_or_null(range_flag), None),
@@ -176,13 +198,9 @@ def finalize(psum: torch.Tensor, b_total: int, med: torch.Tensor, L: int, k: int
     if stage_a is not None and (pre is not None or fuse_stage_a(stage_a[1])):
         x, plan, wblob = stage_a[:3]
         range_flag = stage_a[3] if len(stage_a) > 3 else None
+        ws = pre
         if pre is None:
-            need = lib.ftn_timesblock_workspace_bytes(C.byref(plan), B, L, sel.max_groups, sel.px_bound)
-            if need == 0:
-                raise ValueError(f"ftn_timesblock_workspace_bytes rejected the shape (B={B}, L={L})")
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        else:
-            ws = pre
+            ws = _workspace(dev, _workspace_bytes(lib, plan, B, L, sel.max_groups, sel.px_bound))
         check(lib.ftn_period_finalize_stage_a(_ptr(psum), nparts, int(b_total), _ptr(med), B, L, int(k), int(pmax),
                                               int(min_thr), int(act_dtype), int(max_unique or 0),
                                               float(log_base or 0.0), _ptr(desc), _ptr(amps), _ptr(wts),
@@ -286,11 +304,8 @@ def head_form_of(N: int, D: int, tail_bstride: int = 0, late_bstride: int = 0, m
 def head_form(hidden: torch.Tensor, w_mu: torch.Tensor, tail: torch.Tensor, late=None) -> Tuple[str, int]:
     """``head_form_of`` for the tensors ``head_forward`` would be given (its outputs are fresh, aligned tensors)."""
     B = hidden.shape[0]
-    late_bs = 0
-    if late is not None and late.shape[0] == B and B > 1:
-        late_bs = late.shape[-2] * late.shape[-1]
     mis = (_ptr(tail) | (_ptr(late) if late is not None else 0)) & 15
-    return head_form_of(w_mu.shape[0], hidden.shape[2], tail.stride(0) if B > 1 else 0, late_bs, mis)
+    return head_form_of(w_mu.shape[0], hidden.shape[2], tail.stride(0) if B > 1 else 0, _batch_stride(late, B), mis)
 
 
 def timeproj_form_of(L: int, S: int, D: int, wt_misalign: int = 0) -> str:
@@ -315,11 +330,7 @@ def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel:
     (reference :2050-2058) to the same call.  ``range_flag``: see ``new_range_flag``."""
     lib = _lib.load()
     B, L, _ = x.shape
-    need = lib.ftn_timesblock_workspace_bytes(C.byref(plan), B, L, sel.max_groups, sel.px_bound)
-    if need == 0:
-        raise ValueError(f"ftn_timesblock_workspace_bytes rejected the shape (B={B}, L={L})")
-    # one workspace per call, from the caching allocator: ordered on the calling stream, private to a graph
-    # capture's pool, never shared between calls in flight (a process-wide buffer would be)
+    need = _workspace_bytes(lib, plan, B, L, sel.max_groups, sel.px_bound)
     flags = 0
     pre = getattr(sel, "stage_a", None)
     if pre is not None:
@@ -330,13 +341,11 @@ def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel:
             raise RuntimeError("selection carries stage A of a different input or plan")
         flags = 1   # FTN_FWD_STAGE_A_DONE
     else:
-        ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = _workspace(x.device, need)
     y = torch.empty_like(x)
     if norm is not None:
-        g, b, eps = norm
         check(lib.ftn_timesblock_forward_norm(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
-                                              _ptr(sel.weights), sel.max_groups, sel.px_bound, flags, _ptr(g), _ptr(b),
-                                              float(eps),
+                                              _ptr(sel.weights), sel.max_groups, sel.px_bound, flags, *_norm_args(norm),
                                               _ptr(ws), ws.numel(), _stream(x.device), _ptr_or_null(range_flag)),
               "ftn_timesblock_forward_norm")
         return y
@@ -375,15 +384,11 @@ def head_forward(hidden: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor, w
     rate = torch.empty(B, S, N, dtype=torch.float32, device=dev)
     disp = torch.empty(B, S, N, dtype=torch.float32, device=dev)
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
-    late_bs = 0
-    if late is not None:
-        if late.shape[-2:] != (S, N) or not late.is_contiguous():
-            raise ValueError("late bias must be contiguous [1|B, S, N]")
-        late_bs = S * N if late.shape[0] == B and B > 1 else 0
+    if late is not None and (late.shape[-2:] != (S, N) or not late.is_contiguous()):
+        raise ValueError("late bias must be contiguous [1|B, S, N]")
     check(lib.ftn_head_forward(_ptr(hidden), B * S, S, D, N, _ptr(w_mu), _ptr(b_mu), _ptr(w_sigma), _ptr(b_sigma),
                                _ptr(tail), tail.stride(0) if B > 1 else 0, int(hist),
-                               _ptr(late) if late is not None else None, late_bs,
-                               _ptr(floor_vec) if floor_vec is not None else None, float(floor_scalar),
+                               _ptr_or_null(late), _batch_stride(late, B), _ptr_or_null(floor_vec), float(floor_scalar),
                                _ptr(rate), _ptr(disp), _ptr(bad), _stream(dev)), "ftn_head_forward")
     return rate, disp, bad
 
@@ -418,16 +423,11 @@ def embed_forward(window: torch.Tensor, weight: torch.Tensor, add, norm=None) ->
     D = weight.shape[0]
     if window.stride(2) != 1 or window.stride(1) != N:
         raise ValueError("window rows must be contiguous")
-    add_bs = 0
-    if add is not None:
-        if add.shape[-2:] != (L, D) or not add.is_contiguous():
-            raise ValueError("add must be contiguous [1|B, L, D]")
-        add_bs = L * D if add.dim() == 3 and add.shape[0] == B and B > 1 else 0
+    if add is not None and (add.shape[-2:] != (L, D) or not add.is_contiguous()):
+        raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=window.device)
-    g, b, eps = norm if norm is not None else (None, None, 0.0)
     check(lib.ftn_embed_forward(_ptr(window), window.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
-                                _ptr(add) if add is not None else None, add_bs,
-                                _ptr(g) if g is not None else None, _ptr(b) if b is not None else None, float(eps),
+                                _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
                                 _ptr(out), _stream(window.device)), "ftn_embed_forward")
     return out
 
@@ -455,15 +455,12 @@ def embed_ring(V: torch.Tensor, head: int, add, norm=None) -> torch.Tensor:
     B, L, D = V.shape
     if not V.is_contiguous() or V.dtype != torch.float32:
         raise ValueError("V must be contiguous fp32 [B, L, D]")
-    add_bs = 0
-    if add is not None:
-        if add.dim() != 3 or add.shape[-2:] != (L, D) or add.shape[0] not in (1, B) or not add.is_contiguous():
-            raise ValueError("add must be contiguous [1|B, L, D]")
-        add_bs = L * D if add.shape[0] == B and B > 1 else 0
+    if add is not None and (add.dim() != 3 or add.shape[-2:] != (L, D) or add.shape[0] not in (1, B)
+                            or not add.is_contiguous()):
+        raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=V.device)
-    g, b, eps = norm if norm is not None else (None, None, 0.0)
-    check(lib.ftn_embed_ring(_ptr(V), B, L, D, int(head), _ptr_or_null(add), add_bs, _ptr_or_null(g), _ptr_or_null(b),
-                             float(eps), _ptr(out), _stream(V.device)), "ftn_embed_ring")
+    check(lib.ftn_embed_ring(_ptr(V), B, L, D, int(head), _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
+                             _ptr(out), _stream(V.device)), "ftn_embed_ring")
     return out
 
 
@@ -480,14 +477,10 @@ def rowx_reduce(xch, rows: int, L: int, D: int, device: torch.device, add=None, 
     """This rank's ``[rows, L, D]`` of the rank-order sum of every rank's pushed partials, ``+ add`` (None, or contiguous
     ``[1|rows, L, D]``), then the LayerNorm ``norm = (gamma, beta, eps)`` over D (optional)."""
     out = torch.empty(rows, L, D, dtype=torch.float32, device=device)
-    add_bs = 0
-    if add is not None:
-        if add.shape[-2:] != (L, D) or not add.is_contiguous() or add.dtype != torch.float32:
-            raise ValueError("rowx_reduce: add must be contiguous fp32 [1|rows, L, D]")
-        add_bs = L * D if add.dim() == 3 and add.shape[0] == rows and rows > 1 else 0
-    g, b, eps = norm if norm is not None else (None, None, 0.0)
-    check(_lib.load().ftn_rowx_reduce(xch, int(L), int(D), _ptr_or_null(add), add_bs, _ptr_or_null(g), _ptr_or_null(b),
-                                      float(eps), _ptr(out), _stream(device)), "ftn_rowx_reduce")
+    if add is not None and (add.shape[-2:] != (L, D) or not add.is_contiguous() or add.dtype != torch.float32):
+        raise ValueError("rowx_reduce: add must be contiguous fp32 [1|rows, L, D]")
+    check(_lib.load().ftn_rowx_reduce(xch, int(L), int(D), _ptr_or_null(add), _batch_stride(add, rows),
+                                      *_norm_args(norm), _ptr(out), _stream(device)), "ftn_rowx_reduce")
     return out
 
 
