@@ -71,12 +71,13 @@ extern "C" int ftn_lrtc_basis(float* basis_dev, int L, int R, void* stream) {
 template <int RT, bool VEC, bool ADDX>
 __global__ __launch_bounds__(256) void k_lrtc(const float* __restrict__ coeff, const float* __restrict__ basis,
                                               const float* __restrict__ scale_p, const float* __restrict__ x,
-                                              float* __restrict__ out, int L, int N, int R, int nqb) {
-  // nqb lanes (multiple of 64) span the series quads of this block; the remaining 256/nqb
+                                              float* __restrict__ out, int L, int N, int R, int form) {
+  // form: what lrtc_form chose.  nqb lanes (multiple of 64) span the series quads of this block; the remaining 256/nqb
   // lane groups take further time slabs, so narrow N still fills the workgroup.  The basis
   // rows of the block's slabs are staged once in LDS (broadcast reads), padded to RT columns.
   __shared__ float bs[(256 / 64) * LRTC_LT * RT];
-  const int nsl = 256 / nqb;
+  const int nqb = 64 * (form >> 12), nsl = 256 / nqb;
+  const bool wide = form & FTN_LRTC_WIDE;
   const int b = blockIdx.z;
   const int nq = threadIdx.x % nqb, sl = threadIdx.x / nqb;
   const int n0 = (blockIdx.x * nqb + nq) * 4;
@@ -91,7 +92,8 @@ __global__ __launch_bounds__(256) void k_lrtc(const float* __restrict__ coeff, c
   if (n0 >= N || l0 >= L) return;
   const float scale = *scale_p;
   float co[4][RT];
-  if (RT % 4 == 0 && R == RT && n0 + 3 < N) {
+  if (RT % 4 == 0 && wide && n0 + 3 < N) {
+    // wide (lrtc_form: R == RT and coeff 16-byte aligned; 4*R floats per quad keep every lane's address aligned):
     // the four series of this lane are 4*R contiguous floats: RT unguarded 16-byte loads in flight at once
     // (the guarded scalar form below compiles to one load + branch + wait per coefficient, i.e. 4*RT
     // serialised memory round trips at the head of every wave)
@@ -143,13 +145,33 @@ __global__ __launch_bounds__(256) void k_lrtc(const float* __restrict__ coeff, c
   }
 }
 
+// The form ftn_lrtc_forward takes (include/flowtimes.h): the one place the choice is made - the launch below
+// dispatches on this value and ftn_lrtc_form exports it.  misalign: (out | x) & 15 in bits 0-3, coeff & 15 in bits 4-7.
+static int lrtc_form(int N, int R, bool addx, unsigned misalign) {
+  const int rt = R <= 4 ? 4 : R <= 8 ? 8 : R <= 16 ? 16 : 32;
+  const bool vec = N % 4 == 0 && (misalign & 15) == 0;
+  const bool wide = R == rt && N >= 4 && (misalign & 0xf0) == 0;
+  int nqb = ((ftn_cdiv(N, 4) + 63) / 64) * 64;
+  if (nqb > 256) nqb = 256;
+  if (nqb == 192) nqb = 256;   // 256 / nqb must be integral
+  return (vec ? FTN_LRTC_VEC : 0) | (addx ? FTN_LRTC_ADDX : 0) | (wide ? FTN_LRTC_WIDE : 0) | rt << 4 | (nqb / 64) << 12;
+}
+
+extern "C" int ftn_lrtc_form(int N, int R, int addx, int misalign_or) {
+  FTN_CHECK_ARG(N >= 1 && R >= 1 && R <= 32 && (addx == 0 || addx == 1) && misalign_or >= 0 && misalign_or < 256 &&
+                    misalign_or % 4 == 0 && (misalign_or >> 4) % 4 == 0,
+                "ftn_lrtc_form: N=%d R=%d addx=%d misalign=%d", N, R, addx, misalign_or);
+  return lrtc_form(N, R, addx != 0, (unsigned)misalign_or);
+}
+
 template <int RT>
-static void launch_lrtc(dim3 grid, hipStream_t st, bool vec, bool addx, const float* coeff, const float* basis,
-                        const float* scale, const float* x, float* out, int L, int N, int R, int nqb) {
-  if (vec && addx) hipLaunchKernelGGL((k_lrtc<RT, true, true>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, nqb);
-  else if (vec) hipLaunchKernelGGL((k_lrtc<RT, true, false>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, nqb);
-  else if (addx) hipLaunchKernelGGL((k_lrtc<RT, false, true>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, nqb);
-  else hipLaunchKernelGGL((k_lrtc<RT, false, false>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, nqb);
+static void launch_lrtc(dim3 grid, hipStream_t st, int form, const float* coeff, const float* basis,
+                        const float* scale, const float* x, float* out, int L, int N, int R) {
+  const bool vec = form & FTN_LRTC_VEC, addx = form & FTN_LRTC_ADDX;
+  if (vec && addx) hipLaunchKernelGGL((k_lrtc<RT, true, true>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, form);
+  else if (vec) hipLaunchKernelGGL((k_lrtc<RT, true, false>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, form);
+  else if (addx) hipLaunchKernelGGL((k_lrtc<RT, false, true>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, form);
+  else hipLaunchKernelGGL((k_lrtc<RT, false, false>), grid, dim3(256), 0, st, coeff, basis, scale, x, out, L, N, R, form);
 }
 
 // basis_dev is what ftn_lrtc_basis wrote: [L][R] basis followed by R column means.
@@ -160,17 +182,19 @@ extern "C" int ftn_lrtc_forward(const float* coeff_dev, const float* basis_dev, 
   FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1 && R >= 1, "ftn_lrtc_forward: bad shape B=%d L=%d N=%d R=%d", B, L, N, R);
   FTN_CHECK_ARG(R <= 32, "ftn_lrtc_forward: rank %d > 32 not supported", R);
   FTN_CHECK_ARG(B <= 65535 && ftn_cdiv(L, LRTC_LT) <= 65535, "ftn_lrtc_forward: grid too large");
+  FTN_CHECK_ARG((((uintptr_t)coeff_dev | (uintptr_t)basis_dev | (uintptr_t)scale_dev | (uintptr_t)x_dev_or_null |
+                  (uintptr_t)out_dev) & 3) == 0, "ftn_lrtc_forward: every pointer must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const bool addx = x_dev_or_null != nullptr;
-  const bool vec = (N % 4 == 0) && (((uintptr_t)out_dev & 15) == 0) && (!addx || ((uintptr_t)x_dev_or_null & 15) == 0);
-  int nqb = ((ftn_cdiv(N, 4) + 63) / 64) * 64;
-  if (nqb > 256) nqb = 256;
-  if (nqb == 192) nqb = 256;   // 256 / nqb must be integral
+  const unsigned mis = (unsigned)((((uintptr_t)out_dev | (uintptr_t)x_dev_or_null) & 15) | ((uintptr_t)coeff_dev & 15) << 4);
+  const int form = lrtc_form(N, R, x_dev_or_null != nullptr, mis);
+  const int nqb = 64 * (form >> 12);
   dim3 grid(ftn_cdiv(N, 4 * nqb), ftn_cdiv(L, LRTC_LT * (256 / nqb)), B);
-  if (R <= 4) launch_lrtc<4>(grid, st, vec, addx, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R, nqb);
-  else if (R <= 8) launch_lrtc<8>(grid, st, vec, addx, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R, nqb);
-  else if (R <= 16) launch_lrtc<16>(grid, st, vec, addx, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R, nqb);
-  else launch_lrtc<32>(grid, st, vec, addx, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R, nqb);
+  switch ((form >> 4) & 63) {
+    case 4: launch_lrtc<4>(grid, st, form, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R); break;
+    case 8: launch_lrtc<8>(grid, st, form, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R); break;
+    case 16: launch_lrtc<16>(grid, st, form, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R); break;
+    default: launch_lrtc<32>(grid, st, form, coeff_dev, basis_dev, scale_dev, x_dev_or_null, out_dev, L, N, R); break;
+  }
   FTN_CHECK_LAUNCH();
   return 0;
 }

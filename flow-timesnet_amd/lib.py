@@ -172,6 +172,7 @@ _SIGNATURES = {
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "ftn_lrtc_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_stage_timing": (C.c_int, [C.c_int]),
     "ftn_stage_times": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]),
     "ftn_debug_stamps": (C.c_int, [_P, C.c_size_t, C.c_int]),

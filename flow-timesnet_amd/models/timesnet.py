@@ -753,16 +753,21 @@ class LowRankTemporalContext(nn.Module):
             cf = coeff.detach()
             if cf.dtype != torch.float32 or not cf.is_contiguous():
                 cf = cf.float().contiguous()
+            # the kernel reads add_to as a dense [B, length, N] beside coeff; any other shape, device or dtype mix is
+            # added below as the torch branch adds it (broadcast, promoted, or rejected with torch's own error)
+            fuse = (add_to is not None and add_to.shape == (cf.shape[0], int(length), cf.shape[1])
+                    and add_to.device == cf.device and add_to.dtype == coeff.dtype)
             xa = None
-            if add_to is not None:
+            if fuse:
                 xa = add_to.detach()
                 if xa.dtype != torch.float32 or not xa.is_contiguous():
                     xa = xa.float().contiguous()
-            sc = self.scale.detach()
+            sc = self.scale.detach().reshape(1)
             if sc.dtype != torch.float32 or sc.device != cf.device:
                 sc = sc.to(device=cf.device, dtype=torch.float32)
             out = runtime.lrtc_forward(cf, int(length), sc, xa)
-            return out if out.dtype == coeff.dtype else out.to(coeff.dtype)
+            out = out if out.dtype == coeff.dtype else out.to(coeff.dtype)
+            return out if add_to is None or fuse else add_to + out
         self._last_backend = "torch"
         ctx = torch.einsum("lr,bnr->bln", self._basis(length, coeff), coeff)
         ctx = (ctx - ctx.mean(dim=1, keepdim=True)) * self.scale.to(device=coeff.device, dtype=coeff.dtype)

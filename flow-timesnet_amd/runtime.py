@@ -492,9 +492,37 @@ def rowx_gather(xch, shape, device: torch.device) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------ LRTC
+def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
+    """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch
+    dispatches through the same function): ``("k_lrtc<RT,VEC,ADDX>", wide coefficient loads, nqb)``.
+    ``misalign_or``: ``((out | x) & 15) | (coeff & 15) << 4`` of the byte addresses."""
+    f = _lib.load().ftn_lrtc_form(int(N), int(R), int(addx), int(misalign_or))
+    if f < 0:
+        check(f, "ftn_lrtc_form")
+    tf = ("false", "true")
+    return f"k_lrtc<{(f >> 4) & 63},{tf[f & 1]},{tf[(f >> 1) & 1]}>", bool(f & 4), 64 * (f >> 12)
+
+
+def lrtc_form(coeff: torch.Tensor, x: torch.Tensor | None = None, out: torch.Tensor | None = None):
+    """``lrtc_form_of`` for the tensors ``lrtc_forward(coeff, L, scale, x)`` is given (its own ``out`` is a fresh,
+    aligned tensor; ``out``: the one a direct ``ftn_lrtc_forward`` call would pass)."""
+    mis = ((_ptr(out) if out is not None else 0) | (_ptr(x) if x is not None else 0)) & 15 | (_ptr(coeff) & 15) << 4
+    return lrtc_form_of(coeff.shape[1], coeff.shape[2], x is not None, mis)
+
+
 def lrtc_forward(coeff: torch.Tensor, L: int, scale: torch.Tensor, x: torch.Tensor | None) -> torch.Tensor:
+    """``(x +) scale * (basis - colmean) coeff^T``: ``coeff`` [B,N,R] and the optional ``x`` [B,L,N] contiguous fp32
+    on one device, ``scale`` one fp32 element there.  Returns [B,L,N]."""
     lib = _lib.load()
+    if coeff.dim() != 3 or coeff.dtype != torch.float32 or not coeff.is_cuda or not coeff.is_contiguous():
+        raise ValueError("lrtc_forward takes coeff as a contiguous fp32 device tensor [B, N, R]")
     B, N, R = coeff.shape
+    if x is not None and (x.shape != (B, int(L), N) or x.dtype != torch.float32 or x.device != coeff.device
+                          or not x.is_contiguous()):
+        raise ValueError(f"lrtc_forward: x must be contiguous fp32 [B, L, N] = {(B, int(L), N)} beside coeff, "
+                         f"got {tuple(x.shape)} {x.dtype} on {x.device}")
+    if scale.numel() != 1 or scale.dtype != torch.float32 or scale.device != coeff.device:
+        raise ValueError("lrtc_forward: scale must be one fp32 element beside coeff")
     st = state(coeff.device)
     basis = st.lrtc_basis(L, R)
     out = torch.empty(B, L, N, dtype=torch.float32, device=coeff.device)

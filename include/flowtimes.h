@@ -393,6 +393,19 @@ int ftn_lrtc_basis(float* basis_dev, int L, int R, void* stream);
 int ftn_lrtc_forward(const float* coeff_dev, const float* basis_dev, const float* scale_dev,
                      const float* x_dev_or_null, float* out_dev, int B, int L, int N, int R,
                      void* stream);
+/* The form ftn_lrtc_forward takes (host-only; the launch dispatches through the same function):
+ *   bit 0      FTN_LRTC_VEC   16-byte stores of out (and loads of x): N % 4 == 0, out and x 16-byte aligned
+ *   bit 1      FTN_LRTC_ADDX  fused x +
+ *   bit 2      FTN_LRTC_WIDE  a lane's 4 R coefficients come in as 16-byte loads: R == RT, N >= 4 and coeff 16-byte
+ *                             aligned (a lane whose quad crosses N, and every lane otherwise, loads them one by one)
+ *   bits 4-9   RT: the rank padded to 4 | 8 | 16 | 32
+ *   bits 12-15 nqb / 64: lanes spanning one workgroup's series quads (64 | 128 | 256); gridDim.x = ceil(N / (4 nqb))
+ * misalign_or: ((out | x) & 15) | (coeff & 15) << 4, the pointers as byte addresses (x left out when addx == 0).
+ * Returns < 0 on a bad argument. */
+#define FTN_LRTC_VEC 1
+#define FTN_LRTC_ADDX 2
+#define FTN_LRTC_WIDE 4
+int ftn_lrtc_form(int N, int R, int addx, int misalign_or);
 
 /* ---- model shell around the block stack (TimesNet.forward) ------------------------ */
 /* Rate / dispersion heads (:2066-2102), one pass over hidden[rows = B*S][D] (the output of

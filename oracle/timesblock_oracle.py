@@ -56,15 +56,28 @@ def period_select(
     x: torch.Tensor, k_periods: int, pmax: int, min_period_threshold: int = 1
 ) -> SelectResult:
     """FFTPeriodSelector.forward restated.  :64-159 (ctor clamps :59-62)."""
+    B, L, C = x.shape
+    if int(k_periods) <= 0 or L <= 1 or C <= 0 or B <= 0:             # :89-90 (no spectrum to take)
+        return SelectResult([], [], x.new_zeros(B, 0), x.new_zeros(0), x.new_zeros(B, 0))
+    xf = x.float() if x.dtype in (torch.float16, torch.bfloat16) else x  # :92-94
+    med = channel_median_spectrum(xf)                                  # :109-111
+    return period_select_from_median(med, L, k_periods, pmax, min_period_threshold, x.dtype)
+
+
+def period_select_from_median(
+    med: torch.Tensor, L: int, k_periods: int, pmax: int, min_period_threshold: int = 1, out_dtype=None
+) -> SelectResult:
+    """Everything of ``period_select`` after the channel median ``med`` [B, F = L // 2 + 1]: batch mean, DC kill,
+    log penalty, top-k, periods and their clamps.  :112-159"""
     k_cfg = max(0, int(k_periods))
     pmax = max(1, int(pmax))
     min_thr = min(pmax, max(1, int(min_period_threshold)))
-    B, L, C = x.shape
-    empty = SelectResult([], [], x.new_zeros(B, 0), x.new_zeros(0), x.new_zeros(B, 0))
-    if k_cfg <= 0 or L <= 1 or C <= 0 or B <= 0:                      # :89-90
+    B = med.shape[0]
+    out_dtype = med.dtype if out_dtype is None else out_dtype
+    empty = SelectResult([], [], med.new_zeros(B, 0).to(out_dtype), med.new_zeros(0).to(out_dtype),
+                         med.new_zeros(B, 0).to(out_dtype))
+    if k_cfg <= 0 or L <= 1 or B <= 0:
         return empty
-    xf = x.float() if x.dtype in (torch.float16, torch.bfloat16) else x  # :92-94
-    med = channel_median_spectrum(xf)                                  # :109-111
     amp_mean = med.mean(dim=0)                                         # :112
     Fbins = amp_mean.numel()
     if Fbins <= 1:
@@ -92,7 +105,7 @@ def period_select(
     if not keep:
         return empty
     kept_idx = [safe[j] for j in keep]
-    amps = med[:, kept_idx].to(x.dtype)                                # :133-135,159
+    amps = med[:, kept_idx].to(out_dtype)                              # :133-135,159
     return SelectResult(kept_idx, [periods[j] for j in keep], amps, amp_mean, med, gap)
 
 
