@@ -36,9 +36,7 @@
 #include "ftn_mlp.h"
 #include "ftn_out.h"
 #include "ftn_finalize.h"
-
-void ftn_xch_fill(const FtnExchange* x, int F, FinalizeArgs* fa);   // selector.hip
-bool ftn_xch_ok(const FtnExchange* x, int F);                       // selector.hip
+#include "ftn_exchange.h"
 
 static const bool g_r_keeps_x = [] { const char* e = getenv("FTN_R_KEEPS_X"); return e == nullptr || e[0] != '0'; }();   // stage C leaves x inside R (default on)
 static const bool g_mlp_u1 = [] { const char* e = getenv("FTN_MLP_U1"); return e == nullptr || e[0] != '0'; }();    // 0: the two-unit k_mlp_bf

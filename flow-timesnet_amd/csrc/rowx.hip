@@ -8,6 +8,7 @@
 // peer that shares the GPU (two ranks on one device) must still find room for its push.
 #include <string.h>
 #include "ftn_common.h"
+#include "ftn_exchange.h"
 
 #define ROWX_MAX_WG 1024
 #define ROWX_TIMEOUT_TICKS 200000000ull       // s_memrealtime ticks at 100 MHz: 2 s, as the [F] exchange
@@ -195,49 +196,18 @@ extern "C" size_t ftn_rowx_bytes(int world, int rows_per_rank, int width) {
   return rowx_tail_off(g) + 256;
 }
 
-// Uncached device memory (every access goes to memory, whichever GPU issues it), zeroed; no plain-hipMalloc fallback:
-// a cached buffer could serve a peer's rows from a stale L2 line.
+// No plain-hipMalloc fallback: a cached buffer could serve a peer's rows from a stale L2 line.
 extern "C" int ftn_rowx_alloc(int world, int rows_per_rank, int width, void** buf_out, void* handle64_out) {
   const size_t n = ftn_rowx_bytes(world, rows_per_rank, width);
   FTN_CHECK_ARG(n > 0 && buf_out && handle64_out, "ftn_rowx_alloc: world=%d rows_per_rank=%d width=%d", world,
                 rows_per_rank, width);
-  static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-  void* p = nullptr;
-  hipError_t e = hipExtMallocWithFlags(&p, n, hipDeviceMallocUncached);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    ftn_set_error("ftn_rowx_alloc: uncached allocation of %zu bytes failed: %s", n, hipGetErrorString(e));
-    return (int)e;
-  }
-  e = hipMemset(p, 0, n);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipIpcGetMemHandle((hipIpcMemHandle_t*)handle64_out, p);
-  if (e != hipSuccess) {
-    ftn_set_error("ftn_rowx_alloc: %s", hipGetErrorString(e));
-    (void)hipFree(p);
-    return (int)e;
-  }
-  *buf_out = p;
-  return 0;
+  return ftn_ipc_alloc(n, false, "ftn_rowx_alloc", buf_out, handle64_out);
 }
 extern "C" int ftn_rowx_open(const void* handle64, void** mapped_out) {
-  FTN_CHECK_ARG(handle64 && mapped_out, "ftn_rowx_open: null pointer");
-  hipIpcMemHandle_t h;
-  memcpy(&h, handle64, sizeof(h));
-  hipError_t e = hipIpcOpenMemHandle(mapped_out, h, hipIpcMemLazyEnablePeerAccess);
-  if (e != hipSuccess) { ftn_set_error("ftn_rowx_open: %s", hipGetErrorString(e)); return (int)e; }
-  return 0;
+  return ftn_ipc_open("ftn_rowx_open", "ftn_rowx_open", handle64, mapped_out);
 }
-extern "C" int ftn_rowx_close(void* mapped) {
-  hipError_t e = mapped ? hipIpcCloseMemHandle(mapped) : hipSuccess;
-  if (e != hipSuccess) { ftn_set_error("ftn_rowx_close: %s", hipGetErrorString(e)); return (int)e; }
-  return 0;
-}
-extern "C" int ftn_rowx_free(void* buf) {
-  hipError_t e = buf ? hipFree(buf) : hipSuccess;
-  if (e != hipSuccess) { ftn_set_error("ftn_rowx_free: %s", hipGetErrorString(e)); return (int)e; }
-  return 0;
-}
+extern "C" int ftn_rowx_close(void* mapped) { return ftn_ipc_close("ftn_rowx_close", mapped); }
+extern "C" int ftn_rowx_free(void* buf) { return ftn_ipc_free("ftn_rowx_free", buf); }
 
 static int rowx_read(const void* dev, void* host, size_t n, void* stream, const char* what) {
   hipError_t e = hipMemcpyAsync(host, dev, n, hipMemcpyDeviceToHost, (hipStream_t)stream);

@@ -248,9 +248,10 @@ size_t ftn_dft_table_bytes(int L);
 int ftn_dft_table_init(void* table_dev, int L, void* stream);
 /* S1+S2 (:108-112): med[b][f] = lower-median_c |rfft_t x[b,:,c]|_f, f < L/2+1,
  * psum[f] = sum_b med[b][f] (fp64, fixed order).  med: [B][F] dev, psum: [F] dev.
- * Two kernels, bit-identical results: one workgroup per (row, 32-bin block), or - when a row's folded samples
- * and amplitude tile fit LDS (C <= 64, e.g. L = 336) and B >= 64 - one workgroup per row with x[b] resident in
- * LDS.  FTN_SEL_ROW=1 / 0 in the environment forces / forbids the second form. */
+ * Three kernels: one workgroup per (row, 32-bin block), or - when a row's folded samples and amplitude tile fit
+ * LDS (C <= 64, e.g. L = 336) and B >= 64 - one workgroup per row with x[b] resident in LDS (bit-identical to the
+ * first), folded a second time where L % 4 == 0 (agrees to 2e-6; ftn_period_spectrum_form names the choice).
+ * FTN_SEL_ROW in the environment pins a form where it fits: 0 the first, 1 the row-resident, 2 the twice-folded. */
 /* xch (ABI 9; may be NULL): also publish psum to slot `rank` of every rank's exchange buffer (see FtnExchange). */
 /* scratch_dev (ABI 10; may be NULL): ftn_period_spectrum_scratch_bytes(B, L, C) bytes of device memory.  With it,
  * 64 < C <= 128 (d_model 128) runs the quarter-folded DFT as (row, 32-channel tile) workgroups that park their
