@@ -10,6 +10,7 @@ Sub-modules
 ``models.shell``     mirror of the TimesNet model shell; HIP embedding / head kernels around the blocks
 ``dist``             batch-sharded multi-GPU forward (RCCL via torch.distributed)
 ``forecast``         recursive forecasting with the window state on the device (eager or one HIP graph)
+``score``            NB likelihood and sMAPE of a forecast on the device: ``negative_binomial_nll``, ``ForecastScorer``
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401
@@ -18,6 +19,6 @@ from . import synth  # noqa: F401
 def __getattr__(name):  # lazy: keeps `import flow_timesnet_amd.synth` torch-free
     import importlib
 
-    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast"):
+    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

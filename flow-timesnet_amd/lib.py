@@ -44,6 +44,15 @@ class FtnRowExchange(C.Structure):
                 ("rows_per_rank", C.c_int32), ("width", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FtnScorePart(C.Structure):
+    """Mirror of ``struct FtnScorePart`` (include/flowtimes.h): what scoring leaves per column and per slot."""
+
+    _fields_ = [("nll_sum", C.c_double), ("smape_sum", C.c_double), ("nll_cnt", C.c_int32), ("smape_cnt", C.c_int32)]
+
+
+SCORE_PART_BYTES = C.sizeof(FtnScorePart)
+
+
 class FtnDesc(C.Structure):
     """Mirror of ``struct FtnDesc`` (include/flowtimes.h)."""
 
@@ -169,6 +178,10 @@ _SIGNATURES = {
     "ftn_head_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_timeproj_forward": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "ftn_timeproj_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ftn_score_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_score_columns": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, _P, C.c_int, C.c_float,
+                                    C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "ftn_score_fold": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -491,6 +491,125 @@ def rowx_gather(xch, shape, device: torch.device) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ scoring
+SCORE_PART_BYTES = _lib.SCORE_PART_BYTES
+
+
+def score_form_of(H: int, N: int, strides=(0, 0, 0), misalign_or: int = 0) -> Tuple[str, int, int]:
+    """The kernel ``ftn_score_columns`` runs (``ftn_score_form``, host-only: the launch dispatches through the same
+    function): ``("k_score_cols<4>" | "k_score_cols<1>", nseg, seg)`` - the vector form reads 16 bytes per lane and
+    needs ``N % 4 == 0``, batch ``strides`` (of y, rate, dispersion, in elements) that are multiples of 4 and
+    ``misalign_or == 0``; H is cut into ``nseg`` segments of ``seg`` rows."""
+    f = _lib.load().ftn_score_form(int(H), int(N), int(strides[0]), int(strides[1]), int(strides[2]), int(misalign_or))
+    if f < 0:
+        check(f, "ftn_score_form")
+    return f"k_score_cols<{4 if f & 2 else 1}>", (f >> 4) & 15, f >> 8
+
+
+def _score_operands(operands) -> None:
+    """Shapes, then row layout, then dtype and device of ``(name, tensor)`` pairs, the first being y."""
+    shape = tuple(operands[0][1].shape)
+    for name, t in operands:
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"score_columns: {name} must be a [B, H, N] tensor")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"score_columns: {name} has shape {tuple(t.shape)}, y has {shape}")
+    B, H, N = shape
+    for name, t in operands:
+        if (N > 1 and t.stride(2) != 1) or (H > 1 and t.stride(1) != N) or (B > 1 and t.stride(0) < H * N):
+            raise ValueError(f"score_columns: {name} needs contiguous rows N elements apart, strides {t.stride()}")
+    for name, t in operands:
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f"score_columns: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
+
+
+def _score_mask(mask, y: torch.Tensor):
+    if mask is None:
+        return None, 0
+    if tuple(mask.shape) != tuple(y.shape) or not mask.is_contiguous() or mask.device != y.device:
+        raise ValueError(f"score_columns: mask must be contiguous {tuple(y.shape)} beside y, got "
+                         f"{tuple(mask.shape)} strides {mask.stride()} on {mask.device}")
+    if mask.dtype in (torch.bool, torch.uint8):
+        return mask, 1
+    if mask.dtype == torch.float32:
+        return mask, 2
+    raise ValueError(f"score_columns: mask must be bool, uint8 or fp32, got {mask.dtype}")
+
+
+def _score_misalign(y, rate, disp, mask, kind, ll) -> int:
+    mis = (_ptr(y) | _ptr(rate) | _ptr(disp) | (_ptr(ll) if ll is not None else 0)) & 15
+    if kind == 2:
+        mis |= _ptr(mask) & 15
+    if kind == 1:
+        mis |= (_ptr(mask) & 3) << 2
+    return mis
+
+
+def score_form(y, rate, disp, mask=None, ll_out=None) -> Tuple[str, int, int]:
+    """``score_form_of`` for the tensors ``score_columns`` is given."""
+    B, H, N = y.shape
+    _, kind = _score_mask(mask, y)
+    strides = [t.stride(0) if B > 1 else 0 for t in (y, rate, disp)]
+    return score_form_of(H, N, strides, _score_misalign(y, rate, disp, mask, kind, ll_out))
+
+
+def score_columns(y: torch.Tensor, rate: torch.Tensor, disp: torch.Tensor, mask=None, eps: float = 1e-8,
+                  want_ll: bool = False):
+    """One pass of ``k_score_cols`` over ``y``, ``rate``, ``disp`` [B,H,N] (fp32 device tensors or views with
+    contiguous rows N elements apart) and an optional contiguous [B,H,N] mask (bool / uint8, or fp32 where nonzero is
+    true).  Returns ``(part, ll)``: ``part`` a uint8 tensor of B N ``FtnScorePart`` records, column (b, n) at record
+    ``b N + n``; ``ll`` the fp32 per-element log-likelihood (0 where invalid) when ``want_ll``, else None.  Enqueues
+    only."""
+    lib = _lib.load()
+    if not isinstance(y, torch.Tensor) or y.dim() != 3:
+        raise ValueError("score_columns: y must be a [B, H, N] tensor")
+    _score_operands((("y", y), ("rate", rate), ("dispersion", disp)))
+    if rate.device != y.device or disp.device != y.device:
+        raise ValueError("score_columns: y, rate and dispersion must be on one device")
+    mask, kind = _score_mask(mask, y)
+    B, H, N = y.shape
+    if B < 1 or H < 1 or N < 1:
+        raise ValueError(f"score_columns: empty shape {tuple(y.shape)}")
+    part = torch.empty(B * N * SCORE_PART_BYTES, dtype=torch.uint8, device=y.device)
+    ll = torch.empty(B, H, N, dtype=torch.float32, device=y.device) if want_ll else None
+    check(lib.ftn_score_columns(_ptr(y), y.stride(0), _ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0),
+                                _ptr_or_null(mask), kind, float(eps), B, H, N, _ptr(part), _ptr_or_null(ll),
+                                _stream(y.device)), "ftn_score_columns")
+    return part, ll
+
+
+def score_fold(part: torch.Tensor, B: int, N: int, acc: torch.Tensor, err: torch.Tensor, ids=None, order=None,
+               seg_start=None) -> None:
+    """``acc[slot] += part[b N + n]`` in place (``k_score_fold``), in ascending (b, n) order per slot.  ``acc``: uint8
+    storage of ``FtnScorePart`` records, one per slot; ``err``: one int32 whose bit 0 an out-of-range id sets.
+    No ids: slot = n.  ``ids`` int64 [N] (distinct): slot = ids[n].  ``order`` int64 [B N] with ``seg_start`` int64
+    [n_slots + 1] (the stable argsort of any ids and each slot's first position in it): one owner per slot."""
+    lib = _lib.load()
+    for name, t in (("part", part), ("acc", acc)):
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.numel() % SCORE_PART_BYTES:
+            raise ValueError(f"score_fold: {name} must be contiguous uint8 device storage of FtnScorePart records")
+    n_slots = acc.numel() // SCORE_PART_BYTES
+    if part.numel() != B * N * SCORE_PART_BYTES:
+        raise ValueError(f"score_fold: part holds {part.numel() // SCORE_PART_BYTES} records, B N = {B * N}")
+    if err.dtype != torch.int32 or err.numel() != 1 or not err.is_cuda:
+        raise ValueError("score_fold: err must be one int32 on the device")
+    kind = 0
+    if order is not None or seg_start is not None:
+        kind = 2
+        if ids is not None or order is None or seg_start is None:
+            raise ValueError("score_fold: order and seg_start come together, without ids")
+        for name, t, n in (("order", order, B * N), ("seg_start", seg_start, n_slots + 1)):
+            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != n:
+                raise ValueError(f"score_fold: {name} must be contiguous int64 [{n}] on the device")
+    elif ids is not None:
+        kind = 1
+        if ids.dtype != torch.int64 or not ids.is_cuda or not ids.is_contiguous() or tuple(ids.shape) != (N,):
+            raise ValueError(f"score_fold: ids must be contiguous int64 [{N}] on the device")
+    check(lib.ftn_score_fold(_ptr(part), int(B), int(N), kind, _ptr_or_null(ids), _ptr_or_null(order),
+                             _ptr_or_null(seg_start), _ptr(acc), n_slots, _ptr(err), _stream(part.device)),
+          "ftn_score_fold")
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch

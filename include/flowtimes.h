@@ -484,6 +484,58 @@ int ftn_timeproj_forward(const float* seq_dev, int B, int L, int D, const float*
                          float* hidden_dev, void* stream);
 int ftn_timeproj_form(int L, int S, int D, int wt_misalign);
 
+/* ---- scoring a forecast (losses.py:27-58, train.py:675-765 of the reference) -------------------------
+ * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
+ *
+ * ftn_score_columns (k_score_cols<CPL>): one pass over y, rate, dispersion [B][H][N] (fp32, rows N elements apart,
+ * N fastest, each with its own batch stride in elements) and an optional mask (contiguous [B][H][N]; mask_kind 0
+ * none, 1 uint8, 2 fp32 where nonzero is true).  Per element, in the reference's words:
+ *   yc = y < 0 ? 0 : y,  alpha = max(dispersion, eps),  mu = max(rate, eps)          (a NaN stays a NaN)
+ *   ll = lgamma(yc + 1/alpha) - lgamma(1/alpha) - lgamma(yc + 1) - log1p(alpha mu) / alpha
+ *        + yc (log alpha + log mu - log1p(alpha mu))
+ *   valid = isfinite(yc) & isfinite(mu) & isfinite(alpha) & mask
+ * ll is evaluated in fp64 (Stirling's series above 8 after an upward shift; the last addend as
+ * -yc log1p(1 / (alpha mu))) and rounded once to fp32; that fp32 value goes to ll_out (optional, contiguous
+ * [B][H][N], 0 where invalid) and, negated, into the column's fp64 sum.  The sMAPE term of a valid element with
+ * finite |y| > 1e-8 (the unclamped y) is 2 |rate - y| / (|y| + |rate|) in fp32 operations, summed in fp64.
+ * An invalid element contributes NOTHING (the reference multiplies by a 0 weight, so one masked-out NaN makes its
+ * mean NaN: DESIGN.md section 8).
+ * part_out[b N + n] is column (b, n)'s record.  Its sums run over h ascending; H is cut into nseg <= 8 segments of
+ * seg = max(4, ceil(H / 8)) rows, one wave each, whose partial sums are added in ascending order: the order is a
+ * function of H alone, no atomics, and a column's record is the same bits whatever B is and whichever rows share
+ * the call.  H N and B N must fit an int32.
+ * ftn_score_form (host-only; the launch dispatches through the same function):
+ *   bit 1      FTN_SHELL_VEC  k_score_cols<4>: 16-byte loads, four columns per lane (N % 4 == 0, every batch stride
+ *              a multiple of 4, misalign_or == 0); otherwise k_score_cols<1>, one column per lane
+ *   bits 4-7   nseg, the waves of a workgroup
+ *   bits 8-27  seg, the rows of a segment
+ * misalign_or: the OR of (address & 15) of y, rate, dispersion, ll_out and an fp32 mask, and of (address & 3) << 2
+ * of a uint8 mask. */
+typedef struct FtnScorePart {
+  double nll_sum;      /* sum of -ll over the valid elements                          */
+  double smape_sum;    /* sum of the sMAPE terms that count                           */
+  int32_t nll_cnt;     /* valid elements                                              */
+  int32_t smape_cnt;   /* sMAPE terms that count                                      */
+} FtnScorePart;
+int ftn_score_form(int H, int N, long long y_bstride, long long rate_bstride, long long disp_bstride,
+                   int misalign_or);
+int ftn_score_columns(const float* y_dev, long long y_bstride, const float* rate_dev, long long rate_bstride,
+                      const float* disp_dev, long long disp_bstride, const void* mask_dev, int mask_kind, float eps,
+                      int B, int H, int N, FtnScorePart* part_out_dev, float* ll_out_dev, void* stream);
+/* ftn_score_fold (k_score_fold): acc[slot] += part[b N + n], field by field and IN PLACE, one record at a time in
+ * ascending (b, n) order for every slot, so folding batch X and then batch Y leaves the bits that folding
+ * cat([X, Y]) leaves.  ids_kind:
+ *   0  slot = n (ids, order, seg_start null; N <= n_slots)
+ *   1  slot = ids[n], ids int64 [N], distinct within the row
+ *   2  any ids, e.g. per-sample [B][N] with repeats: order int64 [B N] is the stable argsort of the ids and
+ *      seg_start int64 [n_slots + 1] the first position of every slot in it; one thread owns a slot and walks
+ *      its segment
+ * An id outside [0, n_slots) sets bit 0 of *err_dev (int32, caller-owned, never cleared here) and its record is
+ * dropped; nothing is read or written out of bounds. */
+int ftn_score_fold(const FtnScorePart* part_dev, int B, int N, int ids_kind, const long long* ids_dev,
+                   const long long* order_dev, const long long* seg_start_dev, FtnScorePart* acc_dev, int n_slots,
+                   int* err_dev, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
