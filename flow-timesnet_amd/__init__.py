@@ -10,7 +10,8 @@ Sub-modules
 ``models.shell``     mirror of the TimesNet model shell; HIP embedding / head kernels around the blocks
 ``dist``             batch-sharded multi-GPU forward (RCCL via torch.distributed)
 ``forecast``         recursive forecasting with the window state on the device (eager or one HIP graph)
-``score``            NB likelihood and sMAPE of a forecast on the device: ``negative_binomial_nll``, ``ForecastScorer``
+``score``            NB likelihood and sMAPE of a forecast on the device: ``negative_binomial_nll``, ``ForecastScorer``;
+                     the distribution itself: ``nb_cdf``, ``nb_quantiles``, ``prediction_interval``, ``interval_metrics``
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401

@@ -51,6 +51,8 @@ class FtnScorePart(C.Structure):
 
 
 SCORE_PART_BYTES = C.sizeof(FtnScorePart)
+FTN_QMAX = 8
+FTN_NBQ_RANGE = 2
 
 
 class FtnDesc(C.Structure):
@@ -182,6 +184,11 @@ _SIGNATURES = {
     "ftn_score_columns": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, _P, C.c_int, C.c_float,
                                     C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ftn_score_fold": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
+    "ftn_nbq_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_nb_cdf": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                             C.c_float, _P, _P, _P, _P]),
+    "ftn_nb_quantiles": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
+                                   C.POINTER(C.c_double), C.c_int, C.c_float, _P, _P, _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -610,6 +610,91 @@ def score_fold(part: torch.Tensor, B: int, N: int, acc: torch.Tensor, err: torch
           "ftn_score_fold")
 
 
+# ------------------------------------------------------------------ NB CDF and quantiles
+def nbq_form_of(N: int, strides=(0, 0, 0), misalign_or: int = 0) -> str:
+    """The kernel form ``ftn_nb_cdf`` / ``ftn_nb_quantiles`` take (``ftn_nbq_form``, host-only: the launches dispatch
+    through the same function): ``"vec4"`` (16-byte loads, four elements per lane: ``N % 4 == 0``, batch ``strides``
+    of y, rate, dispersion that are multiples of 4, ``misalign_or == 0``) or ``"scalar"``."""
+    f = _lib.load().ftn_nbq_form(int(N), int(strides[0]), int(strides[1]), int(strides[2]), int(misalign_or))
+    if f < 0:
+        check(f, "ftn_nbq_form")
+    return "vec4" if f & 2 else "scalar"
+
+
+def nbq_form(rate, disp, y=None, out=None) -> str:
+    """``nbq_form_of`` for the tensors ``nb_quantiles(rate, disp, ...)`` or, with ``y``, ``nb_cdf(y, rate, disp)`` is
+    given (``out``: the output a direct ``ftn_nb_cdf`` call would pass; the wrappers' own is fresh and aligned)."""
+    B, H, N = rate.shape
+    ops = [t for t in (y, rate, disp, out) if t is not None]
+    mis = 0
+    for t in ops:
+        mis |= _ptr(t) & 15
+    strides = [t.stride(0) if (t is not None and B > 1) else 0 for t in (y, rate, disp)]
+    return nbq_form_of(N, strides, mis)
+
+
+def nb_cdf(y: torch.Tensor, rate: torch.Tensor, disp: torch.Tensor, eps: float = 1e-8, want64: bool = False,
+           flag: torch.Tensor | None = None):
+    """``k_nb_cdf`` over ``y``, ``rate``, ``disp`` [B,H,N] (fp32 device tensors or views with contiguous rows N
+    elements apart): ``F(floor(max(y, 0)))`` as fp32 [B,H,N]; with ``want64`` returns ``(out, out64)``, the second the
+    fp64 values before the rounding.  ``flag``: one device int32 that receives ``FTN_NBQ_RANGE``.  Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(y, torch.Tensor) or y.dim() != 3:
+        raise ValueError("nb_cdf: y must be a [B, H, N] tensor")
+    _score_operands((("y", y), ("rate", rate), ("dispersion", disp)))
+    if rate.device != y.device or disp.device != y.device:
+        raise ValueError("nb_cdf: y, rate and dispersion must be on one device")
+    B, H, N = y.shape
+    if B < 1 or H < 1 or N < 1:
+        raise ValueError(f"nb_cdf: empty shape {tuple(y.shape)}")
+    _nbq_flag(flag, y.device, "nb_cdf", optional=True)
+    out = torch.empty(B, H, N, dtype=torch.float32, device=y.device)
+    out64 = torch.empty(B, H, N, dtype=torch.float64, device=y.device) if want64 else None
+    check(lib.ftn_nb_cdf(_ptr(y), y.stride(0), _ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0), B, H, N,
+                         float(eps), _ptr(out), _ptr_or_null(out64), _ptr_or_null(flag), _stream(y.device)),
+          "ftn_nb_cdf")
+    return (out, out64) if want64 else out
+
+
+def _nbq_flag(flag, device, who: str, optional: bool = False) -> None:
+    if flag is None and optional:
+        return
+    if (not isinstance(flag, torch.Tensor) or flag.dtype != torch.int32 or flag.numel() != 1 or not flag.is_cuda
+            or flag.device != device):
+        raise ValueError(f"{who}: flag must be one int32 on the operands' device")
+
+
+def nb_quantiles(rate: torch.Tensor, disp: torch.Tensor, levels, eps: float = 1e-8, out: torch.Tensor | None = None,
+                 flag: torch.Tensor | None = None):
+    """``k_nb_quantile`` for 1..8 ``levels`` (floats strictly inside (0, 1), any order): ``out[i]`` [B,H,N] fp32 is the
+    smallest integer k with ``F(k) >= levels[i]``.  ``out``: a contiguous fp32 [Q,B,H,N] to fill (default: fresh);
+    ``flag``: one device int32 that receives ``FTN_NBQ_RANGE`` (default: fresh, zeroed).  Returns ``(out, flag)``.
+    Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(rate, torch.Tensor) or rate.dim() != 3:
+        raise ValueError("nb_quantiles: rate must be a [B, H, N] tensor")
+    _score_operands((("rate", rate), ("dispersion", disp)))
+    if disp.device != rate.device:
+        raise ValueError("nb_quantiles: rate and dispersion must be on one device")
+    B, H, N = rate.shape
+    if B < 1 or H < 1 or N < 1:
+        raise ValueError(f"nb_quantiles: empty shape {tuple(rate.shape)}")
+    lv = [float(q) for q in levels]
+    Q = len(lv)
+    arr = (C.c_double * max(Q, 1))(*lv)
+    if out is None:
+        out = torch.empty(max(Q, 1), B, H, N, dtype=torch.float32, device=rate.device)
+    elif (out.dtype != torch.float32 or out.device != rate.device or not out.is_contiguous()
+          or tuple(out.shape) != (Q, B, H, N)):
+        raise ValueError(f"nb_quantiles: out must be contiguous fp32 {(Q, B, H, N)} beside rate")
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=rate.device)
+    _nbq_flag(flag, rate.device, "nb_quantiles")
+    check(lib.ftn_nb_quantiles(_ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0), B, H, N, arr, Q, float(eps),
+                               _ptr(out), _ptr(flag), _stream(rate.device)), "ftn_nb_quantiles")
+    return out, flag
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch

@@ -10,6 +10,10 @@ into a NaN mean.
 
 ``ForecastScorer`` accumulates per-slot sums over many batches (``update`` only enqueues; ``result`` makes the one
 synchronisation), ``eval_metrics`` is ``_eval_metrics`` as a loop over batch tuples around it.
+
+``nb_cdf`` / ``nb_quantiles`` / ``prediction_interval`` / ``interval_metrics`` use the distribution itself (no
+counterpart in the reference): the regularised incomplete beta function and its inversion, ``k_nb_cdf`` /
+``k_nb_quantile`` on the ``hip`` side and the same method in fp64 torch ops otherwise.
 """
 from __future__ import annotations
 
@@ -327,3 +331,262 @@ def eval_metrics(model, batches, mode: str, pred_len: int, use_loss_mask: bool =
     if scorer is None:
         raise ValueError("eval_metrics: no batches")
     return scorer.result()
+
+
+# ---------------------------------------------------------------------------------------------- quantiles and CDF
+# F(y) = I_p(r, floor(yc) + 1), r = 1 / alpha, p = 1 / (1 + alpha mu), with the scorer's clamps; Q(q) the smallest
+# integer k >= 0 with F(k) >= q.  ``hip``: k_nb_cdf / k_nb_quantile (csrc/quantile.hip).  ``torch``: the same
+# continued fraction and the same bracketed search in fp64 torch ops, so the functions run on CPU tensors.
+NBQ_QMAX = 8                 # levels of one k_nb_quantile launch (FTN_QMAX)
+NBQ_KLIM = float(1 << 24)    # answers below it are exact in fp32; at or beyond it: NaN and flag bit 1
+NBQ_FLAG_RANGE = 2           # bit 1 of the flag word
+_NBQ_CF_MAX = 4096           # continued-fraction iterations (the kernel's NBQ_CF_MAX)
+_NBQ_EVALS = 32              # CDF evaluations of one level: 6 Newton steps, then 25 halvings of [0, 2^24] and one spare
+_NBQ_NEWTON = 6
+_NBQ_WALK = 64               # pmf-recurrence steps after an evaluation
+
+
+def _nbq_params(rate, dispersion, eps):
+    """``(r, t, p, 1 - p, log p, log(1 - p), valid)`` in fp64 from fp32-rounded inputs, the scorer's clamps."""
+    al = dispersion.to(torch.float32)
+    mu = rate.to(torch.float32)
+    e = torch.tensor(eps, dtype=torch.float32, device=al.device)
+    al = torch.where(al < e, e, al)
+    mu = torch.where(mu < e, e, mu)
+    valid = torch.isfinite(al) & torch.isfinite(mu)
+    one = torch.ones_like(al)
+    al, mu = torch.where(valid, al, one).double(), torch.where(valid, mu, one).double()
+    r, t = 1.0 / al, al * mu
+    return r, t, 1.0 / (1.0 + t), t / (1.0 + t), -torch.log1p(t), -torch.log1p(1.0 / t), valid
+
+
+def _stirling_corr(x):
+    z = 1.0 / x
+    z2 = z * z
+    return z * (1.0 / 12.0 + z2 * (-1.0 / 360.0 + z2 * (1.0 / 1260.0 + z2 * (-1.0 / 1680.0))))
+
+
+def _log_inv_beta(a, b):
+    """lgamma(a + b) - lgamma(a) - lgamma(b); for max(a, b) >= 16 the two large lgammas are differenced in
+    Stirling's form, which keeps 1e8-sized terms from cancelling."""
+    L, S = torch.maximum(a, b), torch.minimum(a, b)
+    big = L >= 16.0
+    Ls = torch.where(big, L, torch.full_like(L, 16.0))
+    ratio = S * torch.log(Ls + S) + (Ls - 0.5) * torch.log1p(S / Ls) - S + _stirling_corr(Ls + S) - _stirling_corr(Ls)
+    return torch.where(big, ratio, torch.lgamma(L + S) - torch.lgamma(L)) - torch.lgamma(S)
+
+
+def _betacf(a, b, x, iters=_NBQ_CF_MAX):
+    """The continued fraction of I_x(a, b) by the modified Lentz method; ``(h, converged)``."""
+    tiny = 1e-300
+    qab, qap, qam = a + b, a + 1.0, a - 1.0
+    c = torch.ones_like(a)
+    d = 1.0 - qab * x / qap
+    d = 1.0 / torch.where(d.abs() < tiny, torch.full_like(d, tiny), d)
+    h = d.clone()
+    live = torch.ones_like(a, dtype=torch.bool)
+    for m in range(1, iters + 1):
+        m2 = 2.0 * m
+        aa = m * (b - m) * x / ((qam + m2) * (a + m2))
+        d = 1.0 + aa * d
+        d = 1.0 / torch.where(d.abs() < tiny, torch.full_like(d, tiny), d)
+        c = 1.0 + aa / c
+        c = torch.where(c.abs() < tiny, torch.full_like(c, tiny), c)
+        h1 = h * d * c
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))
+        d = 1.0 + aa * d
+        d = 1.0 / torch.where(d.abs() < tiny, torch.full_like(d, tiny), d)
+        c = 1.0 + aa / c
+        c = torch.where(c.abs() < tiny, torch.full_like(c, tiny), c)
+        de = d * c
+        h = torch.where(live, h1 * de, h)
+        live = live & ~((de - 1.0).abs() < 1e-13)
+        if m % 8 == 0 and not bool(live.any()):
+            break
+    return h, ~live
+
+
+def _nb_cdf_pmf(k, r, p, omp, lp, lomp):
+    """``(F(k), pmf(k), converged)`` for integer-valued fp64 k >= 0."""
+    a, b = r, k + 1.0
+    front = torch.exp(_log_inv_beta(a, b) + a * lp + b * lomp)
+    swap = p * (a + b + 2.0) >= a + 1.0
+    h, ok = _betacf(torch.where(swap, b, a), torch.where(swap, a, b), torch.where(swap, omp, p))
+    F = torch.where(swap, 1.0 - front * h / b, front * h / a)
+    return F.clamp(0.0, 1.0), front / ((k + r) * omp), ok
+
+
+def _nb_cdf_torch(y, rate, dispersion, eps):
+    r, t, p, omp, lp, lomp, valid = _nbq_params(rate, dispersion, eps)
+    yf = y.to(torch.float32)
+    yc = torch.where(yf < 0, torch.zeros_like(yf), yf)
+    valid = valid & torch.isfinite(yc)
+    k = torch.floor(torch.where(valid, yc, torch.zeros_like(yc)).double())
+    inside = k < NBQ_KLIM
+    F, _, ok = _nb_cdf_pmf(torch.where(inside, k, torch.zeros_like(k)), r, p, omp, lp, lomp)
+    bad = valid & ~(inside & ok)
+    F = torch.where(valid & ~bad, F, torch.full_like(F, float("nan")))
+    return F, bad.any().to(torch.int32) * NBQ_FLAG_RANGE
+
+
+def _nbq_guess(z, r, t, omp, p):
+    """Cornish-Fisher start: mean + sd (z + skew (z^2 - 1) / 6), floored into [0, 2^24)."""
+    mean = r * t
+    sd = torch.sqrt(mean * (1.0 + t))
+    skew = (2.0 - p) / torch.sqrt(r * omp)
+    g = torch.floor(mean + sd * (z + skew * (z * z - 1.0) / 6.0))
+    return torch.nan_to_num(g, nan=0.0, posinf=NBQ_KLIM - 1.0, neginf=0.0).clamp(0.0, NBQ_KLIM - 1.0)
+
+
+def _nb_quantiles_torch(rate, dispersion, levels, eps):
+    from statistics import NormalDist
+
+    r, t, p, omp, lp, lomp, valid = _nbq_params(rate, dispersion, eps)
+    order = sorted(range(len(levels)), key=lambda i: levels[i])
+    out = torch.empty((len(levels),) + tuple(rate.shape), dtype=torch.float32, device=rate.device)
+    nan = torch.full_like(r, float("nan"))
+    bad_any = torch.zeros((), dtype=torch.bool, device=rate.device)
+    k = torch.zeros_like(r)
+    F = torch.zeros_like(r)
+    pm = torch.zeros_like(r)
+    have = torch.zeros_like(valid)
+    prev = torch.zeros_like(r)
+    for i in order:
+        q = float(levels[i])
+        g = torch.maximum(_nbq_guess(NormalDist().inv_cdf(q), r, t, omp, p), prev)
+        lo, hi = prev.clone(), torch.full_like(r, NBQ_KLIM)
+        jump = ~(have & (g <= k + _NBQ_WALK))
+        k = torch.where(jump, g, k)
+        need = jump
+        done = ~valid
+        for it in range(_NBQ_EVALS):
+            if bool(need.any()):
+                Fe, pe, ok = _nb_cdf_pmf(k, r, p, omp, lp, lomp)
+                F, pm = torch.where(need, Fe, F), torch.where(need, pe, pm)
+                done = done | (need & ~ok)                      # the fraction's cap: lo < hi stays, so NaN below
+            for _ in range(_NBQ_WALK):
+                act = ~done
+                down = act & (F >= q) & (k > lo) & (F - pm >= q)
+                up = act & (F < q) & (k + 1.0 < NBQ_KLIM)
+                if not bool((down | up).any()):
+                    break
+                Fd, pd = F - pm, pm * k / ((k - 1.0 + r) * omp)
+                pu = pm * (k + r) / (k + 1.0) * omp
+                F = torch.where(down, Fd, torch.where(up, F + pu, F))
+                pm = torch.where(down, pd, torch.where(up, pu, pm))
+                lo = torch.where(up, k + 1.0, lo)
+                k = torch.where(down, k - 1.0, torch.where(up, k + 1.0, k))
+            ge = F >= q
+            hi = torch.where(~done & ge, torch.minimum(hi, k), hi)
+            lo = torch.where(~done & ~ge, k + 1.0, lo)
+            found = ~done & ge & ((k <= lo) | (F - pm < q))
+            lo = torch.where(found, k, lo)
+            hi = torch.where(found, k, hi)
+            done = done | found | (lo >= hi)
+            kn = torch.floor(k + (q - F) / pm + 0.5)
+            newton = (it < _NBQ_NEWTON) & (kn >= lo) & (kn < hi)
+            kn = torch.where(newton, kn, torch.floor(0.5 * (lo + hi)))
+            need = ~done
+            k = torch.where(need, kn.clamp(max=NBQ_KLIM - 1.0), k)
+            if bool(done.all()):
+                break
+        ans_ok = valid & (lo >= hi) & (hi < NBQ_KLIM)
+        bad_any = bad_any | (valid & ~ans_ok).any()
+        out[i] = torch.where(ans_ok, hi, nan).to(torch.float32)
+        have = ans_ok & (k == hi)
+        prev = torch.where(ans_ok, hi, prev)
+    out[:, ~valid] = float("nan")
+    return out, bad_any.to(torch.int32) * NBQ_FLAG_RANGE
+
+
+def _check_levels(levels) -> List[float]:
+    lv = [float(q) for q in levels]
+    if not lv:
+        raise ValueError("nb_quantiles: no levels")
+    for q in lv:
+        if not 0.0 < q < 1.0:
+            raise ValueError(f"nb_quantiles: level {q} is not strictly inside (0, 1)")
+    return lv
+
+
+def nb_cdf(y: torch.Tensor, rate: torch.Tensor, dispersion: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
+    """``F(y)`` of the negative binomial ``(rate, dispersion)`` per element, fp32 [B,H,N]: ``I_p(r, floor(yc) + 1)``
+    with the scorer's clamps (``yc = max(y, 0)``, ``alpha = max(dispersion, eps)``, ``mu = max(rate, eps)``,
+    ``r = 1 / alpha``, ``p = 1 / (1 + alpha mu)``).  NaN where ``yc``, ``alpha`` or ``mu`` is not finite, and where
+    ``floor(yc) >= 2^24``.  Never synchronises on the ``hip`` backend."""
+    global _last_backend
+    if _hip_eligible(y, rate, dispersion):
+        from . import runtime as rt
+
+        out = rt.nb_cdf(_rows(y), _rows(rate), _rows(dispersion), eps)
+        _last_backend = "hip"
+        return out
+    if not (tuple(y.shape) == tuple(rate.shape) == tuple(dispersion.shape)):
+        raise ValueError(f"nb_cdf takes y, rate, dispersion of one shape, got {tuple(y.shape)} {tuple(rate.shape)} "
+                         f"{tuple(dispersion.shape)}")
+    with torch.no_grad():
+        F, _ = _nb_cdf_torch(y, rate, dispersion, eps)
+    _last_backend = "torch"
+    return F.to(torch.float32)
+
+
+def nb_quantiles(rate: torch.Tensor, dispersion: torch.Tensor, levels, eps: float = 1e-8,
+                 check: bool = False) -> torch.Tensor:
+    """``Q(q)`` for every ``q`` of ``levels`` (floats strictly inside (0, 1), any order, any number: the kernel takes
+    8 per launch): the smallest integer k >= 0 with ``F(k) >= q``, as fp32 [Q,B,H,N].  Supported answers are below
+    2^24; an element beyond that is NaN and sets bit 1 of a device flag that only ``check=True`` reads (one
+    synchronisation; raises ``ValueError``).  NaN, without the flag, where ``alpha`` or ``mu`` is not finite."""
+    global _last_backend
+    lv = _check_levels(levels)
+    if _hip_eligible(rate, dispersion):
+        from . import runtime as rt
+
+        r, d = _rows(rate), _rows(dispersion)
+        flag = torch.zeros(1, dtype=torch.int32, device=rate.device)
+        out = torch.empty((len(lv),) + tuple(rate.shape), dtype=torch.float32, device=rate.device)
+        for i in range(0, len(lv), NBQ_QMAX):
+            rt.nb_quantiles(r, d, lv[i:i + NBQ_QMAX], eps, out=out[i:i + NBQ_QMAX], flag=flag)
+        _last_backend = "hip"
+    else:
+        if tuple(rate.shape) != tuple(dispersion.shape):
+            raise ValueError(f"nb_quantiles takes rate and dispersion of one shape, got {tuple(rate.shape)} "
+                             f"{tuple(dispersion.shape)}")
+        with torch.no_grad():
+            out, flag = _nb_quantiles_torch(rate, dispersion, lv, eps)
+        _last_backend = "torch"
+    if check and int(flag.reshape(-1)[0]) & NBQ_FLAG_RANGE:
+        raise ValueError("nb_quantiles: an element's quantile is outside the supported range [0, 2^24) (or its "
+                         "search hit an iteration cap); that element is NaN")
+    return out
+
+
+def prediction_interval(rate: torch.Tensor, dispersion: torch.Tensor, coverage: float = 0.9, eps: float = 1e-8):
+    """``(lo, hi)``: the ``(1 - coverage) / 2`` and ``(1 + coverage) / 2`` quantiles, each fp32 [B,H,N]."""
+    c = float(coverage)
+    if not 0.0 < c < 1.0:
+        raise ValueError(f"prediction_interval: coverage {c} is not strictly inside (0, 1)")
+    q = nb_quantiles(rate, dispersion, [(1.0 - c) / 2.0, (1.0 + c) / 2.0], eps)
+    return q[0], q[1]
+
+
+def interval_metrics(y: torch.Tensor, rate: torch.Tensor, dispersion: torch.Tensor, levels,
+                     mask: torch.Tensor | None = None, eps: float = 1e-8) -> Dict[str, torch.Tensor]:
+    """Calibration of the distribution over the valid elements (``negative_binomial_mask``; an element whose quantile
+    or CDF came out NaN is dropped too), as tensors on ``y``'s device and without a host read: ``coverage`` [Q], the
+    mean of ``y <= Q(q)``; ``pinball`` [Q], the mean of ``max(q (y - Q), (q - 1) (y - Q))``; ``pit_mean``, the mean
+    of ``F(y)``; ``count``, the valid elements (int64)."""
+    lv = _check_levels(levels)
+    Q = nb_quantiles(rate, dispersion, lv, eps)
+    F = nb_cdf(y, rate, dispersion, eps)
+    valid = negative_binomial_mask(y, rate, dispersion, mask) & torch.isfinite(F) & torch.isfinite(Q).all(0)
+    w = valid.to(torch.float32)
+    den = w.sum().clamp(min=1.0)
+    zero = torch.zeros((), dtype=torch.float32, device=y.device)
+    yv = torch.where(valid, y.to(torch.float32), zero)
+    Qv = torch.where(valid, Q, zero)
+    diff = yv - Qv                                              # the levels stay Python scalars: no host-to-device copy
+    pin = torch.stack([torch.maximum(q * diff[i], (q - 1.0) * diff[i]) for i, q in enumerate(lv)]) * w
+    return {"coverage": ((yv <= Qv).to(torch.float32) * w).sum((1, 2, 3)) / den,
+            "pinball": pin.sum((1, 2, 3)) / den,
+            "pit_mean": (torch.where(valid, F, zero)).sum() / den,
+            "count": valid.sum()}

@@ -536,6 +536,38 @@ int ftn_score_fold(const FtnScorePart* part_dev, int B, int N, int ids_kind, con
                    const long long* order_dev, const long long* seg_start_dev, FtnScorePart* acc_dev, int n_slots,
                    int* err_dev, void* stream);
 
+/* ---- using the forecast's distribution: NB CDF and quantiles (no counterpart in the reference) -----------
+ * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
+ *
+ * The parameterisation is ftn_score_columns': alpha = disp < eps ? eps : disp, mu = rate < eps ? eps : rate (a NaN
+ * stays a NaN), r = 1 / alpha, p = 1 / (1 + alpha mu).  F(k) = I_p(r, k + 1), the regularised incomplete beta
+ * function, evaluated in fp64 (continued fraction, modified Lentz) and rounded once.  Operands are fp32 [B][H][N],
+ * rows N elements apart, N fastest, each with its own batch stride in elements; outputs are contiguous.
+ *
+ * ftn_nb_cdf (k_nb_cdf<CPL>): out[b][h][n] = F(floor(yc)), yc = y < 0 ? 0 : y.  NaN where yc, alpha or mu is not
+ * finite (the flag stays clear).  floor(yc) >= 2^24, or a continued fraction that used up its iterations, gives NaN
+ * and sets FTN_NBQ_RANGE in *flag_dev.  out64_dev (optional): the same values before the rounding to fp32.
+ * flag_dev (optional): one int32, OR-ed, never cleared or read here.
+ * ftn_nb_quantiles (k_nb_quantile<CPL>): out[i][b][h][n] = the smallest integer k >= 0 with F(k) >= levels_host[i],
+ * for Q = 1..FTN_QMAX levels strictly inside (0, 1) in any order (they are passed to the kernel by value).
+ * Supported answers are k < 2^24, exact in fp32.  NaN where alpha or mu is not finite (flag clear); an answer
+ * >= 2^24 or a search that used up its evaluations gives NaN and sets FTN_NBQ_RANGE in *flag_dev (required).
+ * Neither allocates; both enqueue on `stream` only.
+ * ftn_nbq_form (host-only; both launches dispatch through the same function):
+ *   bit 1      FTN_SHELL_VEC  16-byte loads, four elements per lane (N % 4 == 0, every batch stride a multiple of 4,
+ *              misalign_or == 0); otherwise one element per lane
+ * misalign_or: the OR of (address & 15) of y, rate, disp and out for ftn_nb_cdf; of rate and disp for
+ * ftn_nb_quantiles, which passes y_bstride = 0 and stores 4 bytes at a time. */
+#define FTN_QMAX 8
+#define FTN_NBQ_RANGE 2
+int ftn_nbq_form(int N, long long y_bstride, long long rate_bstride, long long disp_bstride, int misalign_or);
+int ftn_nb_cdf(const float* y_dev, long long y_bstride, const float* rate_dev, long long rate_bstride,
+               const float* disp_dev, long long disp_bstride, int B, int H, int N, float eps, float* out_dev,
+               double* out64_dev, int* flag_dev, void* stream);
+int ftn_nb_quantiles(const float* rate_dev, long long rate_bstride, const float* disp_dev, long long disp_bstride,
+                     int B, int H, int N, const double* levels_host, int Q, float eps, float* out_dev, int* flag_dev,
+                     void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
