@@ -9,9 +9,12 @@ Sub-modules
 ``models.timesnet``  drop-in mirrors of the reference modules
 ``models.shell``     mirror of the TimesNet model shell; HIP embedding / head kernels around the blocks
 ``dist``             batch-sharded multi-GPU forward (RCCL via torch.distributed)
-``forecast``         recursive forecasting with the window state on the device (eager or one HIP graph)
+``forecast``         recursive forecasting with the window state on the device (eager or one HIP graph);
+                     ``forecast_sample_paths``: the same recursion fed with draws, P paths as one batch
 ``score``            NB likelihood and sMAPE of a forecast on the device: ``negative_binomial_nll``, ``ForecastScorer``;
-                     the distribution itself: ``nb_cdf``, ``nb_quantiles``, ``prediction_interval``, ``interval_metrics``
+                     the distribution itself: ``nb_cdf``, ``nb_quantiles``, ``prediction_interval``, ``interval_metrics``;
+                     sample paths: ``nb_sample`` (counter-based Philox, CDF inversion), ``sample_uniforms``,
+                     ``path_quantiles``
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401

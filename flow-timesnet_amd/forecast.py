@@ -23,6 +23,9 @@ Anything else - CPU tensors, a ``direct``-mode model, autograd, ``embed_norm_mod
 model, a ``last_seq`` whose window takes another embedding kernel than the loop's later windows (a view that is not
 16-byte aligned, or whose batch stride is not a multiple of 4, with N % 4 == 0), ``embed_norm_mode="layer"`` at a
 d_model that is not a multiple of 16 - runs the reference's loop unchanged (``forecast_recursive_batch_loop``).
+
+``forecast_sample_paths`` is the same recursion fed with draws instead of rates (``score.nb_sample`` at
+``offset = step``), P paths as one batch of P B rows; ``forecast_sample_paths_loop`` fixes its semantics.
 """
 from __future__ import annotations
 
@@ -172,9 +175,10 @@ def _mark_window(x_mark, y_mark, L: int, s: int) -> torch.Tensor:
     return seq.narrow(1, T - L, L)
 
 
-def _enqueue(model, last_seq, H, x_mark, y_mark, series_static, series_ids, rate_out, disp_out):
+def _enqueue(model, last_seq, H, x_mark, y_mark, series_static, series_ids, rate_out, disp_out, feedback=None):
     """Enqueue the H steps (no host synchronisation).  Writes step s into ``[:, s]`` of the outputs; returns the heads'
-    finite-positive flags (one per step)."""
+    finite-positive flags (one per step).  ``feedback(s, rate, disp)`` gives the row [B, 1, N] that step s feeds back as
+    the newest observation; the default is the rate itself, the reference's recursion."""
     from . import runtime
 
     L = model.input_len
@@ -200,7 +204,7 @@ def _enqueue(model, last_seq, H, x_mark, y_mark, series_static, series_ids, rate
         bads.append(model._pending_bad)
         rate_out[:, s].copy_(rate[:, 0])
         disp_out[:, s].copy_(disp[:, 0])
-        tail = rate
+        tail = rate if feedback is None else feedback(s, rate, disp)
     model._last_embed_backend = "hip"
     return bads
 
@@ -252,6 +256,115 @@ def forecast_recursive_batch(model, last_seq: torch.Tensor, H: int, x_mark: Opti
     if _device_ok(model, last_seq, H, x_mark, y_mark, series_static, series_ids):
         return _forecast_device(model, last_seq, int(H), x_mark, y_mark, series_static, series_ids)
     return forecast_recursive_batch_loop(model, last_seq, H, x_mark, y_mark, series_static, series_ids)
+
+
+# --------------------------------------------------------------------------------------------------------- sample paths
+def _repeat_paths(P, B, last_seq, x_mark, y_mark, series_static, series_ids):
+    """The inputs of a batch of P B rows, path-major (row p B + b): what has a batch axis is repeated P times."""
+    def rep(t, batched):
+        return t if t is None or not batched else t.repeat(P, *([1] * (t.dim() - 1)))
+
+    return (rep(last_seq, True), rep(x_mark, True), rep(y_mark, True),
+            rep(series_static, series_static is not None and series_static.dim() == 3 and series_static.size(0) == B),
+            rep(series_ids, series_ids is not None and series_ids.dim() == 2 and series_ids.size(0) == B))
+
+
+def _raise_if_sample_range(flags) -> None:
+    for step, flag in enumerate(flags.tolist()):
+        if flag:
+            raise RuntimeError(f"forecast_sample_paths: a draw of step {step} is outside the supported range "
+                               f"[0, 2^24) (its rate or dispersion is too large to sample)")
+
+
+def forecast_sample_paths_loop(model, last_seq, H, n_paths, seed=0, x_mark=None, y_mark=None, series_static=None,
+                               series_ids=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """What ``forecast_sample_paths`` means, as a host loop: the P paths of the B rows are the rows of one batch of
+    P B (path-major); step s calls the model on that batch, draws ``score.nb_sample(rate_s, disp_s, 1, seed,
+    offset=s)[0]`` and feeds the draw - not the rate - back as the newest row of every path's window."""
+    from . import score
+
+    P, B = int(n_paths), last_seq.size(0)
+    if P < 1 or int(H) < 1:
+        raise ValueError(f"forecast_sample_paths: n_paths={n_paths}, H={H}")
+    seq, mark_seq, y_mark, series_static, series_ids = _repeat_paths(P, B, last_seq, x_mark, y_mark, series_static,
+                                                                     series_ids)
+    samples: List[torch.Tensor] = []
+    rates: List[torch.Tensor] = []
+    dispersions: List[torch.Tensor] = []
+    for step in range(int(H)):
+        rate_step, dispersion_step = _invoke_model(model, seq, x_mark=mark_seq, series_static=series_static,
+                                                   series_ids=series_ids)
+        flag = torch.zeros(1, dtype=torch.int32, device=rate_step.device)
+        with torch.no_grad():
+            draw = score.nb_sample(rate_step.detach().float(), dispersion_step.detach().float(), 1, seed, offset=step,
+                                   flag=flag)[0]
+        _raise_if_sample_range(flag)
+        samples.append(draw)
+        rates.append(rate_step)
+        dispersions.append(dispersion_step)
+        seq = torch.cat([seq[:, 1:, :], draw.to(seq.dtype)], dim=1)
+        if mark_seq is not None:
+            if y_mark is None:
+                raise ValueError(_MISSING_Y_MARK)
+            if y_mark.size(1) <= step:
+                raise ValueError(_SHORT_Y_MARK)
+            mark_seq = torch.cat([mark_seq[:, 1:, :], y_mark[:, step: step + 1, :]], dim=1)
+    N = last_seq.size(2)
+    return tuple(torch.cat(v, dim=1).reshape(P, B, int(H), N) for v in (samples, rates, dispersions))
+
+
+def _sample_paths_device(model, seq, H, seed, x_mark, y_mark, series_static, series_ids):
+    """``_forecast_device`` with the draw fed back: the sample range flags of all H steps are one device vector, read
+    after the forecast with the heads' and the blocks' flags."""
+    from . import score
+
+    def run():
+        rate = torch.empty(seq.size(0), H, seq.size(2), dtype=torch.float32, device=seq.device)
+        disp, samples = torch.empty_like(rate), torch.empty_like(rate)
+        flags = torch.zeros(H, dtype=torch.int32, device=seq.device)
+
+        def feedback(s, rate_s, disp_s):
+            draw = score.nb_sample(rate_s, disp_s, 1, seed, offset=s, backend="hip", flag=flags[s:s + 1])[0]
+            samples[:, s].copy_(draw[:, 0])
+            return draw
+
+        bads = _enqueue(model, seq, H, x_mark, y_mark, series_static, series_ids, rate, disp, feedback)
+        return samples, rate, disp, bads, flags
+
+    with _deferred_checks(model):
+        samples, rate, disp, bads, flags = range_guard.repeat_on_trip(model.blocks, run, message=_RANGE_WARNING)
+    _raise_if_sample_range(flags)           # a draw out of range is a NaN in the next window: the cause comes first
+    _raise_if_bad(bads)
+    return samples, rate, disp
+
+
+def forecast_sample_paths(model, last_seq: torch.Tensor, H: int, n_paths: int, seed=0,
+                          x_mark: Optional[torch.Tensor] = None, y_mark: Optional[torch.Tensor] = None,
+                          series_static: Optional[torch.Tensor] = None, series_ids: Optional[torch.Tensor] = None
+                          ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``n_paths`` sample paths of an H-step recursive forecast: ``(samples, rate, dispersion)``, each [P, B, H, N].
+    Path p of row b draws its step-s count from the model's distribution given its own earlier draws, so the spread
+    of ``samples[:, b, s]`` grows with s as the forecast's uncertainty does; ``rate`` and ``dispersion`` are the
+    distributions each path drew from.  ``score.path_quantiles`` turns the paths into intervals of sums and maxima.
+
+    The semantics are ``forecast_sample_paths_loop``'s, bit for bit.  The paths are the rows of one batch of P B, and
+    the period selector averages amplitudes over its batch, so the paths see each other through the selected periods
+    (and a forecast with other ``n_paths`` is not a prefix of this one): that is the model's own behaviour on such a
+    batch.  A draw is a pure function of ``(seed, step, row, series)`` and the step's distribution
+    (``score.nb_sample`` at ``offset = step``).  Runs on the device, without a host synchronisation per step, where
+    ``forecast_recursive_batch`` would for the repeated batch; the loop otherwise.  A draw outside [0, 2^24) raises a
+    RuntimeError that names its step."""
+    P = int(n_paths)
+    if P < 1 or int(H) < 1:
+        raise ValueError(f"forecast_sample_paths: n_paths={n_paths}, H={H}")
+    if isinstance(last_seq, torch.Tensor) and last_seq.dim() == 3:
+        B, N = last_seq.size(0), last_seq.size(2)
+        seq, xm, ym, st, ids = _repeat_paths(P, B, last_seq, x_mark, y_mark, series_static, series_ids)
+        seed_ok = not isinstance(seed, torch.Tensor) or seed.device == last_seq.device
+        if seed_ok and _device_ok(model, seq, H, xm, ym, st, ids):
+            out = _sample_paths_device(model, seq, int(H), seed, xm, ym, st, ids)
+            return tuple(t.view(P, B, int(H), N) for t in out)
+    return forecast_sample_paths_loop(model, last_seq, H, n_paths, seed, x_mark, y_mark, series_static, series_ids)
 
 
 # --------------------------------------------------------------------------------------------------------- graph replay

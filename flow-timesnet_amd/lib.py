@@ -189,6 +189,9 @@ _SIGNATURES = {
                              C.c_float, _P, _P, _P, _P]),
     "ftn_nb_quantiles": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(C.c_double), C.c_int, C.c_float, _P, _P, _P]),
+    "ftn_nb_sample_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_nb_sample": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
+                                _P, C.c_uint, C.c_float, _P, _P, _P, _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -695,6 +695,59 @@ def nb_quantiles(rate: torch.Tensor, disp: torch.Tensor, levels, eps: float = 1e
     return out, flag
 
 
+# ------------------------------------------------------------------ NB sampling
+def nb_sample_form(rate, disp) -> str:
+    """The kernel form ``ftn_nb_sample`` takes for these tensors (``ftn_nb_sample_form``): ``"vec4"`` or
+    ``"scalar"``, by ``nbq_form_of``'s rule for rate and dispersion."""
+    B, H, N = rate.shape
+    f = _lib.load().ftn_nb_sample_form(int(N), rate.stride(0) if B > 1 else 0, disp.stride(0) if B > 1 else 0,
+                                       (_ptr(rate) | _ptr(disp)) & 15)
+    if f < 0:
+        check(f, "ftn_nb_sample_form")
+    return "vec4" if f & 2 else "scalar"
+
+
+def nb_sample(rate: torch.Tensor, disp: torch.Tensor, n_samples: int = 1, seed=0, offset: int = 0, eps: float = 1e-8,
+              out: torch.Tensor | None = None, flag: torch.Tensor | None = None, want_uniforms: bool = False):
+    """``k_nb_sample``: ``out[s]`` [B,H,N] fp32 is draw s of the negative binomial ``(rate, disp)`` per element
+    (include/flowtimes.h states the generator).  ``seed``: a Python int, or one int64 / uint64 element on the
+    operands' device that the kernel reads.  ``out``: a contiguous fp32 [S,B,H,N] to fill (default: fresh); ``flag``:
+    one device int32 that receives ``FTN_NBQ_RANGE`` (default: fresh, zeroed).  Returns ``(out, flag, u)``, ``u`` the
+    fp64 uniforms [S,B,H,N] with ``want_uniforms``, else None.  Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(rate, torch.Tensor) or rate.dim() != 3:
+        raise ValueError("nb_sample: rate must be a [B, H, N] tensor")
+    _score_operands((("rate", rate), ("dispersion", disp)))
+    if disp.device != rate.device:
+        raise ValueError("nb_sample: rate and dispersion must be on one device")
+    B, H, N = rate.shape
+    S = int(n_samples)
+    if B < 1 or H < 1 or N < 1 or S < 1:
+        raise ValueError(f"nb_sample: empty shape {tuple(rate.shape)} or n_samples={n_samples}")
+    if not 0 <= int(offset) <= 0xFFFFFFFF:
+        raise ValueError(f"nb_sample: offset={offset} is not a 32-bit word")
+    seed_dev, seed_val = None, 0
+    if isinstance(seed, torch.Tensor):
+        if (seed.numel() != 1 or seed.dtype not in (torch.int64, torch.uint64) or seed.device != rate.device):
+            raise ValueError("nb_sample: a seed tensor must be one int64 / uint64 element on the operands' device")
+        seed_dev = seed
+    else:
+        seed_val = int(seed) & 0xFFFFFFFFFFFFFFFF
+    if out is None:
+        out = torch.empty(S, B, H, N, dtype=torch.float32, device=rate.device)
+    elif (out.dtype != torch.float32 or out.device != rate.device or not out.is_contiguous()
+          or tuple(out.shape) != (S, B, H, N)):
+        raise ValueError(f"nb_sample: out must be contiguous fp32 {(S, B, H, N)} beside rate")
+    u = torch.empty(S, B, H, N, dtype=torch.float64, device=rate.device) if want_uniforms else None
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=rate.device)
+    _nbq_flag(flag, rate.device, "nb_sample")
+    check(lib.ftn_nb_sample(_ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0), B, H, N, S, seed_val,
+                            _ptr_or_null(seed_dev), int(offset), float(eps), _ptr(out), _ptr_or_null(u), _ptr(flag),
+                            _stream(rate.device)), "ftn_nb_sample")
+    return out, flag, u
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch

@@ -14,6 +14,10 @@ synchronisation), ``eval_metrics`` is ``_eval_metrics`` as a loop over batch tup
 ``nb_cdf`` / ``nb_quantiles`` / ``prediction_interval`` / ``interval_metrics`` use the distribution itself (no
 counterpart in the reference): the regularised incomplete beta function and its inversion, ``k_nb_cdf`` /
 ``k_nb_quantile`` on the ``hip`` side and the same method in fp64 torch ops otherwise.
+
+``nb_sample`` / ``sample_uniforms`` / ``path_quantiles`` draw from it: a counter-based Philox4x32-10 and the inversion
+of that CDF (``k_nb_sample``, or the same generator and search in torch ops), so a draw is a pure function of
+``(seed, offset, element, draw index)``; ``forecast.forecast_sample_paths`` feeds the draws back into the recursion.
 """
 from __future__ import annotations
 
@@ -590,3 +594,190 @@ def interval_metrics(y: torch.Tensor, rate: torch.Tensor, dispersion: torch.Tens
             "pinball": pin.sum((1, 2, 3)) / den,
             "pit_mean": (torch.where(valid, F, zero)).sum() / den,
             "count": valid.sum()}
+
+
+# --------------------------------------------------------------------------------------------------------- sampling
+# Draw s of element e is the smallest integer k >= 0 with F(k) >= u(e, s): one uniform per draw, so a draw is a pure
+# function of (seed, offset, e, s) - the same on any device, grid, kernel form and backend.  The uniforms:
+#   Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (e & 0xffffffff, e >> 32, s >> 2, offset),
+#   e the row-major index of the element in ``shape``; draw s takes output word s & 3; u = (word + 0.5) 2^-32 (fp64).
+# ``hip``: k_nb_sample (csrc/sample.hip).  ``torch``: the same Philox in int64 ops and the quantile search above at a
+# level per element, started as the kernel starts it (from pmf(0) = p^r where the first guess is near 0).
+_M32 = 0xFFFFFFFF
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def _mulhilo32(m: int, c: torch.Tensor):
+    """``(high, low)`` 32-bit words of ``m * c`` for a 32-bit constant m and int64 c in [0, 2^32): by 16-bit halves of
+    c, so nothing leaves int64."""
+    a, b = m * (c & 0xFFFF), m * (c >> 16)                      # each below 2^48
+    return (b + (a >> 16)) >> 16, (a + ((b & 0xFFFF) << 16)) & _M32
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon et al., SC 2011) in int64 torch ops: ``counter`` four and ``key`` two 32-bit words, each
+    an int or an int64 tensor (broadcast together); returns the four output words as int64 tensors in [0, 2^32)."""
+    c = [w if isinstance(w, torch.Tensor) else torch.tensor(int(w) & _M32, dtype=torch.int64) for w in counter]
+    dev = next((w.device for w in list(counter) + list(key) if isinstance(w, torch.Tensor)), torch.device("cpu"))
+    c0, c1, c2, c3 = (w.to(device=dev, dtype=torch.int64) for w in c)
+    k0, k1 = (w.to(device=dev, dtype=torch.int64) if isinstance(w, torch.Tensor) else int(w) & _M32 for w in key)
+    for _ in range(10):
+        h0, l0 = _mulhilo32(_PHILOX_M[0], c0)
+        h1, l1 = _mulhilo32(_PHILOX_M[1], c2)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0, k1 = (k0 + _PHILOX_W[0]) & _M32, (k1 + _PHILOX_W[1]) & _M32
+    return c0, c1, c2, c3
+
+
+def _seed_key(seed, device):
+    """The key words of ``seed``: a Python int (its low 64 bits) or a one-element int64 / uint64 tensor."""
+    if isinstance(seed, torch.Tensor):
+        if seed.numel() != 1 or seed.dtype not in (torch.int64, torch.uint64):
+            raise ValueError("seed must be a Python int or a one-element int64 / uint64 tensor")
+        w = seed.reshape(1).view(torch.int64).to(device)
+        return w & _M32, (w >> 32) & _M32
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return s & _M32, s >> 32
+
+
+def sample_uniforms(n_samples: int, shape, seed=0, offset: int = 0, device=None) -> torch.Tensor:
+    """The uniforms of ``nb_sample`` for elements of ``shape`` (row-major index e): fp64 ``[n_samples, *shape]``,
+    ``u[s, e] = (word + 0.5) 2^-32`` with ``word`` output ``s & 3`` of Philox4x32-10 at counter
+    ``(e & 0xffffffff, e >> 32, s >> 2, offset)`` and key ``(seed & 0xffffffff, seed >> 32)``.  Strictly inside
+    (0, 1); draws ``s < S1`` of a longer call are those of the ``S1`` call."""
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError(f"sample_uniforms: n_samples={n_samples}")
+    if not 0 <= int(offset) <= _M32:
+        raise ValueError(f"sample_uniforms: offset={offset} is not a 32-bit word")
+    shape = tuple(int(v) for v in shape)
+    dev = torch.device(device) if device is not None else (seed.device if isinstance(seed, torch.Tensor)
+                                                           else torch.device("cpu"))
+    n = 1
+    for v in shape:
+        n *= v
+    e = torch.arange(n, dtype=torch.int64, device=dev)
+    key = _seed_key(seed, dev)
+    words = []
+    for blk in range((S + 3) // 4):
+        words.extend(philox4x32((e & _M32, e >> 32, blk, int(offset)), key))
+    w = torch.stack([t.expand(n) for t in words[:S]])
+    return ((w.to(torch.float64) + 0.5) * 2.0 ** -32).reshape((S,) + shape)
+
+
+def _nb_invert_torch(q, rate, dispersion, eps):
+    """The smallest integer k >= 0 with F(k) >= q for a level per element: ``q`` fp64 ``[S, *rate.shape]`` strictly
+    inside (0, 1).  The search of ``_nb_quantiles_torch`` with the kernel's start (k_nb_sample): from the known point
+    (0, p^r, p^r) where p^r has not underflowed and the Cornish-Fisher guess is within the walk of 0, else from the
+    guess.  Evaluations are made for the elements that still search only.  ``(out fp32, flag)``."""
+    shape = tuple(q.shape)
+    par = _nbq_params(rate, dispersion, eps)
+    r, t, p, omp, lp, lomp, valid = (v.expand(shape).reshape(-1) for v in par)
+    q = q.reshape(-1)
+    g = _nbq_guess(torch.special.ndtri(q), r, t, omp, p)
+    pm0 = torch.exp(r * lp)
+    k = torch.zeros_like(r)
+    F, pm = pm0.clone(), pm0.clone()
+    lo, hi = torch.zeros_like(r), torch.full_like(r, NBQ_KLIM)
+    need = ~((pm0 > 0.0) & (g <= float(_NBQ_WALK)))
+    k = torch.where(need, g, k)
+    done = ~valid
+    for it in range(_NBQ_EVALS):
+        i = (need & ~done).nonzero().squeeze(1)
+        if i.numel():
+            Fe, pe, ok = _nb_cdf_pmf(k[i], r[i], p[i], omp[i], lp[i], lomp[i])
+            F[i], pm[i] = Fe, pe
+            done[i[~ok]] = True                                 # the fraction's cap: lo < hi stays, so NaN below
+        for _ in range(_NBQ_WALK):
+            act = ~done
+            down = act & (F >= q) & (k > lo) & (F - pm >= q)
+            up = act & (F < q) & (k + 1.0 < NBQ_KLIM)
+            if not bool((down | up).any()):
+                break
+            Fd, pd = F - pm, pm * k / ((k - 1.0 + r) * omp)
+            pu = pm * (k + r) / (k + 1.0) * omp
+            F = torch.where(down, Fd, torch.where(up, F + pu, F))
+            pm = torch.where(down, pd, torch.where(up, pu, pm))
+            lo = torch.where(up, k + 1.0, lo)
+            k = torch.where(down, k - 1.0, torch.where(up, k + 1.0, k))
+        ge = F >= q
+        hi = torch.where(~done & ge, torch.minimum(hi, k), hi)
+        lo = torch.where(~done & ~ge, k + 1.0, lo)
+        found = ~done & ge & ((k <= lo) | (F - pm < q))
+        lo = torch.where(found, k, lo)
+        hi = torch.where(found, k, hi)
+        done = done | found | (lo >= hi)
+        kn = torch.floor(k + (q - F) / pm + 0.5)
+        newton = (it < _NBQ_NEWTON) & (kn >= lo) & (kn < hi)
+        kn = torch.where(newton, kn, torch.floor(0.5 * (lo + hi)))
+        need = ~done
+        k = torch.where(need, kn.clamp(max=NBQ_KLIM - 1.0), k)
+        if bool(done.all()):
+            break
+    ans_ok = valid & (lo >= hi) & (hi < NBQ_KLIM)
+    out = torch.where(ans_ok, hi, torch.full_like(hi, float("nan"))).to(torch.float32).reshape(shape)
+    return out, (valid & ~ans_ok).any().to(torch.int32) * NBQ_FLAG_RANGE
+
+
+def nb_sample(rate: torch.Tensor, dispersion: torch.Tensor, n_samples: int = 1, seed=0, offset: int = 0,
+              eps: float = 1e-8, backend: Optional[str] = None, return_uniforms: bool = False,
+              flag: Optional[torch.Tensor] = None):
+    """``n_samples`` draws of the negative binomial ``(rate, dispersion)`` per element, fp32 [S,B,H,N], in
+    ``nb_quantiles``' parameterisation: draw s of element e is ``Q(u[s, e])`` with ``u = sample_uniforms(S, rate.shape,
+    seed, offset)``, so a draw depends on nothing but ``(seed, offset, e, s)`` and the element's distribution.
+    ``seed``: a Python int or a one-element int64 / uint64 tensor on ``rate``'s device (read on the device: no
+    synchronisation).  ``backend``: ``"hip"`` (k_nb_sample; fp32 [B,H,N] tensors on a ROCm device, nothing for autograd
+    to record), ``"torch"`` (the same generator and search in torch ops, any device), or None: ``hip`` where it can
+    run.  NaN where alpha or mu is not finite; an answer >= 2^24 is NaN too and ORs bit 1 into ``flag`` (one int32 on
+    ``rate``'s device, optional).  ``return_uniforms``: ``(samples, u)``.  Never synchronises on the ``hip`` backend."""
+    global _last_backend
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError(f"nb_sample: n_samples={n_samples}")
+    if backend not in (None, "hip", "torch"):
+        raise ValueError(f"nb_sample: backend {backend!r} is not 'hip', 'torch' or None")
+    if not 0 <= int(offset) <= _M32:
+        raise ValueError(f"nb_sample: offset={offset} is not a 32-bit word")
+    if tuple(rate.shape) != tuple(dispersion.shape) or rate.dim() != 3:
+        raise ValueError(f"nb_sample takes rate and dispersion of one shape [B, H, N], got {tuple(rate.shape)} "
+                         f"{tuple(dispersion.shape)}")
+    eligible = _hip_eligible(rate, dispersion)
+    if backend == "hip" and not eligible:
+        raise ValueError("nb_sample: backend 'hip' takes fp32 [B, H, N] tensors on one ROCm device, without autograd")
+    if eligible and backend != "torch":
+        from . import runtime as rt
+
+        out, _, u = rt.nb_sample(_rows(rate), _rows(dispersion), S, seed, offset, eps, flag=flag,
+                                 want_uniforms=return_uniforms)
+        _last_backend = "hip"
+    else:
+        with torch.no_grad():
+            u = sample_uniforms(S, rate.shape, seed, offset, device=rate.device)
+            out, bad = _nb_invert_torch(u, rate, dispersion, eps)
+            if flag is not None:
+                flag |= bad.to(flag.device)
+        _last_backend = "torch"
+    return (out, u) if return_uniforms else out
+
+
+def path_quantiles(samples: torch.Tensor, levels, window: Optional[int] = None) -> torch.Tensor:
+    """Quantiles over sample paths: ``samples`` [P,B,H,N] -> [Q,B,H',N].  With ``window``, every path is first summed
+    over non-overlapping windows of ``window`` steps along H (``H' = H / window``; a ragged last window is an error).
+    The quantile is the order statistic ``ceil(q P)`` of the P paths (the inverted-CDF definition: the smallest value
+    whose empirical CDF reaches q), consistent with ``nb_quantiles``."""
+    import math
+
+    lv = _check_levels(levels)
+    if samples.dim() != 4:
+        raise ValueError(f"path_quantiles takes samples [P, B, H, N], got {tuple(samples.shape)}")
+    P, B, H, N = samples.shape
+    x = samples
+    if window is not None:
+        w = int(window)
+        if w < 1 or H % w:
+            raise ValueError(f"path_quantiles: window={window} does not divide H={H}")
+        x = x.reshape(P, B, H // w, w, N).sum(3)
+    ordered = torch.sort(x, dim=0).values
+    rows = [min(max(math.ceil(q * P), 1), P) - 1 for q in lv]
+    return ordered[rows]

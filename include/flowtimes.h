@@ -568,6 +568,24 @@ int ftn_nb_quantiles(const float* rate_dev, long long rate_bstride, const float*
                      int B, int H, int N, const double* levels_host, int Q, float eps, float* out_dev, int* flag_dev,
                      void* stream);
 
+/* ---- sampling the forecast's distribution (sample.hip) ----
+ * ftn_nb_sample (k_nb_sample<CPL>): out[s][b][h][n], s < S, is draw s of the negative binomial (rate, disp) of the
+ * element, in the parameterisation, clamps and operand layout of ftn_nb_quantiles: the smallest integer k >= 0 with
+ * F(k) >= u, F as ftn_nb_cdf defines it.  The uniforms are the contract:
+ *   Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (e & 0xffffffff, e >> 32, s >> 2, offset) with
+ *   e = (b H + h) N + n the logical element index (independent of strides and of the kernel form); draw s takes
+ *   output word s & 3; u = (word + 0.5) 2^-32 in fp64.
+ * seed_dev (optional): one 64-bit word in device memory, 8-byte aligned, read by the kernel instead of `seed`, so a
+ * captured launch can be replayed with another seed.  u_out_dev (optional): the uniforms, fp64 [S][B][H][N].
+ * NaN where alpha or mu is not finite (flag clear); an answer >= 2^24 or a search that used up a cap gives NaN and
+ * sets FTN_NBQ_RANGE in *flag_dev (required).  S >= 1.  Never allocates; enqueues on `stream` only.
+ * ftn_nb_sample_form (host-only; the launch dispatches through the same rule as ftn_nbq_form): bit 1 FTN_SHELL_VEC.
+ * misalign_or: the OR of (address & 15) of rate and disp. */
+int ftn_nb_sample_form(int N, long long rate_bstride, long long disp_bstride, int misalign_or);
+int ftn_nb_sample(const float* rate_dev, long long rate_bstride, const float* disp_dev, long long disp_bstride,
+                  int B, int H, int N, int S, unsigned long long seed, const unsigned long long* seed_dev,
+                  unsigned offset, float eps, float* out_dev, double* u_out_dev, int* flag_dev, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
