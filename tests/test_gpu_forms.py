@@ -92,13 +92,13 @@ def _stub_amps():
     return np.random.RandomState(STUB["seed"]).standard_normal(size=(STUB["B"], len(STUB["periods"]))).astype(np.float32)
 
 
-def oracle_fp64(x, P, act, k, L, periods=None, amps=None):
+def oracle_fp64(x, P, act, k, L, periods=None, amps=None, ks=KS):
     """The block in fp64: periods chosen by the fp32 oracle selector on fp32 x (as the seeded parity tests do), then
-    ``orc.timesblock_forward`` on double x / parameters / amplitudes with those periods."""
+    ``orc.timesblock_forward`` on double x / parameters / amplitudes with those periods (kernel set ``ks``)."""
     if periods is None:
         sel = orc.period_select(x, k, L, 1)
         periods, amps = sel.periods, sel.amps
-    y, _ = orc.timesblock_forward(x.double(), {n: v.double() for n, v in P.items()}, KS, act, 0, L, 1,
+    y, _ = orc.timesblock_forward(x.double(), {n: v.double() for n, v in P.items()}, ks, act, 0, L, 1,
                                   periods=list(periods), amps=torch.as_tensor(amps).double())
     return y, list(periods)
 
