@@ -6,7 +6,8 @@
 // a C x C rank count.  NR independent rows share one instruction stream: the dependent steps of a single sort (each a
 // cross-lane move) would leave the wave waiting on its own latency chain, and every workgroup of a launch reaches
 // this phase at the same time.  Values are only permuted - NaN-free, non-negative amplitudes - so the median is the
-// same bits whatever V and NR a caller picks.
+// same bits whatever V and NR a caller picks.  A row that holds a NaN (one NaN sample of x makes its channel NaN in
+// every bin) reads NaN, as torch.median does: the network itself would lose it.
 #pragma once
 #include <math.h>
 #include "ftn_common.h"
@@ -88,6 +89,14 @@ __device__ __forceinline__ void wave_lower_median_rows(const float* __restrict__
   for (int i = 0; i < V; ++i)
 #pragma unroll
     for (int r = 0; r < NR; ++r) v[i][r] = 64 * i + lane < C ? base[r * stride + 64 * i + lane] : INFINITY;
+  // torch.median propagates NaN; v_med3_f32 drops it (and hands its partner the +-inf selector instead).  Lanes that
+  // hold one in any row: one unordered compare (v_cmp_u_f32) per TWO values, which is all a NaN-free call pays
+  unsigned long long anynan = 0;
+#pragma unroll
+  for (int j = 0; j < V * NR; j += 2) {
+    const float a = v[j / NR][j % NR], b = j + 1 < V * NR ? v[(j + 1) / NR][(j + 1) % NR] : a;
+    anynan |= __builtin_amdgcn_ballot_w64(__builtin_isunordered(a, b));
+  }
   bitonic_from<V, NR, 2, 1>(v, lane);
   const int t = (C - 1) >> 1;
 #pragma unroll
@@ -97,5 +106,13 @@ __device__ __forceinline__ void wave_lower_median_rows(const float* __restrict__
     for (int i = 1; i < V; ++i)
       if ((t >> 6) == i) s = v[i][r];
     m[r] = __shfl(s, t & 63);
+  }
+  if (anynan != 0) {                                     // wave-uniform and rare: which rows
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      bool bad = false;
+      for (int c = lane; c < C; c += 64) bad |= base[r * stride + c] != base[r * stride + c];
+      if (__builtin_amdgcn_ballot_w64(bad) != 0) m[r] = NAN;
+    }
   }
 }

@@ -225,7 +225,13 @@ __global__ __launch_bounds__(256) void k_spectrum(const float* __restrict__ x, i
       else wave_lower_median_rows<4, 1>(row, 0, C, lane, m);
       if (lane == 0) med[(size_t)b * F + f0 + fl] = m[0];
     } else {
-      // generic: stable rank count
+      // generic: stable rank count; a NaN ranks nowhere, so a row that holds one is NaN (torch.median)
+      bool bad = false;
+      for (int c = lane; c < C; c += 64) bad |= row[c] != row[c];
+      if (__builtin_amdgcn_ballot_w64(bad) != 0) {
+        if (lane == 0) med[(size_t)b * F + f0 + fl] = NAN;
+        continue;
+      }
       for (int c = lane; c < C; c += 64) {
         const float v = row[c];
         int cnt = 0;
