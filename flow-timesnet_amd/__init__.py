@@ -14,7 +14,8 @@ Sub-modules
 ``score``            NB likelihood and sMAPE of a forecast on the device: ``negative_binomial_nll``, ``ForecastScorer``;
                      the distribution itself: ``nb_cdf``, ``nb_quantiles``, ``prediction_interval``, ``interval_metrics``;
                      sample paths: ``nb_sample`` (counter-based Philox, CDF inversion), ``sample_uniforms``,
-                     ``path_quantiles``
+                     ``path_quantiles``; summaries of the paths in one kernel pass: ``path_summary`` (order statistics,
+                     mean and sample CRPS of window sums or maxima), ``path_metrics``
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401

@@ -345,7 +345,8 @@ def forecast_sample_paths(model, last_seq: torch.Tensor, H: int, n_paths: int, s
     """``n_paths`` sample paths of an H-step recursive forecast: ``(samples, rate, dispersion)``, each [P, B, H, N].
     Path p of row b draws its step-s count from the model's distribution given its own earlier draws, so the spread
     of ``samples[:, b, s]`` grows with s as the forecast's uncertainty does; ``rate`` and ``dispersion`` are the
-    distributions each path drew from.  ``score.path_quantiles`` turns the paths into intervals of sums and maxima.
+    distributions each path drew from.  ``score.path_summary`` turns the paths into intervals, means and CRPS scores of
+    window sums (``reduce="sum"``) and window maxima (``path_summary(..., reduce="max")``) on the device.
 
     The semantics are ``forecast_sample_paths_loop``'s, bit for bit.  The paths are the rows of one batch of P B, and
     the period selector averages amplitudes over its batch, so the paths see each other through the selected periods

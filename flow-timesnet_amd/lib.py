@@ -53,6 +53,9 @@ class FtnScorePart(C.Structure):
 SCORE_PART_BYTES = C.sizeof(FtnScorePart)
 FTN_QMAX = 8
 FTN_NBQ_RANGE = 2
+FTN_PATHS_MAX = 1024
+FTN_PATH_SUM, FTN_PATH_MAX = 0, 1
+FTN_PATH_LDS = 16
 
 
 class FtnDesc(C.Structure):
@@ -192,6 +195,9 @@ _SIGNATURES = {
     "ftn_nb_sample_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_nb_sample": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong,
                                 _P, C.c_uint, C.c_float, _P, _P, _P, _P]),
+    "ftn_path_summary_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_path_summary": (C.c_int, [_P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, _P, C.c_longlong, C.POINTER(C.c_int), C.c_int, _P, _P, _P, _P, _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -748,6 +748,115 @@ def nb_sample(rate: torch.Tensor, disp: torch.Tensor, n_samples: int = 1, seed=0
     return out, flag, u
 
 
+# ------------------------------------------------------------------ path summaries
+PATH_REDUCE = {"sum": _lib.FTN_PATH_SUM, "max": _lib.FTN_PATH_MAX}
+
+
+def path_summary_form_of(P: int, N: int, window: int = 1, strides=(0, 0, 0), misalign_or: int = 0) -> str:
+    """The kernel form ``ftn_path_summary`` takes (``ftn_path_summary_form``, host-only: the launch dispatches through
+    the same function): ``"reg<PP>/vec4"``, ``"reg<PP>/scalar"`` (a lane sorts its columns in registers, PP the
+    padded P) or ``"lds<PP>x<T>/vec4"``, ``"lds<PP>x<T>/scalar"`` (a workgroup sorts a tile of T columns in LDS).
+    ``strides``: the path and batch strides of samples and the batch stride of y, in elements."""
+    f = _lib.load().ftn_path_summary_form(int(P), int(N), int(window), int(strides[0]), int(strides[1]),
+                                          int(strides[2]), int(misalign_or))
+    if f < 0:
+        check(f, "ftn_path_summary_form")
+    width = "vec4" if f & 2 else "scalar"
+    pp = (f >> 8) & 0xFFF
+    return f"lds{pp}x{f >> 20}/{width}" if f & _lib.FTN_PATH_LDS else f"reg{pp}/{width}"
+
+
+def _path_strides(samples, y):
+    P, B, H, N = samples.shape
+    return (samples.stride(0) if P > 1 else 0, samples.stride(1) if B > 1 else 0,
+            y.stride(0) if (y is not None and B > 1) else 0)
+
+
+def path_summary_form(samples, y=None, window: int = 1, outs=()) -> str:
+    """``path_summary_form_of`` for the tensors ``path_summary(samples, ..., y=y)`` is given (``outs``: outputs a
+    direct call would pass; the wrapper's own are fresh and aligned)."""
+    mis = 0
+    for t in (samples, y, *outs):
+        if t is not None:
+            mis |= _ptr(t) & 15
+    return path_summary_form_of(samples.shape[0], samples.shape[3], window, _path_strides(samples, y), mis)
+
+
+def _path_operands(samples, y) -> None:
+    """Shape, then row layout, then dtype and device of samples [P,B,H,N] and y [B,H,N], as ``_score_operands``."""
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 4:
+        raise ValueError("path_summary: samples must be a [P, B, H, N] tensor")
+    P, B, H, N = samples.shape
+    if P < 1 or B < 1 or H < 1 or N < 1:
+        raise ValueError(f"path_summary: empty shape {tuple(samples.shape)}")
+    if y is not None and (not isinstance(y, torch.Tensor) or tuple(y.shape) != (B, H, N)):
+        raise ValueError(f"path_summary: y must be a {(B, H, N)} tensor beside samples {tuple(samples.shape)}")
+    s = samples.stride()
+    if ((N > 1 and s[3] != 1) or (H > 1 and s[2] != N) or (B > 1 and s[1] < H * N)
+            or (P > 1 and s[0] < (B - 1) * (s[1] if B > 1 else 0) + H * N)):
+        raise ValueError(f"path_summary: samples need contiguous rows N elements apart, strides {s}")
+    if y is not None:
+        t = y.stride()
+        if (N > 1 and t[2] != 1) or (H > 1 and t[1] != N) or (B > 1 and t[0] < H * N):
+            raise ValueError(f"path_summary: y needs contiguous rows N elements apart, strides {t}")
+    for name, t in (("samples", samples), ("y", y)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_cuda or t.device != samples.device):
+            raise ValueError(f"path_summary: {name} must be an fp32 tensor on samples' device, got {t.dtype} on "
+                             f"{t.device}")
+
+
+def path_summary(samples: torch.Tensor, ranks, window: int = 1, reduce: str = "sum", y: torch.Tensor | None = None,
+                 want_mean: bool = True, want_sorted: bool = False, out: dict | None = None):
+    """``ftn_path_summary`` over ``samples`` [P,B,H,N] (an fp32 device tensor or a view with contiguous rows N
+    elements apart): per element of [B,H',N], ``H' = H / window``, of the window sums or maxima of every path, the
+    order statistics at ``ranks`` (ints in 1..P, any number: one launch per 8), the mean, the sample CRPS against
+    ``y`` [B,H,N] when it is given, and the sorted column with ``want_sorted``.  Mean, CRPS and sorted column come
+    from the first launch.  ``out``: contiguous fp32 tensors to fill under the keys of the result (default: fresh).
+    Returns ``{"quantiles": [Q,B,H',N], "mean": .., "crps": .., "sorted": [P,B,H',N]}`` with None for what was not
+    asked for.  Enqueues only."""
+    lib = _lib.load()
+    _path_operands(samples, y)
+    if reduce not in PATH_REDUCE:
+        raise ValueError(f"path_summary: reduce {reduce!r} is not 'sum' or 'max'")
+    P, B, H, N = samples.shape
+    w = int(window)
+    if w < 1 or H % w:
+        raise ValueError(f"path_summary: window={window} does not divide H={H}")
+    Hp = H // w
+    rk = [int(r) for r in ranks]
+    for r in rk:
+        if not 1 <= r <= P:
+            raise ValueError(f"path_summary: rank {r} is outside 1..{P}")
+    Q = len(rk)
+    shapes = {"quantiles": (Q, B, Hp, N) if Q else None, "mean": (B, Hp, N) if want_mean else None,
+              "crps": (B, Hp, N) if y is not None else None, "sorted": (P, B, Hp, N) if want_sorted else None}
+    res = {}
+    for key, shape in shapes.items():
+        t = None if out is None else out.get(key)
+        if shape is None:
+            t = None
+        elif t is None:
+            t = torch.empty(shape, dtype=torch.float32, device=samples.device)
+        elif (t.dtype != torch.float32 or t.device != samples.device or not t.is_contiguous()
+              or tuple(t.shape) != shape):
+            raise ValueError(f"path_summary: out[{key!r}] must be contiguous fp32 {shape} beside samples")
+        res[key] = t
+    ps, bs, ybs = samples.stride(0), samples.stride(1), (y.stride(0) if y is not None else 0)
+    first = True
+    for i in range(0, max(Q, 1), _lib.FTN_QMAX):
+        part = rk[i:i + _lib.FTN_QMAX]
+        arr = (C.c_int * max(len(part), 1))(*part)
+        q_out = res["quantiles"][i:i + len(part)] if part else None
+        check(lib.ftn_path_summary(_ptr(samples), ps, bs, P, B, H, N, w, PATH_REDUCE[reduce],
+                                   _ptr_or_null(y if first else None), ybs, arr, len(part), _ptr_or_null(q_out),
+                                   _ptr_or_null(res["mean"] if first else None),
+                                   _ptr_or_null(res["crps"] if first else None),
+                                   _ptr_or_null(res["sorted"] if first else None), _stream(samples.device)),
+              "ftn_path_summary")
+        first = False
+    return res
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch

@@ -18,6 +18,10 @@ counterpart in the reference): the regularised incomplete beta function and its 
 ``nb_sample`` / ``sample_uniforms`` / ``path_quantiles`` draw from it: a counter-based Philox4x32-10 and the inversion
 of that CDF (``k_nb_sample``, or the same generator and search in torch ops), so a draw is a pure function of
 ``(seed, offset, element, draw index)``; ``forecast.forecast_sample_paths`` feeds the draws back into the recursion.
+
+``path_summary`` / ``path_metrics`` summarise sample paths [P,B,H,N]: order statistics, mean and sample CRPS of window
+sums or maxima, ``ftn_path_summary`` on the ``hip`` side (one pass over the paths, one sort per column in registers or
+LDS) and the same definitions in fp64 torch ops otherwise.
 """
 from __future__ import annotations
 
@@ -765,7 +769,8 @@ def path_quantiles(samples: torch.Tensor, levels, window: Optional[int] = None) 
     """Quantiles over sample paths: ``samples`` [P,B,H,N] -> [Q,B,H',N].  With ``window``, every path is first summed
     over non-overlapping windows of ``window`` steps along H (``H' = H / window``; a ragged last window is an error).
     The quantile is the order statistic ``ceil(q P)`` of the P paths (the inverted-CDF definition: the smallest value
-    whose empirical CDF reaches q), consistent with ``nb_quantiles``."""
+    whose empirical CDF reaches q), consistent with ``nb_quantiles``.  ``path_summary`` computes the same order
+    statistics on the device in one pass, for window maxima too, with the mean and the CRPS beside them."""
     import math
 
     lv = _check_levels(levels)
@@ -781,3 +786,147 @@ def path_quantiles(samples: torch.Tensor, levels, window: Optional[int] = None) 
     ordered = torch.sort(x, dim=0).values
     rows = [min(max(math.ceil(q * P), 1), P) - 1 for q in lv]
     return ordered[rows]
+
+
+# --------------------------------------------------------------------------------------------------- path summaries
+# Per element (b, h', n): v[p] the window sum (fp64, rounded once to fp32) or window maximum (NaN stays) of path p,
+# x(1) <= .. <= x(P) its sorted values (NaN last), quantile q = x(min(max(ceil(q P), 1), P)), mean = sum x / P and
+#   crps = (A P - G) / P^2,  A = sum_p |x(p) - yw|,  G = sum_i (2 i - P - 1) x(i)
+# the ensemble estimator (1/P) sum |v - yw| - (1/(2 P^2)) sum sum |v - v'|, every sum in fp64 and one rounding to fp32
+# (include/flowtimes.h).  ``hip``: ftn_path_summary (csrc/paths.hip).  ``torch``: the same in torch ops, anywhere.
+PATHS_MAX = 1024             # paths of one ftn_path_summary call (FTN_PATHS_MAX)
+
+
+def _path_levels(levels, who: str) -> List[float]:
+    lv = [float(q) for q in levels]
+    for q in lv:
+        if not 0.0 < q < 1.0:
+            raise ValueError(f"{who}: level {q} is not strictly inside (0, 1)")
+    return lv
+
+
+def _path_window(x: torch.Tensor, w: int, reduce: str) -> torch.Tensor:
+    """``x`` [..., H, N] fp32 -> [..., H / w, N] fp32: window sums in fp64 rounded once, or window maxima."""
+    H, N = x.shape[-2], x.shape[-1]
+    g = x.reshape(*x.shape[:-2], H // w, w, N)
+    if reduce == "max":
+        return g.amax(-2)
+    acc = torch.zeros(g.shape[:-2] + (N,), dtype=torch.float64, device=x.device)
+    for j in range(w):                                          # ascending j, as the kernel adds
+        acc = acc + g[..., j, :].double()
+    return acc.to(torch.float32)
+
+
+def _path_summary_torch(samples, ranks, w, reduce, y, want_sorted):
+    P = samples.shape[0]
+    xs = torch.sort(_path_window(samples, w, reduce), dim=0).values
+    xd = xs.double()
+    out = {"quantiles": xs[[r - 1 for r in ranks]] if ranks else xs[:0], "mean": (xd.sum(0) / P).to(torch.float32)}
+    if y is not None:
+        yw = _path_window(y, w, reduce).double()
+        coef = (2.0 * torch.arange(1, P + 1, dtype=torch.float64, device=xs.device) - (P + 1)).view(P, 1, 1, 1)
+        A, G = (xd - yw).abs().sum(0), (coef * xd).sum(0)
+        out["crps"] = ((A * P - G) / float(P * P)).to(torch.float32)
+    if want_sorted:
+        out["sorted"] = xs
+    return out
+
+
+def _path_rows(t: torch.Tensor) -> torch.Tensor:
+    """``t`` [P,B,H,N] as the kernel takes it: rows contiguous and N apart, batch and path strides of its own."""
+    P, B, H, N = t.shape
+    s = t.stride()
+    ok = ((N == 1 or s[3] == 1) and (H == 1 or s[2] == N) and (B == 1 or s[1] >= H * N)
+          and (P == 1 or s[0] >= (B - 1) * (s[1] if B > 1 else 0) + H * N))
+    return t if ok else t.contiguous()
+
+
+def path_summary(samples: torch.Tensor, levels=(), y: torch.Tensor | None = None, window: Optional[int] = None,
+                 reduce: str = "sum", want_sorted: bool = False, backend: Optional[str] = None
+                 ) -> Dict[str, torch.Tensor]:
+    """Summaries of sample paths ``samples`` [P,B,H,N] per element of [B,H',N]: every path is first reduced over
+    non-overlapping windows of ``window`` steps along H (``H' = H / window``; None: 1; a ragged last window is an
+    error) by ``reduce``: ``"sum"`` or ``"max"``.  Returns fp32 tensors: ``quantiles`` [Q,B,H',N], the order statistic
+    ``ceil(q P)`` of the P values for every ``q`` of ``levels`` (``path_quantiles``' definition; any number, none is
+    fine); ``mean`` [B,H',N]; with ``y`` [B,H,N], ``crps`` [B,H',N], the sample CRPS of the P values against the same
+    reduce of ``y`` (the plain ensemble estimator, 0 for P = 1 and y on the sample); with ``want_sorted``, ``sorted``
+    [P,B,H',N].  NaN sorts last and makes mean and CRPS NaN.  ``backend``: ``"hip"`` (one ``ftn_path_summary`` launch
+    per 8 levels; fp32 samples on a ROCm device, nothing for autograd to record, P <= 1024), ``"torch"`` (the same
+    definitions in torch ops, any device; other dtypes are converted to fp32 first), or None: ``hip`` where it can
+    run.  Never synchronises on the ``hip`` backend."""
+    import math
+
+    global _last_backend
+    lv = _path_levels(levels, "path_summary")
+    if backend not in (None, "hip", "torch"):
+        raise ValueError(f"path_summary: backend {backend!r} is not 'hip', 'torch' or None")
+    if reduce not in ("sum", "max"):
+        raise ValueError(f"path_summary: reduce {reduce!r} is not 'sum' or 'max'")
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 4 or samples.numel() == 0:
+        raise ValueError(f"path_summary takes samples [P, B, H, N], got "
+                         f"{tuple(samples.shape) if isinstance(samples, torch.Tensor) else type(samples)}")
+    P, B, H, N = samples.shape
+    w = 1 if window is None else int(window)
+    if w < 1 or H % w:
+        raise ValueError(f"path_summary: window={window} does not divide H={H}")
+    if y is not None and (not isinstance(y, torch.Tensor) or tuple(y.shape) != (B, H, N)):
+        raise ValueError(f"path_summary: y must be [B, H, N] = {(B, H, N)}, got "
+                         f"{tuple(y.shape) if isinstance(y, torch.Tensor) else type(y)}")
+    ranks = [min(max(math.ceil(q * P), 1), P) for q in lv]
+    eligible = (samples.is_cuda and samples.dtype == torch.float32 and P <= PATHS_MAX
+                and not (torch.is_grad_enabled() and (samples.requires_grad or (y is not None and y.requires_grad))))
+    if backend == "hip" and not eligible:
+        raise ValueError(f"path_summary: backend 'hip' takes fp32 [P, B, H, N] samples on a ROCm device, without "
+                         f"autograd, P <= {PATHS_MAX}")
+    if eligible and backend != "torch":
+        from . import runtime as rt
+
+        yk = None
+        if y is not None:
+            yk = _rows(y.detach().to(device=samples.device, dtype=torch.float32))
+        res = rt.path_summary(_path_rows(samples.detach()), ranks, w, reduce, y=yk, want_mean=True,
+                              want_sorted=want_sorted)
+        if res["quantiles"] is None:
+            res["quantiles"] = torch.empty((0, B, H // w, N), dtype=torch.float32, device=samples.device)
+        out = {k: v for k, v in res.items() if v is not None}
+        _last_backend = "hip"
+    else:
+        with torch.no_grad():
+            yt = None if y is None else y.to(device=samples.device, dtype=torch.float32)
+            out = _path_summary_torch(samples.to(torch.float32), ranks, w, reduce, yt, want_sorted)
+        _last_backend = "torch"
+    return out
+
+
+def path_metrics(samples: torch.Tensor, y: torch.Tensor, levels, window: Optional[int] = None, reduce: str = "sum",
+                 mask: torch.Tensor | None = None) -> Dict[str, torch.Tensor]:
+    """``interval_metrics`` for sample paths: calibration and score of the paths' window sums or maxima against the
+    same reduce ``yw`` of ``y`` [B,H,N], over the valid elements, as tensors on ``samples``' device and without a
+    host read: ``coverage`` [Q], the mean of ``yw <= Q(q)``; ``pinball`` [Q], the mean of
+    ``max(q (yw - Q), (q - 1) (yw - Q))``; ``crps``, the mean sample CRPS; ``count``, the valid elements (int64).
+    An element is valid where ``yw``, its quantiles and its CRPS are finite and, with ``mask`` [B,H,N], every step
+    of its window is inside the mask."""
+    lv = _path_levels(levels, "path_metrics")
+    if not lv:
+        raise ValueError("path_metrics: no levels")
+    s = path_summary(samples, lv, y, window, reduce)
+    Q, crps = s["quantiles"], s["crps"]
+    P, B, H, N = samples.shape
+    w = 1 if window is None else int(window)
+    yw = _path_window(y.detach().to(device=Q.device, dtype=torch.float32), w, reduce)
+    valid = torch.isfinite(yw) & torch.isfinite(Q).all(0) & torch.isfinite(crps)
+    if mask is not None:
+        if tuple(mask.shape) != (B, H, N):
+            raise ValueError(f"path_metrics: mask must be [B, H, N] = {(B, H, N)}, got {tuple(mask.shape)}")
+        valid = valid & mask.to(device=Q.device).to(torch.bool).reshape(B, H // w, w, N).all(2)
+    wgt = valid.to(torch.float32)
+    den = wgt.sum().clamp(min=1.0)
+    zero = torch.zeros((), dtype=torch.float32, device=Q.device)
+    yv = torch.where(valid, yw, zero)
+    Qv = torch.where(valid, Q, zero)
+    diff = yv - Qv
+    pin = torch.stack([torch.maximum(q * diff[i], (q - 1.0) * diff[i]) for i, q in enumerate(lv)]) * wgt
+    return {"coverage": ((yv <= Qv).to(torch.float32) * wgt).sum((1, 2, 3)) / den,
+            "pinball": pin.sum((1, 2, 3)) / den,
+            "crps": torch.where(valid, crps, zero).sum() / den,
+            "count": valid.sum()}

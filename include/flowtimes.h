@@ -586,6 +586,53 @@ int ftn_nb_sample(const float* rate_dev, long long rate_bstride, const float* di
                   int B, int H, int N, int S, unsigned long long seed, const unsigned long long* seed_dev,
                   unsigned offset, float eps, float* out_dev, double* u_out_dev, int* flag_dev, void* stream);
 
+/* ---- summarising sample paths (paths.hip) ----
+ * Additions only, as the three sections above: FTN_ABI_VERSION stays 14.
+ *
+ * ftn_path_summary (k_path_reg<PP,CPL> / k_path_lds<CPL>): samples is fp32 [P][B][H][N], rows N elements apart, N
+ * fastest, with a path stride and a batch stride in elements; y (optional) fp32 [B][H][N] with its own batch stride;
+ * outputs are contiguous.  H % window == 0, H' = H / window, 1 <= P <= FTN_PATHS_MAX; sample addresses are formed in
+ * 64 bits, B H' N must fit an int32.  Per output element (b, h', n):
+ *   v[p]  the reduce over j = 0 .. window - 1, ascending, of samples[p][b][h' window + j][n]: FTN_PATH_SUM accumulates
+ *         in fp64 and rounds once to fp32; FTN_PATH_MAX is the maximum, a NaN staying as in torch.amax.  yw is the
+ *         same reduce of y.
+ *   x(1) <= .. <= x(P)  v sorted ascending in torch.sort's value order, NaN after +inf.  Values are only permuted:
+ *         the sorted column holds the bits of v, except that every NaN comes out as the quiet NaN 0x7FC00000 and that
+ *         -0 sorts before +0 (torch leaves their order to the input).
+ *   q_out[i]  = x(ranks_host[i]), Q = 0 .. FTN_QMAX ranks in 1 .. P, passed to the kernel by value
+ *   mean_out  = (sum_p x(p)) / P: the sum in fp64, one fp64 division, one rounding to fp32
+ *   crps_out  = (A P - G) / (P P), A = sum_p |x(p) - yw|, G = sum_{i=1..P} (2 i - P - 1) x(i), both sums in fp64 (every
+ *         product exact), then one fp64 product, difference and division and one rounding to fp32.  This is the
+ *         ensemble estimator (1/P) sum_p |v[p] - yw| - (1/(2 P P)) sum_p sum_p' |v[p] - v[p']|; for integer-valued
+ *         samples A, G and the numerator are exact and the result is the correctly rounded quotient.  A value that is
+ *         not finite gives what IEEE arithmetic gives from these formulas (NaN).
+ *   sorted_out[p] = x(p + 1)
+ * The sums run in ascending rank; above 64 paths they are R = 256 / T interleaved partial sums (ranks r, r + R, ..)
+ * added in ascending r, so their order is a function of P alone.  An element's result does not depend on the grid,
+ * on the load width or on which other elements share the call.  Anything outside these rules (a rank outside 1 .. P,
+ * crps_out without y, Q > FTN_QMAX, q_out null with Q > 0, no output at all, a stride below its span) is a negative
+ * return with ftn_last_error set and nothing launched.  Never allocates, never synchronises; enqueues one kernel on
+ * `stream`; no atomics.
+ * ftn_path_summary_form (host-only; the launch dispatches through the same function):
+ *   bit 1       FTN_SHELL_VEC  16-byte loads (and stores in the register form), four columns per lane: N % 4 == 0,
+ *               every stride a multiple of 4, misalign_or == 0, and the padded P at most 16 or above 64 (four columns
+ *               of 32 or 64 keys do not fit a lane's registers); otherwise 4-byte accesses, one column per lane.
+ *               Either way consecutive n lie on consecutive lanes.
+ *   bit 4       FTN_PATH_LDS   k_path_lds (padded P above 64): a workgroup sorts a tile of T columns in LDS;
+ *               otherwise k_path_reg: a lane sorts its columns in registers
+ *   bits 8-19   the padded P: the power of two >= max(P, 2), the size of the bitonic network
+ *   bits 20-27  T, the columns of an LDS tile (padded P x T x 4 bytes <= 64 KiB, T <= 64), 0 in the register form
+ * misalign_or: the OR of (address & 15) of samples, y and every output of the call. */
+#define FTN_PATHS_MAX 1024
+#define FTN_PATH_SUM 0
+#define FTN_PATH_MAX 1
+#define FTN_PATH_LDS 16
+int ftn_path_summary_form(int P, int N, int window, long long p_stride, long long b_stride, long long y_bstride,
+                          int misalign_or);
+int ftn_path_summary(const float* samples_dev, long long p_stride, long long b_stride, int P, int B, int H, int N,
+                     int window, int reduce, const float* y_dev, long long y_bstride, const int* ranks_host, int Q,
+                     float* q_out_dev, float* mean_out_dev, float* crps_out_dev, float* sorted_out_dev, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
