@@ -56,6 +56,9 @@ FTN_NBQ_RANGE = 2
 FTN_PATHS_MAX = 1024
 FTN_PATH_SUM, FTN_PATH_MAX = 0, 1
 FTN_PATH_LDS = 16
+FTN_GROUP_CHUNK = 32
+FTN_GROUP_NMAX, FTN_GROUP_GMAX, FTN_GROUP_CHUNKS_MAX = 8192, 2048, 2048
+FTN_GROUP_TILE_BYTES, FTN_GROUP_TILE_ROWS = 32768, 64
 
 
 class FtnDesc(C.Structure):
@@ -198,6 +201,8 @@ _SIGNATURES = {
     "ftn_path_summary_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_path_summary": (C.c_int, [_P, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int, _P, C.c_longlong, C.POINTER(C.c_int), C.c_int, _P, _P, _P, _P, _P]),
+    "ftn_group_sum_form": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int]),
+    "ftn_group_sum": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -857,6 +857,60 @@ def path_summary(samples: torch.Tensor, ranks, window: int = 1, reduce: str = "s
     return res
 
 
+# ------------------------------------------------------------------ series groups
+def group_sum_form_of(N: int, row_stride: int | None = None, misalign_or: int = 0, n_chunks: int = 0) -> str:
+    """The kernel form ``ftn_group_sum`` takes (``ftn_group_sum_form``, host-only: the launch dispatches through the
+    same function): ``"vec4/t<T>"`` or ``"scalar/t<T>"``, the load width of x and the rows of a tile.  ``row_stride``
+    in elements (default: N), ``misalign_or`` the address of x modulo 16, ``n_chunks`` the chunks of 32 members over
+    all groups."""
+    f = _lib.load().ftn_group_sum_form(int(N), int(N if row_stride is None else row_stride), int(misalign_or),
+                                       int(n_chunks))
+    if f < 0:
+        check(f, "ftn_group_sum_form")
+    return f"{'vec4' if f & 2 else 'scalar'}/t{f >> 8}"
+
+
+def group_sum_form(x: torch.Tensor, offsets_host) -> str:
+    """``group_sum_form_of`` for the tensors ``group_sum(x, order, offsets, offsets_host)`` is given."""
+    rows, N = x.shape
+    sizes = [int(b) - int(a) for a, b in zip(offsets_host[:-1], offsets_host[1:])]
+    chunks = sum((m + _lib.FTN_GROUP_CHUNK - 1) // _lib.FTN_GROUP_CHUNK for m in sizes)
+    return group_sum_form_of(N, x.stride(0) if rows > 1 else N, _ptr(x) & 15, chunks)
+
+
+def group_sum(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, offsets_host, out: torch.Tensor | None = None
+              ) -> torch.Tensor:
+    """``ftn_group_sum``: ``x`` [rows, N] fp32 on a ROCm device, elements contiguous and rows ``x.stride(0) >= N``
+    apart; ``order`` [M] and ``offsets`` [G+1] the int32 CSR member lists on that device, ``offsets_host`` the same
+    G+1 offsets as a contiguous int32 numpy array.  Returns ``out`` [rows, G] fp32 (default: fresh; else a contiguous
+    one to fill).  Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.numel() == 0:
+        raise ValueError("group_sum: x must be a non-empty [rows, N] tensor")
+    rows, N = x.shape
+    if (N > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) < N):
+        raise ValueError(f"group_sum: x needs contiguous rows at least N apart, strides {x.stride()}")
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f"group_sum: x must be an fp32 tensor on a ROCm device, got {x.dtype} on {x.device}")
+    for name, t in (("order", order), ("offsets", offsets)):
+        if (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.device != x.device
+                or not t.is_contiguous()):
+            raise ValueError(f"group_sum: {name} must be a contiguous int32 vector on x's device")
+    G, M = offsets.numel() - 1, order.numel()
+    if (getattr(offsets_host, "dtype", None) != "int32" or offsets_host.ndim != 1 or offsets_host.size != G + 1
+            or not offsets_host.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"group_sum: offsets_host must be a contiguous int32 numpy array of {G + 1} offsets")
+    if out is None:
+        out = torch.empty(rows, G, dtype=torch.float32, device=x.device)
+    elif (out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous()
+          or tuple(out.shape) != (rows, G)):
+        raise ValueError(f"group_sum: out must be contiguous fp32 {(rows, G)} beside x")
+    check(lib.ftn_group_sum(_ptr(x), rows, N, x.stride(0) if rows > 1 else N, _ptr(order) if M else None,
+                            _ptr(offsets), offsets_host.ctypes.data, G, M, _ptr(out), _stream(x.device)),
+          "ftn_group_sum")
+    return out
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch

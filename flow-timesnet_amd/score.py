@@ -22,6 +22,10 @@ of that CDF (``k_nb_sample``, or the same generator and search in torch ops), so
 ``path_summary`` / ``path_metrics`` summarise sample paths [P,B,H,N]: order statistics, mean and sample CRPS of window
 sums or maxima, ``ftn_path_summary`` on the ``hip`` side (one pass over the paths, one sort per column in registers or
 LDS) and the same definitions in fp64 torch ops otherwise.
+
+``SeriesGroups`` / ``group_sums`` / ``group_path_summary`` / ``group_path_metrics`` total series over groups (a store's
+items, the whole site) before summarising: a segmented sum along the series axis in a stated order,
+``ftn_group_sum`` on the ``hip`` side and the same additions in fp64 torch ops otherwise, bit for bit.
 """
 from __future__ import annotations
 
@@ -930,3 +934,232 @@ def path_metrics(samples: torch.Tensor, y: torch.Tensor, levels, window: Optiona
             "pinball": pin.sum((1, 2, 3)) / den,
             "crps": torch.where(valid, crps, zero).sum() / den,
             "count": valid.sum()}
+
+
+# ----------------------------------------------------------------------------------------------------- series groups
+# out[.., g] = the sum of x[.., i] over the members i of group g, defined to the bit (include/flowtimes.h): the members
+# in chunks of 32, a chunk's sum in fp64 left to right from +0.0, the chunk sums in ascending order in fp64, one
+# rounding to fp32.  ``hip``: ftn_group_sum (csrc/groups.hip).  ``torch``: the same additions in torch ops, anywhere.
+GROUP_CHUNK = 32             # FTN_GROUP_CHUNK
+GROUP_NMAX = 8192            # series, groups and chunks of one ftn_group_sum call (FTN_GROUP_NMAX / GMAX / CHUNKS_MAX)
+GROUP_GMAX = 2048
+GROUP_CHUNKS_MAX = 2048
+
+
+def _store_key(series_id: str) -> str:
+    """The reference's store of a series id ``"store_menu"`` (utils/metrics.py: ``c.split("_", 1)[0]``)."""
+    return series_id.split("_", 1)[0]
+
+
+class SeriesGroups:
+    """Groups of series as member lists, built once on the host: ``names`` [G], ``n_series`` N, ``n_groups`` G, and
+    the CSR ``order`` [M] / ``offsets`` [G+1] as int32 tensors on ``device`` (group g's members are
+    ``order[offsets[g]:offsets[g+1]]``, in that order, which is the order ``group_sums`` adds them in).  A series may
+    be in no group, in one or in several; an empty group is fine.  Rejected: an index outside 0..N-1, a series
+    repeated inside one group, no group at all."""
+
+    def __init__(self, members, n_series: int, names=None, device=None):
+        N = int(n_series)
+        if N < 1:
+            raise ValueError(f"SeriesGroups: n_series={n_series} is not positive")
+        lists = [[int(i) for i in m] for m in members]
+        if not lists:
+            raise ValueError("SeriesGroups: no group (G == 0)")
+        for g, m in enumerate(lists):
+            for i in m:
+                if not 0 <= i < N:
+                    raise ValueError(f"SeriesGroups: group {g} holds index {i} outside 0..{N - 1}")
+            if len(set(m)) != len(m):
+                raise ValueError(f"SeriesGroups: group {g} holds a series more than once (a duplicate)")
+        self.names = [str(g) for g in range(len(lists))] if names is None else [str(n) for n in names]
+        if len(self.names) != len(lists):
+            raise ValueError(f"SeriesGroups: {len(self.names)} names for {len(lists)} groups")
+        self.n_series, self.n_groups = N, len(lists)
+        self.members = lists
+        self.offsets_host = np.zeros(len(lists) + 1, dtype=np.int32)
+        np.cumsum([len(m) for m in lists], out=self.offsets_host[1:])
+        self.order_host = np.array([i for m in lists for i in m], dtype=np.int32).reshape(-1)
+        self.n_chunks = sum((len(m) + GROUP_CHUNK - 1) // GROUP_CHUNK for m in lists)
+        self.device = torch.device("cpu" if device is None else device)
+        self.order = torch.from_numpy(self.order_host).to(self.device)
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self._tables = None
+        self._moved: Dict[torch.device, "SeriesGroups"] = {}
+
+    @classmethod
+    def from_ids(cls, ids, key=None, device=None) -> "SeriesGroups":
+        """One group per distinct ``key(id)`` (default: the reference's store rule, the text before the first
+        ``"_"``), the groups in first-appearance order as the reference's ``store_to_idx``, members ascending."""
+        key = _store_key if key is None else key
+        index: Dict[str, int] = {}
+        members: List[List[int]] = []
+        for i, s in enumerate(ids):
+            k = key(s)
+            if k not in index:
+                index[k] = len(members)
+                members.append([])
+            members[index[k]].append(i)
+        n = sum(len(m) for m in members)
+        return cls(members, max(n, 1), list(index), device)
+
+    @classmethod
+    def from_labels(cls, labels, device=None) -> "SeriesGroups":
+        """``labels`` int [N]: series n is in group ``labels[n]``, or in none where that is -1; G = max label + 1."""
+        lab = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels)
+        if lab.ndim != 1 or lab.size == 0 or lab.dtype.kind not in "iu":
+            raise ValueError("SeriesGroups.from_labels takes a non-empty integer vector [N]")
+        if int(lab.min()) < -1:
+            raise ValueError(f"SeriesGroups.from_labels: label {int(lab.min())} is below -1")
+        G = int(lab.max()) + 1
+        return cls([np.nonzero(lab == g)[0].tolist() for g in range(G)], lab.size, None, device)
+
+    @classmethod
+    def from_members(cls, members, names=None, n_series: Optional[int] = None, device=None) -> "SeriesGroups":
+        """The general form: one list of series indices per group, overlap allowed.  ``n_series``: N (default: the
+        largest index + 1)."""
+        lists = [[int(i) for i in m] for m in members]
+        if n_series is None:
+            n_series = max([i for m in lists for i in m], default=0) + 1
+        return cls(lists, n_series, names, device)
+
+    def with_total(self, name: str = "total") -> "SeriesGroups":
+        """These groups and one more that holds every series, in ascending index."""
+        return SeriesGroups(self.members + [list(range(self.n_series))], self.n_series, self.names + [name],
+                            self.device)
+
+    def to(self, device) -> "SeriesGroups":
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device == self.device:
+            return self
+        if device not in self._moved:                           # one upload per device, whoever asks
+            self._moved[device] = SeriesGroups(self.members, self.n_series, self.names, device)
+        return self._moved[device]
+
+    def sizes(self) -> List[int]:
+        return [len(m) for m in self.members]
+
+    def _torch_tables(self):
+        """``(idx [C,32], cidx [G,K])`` on the device: the members of every chunk, padded with N (a zero column), and
+        the chunks of every group, padded with C (a zero column)."""
+        if self._tables is None:
+            C, N = self.n_chunks, self.n_series
+            idx = np.full((max(C, 1), GROUP_CHUNK), N, dtype=np.int64)
+            per = [(len(m) + GROUP_CHUNK - 1) // GROUP_CHUNK for m in self.members]
+            cidx = np.full((self.n_groups, max(max(per), 1)), C, dtype=np.int64)
+            c = 0
+            for g, m in enumerate(self.members):
+                for k in range(per[g]):
+                    part = m[k * GROUP_CHUNK:(k + 1) * GROUP_CHUNK]
+                    idx[c, :len(part)] = part
+                    cidx[g, k] = c
+                    c += 1
+            self._tables = (torch.from_numpy(idx[:C]).to(self.device), torch.from_numpy(cidx).to(self.device))
+        return self._tables
+
+
+def _group_sums_torch(x: torch.Tensor, groups: SeriesGroups) -> torch.Tensor:
+    idx, cidx = groups._torch_tables()
+    N, G, C = groups.n_series, groups.n_groups, groups.n_chunks
+    rows = x.to(torch.float32).reshape(-1, N)
+    R = rows.shape[0]
+    xz = torch.cat([rows.double(), torch.zeros(R, 1, dtype=torch.float64, device=x.device)], 1)
+    acc = torch.zeros(R, C, dtype=torch.float64, device=x.device)
+    for j in range(GROUP_CHUNK):                                # left to right; a slot beyond the chunk adds +0.0
+        acc = acc + xz[:, idx[:, j]]
+    cz = torch.cat([acc, torch.zeros(R, 1, dtype=torch.float64, device=x.device)], 1)
+    tot = torch.zeros(R, G, dtype=torch.float64, device=x.device)
+    for k in range(cidx.shape[1]):                              # ascending chunk
+        tot = tot + cz[:, cidx[:, k]]
+    return tot.to(torch.float32).reshape(*x.shape[:-1], G)
+
+
+def _group_rows(x: torch.Tensor) -> torch.Tensor:
+    """``x`` [..., N] as [rows, N] with one row stride: a view where the leading dims collapse, else a copy."""
+    N = x.shape[-1]
+    if N > 1 and x.stride(-1) != 1:
+        x = x.contiguous()
+    try:
+        v = x.view(-1, N)
+    except RuntimeError:
+        v = x.contiguous().view(-1, N)
+    if v.shape[0] > 1 and v.stride(0) < N:                      # an expanded row
+        v = v.contiguous()
+    return v
+
+
+def group_sums(x: torch.Tensor, groups: SeriesGroups, backend: Optional[str] = None) -> torch.Tensor:
+    """Totals over groups of series: ``x`` [..., N] -> fp32 [..., G], ``out[.., g]`` the sum of ``x[.., i]`` over the
+    members of group g in the order and precision stated above (exact for integer-valued x whose totals stay below
+    2^24; NaN and inf reach only the groups that hold them; an empty group gives +0).  Works on sample paths
+    [P,B,H,N] (``path_summary`` then applies to the totals), on ``rate`` (means add), on ``y`` and on 0/1 masks.
+    ``backend``: ``"hip"`` (one ``ftn_group_sum`` launch; fp32 on a ROCm device, nothing for autograd to record,
+    N <= 8192, at most 2048 groups and 2048 chunks of 32 members; leading dims that collapse to one row stride are
+    passed as a view, anything else is copied), ``"torch"`` (the same additions in torch ops, any device, bit-equal;
+    other dtypes are converted to fp32 first), or None: ``hip`` where it can run.  Never synchronises on ``hip``."""
+    global _last_backend
+    if backend not in (None, "hip", "torch"):
+        raise ValueError(f"group_sums: backend {backend!r} is not 'hip', 'torch' or None")
+    if not isinstance(groups, SeriesGroups):
+        raise ValueError(f"group_sums: groups must be a SeriesGroups, got {type(groups)}")
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != groups.n_series or x.numel() == 0:
+        raise ValueError(f"group_sums takes x [..., N] with N = {groups.n_series} series, got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    eligible = (x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)
+                and groups.n_series <= GROUP_NMAX and groups.n_groups <= GROUP_GMAX
+                and groups.n_chunks <= GROUP_CHUNKS_MAX)
+    if backend == "hip" and not eligible:
+        raise ValueError(f"group_sums: backend 'hip' takes fp32 [..., N] on a ROCm device, without autograd, "
+                         f"N <= {GROUP_NMAX}, at most {GROUP_GMAX} groups and {GROUP_CHUNKS_MAX} chunks of "
+                         f"{GROUP_CHUNK} members")
+    groups = groups.to(x.device)
+    if eligible and backend != "torch":
+        from . import runtime as rt
+
+        out = rt.group_sum(_group_rows(x.detach()), groups.order, groups.offsets, groups.offsets_host)
+        out = out.view(*x.shape[:-1], groups.n_groups)
+        _last_backend = "hip"
+    else:
+        with torch.no_grad():
+            out = _group_sums_torch(x, groups)
+        _last_backend = "torch"
+    return out
+
+
+def group_path_summary(samples: torch.Tensor, groups: SeriesGroups, levels=(), y: torch.Tensor | None = None,
+                       window: Optional[int] = None, reduce: str = "sum", want_sorted: bool = False,
+                       backend: Optional[str] = None) -> Dict[str, torch.Tensor]:
+    """``path_summary`` of the group totals: ``samples`` [P,B,H,N] -> ``group_sums`` [P,B,H,G], summarised against
+    ``group_sums(y)``.  The total over the group is taken first and the window reduce second, so ``reduce="max"``
+    is the peak of a store's total, not the total of its items' peaks.  Returns [.., B, H', G] tensors."""
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 4:
+        raise ValueError("group_path_summary takes samples [P, B, H, N]")
+    totals = group_sums(samples, groups, backend)
+    yt = None
+    if y is not None:
+        if not isinstance(y, torch.Tensor) or tuple(y.shape) != tuple(samples.shape[1:]):
+            raise ValueError(f"group_path_summary: y must be [B, H, N] = {tuple(samples.shape[1:])}")
+        yt = group_sums(y.detach().to(device=samples.device, dtype=torch.float32), groups, backend)
+    return path_summary(totals, levels, yt, window, reduce, want_sorted, backend)
+
+
+def group_path_metrics(samples: torch.Tensor, y: torch.Tensor, groups: SeriesGroups, levels,
+                       window: Optional[int] = None, reduce: str = "sum", mask: torch.Tensor | None = None
+                       ) -> Dict[str, torch.Tensor]:
+    """``path_metrics`` on the group totals of ``samples`` [P,B,H,N] and ``y`` [B,H,N].  With ``mask`` [B,H,N] an
+    element (b, h', g) is valid only if every member series of g is inside the mask at every step of its window: the
+    group total of the masked-out indicator is 0 there (a count, exact), formed on the device."""
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 4:
+        raise ValueError("group_path_metrics takes samples [P, B, H, N]")
+    if not isinstance(y, torch.Tensor) or tuple(y.shape) != tuple(samples.shape[1:]):
+        raise ValueError(f"group_path_metrics: y must be [B, H, N] = {tuple(samples.shape[1:])}")
+    totals = group_sums(samples, groups)
+    yt = group_sums(y.detach().to(device=samples.device, dtype=torch.float32), groups)
+    gmask = None
+    if mask is not None:
+        if tuple(mask.shape) != tuple(y.shape):
+            raise ValueError(f"group_path_metrics: mask must be [B, H, N] = {tuple(y.shape)}, got {tuple(mask.shape)}")
+        outside = (~mask.to(device=samples.device).to(torch.bool)).to(torch.float32)
+        gmask = group_sums(outside, groups) == 0
+    return path_metrics(totals, yt, levels, window, reduce, gmask)

@@ -633,6 +633,51 @@ int ftn_path_summary(const float* samples_dev, long long p_stride, long long b_s
                      int window, int reduce, const float* y_dev, long long y_bstride, const int* ranks_host, int Q,
                      float* q_out_dev, float* mean_out_dev, float* crps_out_dev, float* sorted_out_dev, void* stream);
 
+/* ---- series groups: segmented sums along the series axis (groups.hip) ----
+ * Additions only, as the four sections above: FTN_ABI_VERSION stays 14.
+ *
+ * ftn_group_sum (k_group_sum<VEC>): x is fp32 [rows][N], rows row_stride >= N elements apart; out is fp32 [rows][G],
+ * contiguous.  The groups are member lists in CSR form, int32, on the device:
+ *   order    [M]      series indices in 0 .. N - 1
+ *   offsets  [G + 1]  non-decreasing, offsets[0] = 0, offsets[G] = M
+ * and group g's members are order[offsets[g] .. offsets[g + 1]), in that order.  A series may belong to no group, to
+ * one or to several; an empty group is allowed.  offsets_host is the same G + 1 words in host memory: the call
+ * validates them and sizes the launch from them, so nothing is read back.  For a row x[0 .. N) and a group of m
+ * members i_0 .. i_{m-1}:
+ *   1. the members are split into chunks of FTN_GROUP_CHUNK = 32 consecutive members, the last possibly shorter;
+ *   2. a chunk's sum is formed in fp64, left to right, starting from +0.0;
+ *   3. the chunk sums are added in ascending chunk order in fp64;
+ *   4. the total is rounded once to fp32.
+ * An empty group gives +0.  NaN and inf behave as IEEE addition gives them and reach only the groups that hold the
+ * element.  A group's result is a function of its member list and of the row alone: not of the number of rows, of
+ * the other groups, of the load width or of the grid.  For integer-valued x whose totals stay below 2^24 the result
+ * is exact.  No atomics; no loop bound depends on the data, only on the CSR.  A member outside 0 .. N - 1 (the
+ * device words are not validated) contributes +0 and touches no memory.
+ * Limits, checked before the launch: 1 <= N <= FTN_GROUP_NMAX, 1 <= G <= FTN_GROUP_GMAX, at most FTN_GROUP_CHUNKS_MAX
+ * chunks over all groups (a group of m members has ceil(m / 32)); rows >= 1, rows row_stride and rows G formed in 64
+ * bits; row_stride >= N; offsets_host monotone from 0 to M; every pointer non-null (order may be null when M = 0)
+ * and 4-byte aligned.  Anything else is a negative return with ftn_last_error set and nothing launched.  Never
+ * allocates, never synchronises; enqueues one kernel on `stream`.
+ * A workgroup takes tiles of T rows: it stages each row into LDS (element i at word i + (i >> 5) of its row, so the
+ * 32 lanes that walk 32 chunks of consecutive series hit 32 banks), a work item (row, chunk) adds its chunk out of
+ * LDS, and after a barrier one thread per (row, group) adds that group's chunk sums and stores, G fastest.
+ * ftn_group_sum_form (host-only; the launch dispatches through the same function):
+ *   bit 1      FTN_SHELL_VEC  16-byte loads of x: N % 4 == 0, row_stride % 4 == 0 and misalign_or == 0; otherwise
+ *              4-byte loads.  Either way consecutive elements lie on consecutive lanes.
+ *   bits 8-15  T, the rows of a tile: a row takes 4 (N + N / 32 + 1) + 8 n_chunks bytes of LDS (the staged row, one
+ *              zero word, the fp64 chunk sums); T = FTN_GROUP_TILE_BYTES / that, at most FTN_GROUP_TILE_ROWS and at
+ *              least 1 (within the limits one row takes at most 50180 bytes).
+ * misalign_or: (address of x) & 15. */
+#define FTN_GROUP_CHUNK 32
+#define FTN_GROUP_NMAX 8192
+#define FTN_GROUP_GMAX 2048
+#define FTN_GROUP_CHUNKS_MAX 2048
+#define FTN_GROUP_TILE_BYTES 32768
+#define FTN_GROUP_TILE_ROWS 64
+int ftn_group_sum_form(int N, long long row_stride, int misalign_or, int n_chunks);
+int ftn_group_sum(const float* x_dev, long long rows, int N, long long row_stride, const int* order_dev,
+                  const int* offsets_dev, const int* offsets_host, int G, int M, float* out_dev, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
