@@ -16,6 +16,9 @@ Sub-modules
                      sample paths: ``nb_sample`` (counter-based Philox, CDF inversion), ``sample_uniforms``,
                      ``path_quantiles``; summaries of the paths in one kernel pass: ``path_summary`` (order statistics,
                      mean and sample CRPS of window sums or maxima), ``path_metrics``
+``nbdist``           the distribution's reference in torch ops, on any device: the NB CDF, the one bracketed quantile
+                     search behind ``nb_quantiles`` and ``nb_sample``, Philox4x32-10 and ``sample_uniforms``; pure
+                     functions without a backend choice (``score`` re-exports what callers use)
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401
@@ -24,6 +27,6 @@ from . import synth  # noqa: F401
 def __getattr__(name):  # lazy: keeps `import flow_timesnet_amd.synth` torch-free
     import importlib
 
-    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score"):
+    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score", "nbdist"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

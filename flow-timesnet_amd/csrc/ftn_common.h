@@ -32,6 +32,12 @@ unsigned long long* ftn_stamp_buf(int which_bit, size_t* cap);
 static inline int ftn_pad16(int v) { return (v + 15) & ~15; }
 static inline int ftn_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// The vector-load rule of the [B][H][N] scoring kernels (score.hip, quantile.hip, sample.hip): a lane may take 4
+// series with one 16-byte load when N and every batch stride are multiples of 4 and no operand is off 16 bytes.
+static inline bool ftn_vec4_ok(int N, long long s0, long long s1, long long s2, unsigned misalign_or) {
+  return N % 4 == 0 && s0 % 4 == 0 && s1 % 4 == 0 && s2 % 4 == 0 && (misalign_or & 15) == 0;
+}
+
 // ---- conv tiling: one rule shared by the device finalize kernel and the host --
 // A conv tile is th x tw grid pixels (<= FTN_TILE_PX = 22 units of 16 px);
 // the kernel stages the tile plus its halo, CLIPPED to the grid, in LDS.  Tiles

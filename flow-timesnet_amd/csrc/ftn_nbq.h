@@ -5,6 +5,7 @@
 #include "ftn_common.h"
 #include "ftn_nbmath.h"
 #include <math.h>
+#include <initializer_list>
 
 #define NBQ_CF_MAX 4096
 #define NBQ_CF_EPS 1e-13     // where a = 1e8 makes aa -> -1 the factor's own rounding noise is a few 1e-15
@@ -163,11 +164,31 @@ __device__ inline bool nq_cdf_pmf(const NbDist& D, double k, double& F, double& 
   return ok;
 }
 
-// element e of [B][H][N] in an operand with batch stride bs
-__device__ inline long long nq_off(long long e, long long HN, long long bs) {
-  const long long b = e / HN;
-  return b * bs + (e - b * HN);
+// The element loop the three kernels share.  A lane owns CPL consecutive elements of [B][H][N] from nq_first (4 with
+// 16-byte loads, where B H N % 4 == 0 and a quad lies in one row; else 1): nq_at splits the first into its batch row
+// and the offset within it, nq_load reads the lane's elements of an operand with batch stride bs, NQ_LANE picks one.
+struct NbAt { long long b, o; };
+
+template <int CPL>
+__device__ inline long long nq_first() { return ((long long)blockIdx.x * NBQ_THREADS + threadIdx.x) * CPL; }
+
+__device__ inline NbAt nq_at(long long e0, long long HN) {
+  const long long b = e0 / HN;
+  return {b, e0 - b * HN};
 }
+
+template <int CPL>
+__device__ inline f4 nq_load(const float* p, long long bs, NbAt at) {
+  if (CPL == 4) return *(const f4*)(p + at.b * bs + at.o);
+  return f4{p[at.b * bs + at.o], 0.f, 0.f, 0.f};
+}
+
+// As macros: either one as a function changes the kernels' register allocation (tools/kres.sh, the disassembly).
+#define NQ_LANE(v, j) ((j) == 0 ? (v).x : (j) == 1 ? (v).y : (j) == 2 ? (v).z : (v).w)
+
+// FTN_NBQ_RANGE into *flag when any lane of the workgroup saw a bad element: every lane of the workgroup runs it
+#define NQ_RAISE(flag, bad) \
+  do { if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(flag, FTN_NBQ_RANGE); } while (0)
 
 // Cornish-Fisher start: mean + sd (z + skew (z^2 - 1) / 6), floored into [0, 2^24); hardware sqrt / rsq estimates
 __device__ inline double nq_guess(const NbDist& D, double z) {
@@ -252,19 +273,30 @@ __host__ __device__ inline double nbq_normal_quantile(double q) {
 
 // The form every entry point takes (include/flowtimes.h): the one place the choice is made.
 static inline int nbq_form(int N, long long ybs, long long rbs, long long dbs, unsigned misalign_or) {
-  const bool vec = N % 4 == 0 && ybs % 4 == 0 && rbs % 4 == 0 && dbs % 4 == 0 && (misalign_or & 15) == 0;
-  return vec ? FTN_SHELL_VEC : 0;
+  return ftn_vec4_ok(N, ybs, rbs, dbs, misalign_or) ? FTN_SHELL_VEC : 0;
 }
 
-// the shape and layout checks the entry points share; 0 or < 0
-static inline int nbq_check(const char* who, int B, int H, int N, long long s0, long long s1, long long s2, float eps) {
+// the shape and layout checks the entry points share, for any number of operands' batch strides; 0 or < 0
+static inline int nbq_check(const char* who, int B, int H, int N, std::initializer_list<long long> bstrides, float eps) {
   FTN_CHECK_ARG(B >= 1 && H >= 1 && N >= 1, "%s: bad shape B=%d H=%d N=%d", who, B, H, N);
   const long long row = (long long)H * N;
   FTN_CHECK_ARG(row <= 0x7fffffffLL && (long long)B * row / 4 / NBQ_THREADS < 0x7fffffffLL,
                 "%s: H N = %lld or the grid beyond int32", who, row);
-  FTN_CHECK_ARG(s0 >= 0 && s1 >= 0 && s2 >= 0, "%s: negative batch stride", who);
-  FTN_CHECK_ARG(B == 1 || (s0 >= row && s1 >= row && s2 >= row), "%s: batch strides %lld %lld %lld are below H N = %lld",
-                who, s0, s1, s2, row);
+  for (const long long s : bstrides) {
+    FTN_CHECK_ARG(s >= 0, "%s: negative batch stride", who);
+    FTN_CHECK_ARG(B == 1 || s >= row, "%s: batch stride %lld is below H N = %lld", who, s, row);
+  }
   FTN_CHECK_ARG(eps > 0.f && eps < 1.f, "%s: eps=%g", who, (double)eps);
   return 0;
 }
+
+// The launch tail of the three entry points: form -> elements per lane -> grid -> kernel K<4> or K<1>
+#define NBQ_LAUNCH(K, form, args, stream)                                                   \
+  do {                                                                                      \
+    const int cpl_ = (form) & FTN_SHELL_VEC ? 4 : 1;                                        \
+    const long long per_ = (long long)NBQ_THREADS * cpl_;                                   \
+    const dim3 grid_((unsigned)(((args).total + per_ - 1) / per_)), block_(NBQ_THREADS);    \
+    if (cpl_ == 4) hipLaunchKernelGGL(K<4>, grid_, block_, 0, (hipStream_t)(stream), args); \
+    else hipLaunchKernelGGL(K<1>, grid_, block_, 0, (hipStream_t)(stream), args);           \
+    FTN_CHECK_LAUNCH();                                                                     \
+  } while (0)

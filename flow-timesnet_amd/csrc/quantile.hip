@@ -51,26 +51,19 @@ struct NbqArgs {
 
 template <int CPL>
 __global__ __launch_bounds__(NBQ_THREADS) void k_nb_cdf(NbqArgs a) {
-  const long long e0 = ((long long)blockIdx.x * NBQ_THREADS + threadIdx.x) * CPL;
+  const long long e0 = nq_first<CPL>();
   int bad = 0;
-  if (e0 < a.total) {                                           // CPL == 4: total % 4 == 0, a quad has one row
-    const long long b = e0 / a.HN, o = e0 - b * a.HN;
-    f4 yv = {0.f, 0.f, 0.f, 0.f}, rv = yv, dv = yv, fv = yv;
-    if (CPL == 4) {
-      yv = *(const f4*)(a.y + b * a.ybs + o);
-      rv = *(const f4*)(a.rate + b * a.rbs + o);
-      dv = *(const f4*)(a.disp + b * a.dbs + o);
-    } else {
-      yv.x = a.y[b * a.ybs + o]; rv.x = a.rate[b * a.rbs + o]; dv.x = a.disp[b * a.dbs + o];
-    }
+  if (e0 < a.total) {
+    const NbAt at = nq_at(e0, a.HN);
+    const f4 yv = nq_load<CPL>(a.y, a.ybs, at), rv = nq_load<CPL>(a.rate, a.rbs, at),
+             dv = nq_load<CPL>(a.disp, a.dbs, at);
+    f4 fv = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
     for (int j = 0; j < CPL; ++j) {
-      const float y = j == 0 ? yv.x : j == 1 ? yv.y : j == 2 ? yv.z : yv.w;
-      const float rt = j == 0 ? rv.x : j == 1 ? rv.y : j == 2 ? rv.z : rv.w;
-      const float ds = j == 0 ? dv.x : j == 1 ? dv.y : j == 2 ? dv.z : dv.w;
+      const float y = NQ_LANE(yv, j);
       const float yc = y < 0.f ? 0.f : y;
       NbDist D;
-      const bool valid = nq_dist(rt, ds, a.eps, D) && __builtin_isfinite(yc);
+      const bool valid = nq_dist(NQ_LANE(rv, j), NQ_LANE(dv, j), a.eps, D) && __builtin_isfinite(yc);
       const double k = floor(valid ? (double)yc : 0.0);
       const bool inside = k < NBQ_KLIM;
       double F, pm;
@@ -84,36 +77,27 @@ __global__ __launch_bounds__(NBQ_THREADS) void k_nb_cdf(NbqArgs a) {
     if (CPL == 4) *(f4*)(a.out + e0) = fv;
     else a.out[e0] = fv.x;
   }
-  if (a.flag && __syncthreads_or(bad) && threadIdx.x == 0) atomicOr(a.flag, FTN_NBQ_RANGE);
+  if (a.flag) NQ_RAISE(a.flag, bad);
 }
-
 
 template <int CPL>
 __global__ __launch_bounds__(NBQ_THREADS) void k_nb_quantile(NbqArgs a) {
-  const long long e0 = ((long long)blockIdx.x * NBQ_THREADS + threadIdx.x) * CPL;
+  const long long e0 = nq_first<CPL>();
   int bad = 0;
-  if (e0 < a.total) {                                           // CPL == 4: total % 4 == 0, a quad has one row
-    const long long b = e0 / a.HN, o = e0 - b * a.HN;
-    f4 rv = {0.f, 0.f, 0.f, 0.f}, dv = rv;
-    if (CPL == 4) {
-      rv = *(const f4*)(a.rate + b * a.rbs + o);
-      dv = *(const f4*)(a.disp + b * a.dbs + o);
-    } else {
-      rv.x = a.rate[b * a.rbs + o]; dv.x = a.disp[b * a.dbs + o];
-    }
+  if (e0 < a.total) {
+    const NbAt at = nq_at(e0, a.HN);
+    const f4 rv = nq_load<CPL>(a.rate, a.rbs, at), dv = nq_load<CPL>(a.disp, a.dbs, at);
 #pragma unroll 1
     for (int j = 0; j < CPL; ++j) {
-      const float rt = j == 0 ? rv.x : j == 1 ? rv.y : j == 2 ? rv.z : rv.w;
-      const float ds = j == 0 ? dv.x : j == 1 ? dv.y : j == 2 ? dv.z : dv.w;
       NbDist D;
-      const bool valid = nq_dist(rt, ds, a.eps, D);
+      const bool valid = nq_dist(NQ_LANE(rv, j), NQ_LANE(dv, j), a.eps, D);
       NbWalk w = {0.0, 0.0, 0.0, 0.0, false};
 #pragma unroll 1
       for (int i = 0; i < a.nq; ++i)
         a.out[(long long)a.row[i] * a.total + e0 + j] = nq_level(D, valid, a.lev[i], a.z[i], w, bad);
     }
   }
-  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(a.flag, FTN_NBQ_RANGE);
+  NQ_RAISE(a.flag, bad);
 }
 
 extern "C" int ftn_nbq_form(int N, long long y_bstride, long long rate_bstride, long long disp_bstride,
@@ -129,8 +113,7 @@ extern "C" int ftn_nb_cdf(const float* y_dev, long long y_bstride, const float* 
                           const float* disp_dev, long long disp_bstride, int B, int H, int N, float eps,
                           float* out_dev, double* out64_dev, int* flag_dev, void* stream) {
   FTN_CHECK_ARG(y_dev && rate_dev && disp_dev && out_dev, "ftn_nb_cdf: null pointer");
-  const long long row = (long long)H * N;
-  if (nbq_check("ftn_nb_cdf", B, H, N, y_bstride, rate_bstride, disp_bstride, eps) < 0) return -1;
+  if (nbq_check("ftn_nb_cdf", B, H, N, {y_bstride, rate_bstride, disp_bstride}, eps) < 0) return -1;
   FTN_CHECK_ARG((((uintptr_t)y_dev | (uintptr_t)rate_dev | (uintptr_t)disp_dev | (uintptr_t)out_dev |
                   (uintptr_t)flag_dev) & 3) == 0 && ((uintptr_t)out64_dev & 7) == 0,
                 "ftn_nb_cdf: operands must be 4-byte aligned, out64 8-byte aligned");
@@ -138,13 +121,8 @@ extern "C" int ftn_nb_cdf(const float* y_dev, long long y_bstride, const float* 
   NbqArgs a = {};
   a.y = y_dev; a.rate = rate_dev; a.disp = disp_dev; a.out = out_dev; a.out64 = out64_dev; a.flag = flag_dev;
   a.ybs = B > 1 ? y_bstride : 0; a.rbs = B > 1 ? rate_bstride : 0; a.dbs = B > 1 ? disp_bstride : 0;
-  a.HN = row; a.total = (long long)B * row; a.eps = eps;
-  const int cpl = nbq_form(N, a.ybs, a.rbs, a.dbs, mis) & FTN_SHELL_VEC ? 4 : 1;
-  const long long per = (long long)NBQ_THREADS * cpl;
-  const dim3 grid((unsigned)((a.total + per - 1) / per)), block(NBQ_THREADS);
-  if (cpl == 4) hipLaunchKernelGGL(k_nb_cdf<4>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_nb_cdf<1>, grid, block, 0, (hipStream_t)stream, a);
-  FTN_CHECK_LAUNCH();
+  a.HN = (long long)H * N; a.total = (long long)B * a.HN; a.eps = eps;
+  NBQ_LAUNCH(k_nb_cdf, nbq_form(N, a.ybs, a.rbs, a.dbs, mis), a, stream);
   return 0;
 }
 
@@ -156,7 +134,7 @@ extern "C" int ftn_nb_quantiles(const float* rate_dev, long long rate_bstride, c
   for (int i = 0; i < Q; ++i)
     FTN_CHECK_ARG(levels_host[i] > 0.0 && levels_host[i] < 1.0, "ftn_nb_quantiles: level %d = %g is not inside (0, 1)",
                   i, levels_host[i]);
-  if (nbq_check("ftn_nb_quantiles", B, H, N, rate_bstride, rate_bstride, disp_bstride, eps) < 0) return -1;
+  if (nbq_check("ftn_nb_quantiles", B, H, N, {rate_bstride, disp_bstride}, eps) < 0) return -1;
   FTN_CHECK_ARG((((uintptr_t)rate_dev | (uintptr_t)disp_dev | (uintptr_t)out_dev | (uintptr_t)flag_dev) & 3) == 0,
                 "ftn_nb_quantiles: operands must be 4-byte aligned");
   const unsigned mis = (unsigned)(((uintptr_t)rate_dev | (uintptr_t)disp_dev) & 15);
@@ -171,11 +149,6 @@ extern "C" int ftn_nb_quantiles(const float* rate_dev, long long rate_bstride, c
     a.row[j] = i;
   }
   for (int i = 0; i < Q; ++i) a.z[i] = nbq_normal_quantile(a.lev[i]);
-  const int cpl = nbq_form(N, 0, a.rbs, a.dbs, mis) & FTN_SHELL_VEC ? 4 : 1;
-  const long long per = (long long)NBQ_THREADS * cpl;
-  const dim3 grid((unsigned)((a.total + per - 1) / per)), block(NBQ_THREADS);
-  if (cpl == 4) hipLaunchKernelGGL(k_nb_quantile<4>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_nb_quantile<1>, grid, block, 0, (hipStream_t)stream, a);
-  FTN_CHECK_LAUNCH();
+  NBQ_LAUNCH(k_nb_quantile, nbq_form(N, 0, a.rbs, a.dbs, mis), a, stream);
   return 0;
 }

@@ -48,25 +48,17 @@ __device__ inline NbsWords ns_philox(unsigned c0, unsigned c1, unsigned c2, unsi
 
 template <int CPL>
 __global__ __launch_bounds__(NBQ_THREADS) void k_nb_sample(NbsArgs a) {
-  const long long e0 = ((long long)blockIdx.x * NBQ_THREADS + threadIdx.x) * CPL;
+  const long long e0 = nq_first<CPL>();
   int bad = 0;
-  if (e0 < a.total) {                                           // CPL == 4: total % 4 == 0, a quad has one row
+  if (e0 < a.total) {
     const unsigned long long seed = a.seed_dev ? *a.seed_dev : a.seed;
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    const long long b = e0 / a.HN, o = e0 - b * a.HN;
-    f4 rv = {0.f, 0.f, 0.f, 0.f}, dv = rv;
-    if (CPL == 4) {
-      rv = *(const f4*)(a.rate + b * a.rbs + o);
-      dv = *(const f4*)(a.disp + b * a.dbs + o);
-    } else {
-      rv.x = a.rate[b * a.rbs + o]; dv.x = a.disp[b * a.dbs + o];
-    }
+    const NbAt at = nq_at(e0, a.HN);
+    const f4 rv = nq_load<CPL>(a.rate, a.rbs, at), dv = nq_load<CPL>(a.disp, a.dbs, at);
 #pragma unroll 1
     for (int j = 0; j < CPL; ++j) {
-      const float rt = j == 0 ? rv.x : j == 1 ? rv.y : j == 2 ? rv.z : rv.w;
-      const float ds = j == 0 ? dv.x : j == 1 ? dv.y : j == 2 ? dv.z : dv.w;
       NbDist D;
-      const bool valid = nq_dist(rt, ds, a.eps, D);
+      const bool valid = nq_dist(NQ_LANE(rv, j), NQ_LANE(dv, j), a.eps, D);
       const double pm0 = nq_exp(D.r * D.lp);                    // pmf(0) = F(0) = p^r; 0 where it underflows
       const unsigned long long e = (unsigned long long)(e0 + j);
       NbsWords wd = {0u, 0u, 0u, 0u};
@@ -82,7 +74,7 @@ __global__ __launch_bounds__(NBQ_THREADS) void k_nb_sample(NbsArgs a) {
       }
     }
   }
-  if (__syncthreads_or(bad) && threadIdx.x == 0) atomicOr(a.flag, FTN_NBQ_RANGE);
+  NQ_RAISE(a.flag, bad);
 }
 
 extern "C" int ftn_nb_sample_form(int N, long long rate_bstride, long long disp_bstride, int misalign_or) {
@@ -98,7 +90,7 @@ extern "C" int ftn_nb_sample(const float* rate_dev, long long rate_bstride, cons
                              double* u_out_dev, int* flag_dev, void* stream) {
   FTN_CHECK_ARG(rate_dev && disp_dev && out_dev && flag_dev, "ftn_nb_sample: null pointer");
   FTN_CHECK_ARG(S >= 1, "ftn_nb_sample: S=%d", S);
-  if (nbq_check("ftn_nb_sample", B, H, N, rate_bstride, rate_bstride, disp_bstride, eps) < 0) return -1;
+  if (nbq_check("ftn_nb_sample", B, H, N, {rate_bstride, disp_bstride}, eps) < 0) return -1;
   FTN_CHECK_ARG((((uintptr_t)rate_dev | (uintptr_t)disp_dev | (uintptr_t)out_dev | (uintptr_t)flag_dev) & 3) == 0 &&
                     (((uintptr_t)u_out_dev | (uintptr_t)seed_dev) & 7) == 0,
                 "ftn_nb_sample: operands must be 4-byte aligned, u_out and seed_dev 8-byte aligned");
@@ -108,11 +100,6 @@ extern "C" int ftn_nb_sample(const float* rate_dev, long long rate_bstride, cons
   a.seed_dev = seed_dev; a.seed = seed; a.offset = offset;
   a.rbs = B > 1 ? rate_bstride : 0; a.dbs = B > 1 ? disp_bstride : 0;
   a.HN = (long long)H * N; a.total = (long long)B * a.HN; a.eps = eps; a.S = S;
-  const int cpl = nbq_form(N, 0, a.rbs, a.dbs, mis) & FTN_SHELL_VEC ? 4 : 1;
-  const long long per = (long long)NBQ_THREADS * cpl;
-  const dim3 grid((unsigned)((a.total + per - 1) / per)), block(NBQ_THREADS);
-  if (cpl == 4) hipLaunchKernelGGL(k_nb_sample<4>, grid, block, 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_nb_sample<1>, grid, block, 0, (hipStream_t)stream, a);
-  FTN_CHECK_LAUNCH();
+  NBQ_LAUNCH(k_nb_sample, nbq_form(N, 0, a.rbs, a.dbs, mis), a, stream);
   return 0;
 }

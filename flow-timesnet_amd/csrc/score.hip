@@ -179,8 +179,7 @@ static int score_form(int H, int N, long long ybs, long long rbs, long long dbs,
   int seg = (H + SC_MAXSEG - 1) / SC_MAXSEG;
   if (seg < SC_MINROWS) seg = SC_MINROWS;
   const int nseg = (H + seg - 1) / seg;
-  const bool vec = N % 4 == 0 && ybs % 4 == 0 && rbs % 4 == 0 && dbs % 4 == 0 && (misalign_or & 15) == 0;
-  return (vec ? FTN_SHELL_VEC : 0) | nseg << 4 | seg << 8;
+  return (ftn_vec4_ok(N, ybs, rbs, dbs, misalign_or) ? FTN_SHELL_VEC : 0) | nseg << 4 | seg << 8;
 }
 
 extern "C" int ftn_score_form(int H, int N, long long y_bstride, long long rate_bstride, long long disp_bstride,

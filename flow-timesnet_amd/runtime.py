@@ -30,6 +30,14 @@ def _ptr_or_null(t):
     return None if t is None else t.data_ptr()
 
 
+def _form(name: str, *args) -> int:
+    """The form word of a host-only ``ftn_*_form`` function for integer ``args``; its error through ``check``."""
+    f = getattr(_lib.load(), name)(*(int(a) for a in args))
+    if f < 0:
+        check(f, name)
+    return f
+
+
 def _batch_stride(t, B: int) -> int:
     """Elements between the batch rows of an optional contiguous ``[1|B, R, C]`` operand: 0 when one ``[R, C]`` block
     serves every row of the batch (or there is no operand)."""
@@ -238,10 +246,7 @@ _SPECTRUM_FORMS = ("k_spectrum", "k_spectrum_row", "k_spectrum_rowq", "k_spectru
 def spectrum_form(B: int, L: int, C: int, x_misalign: int = 0, scratch: bool = True) -> Tuple[str, bool]:
     """The kernel ``ftn_period_spectrum`` runs for this shape (host-only query; ``scratch``: the caller passes the
     scratch buffer, as ``spectrum`` does) and whether it reads x with 16-byte vector loads."""
-    lib = _lib.load()
-    f = lib.ftn_period_spectrum_form(int(B), int(L), int(C), int(x_misalign), int(bool(scratch)))
-    if f < 0:
-        check(f, "ftn_period_spectrum_form")
+    f = _form("ftn_period_spectrum_form", B, L, C, x_misalign, bool(scratch))
     return _SPECTRUM_FORMS[f & 3], bool(f & 4)
 
 
@@ -279,9 +284,7 @@ def embed_form_of(N: int, D: int, x_bstride: int = 0, x_misalign: int = 0, w_mis
     """The kernel ``ftn_embed_forward`` / ``ftn_embed_rows_strided`` run for a window of N series into d_model D with
     this batch stride (elements) and these byte offsets of x and W from a 16-byte boundary (``ftn_embed_form``,
     host-only: the launch dispatches through the same function, switches included)."""
-    f = _lib.load().ftn_embed_form(int(N), int(D), int(x_bstride), int(x_misalign), int(w_misalign))
-    if f < 0:
-        check(f, "ftn_embed_form")
+    f = _form("ftn_embed_form", N, D, x_bstride, x_misalign, w_misalign)
     return _embed_form_name(f)
 
 
@@ -294,9 +297,7 @@ def embed_form(window: torch.Tensor, weight: torch.Tensor) -> str:
 def head_form_of(N: int, D: int, tail_bstride: int = 0, late_bstride: int = 0, misalign_or: int = 0) -> Tuple[str, int]:
     """The kernel ``ftn_head_forward`` runs (``ftn_head_form``, host-only) and the cap on its ``gridDim.y``: the
     row loop of a workgroup iterates when ``rows > 64 * cap``."""
-    f = _lib.load().ftn_head_form(int(N), int(D), int(tail_bstride), int(late_bstride), int(misalign_or))
-    if f < 0:
-        check(f, "ftn_head_form")
+    f = _form("ftn_head_form", N, D, tail_bstride, late_bstride, misalign_or)
     p0, p1, cap = (f >> 4) & 15, (f >> 8) & 15, f >> 16
     return (f"k_head_bf<{p0},{p1}>" if f & 1 else f"k_head<{p0},{'true' if f & 2 else 'false'}>"), cap
 
@@ -312,9 +313,7 @@ def timeproj_form_of(L: int, S: int, D: int, wt_misalign: int = 0) -> str:
     """The kernel ``ftn_timeproj_forward`` runs for an ``L -> S`` projection at d_model D with W_t at this byte
     offset from a 16-byte boundary (``ftn_timeproj_form``, host-only: the launch dispatches through the same
     function): ``k_timeproj_row`` for S == 1, else ``k_timeproj_bf<NST,WV>``."""
-    f = _lib.load().ftn_timeproj_form(int(L), int(S), int(D), int(wt_misalign))
-    if f < 0:
-        check(f, "ftn_timeproj_form")
+    f = _form("ftn_timeproj_form", L, S, D, wt_misalign)
     return f"k_timeproj_bf<{(f >> 4) & 15},{'true' if f & 2 else 'false'}>" if f & 1 else "k_timeproj_row"
 
 
@@ -500,27 +499,65 @@ def score_form_of(H: int, N: int, strides=(0, 0, 0), misalign_or: int = 0) -> Tu
     function): ``("k_score_cols<4>" | "k_score_cols<1>", nseg, seg)`` - the vector form reads 16 bytes per lane and
     needs ``N % 4 == 0``, batch ``strides`` (of y, rate, dispersion, in elements) that are multiples of 4 and
     ``misalign_or == 0``; H is cut into ``nseg`` segments of ``seg`` rows."""
-    f = _lib.load().ftn_score_form(int(H), int(N), int(strides[0]), int(strides[1]), int(strides[2]), int(misalign_or))
-    if f < 0:
-        check(f, "ftn_score_form")
+    f = _form("ftn_score_form", H, N, strides[0], strides[1], strides[2], misalign_or)
     return f"k_score_cols<{4 if f & 2 else 1}>", (f >> 4) & 15, f >> 8
 
 
-def _score_operands(operands) -> None:
-    """Shapes, then row layout, then dtype and device of ``(name, tensor)`` pairs, the first being y."""
-    shape = tuple(operands[0][1].shape)
+def rows_ok(t: torch.Tensor) -> bool:
+    """Whether ``t`` [.., H, N] (3-d [B,H,N] or 4-d path-major [P,B,H,N]) has the layout the scoring kernels take: rows
+    contiguous and N apart, and every outer stride at least the extent of what lies beneath it."""
+    s, (H, N) = t.stride(), t.shape[-2:]
+    if (N > 1 and s[-1] != 1) or (H > 1 and s[-2] != N):
+        return False
+    extent = H * N
+    for d in range(t.dim() - 3, -1, -1):
+        if t.shape[d] > 1:
+            if s[d] < extent:
+                return False
+            extent += (t.shape[d] - 1) * s[d]
+    return True
+
+
+def _bhn_operands(who: str, operands) -> Tuple[int, int, int]:
+    """The preamble of the [B,H,N] wrappers for ``(name, tensor)`` pairs: shapes, then row layout, then dtype and
+    device, one device, no empty shape.  Returns ``(B, H, N)``."""
+    first = operands[0][0]
     for name, t in operands:
         if not isinstance(t, torch.Tensor) or t.dim() != 3:
-            raise ValueError(f"score_columns: {name} must be a [B, H, N] tensor")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"score_columns: {name} has shape {tuple(t.shape)}, y has {shape}")
-    B, H, N = shape
+            raise ValueError(f"{who}: {name} must be a [B, H, N] tensor")
+        if t.shape != operands[0][1].shape:
+            raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, {first} has {tuple(operands[0][1].shape)}")
     for name, t in operands:
-        if (N > 1 and t.stride(2) != 1) or (H > 1 and t.stride(1) != N) or (B > 1 and t.stride(0) < H * N):
-            raise ValueError(f"score_columns: {name} needs contiguous rows N elements apart, strides {t.stride()}")
+        if not rows_ok(t):
+            raise ValueError(f"{who}: {name} needs contiguous rows N elements apart, strides {t.stride()}")
     for name, t in operands:
         if t.dtype != torch.float32 or not t.is_cuda:
-            raise ValueError(f"score_columns: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
+            raise ValueError(f"{who}: {name} must be an fp32 device tensor, got {t.dtype} on {t.device}")
+    if len({t.device for _, t in operands}) != 1:
+        raise ValueError(f"{who}: {', '.join(n for n, _ in operands)} must be on one device")
+    B, H, N = operands[0][1].shape
+    if B < 1 or H < 1 or N < 1:
+        raise ValueError(f"{who}: empty shape {(B, H, N)}")
+    return B, H, N
+
+
+def _out_or_fresh(who: str, out, shape, like: torch.Tensor, name: str = "out") -> torch.Tensor:
+    """``out`` when it is a contiguous fp32 tensor of ``shape`` beside ``like``, a fresh one when it is None."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if out.dtype != torch.float32 or out.device != like.device or not out.is_contiguous() or tuple(out.shape) != shape:
+        raise ValueError(f"{who}: {name} must be contiguous fp32 {shape} beside its operands")
+    return out
+
+
+def _flag_or_fresh(who: str, flag, device, optional: bool = False):
+    """``flag`` when it is one int32 on ``device``; for None a fresh zeroed one, or None where it is ``optional``."""
+    if flag is None:
+        return None if optional else torch.zeros(1, dtype=torch.int32, device=device)
+    if (not isinstance(flag, torch.Tensor) or flag.dtype != torch.int32 or flag.numel() != 1 or not flag.is_cuda
+            or flag.device != device):
+        raise ValueError(f"{who}: flag must be one int32 on the operands' device")
+    return flag
 
 
 def _score_mask(mask, y: torch.Tensor):
@@ -561,15 +598,8 @@ def score_columns(y: torch.Tensor, rate: torch.Tensor, disp: torch.Tensor, mask=
     ``b N + n``; ``ll`` the fp32 per-element log-likelihood (0 where invalid) when ``want_ll``, else None.  Enqueues
     only."""
     lib = _lib.load()
-    if not isinstance(y, torch.Tensor) or y.dim() != 3:
-        raise ValueError("score_columns: y must be a [B, H, N] tensor")
-    _score_operands((("y", y), ("rate", rate), ("dispersion", disp)))
-    if rate.device != y.device or disp.device != y.device:
-        raise ValueError("score_columns: y, rate and dispersion must be on one device")
+    B, H, N = _bhn_operands("score_columns", (("y", y), ("rate", rate), ("dispersion", disp)))
     mask, kind = _score_mask(mask, y)
-    B, H, N = y.shape
-    if B < 1 or H < 1 or N < 1:
-        raise ValueError(f"score_columns: empty shape {tuple(y.shape)}")
     part = torch.empty(B * N * SCORE_PART_BYTES, dtype=torch.uint8, device=y.device)
     ll = torch.empty(B, H, N, dtype=torch.float32, device=y.device) if want_ll else None
     check(lib.ftn_score_columns(_ptr(y), y.stride(0), _ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0),
@@ -615,9 +645,7 @@ def nbq_form_of(N: int, strides=(0, 0, 0), misalign_or: int = 0) -> str:
     """The kernel form ``ftn_nb_cdf`` / ``ftn_nb_quantiles`` take (``ftn_nbq_form``, host-only: the launches dispatch
     through the same function): ``"vec4"`` (16-byte loads, four elements per lane: ``N % 4 == 0``, batch ``strides``
     of y, rate, dispersion that are multiples of 4, ``misalign_or == 0``) or ``"scalar"``."""
-    f = _lib.load().ftn_nbq_form(int(N), int(strides[0]), int(strides[1]), int(strides[2]), int(misalign_or))
-    if f < 0:
-        check(f, "ftn_nbq_form")
+    f = _form("ftn_nbq_form", N, strides[0], strides[1], strides[2], misalign_or)
     return "vec4" if f & 2 else "scalar"
 
 
@@ -639,29 +667,14 @@ def nb_cdf(y: torch.Tensor, rate: torch.Tensor, disp: torch.Tensor, eps: float =
     elements apart): ``F(floor(max(y, 0)))`` as fp32 [B,H,N]; with ``want64`` returns ``(out, out64)``, the second the
     fp64 values before the rounding.  ``flag``: one device int32 that receives ``FTN_NBQ_RANGE``.  Enqueues only."""
     lib = _lib.load()
-    if not isinstance(y, torch.Tensor) or y.dim() != 3:
-        raise ValueError("nb_cdf: y must be a [B, H, N] tensor")
-    _score_operands((("y", y), ("rate", rate), ("dispersion", disp)))
-    if rate.device != y.device or disp.device != y.device:
-        raise ValueError("nb_cdf: y, rate and dispersion must be on one device")
-    B, H, N = y.shape
-    if B < 1 or H < 1 or N < 1:
-        raise ValueError(f"nb_cdf: empty shape {tuple(y.shape)}")
-    _nbq_flag(flag, y.device, "nb_cdf", optional=True)
+    B, H, N = _bhn_operands("nb_cdf", (("y", y), ("rate", rate), ("dispersion", disp)))
+    flag = _flag_or_fresh("nb_cdf", flag, y.device, optional=True)
     out = torch.empty(B, H, N, dtype=torch.float32, device=y.device)
     out64 = torch.empty(B, H, N, dtype=torch.float64, device=y.device) if want64 else None
     check(lib.ftn_nb_cdf(_ptr(y), y.stride(0), _ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0), B, H, N,
                          float(eps), _ptr(out), _ptr_or_null(out64), _ptr_or_null(flag), _stream(y.device)),
           "ftn_nb_cdf")
     return (out, out64) if want64 else out
-
-
-def _nbq_flag(flag, device, who: str, optional: bool = False) -> None:
-    if flag is None and optional:
-        return
-    if (not isinstance(flag, torch.Tensor) or flag.dtype != torch.int32 or flag.numel() != 1 or not flag.is_cuda
-            or flag.device != device):
-        raise ValueError(f"{who}: flag must be one int32 on the operands' device")
 
 
 def nb_quantiles(rate: torch.Tensor, disp: torch.Tensor, levels, eps: float = 1e-8, out: torch.Tensor | None = None,
@@ -671,25 +684,12 @@ def nb_quantiles(rate: torch.Tensor, disp: torch.Tensor, levels, eps: float = 1e
     ``flag``: one device int32 that receives ``FTN_NBQ_RANGE`` (default: fresh, zeroed).  Returns ``(out, flag)``.
     Enqueues only."""
     lib = _lib.load()
-    if not isinstance(rate, torch.Tensor) or rate.dim() != 3:
-        raise ValueError("nb_quantiles: rate must be a [B, H, N] tensor")
-    _score_operands((("rate", rate), ("dispersion", disp)))
-    if disp.device != rate.device:
-        raise ValueError("nb_quantiles: rate and dispersion must be on one device")
-    B, H, N = rate.shape
-    if B < 1 or H < 1 or N < 1:
-        raise ValueError(f"nb_quantiles: empty shape {tuple(rate.shape)}")
+    B, H, N = _bhn_operands("nb_quantiles", (("rate", rate), ("dispersion", disp)))
     lv = [float(q) for q in levels]
     Q = len(lv)
     arr = (C.c_double * max(Q, 1))(*lv)
-    if out is None:
-        out = torch.empty(max(Q, 1), B, H, N, dtype=torch.float32, device=rate.device)
-    elif (out.dtype != torch.float32 or out.device != rate.device or not out.is_contiguous()
-          or tuple(out.shape) != (Q, B, H, N)):
-        raise ValueError(f"nb_quantiles: out must be contiguous fp32 {(Q, B, H, N)} beside rate")
-    if flag is None:
-        flag = torch.zeros(1, dtype=torch.int32, device=rate.device)
-    _nbq_flag(flag, rate.device, "nb_quantiles")
+    out = _out_or_fresh("nb_quantiles", out, (Q if out is not None else max(Q, 1), B, H, N), rate)
+    flag = _flag_or_fresh("nb_quantiles", flag, rate.device)
     check(lib.ftn_nb_quantiles(_ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0), B, H, N, arr, Q, float(eps),
                                _ptr(out), _ptr(flag), _stream(rate.device)), "ftn_nb_quantiles")
     return out, flag
@@ -700,10 +700,8 @@ def nb_sample_form(rate, disp) -> str:
     """The kernel form ``ftn_nb_sample`` takes for these tensors (``ftn_nb_sample_form``): ``"vec4"`` or
     ``"scalar"``, by ``nbq_form_of``'s rule for rate and dispersion."""
     B, H, N = rate.shape
-    f = _lib.load().ftn_nb_sample_form(int(N), rate.stride(0) if B > 1 else 0, disp.stride(0) if B > 1 else 0,
-                                       (_ptr(rate) | _ptr(disp)) & 15)
-    if f < 0:
-        check(f, "ftn_nb_sample_form")
+    f = _form("ftn_nb_sample_form", N, rate.stride(0) if B > 1 else 0, disp.stride(0) if B > 1 else 0,
+              (_ptr(rate) | _ptr(disp)) & 15)
     return "vec4" if f & 2 else "scalar"
 
 
@@ -715,15 +713,10 @@ def nb_sample(rate: torch.Tensor, disp: torch.Tensor, n_samples: int = 1, seed=0
     one device int32 that receives ``FTN_NBQ_RANGE`` (default: fresh, zeroed).  Returns ``(out, flag, u)``, ``u`` the
     fp64 uniforms [S,B,H,N] with ``want_uniforms``, else None.  Enqueues only."""
     lib = _lib.load()
-    if not isinstance(rate, torch.Tensor) or rate.dim() != 3:
-        raise ValueError("nb_sample: rate must be a [B, H, N] tensor")
-    _score_operands((("rate", rate), ("dispersion", disp)))
-    if disp.device != rate.device:
-        raise ValueError("nb_sample: rate and dispersion must be on one device")
-    B, H, N = rate.shape
+    B, H, N = _bhn_operands("nb_sample", (("rate", rate), ("dispersion", disp)))
     S = int(n_samples)
-    if B < 1 or H < 1 or N < 1 or S < 1:
-        raise ValueError(f"nb_sample: empty shape {tuple(rate.shape)} or n_samples={n_samples}")
+    if S < 1:
+        raise ValueError(f"nb_sample: n_samples={n_samples}")
     if not 0 <= int(offset) <= 0xFFFFFFFF:
         raise ValueError(f"nb_sample: offset={offset} is not a 32-bit word")
     seed_dev, seed_val = None, 0
@@ -733,15 +726,9 @@ def nb_sample(rate: torch.Tensor, disp: torch.Tensor, n_samples: int = 1, seed=0
         seed_dev = seed
     else:
         seed_val = int(seed) & 0xFFFFFFFFFFFFFFFF
-    if out is None:
-        out = torch.empty(S, B, H, N, dtype=torch.float32, device=rate.device)
-    elif (out.dtype != torch.float32 or out.device != rate.device or not out.is_contiguous()
-          or tuple(out.shape) != (S, B, H, N)):
-        raise ValueError(f"nb_sample: out must be contiguous fp32 {(S, B, H, N)} beside rate")
+    out = _out_or_fresh("nb_sample", out, (S, B, H, N), rate)
     u = torch.empty(S, B, H, N, dtype=torch.float64, device=rate.device) if want_uniforms else None
-    if flag is None:
-        flag = torch.zeros(1, dtype=torch.int32, device=rate.device)
-    _nbq_flag(flag, rate.device, "nb_sample")
+    flag = _flag_or_fresh("nb_sample", flag, rate.device)
     check(lib.ftn_nb_sample(_ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0), B, H, N, S, seed_val,
                             _ptr_or_null(seed_dev), int(offset), float(eps), _ptr(out), _ptr_or_null(u), _ptr(flag),
                             _stream(rate.device)), "ftn_nb_sample")
@@ -757,10 +744,7 @@ def path_summary_form_of(P: int, N: int, window: int = 1, strides=(0, 0, 0), mis
     the same function): ``"reg<PP>/vec4"``, ``"reg<PP>/scalar"`` (a lane sorts its columns in registers, PP the
     padded P) or ``"lds<PP>x<T>/vec4"``, ``"lds<PP>x<T>/scalar"`` (a workgroup sorts a tile of T columns in LDS).
     ``strides``: the path and batch strides of samples and the batch stride of y, in elements."""
-    f = _lib.load().ftn_path_summary_form(int(P), int(N), int(window), int(strides[0]), int(strides[1]),
-                                          int(strides[2]), int(misalign_or))
-    if f < 0:
-        check(f, "ftn_path_summary_form")
+    f = _form("ftn_path_summary_form", P, N, window, strides[0], strides[1], strides[2], misalign_or)
     width = "vec4" if f & 2 else "scalar"
     pp = (f >> 8) & 0xFFF
     return f"lds{pp}x{f >> 20}/{width}" if f & _lib.FTN_PATH_LDS else f"reg{pp}/{width}"
@@ -783,7 +767,7 @@ def path_summary_form(samples, y=None, window: int = 1, outs=()) -> str:
 
 
 def _path_operands(samples, y) -> None:
-    """Shape, then row layout, then dtype and device of samples [P,B,H,N] and y [B,H,N], as ``_score_operands``."""
+    """Shape, then row layout, then dtype and device of samples [P,B,H,N] and y [B,H,N], as ``_bhn_operands``."""
     if not isinstance(samples, torch.Tensor) or samples.dim() != 4:
         raise ValueError("path_summary: samples must be a [P, B, H, N] tensor")
     P, B, H, N = samples.shape
@@ -791,14 +775,10 @@ def _path_operands(samples, y) -> None:
         raise ValueError(f"path_summary: empty shape {tuple(samples.shape)}")
     if y is not None and (not isinstance(y, torch.Tensor) or tuple(y.shape) != (B, H, N)):
         raise ValueError(f"path_summary: y must be a {(B, H, N)} tensor beside samples {tuple(samples.shape)}")
-    s = samples.stride()
-    if ((N > 1 and s[3] != 1) or (H > 1 and s[2] != N) or (B > 1 and s[1] < H * N)
-            or (P > 1 and s[0] < (B - 1) * (s[1] if B > 1 else 0) + H * N)):
-        raise ValueError(f"path_summary: samples need contiguous rows N elements apart, strides {s}")
-    if y is not None:
-        t = y.stride()
-        if (N > 1 and t[2] != 1) or (H > 1 and t[1] != N) or (B > 1 and t[0] < H * N):
-            raise ValueError(f"path_summary: y needs contiguous rows N elements apart, strides {t}")
+    if not rows_ok(samples):
+        raise ValueError(f"path_summary: samples need contiguous rows N elements apart, strides {samples.stride()}")
+    if y is not None and not rows_ok(y):
+        raise ValueError(f"path_summary: y needs contiguous rows N elements apart, strides {y.stride()}")
     for name, t in (("samples", samples), ("y", y)):
         if t is not None and (t.dtype != torch.float32 or not t.is_cuda or t.device != samples.device):
             raise ValueError(f"path_summary: {name} must be an fp32 tensor on samples' device, got {t.dtype} on "
@@ -832,15 +812,8 @@ def path_summary(samples: torch.Tensor, ranks, window: int = 1, reduce: str = "s
               "crps": (B, Hp, N) if y is not None else None, "sorted": (P, B, Hp, N) if want_sorted else None}
     res = {}
     for key, shape in shapes.items():
-        t = None if out is None else out.get(key)
-        if shape is None:
-            t = None
-        elif t is None:
-            t = torch.empty(shape, dtype=torch.float32, device=samples.device)
-        elif (t.dtype != torch.float32 or t.device != samples.device or not t.is_contiguous()
-              or tuple(t.shape) != shape):
-            raise ValueError(f"path_summary: out[{key!r}] must be contiguous fp32 {shape} beside samples")
-        res[key] = t
+        given = None if out is None else out.get(key)
+        res[key] = None if shape is None else _out_or_fresh("path_summary", given, shape, samples, f"out[{key!r}]")
     ps, bs, ybs = samples.stride(0), samples.stride(1), (y.stride(0) if y is not None else 0)
     first = True
     for i in range(0, max(Q, 1), _lib.FTN_QMAX):
@@ -863,10 +836,7 @@ def group_sum_form_of(N: int, row_stride: int | None = None, misalign_or: int = 
     same function): ``"vec4/t<T>"`` or ``"scalar/t<T>"``, the load width of x and the rows of a tile.  ``row_stride``
     in elements (default: N), ``misalign_or`` the address of x modulo 16, ``n_chunks`` the chunks of 32 members over
     all groups."""
-    f = _lib.load().ftn_group_sum_form(int(N), int(N if row_stride is None else row_stride), int(misalign_or),
-                                       int(n_chunks))
-    if f < 0:
-        check(f, "ftn_group_sum_form")
+    f = _form("ftn_group_sum_form", N, N if row_stride is None else row_stride, misalign_or, n_chunks)
     return f"{'vec4' if f & 2 else 'scalar'}/t{f >> 8}"
 
 
@@ -900,11 +870,7 @@ def group_sum(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, offse
     if (getattr(offsets_host, "dtype", None) != "int32" or offsets_host.ndim != 1 or offsets_host.size != G + 1
             or not offsets_host.flags["C_CONTIGUOUS"]):
         raise ValueError(f"group_sum: offsets_host must be a contiguous int32 numpy array of {G + 1} offsets")
-    if out is None:
-        out = torch.empty(rows, G, dtype=torch.float32, device=x.device)
-    elif (out.dtype != torch.float32 or out.device != x.device or not out.is_contiguous()
-          or tuple(out.shape) != (rows, G)):
-        raise ValueError(f"group_sum: out must be contiguous fp32 {(rows, G)} beside x")
+    out = _out_or_fresh("group_sum", out, (rows, G), x)
     check(lib.ftn_group_sum(_ptr(x), rows, N, x.stride(0) if rows > 1 else N, _ptr(order) if M else None,
                             _ptr(offsets), offsets_host.ctypes.data, G, M, _ptr(out), _stream(x.device)),
           "ftn_group_sum")
@@ -916,9 +882,7 @@ def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tu
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch
     dispatches through the same function): ``("k_lrtc<RT,VEC,ADDX>", wide coefficient loads, nqb)``.
     ``misalign_or``: ``((out | x) & 15) | (coeff & 15) << 4`` of the byte addresses."""
-    f = _lib.load().ftn_lrtc_form(int(N), int(R), int(addx), int(misalign_or))
-    if f < 0:
-        check(f, "ftn_lrtc_form")
+    f = _form("ftn_lrtc_form", N, R, addx, misalign_or)
     tf = ("false", "true")
     return f"k_lrtc<{(f >> 4) & 63},{tf[f & 1]},{tf[(f >> 1) & 1]}>", bool(f & 4), 64 * (f >> 12)
 

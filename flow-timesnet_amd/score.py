@@ -13,11 +13,11 @@ synchronisation), ``eval_metrics`` is ``_eval_metrics`` as a loop over batch tup
 
 ``nb_cdf`` / ``nb_quantiles`` / ``prediction_interval`` / ``interval_metrics`` use the distribution itself (no
 counterpart in the reference): the regularised incomplete beta function and its inversion, ``k_nb_cdf`` /
-``k_nb_quantile`` on the ``hip`` side and the same method in fp64 torch ops otherwise.
+``k_nb_quantile`` on the ``hip`` side and the same method in fp64 torch ops otherwise (``nbdist``).
 
 ``nb_sample`` / ``sample_uniforms`` / ``path_quantiles`` draw from it: a counter-based Philox4x32-10 and the inversion
-of that CDF (``k_nb_sample``, or the same generator and search in torch ops), so a draw is a pure function of
-``(seed, offset, element, draw index)``; ``forecast.forecast_sample_paths`` feeds the draws back into the recursion.
+of that CDF (``k_nb_sample``, or the same generator and search in torch ops, ``nbdist``), so a draw is a pure function
+of ``(seed, offset, element, draw index)``; ``forecast.forecast_sample_paths`` feeds the draws back into the recursion.
 
 ``path_summary`` / ``path_metrics`` summarise sample paths [P,B,H,N]: order statistics, mean and sample CRPS of window
 sums or maxima, ``ftn_path_summary`` on the ``hip`` side (one pass over the paths, one sort per column in registers or
@@ -33,6 +33,9 @@ from typing import Dict, List, Optional
 
 import numpy as np
 import torch
+
+from .nbdist import (NBQ_FLAG_RANGE, NBQ_KLIM, NBQ_QMAX, _M32, _nb_cdf_torch, _nb_invert_torch,  # noqa: F401
+                     _nb_quantiles_torch, philox4x32, sample_uniforms)
 
 _last_backend: Optional[str] = None
 
@@ -90,10 +93,11 @@ def _hip_eligible(*tensors) -> bool:
 
 
 def _rows(t: torch.Tensor) -> torch.Tensor:
-    """``t`` [B,H,N] as the kernel takes it: rows contiguous and N apart (a batch stride of its own is fine)."""
-    B, H, N = t.shape
-    ok = (N == 1 or t.stride(2) == 1) and (H == 1 or t.stride(1) == N) and (B == 1 or t.stride(0) >= H * N)
-    return t if ok else t.contiguous()
+    """``t`` [B,H,N] or [P,B,H,N] as the kernels take it: rows contiguous and N apart (batch and path strides of its
+    own are fine, ``runtime.rows_ok``), else a contiguous copy."""
+    from . import runtime as rt
+
+    return t if rt.rows_ok(t) else t.contiguous()
 
 
 def _full_mask(mask, like: torch.Tensor):
@@ -346,179 +350,42 @@ def eval_metrics(model, batches, mode: str, pred_len: int, use_loss_mask: bool =
 
 
 # ---------------------------------------------------------------------------------------------- quantiles and CDF
-# F(y) = I_p(r, floor(yc) + 1), r = 1 / alpha, p = 1 / (1 + alpha mu), with the scorer's clamps; Q(q) the smallest
-# integer k >= 0 with F(k) >= q.  ``hip``: k_nb_cdf / k_nb_quantile (csrc/quantile.hip).  ``torch``: the same
-# continued fraction and the same bracketed search in fp64 torch ops, so the functions run on CPU tensors.
-NBQ_QMAX = 8                 # levels of one k_nb_quantile launch (FTN_QMAX)
-NBQ_KLIM = float(1 << 24)    # answers below it are exact in fp32; at or beyond it: NaN and flag bit 1
-NBQ_FLAG_RANGE = 2           # bit 1 of the flag word
-_NBQ_CF_MAX = 4096           # continued-fraction iterations (the kernel's NBQ_CF_MAX)
-_NBQ_EVALS = 32              # CDF evaluations of one level: 6 Newton steps, then 25 halvings of [0, 2^24] and one spare
-_NBQ_NEWTON = 6
-_NBQ_WALK = 64               # pmf-recurrence steps after an evaluation
+# ``hip``: k_nb_cdf / k_nb_quantile (csrc/quantile.hip).  ``torch``: the same continued fraction and the same bracketed
+# search in fp64 torch ops (nbdist.py), so the functions run on CPU tensors.
 
 
-def _nbq_params(rate, dispersion, eps):
-    """``(r, t, p, 1 - p, log p, log(1 - p), valid)`` in fp64 from fp32-rounded inputs, the scorer's clamps."""
-    al = dispersion.to(torch.float32)
-    mu = rate.to(torch.float32)
-    e = torch.tensor(eps, dtype=torch.float32, device=al.device)
-    al = torch.where(al < e, e, al)
-    mu = torch.where(mu < e, e, mu)
-    valid = torch.isfinite(al) & torch.isfinite(mu)
-    one = torch.ones_like(al)
-    al, mu = torch.where(valid, al, one).double(), torch.where(valid, mu, one).double()
-    r, t = 1.0 / al, al * mu
-    return r, t, 1.0 / (1.0 + t), t / (1.0 + t), -torch.log1p(t), -torch.log1p(1.0 / t), valid
-
-
-def _stirling_corr(x):
-    z = 1.0 / x
-    z2 = z * z
-    return z * (1.0 / 12.0 + z2 * (-1.0 / 360.0 + z2 * (1.0 / 1260.0 + z2 * (-1.0 / 1680.0))))
-
-
-def _log_inv_beta(a, b):
-    """lgamma(a + b) - lgamma(a) - lgamma(b); for max(a, b) >= 16 the two large lgammas are differenced in
-    Stirling's form, which keeps 1e8-sized terms from cancelling."""
-    L, S = torch.maximum(a, b), torch.minimum(a, b)
-    big = L >= 16.0
-    Ls = torch.where(big, L, torch.full_like(L, 16.0))
-    ratio = S * torch.log(Ls + S) + (Ls - 0.5) * torch.log1p(S / Ls) - S + _stirling_corr(Ls + S) - _stirling_corr(Ls)
-    return torch.where(big, ratio, torch.lgamma(L + S) - torch.lgamma(L)) - torch.lgamma(S)
-
-
-def _betacf(a, b, x, iters=_NBQ_CF_MAX):
-    """The continued fraction of I_x(a, b) by the modified Lentz method; ``(h, converged)``."""
-    tiny = 1e-300
-    qab, qap, qam = a + b, a + 1.0, a - 1.0
-    c = torch.ones_like(a)
-    d = 1.0 - qab * x / qap
-    d = 1.0 / torch.where(d.abs() < tiny, torch.full_like(d, tiny), d)
-    h = d.clone()
-    live = torch.ones_like(a, dtype=torch.bool)
-    for m in range(1, iters + 1):
-        m2 = 2.0 * m
-        aa = m * (b - m) * x / ((qam + m2) * (a + m2))
-        d = 1.0 + aa * d
-        d = 1.0 / torch.where(d.abs() < tiny, torch.full_like(d, tiny), d)
-        c = 1.0 + aa / c
-        c = torch.where(c.abs() < tiny, torch.full_like(c, tiny), c)
-        h1 = h * d * c
-        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2))
-        d = 1.0 + aa * d
-        d = 1.0 / torch.where(d.abs() < tiny, torch.full_like(d, tiny), d)
-        c = 1.0 + aa / c
-        c = torch.where(c.abs() < tiny, torch.full_like(c, tiny), c)
-        de = d * c
-        h = torch.where(live, h1 * de, h)
-        live = live & ~((de - 1.0).abs() < 1e-13)
-        if m % 8 == 0 and not bool(live.any()):
-            break
-    return h, ~live
-
-
-def _nb_cdf_pmf(k, r, p, omp, lp, lomp):
-    """``(F(k), pmf(k), converged)`` for integer-valued fp64 k >= 0."""
-    a, b = r, k + 1.0
-    front = torch.exp(_log_inv_beta(a, b) + a * lp + b * lomp)
-    swap = p * (a + b + 2.0) >= a + 1.0
-    h, ok = _betacf(torch.where(swap, b, a), torch.where(swap, a, b), torch.where(swap, omp, p))
-    F = torch.where(swap, 1.0 - front * h / b, front * h / a)
-    return F.clamp(0.0, 1.0), front / ((k + r) * omp), ok
-
-
-def _nb_cdf_torch(y, rate, dispersion, eps):
-    r, t, p, omp, lp, lomp, valid = _nbq_params(rate, dispersion, eps)
-    yf = y.to(torch.float32)
-    yc = torch.where(yf < 0, torch.zeros_like(yf), yf)
-    valid = valid & torch.isfinite(yc)
-    k = torch.floor(torch.where(valid, yc, torch.zeros_like(yc)).double())
-    inside = k < NBQ_KLIM
-    F, _, ok = _nb_cdf_pmf(torch.where(inside, k, torch.zeros_like(k)), r, p, omp, lp, lomp)
-    bad = valid & ~(inside & ok)
-    F = torch.where(valid & ~bad, F, torch.full_like(F, float("nan")))
-    return F, bad.any().to(torch.int32) * NBQ_FLAG_RANGE
-
-
-def _nbq_guess(z, r, t, omp, p):
-    """Cornish-Fisher start: mean + sd (z + skew (z^2 - 1) / 6), floored into [0, 2^24)."""
-    mean = r * t
-    sd = torch.sqrt(mean * (1.0 + t))
-    skew = (2.0 - p) / torch.sqrt(r * omp)
-    g = torch.floor(mean + sd * (z + skew * (z * z - 1.0) / 6.0))
-    return torch.nan_to_num(g, nan=0.0, posinf=NBQ_KLIM - 1.0, neginf=0.0).clamp(0.0, NBQ_KLIM - 1.0)
-
-
-def _nb_quantiles_torch(rate, dispersion, levels, eps):
-    from statistics import NormalDist
-
-    r, t, p, omp, lp, lomp, valid = _nbq_params(rate, dispersion, eps)
-    order = sorted(range(len(levels)), key=lambda i: levels[i])
-    out = torch.empty((len(levels),) + tuple(rate.shape), dtype=torch.float32, device=rate.device)
-    nan = torch.full_like(r, float("nan"))
-    bad_any = torch.zeros((), dtype=torch.bool, device=rate.device)
-    k = torch.zeros_like(r)
-    F = torch.zeros_like(r)
-    pm = torch.zeros_like(r)
-    have = torch.zeros_like(valid)
-    prev = torch.zeros_like(r)
-    for i in order:
-        q = float(levels[i])
-        g = torch.maximum(_nbq_guess(NormalDist().inv_cdf(q), r, t, omp, p), prev)
-        lo, hi = prev.clone(), torch.full_like(r, NBQ_KLIM)
-        jump = ~(have & (g <= k + _NBQ_WALK))
-        k = torch.where(jump, g, k)
-        need = jump
-        done = ~valid
-        for it in range(_NBQ_EVALS):
-            if bool(need.any()):
-                Fe, pe, ok = _nb_cdf_pmf(k, r, p, omp, lp, lomp)
-                F, pm = torch.where(need, Fe, F), torch.where(need, pe, pm)
-                done = done | (need & ~ok)                      # the fraction's cap: lo < hi stays, so NaN below
-            for _ in range(_NBQ_WALK):
-                act = ~done
-                down = act & (F >= q) & (k > lo) & (F - pm >= q)
-                up = act & (F < q) & (k + 1.0 < NBQ_KLIM)
-                if not bool((down | up).any()):
-                    break
-                Fd, pd = F - pm, pm * k / ((k - 1.0 + r) * omp)
-                pu = pm * (k + r) / (k + 1.0) * omp
-                F = torch.where(down, Fd, torch.where(up, F + pu, F))
-                pm = torch.where(down, pd, torch.where(up, pu, pm))
-                lo = torch.where(up, k + 1.0, lo)
-                k = torch.where(down, k - 1.0, torch.where(up, k + 1.0, k))
-            ge = F >= q
-            hi = torch.where(~done & ge, torch.minimum(hi, k), hi)
-            lo = torch.where(~done & ~ge, k + 1.0, lo)
-            found = ~done & ge & ((k <= lo) | (F - pm < q))
-            lo = torch.where(found, k, lo)
-            hi = torch.where(found, k, hi)
-            done = done | found | (lo >= hi)
-            kn = torch.floor(k + (q - F) / pm + 0.5)
-            newton = (it < _NBQ_NEWTON) & (kn >= lo) & (kn < hi)
-            kn = torch.where(newton, kn, torch.floor(0.5 * (lo + hi)))
-            need = ~done
-            k = torch.where(need, kn.clamp(max=NBQ_KLIM - 1.0), k)
-            if bool(done.all()):
-                break
-        ans_ok = valid & (lo >= hi) & (hi < NBQ_KLIM)
-        bad_any = bad_any | (valid & ~ans_ok).any()
-        out[i] = torch.where(ans_ok, hi, nan).to(torch.float32)
-        have = ans_ok & (k == hi)
-        prev = torch.where(ans_ok, hi, prev)
-    out[:, ~valid] = float("nan")
-    return out, bad_any.to(torch.int32) * NBQ_FLAG_RANGE
-
-
-def _check_levels(levels) -> List[float]:
+def _check_levels(levels, who: str = "nb_quantiles", allow_empty: bool = False) -> List[float]:
     lv = [float(q) for q in levels]
-    if not lv:
-        raise ValueError("nb_quantiles: no levels")
+    if not lv and not allow_empty:
+        raise ValueError(f"{who}: no levels")
     for q in lv:
         if not 0.0 < q < 1.0:
-            raise ValueError(f"nb_quantiles: level {q} is not strictly inside (0, 1)")
+            raise ValueError(f"{who}: level {q} is not strictly inside (0, 1)")
     return lv
+
+
+def _use_hip(who: str, backend, eligible: bool, takes: str) -> bool:
+    """Which backend a call with a ``backend`` argument runs: ``hip`` where it can unless ``"torch"`` is asked for;
+    asking for ``"hip"`` where it cannot run is an error, as is any other name."""
+    if backend not in (None, "hip", "torch"):
+        raise ValueError(f"{who}: backend {backend!r} is not 'hip', 'torch' or None")
+    if backend == "hip" and not eligible:
+        raise ValueError(f"{who}: backend 'hip' takes {takes}")
+    return eligible and backend != "torch"
+
+
+def _calibration(valid, target, Q, lv):
+    """``(coverage [Q], pinball [Q], den)`` of the quantiles ``Q`` [Q,B,H,N] at levels ``lv`` against ``target``
+    [B,H,N] over the ``valid`` elements: the means of ``target <= Q`` and of ``max(q d, (q - 1) d)`` with
+    ``d = target - Q``, and the fp32 count they were divided by (at least 1)."""
+    w = valid.to(torch.float32)
+    den = w.sum().clamp(min=1.0)
+    zero = torch.zeros((), dtype=torch.float32, device=Q.device)
+    yv = torch.where(valid, target, zero)
+    Qv = torch.where(valid, Q, zero)
+    diff = yv - Qv                                              # the levels stay Python scalars: no host-to-device copy
+    pin = torch.stack([torch.maximum(q * diff[i], (q - 1.0) * diff[i]) for i, q in enumerate(lv)]) * w
+    return ((yv <= Qv).to(torch.float32) * w).sum((1, 2, 3)) / den, pin.sum((1, 2, 3)) / den, den
 
 
 def nb_cdf(y: torch.Tensor, rate: torch.Tensor, dispersion: torch.Tensor, eps: float = 1e-8) -> torch.Tensor:
@@ -591,141 +458,14 @@ def interval_metrics(y: torch.Tensor, rate: torch.Tensor, dispersion: torch.Tens
     Q = nb_quantiles(rate, dispersion, lv, eps)
     F = nb_cdf(y, rate, dispersion, eps)
     valid = negative_binomial_mask(y, rate, dispersion, mask) & torch.isfinite(F) & torch.isfinite(Q).all(0)
-    w = valid.to(torch.float32)
-    den = w.sum().clamp(min=1.0)
-    zero = torch.zeros((), dtype=torch.float32, device=y.device)
-    yv = torch.where(valid, y.to(torch.float32), zero)
-    Qv = torch.where(valid, Q, zero)
-    diff = yv - Qv                                              # the levels stay Python scalars: no host-to-device copy
-    pin = torch.stack([torch.maximum(q * diff[i], (q - 1.0) * diff[i]) for i, q in enumerate(lv)]) * w
-    return {"coverage": ((yv <= Qv).to(torch.float32) * w).sum((1, 2, 3)) / den,
-            "pinball": pin.sum((1, 2, 3)) / den,
-            "pit_mean": (torch.where(valid, F, zero)).sum() / den,
+    coverage, pinball, den = _calibration(valid, y.to(torch.float32), Q, lv)
+    return {"coverage": coverage, "pinball": pinball, "pit_mean": torch.where(valid, F, F.new_zeros(())).sum() / den,
             "count": valid.sum()}
 
 
 # --------------------------------------------------------------------------------------------------------- sampling
-# Draw s of element e is the smallest integer k >= 0 with F(k) >= u(e, s): one uniform per draw, so a draw is a pure
-# function of (seed, offset, e, s) - the same on any device, grid, kernel form and backend.  The uniforms:
-#   Philox4x32-10, key = (seed & 0xffffffff, seed >> 32), counter = (e & 0xffffffff, e >> 32, s >> 2, offset),
-#   e the row-major index of the element in ``shape``; draw s takes output word s & 3; u = (word + 0.5) 2^-32 (fp64).
-# ``hip``: k_nb_sample (csrc/sample.hip).  ``torch``: the same Philox in int64 ops and the quantile search above at a
-# level per element, started as the kernel starts it (from pmf(0) = p^r where the first guess is near 0).
-_M32 = 0xFFFFFFFF
-_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
-_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
-
-
-def _mulhilo32(m: int, c: torch.Tensor):
-    """``(high, low)`` 32-bit words of ``m * c`` for a 32-bit constant m and int64 c in [0, 2^32): by 16-bit halves of
-    c, so nothing leaves int64."""
-    a, b = m * (c & 0xFFFF), m * (c >> 16)                      # each below 2^48
-    return (b + (a >> 16)) >> 16, (a + ((b & 0xFFFF) << 16)) & _M32
-
-
-def philox4x32(counter, key):
-    """Philox4x32-10 (Salmon et al., SC 2011) in int64 torch ops: ``counter`` four and ``key`` two 32-bit words, each
-    an int or an int64 tensor (broadcast together); returns the four output words as int64 tensors in [0, 2^32)."""
-    c = [w if isinstance(w, torch.Tensor) else torch.tensor(int(w) & _M32, dtype=torch.int64) for w in counter]
-    dev = next((w.device for w in list(counter) + list(key) if isinstance(w, torch.Tensor)), torch.device("cpu"))
-    c0, c1, c2, c3 = (w.to(device=dev, dtype=torch.int64) for w in c)
-    k0, k1 = (w.to(device=dev, dtype=torch.int64) if isinstance(w, torch.Tensor) else int(w) & _M32 for w in key)
-    for _ in range(10):
-        h0, l0 = _mulhilo32(_PHILOX_M[0], c0)
-        h1, l1 = _mulhilo32(_PHILOX_M[1], c2)
-        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
-        k0, k1 = (k0 + _PHILOX_W[0]) & _M32, (k1 + _PHILOX_W[1]) & _M32
-    return c0, c1, c2, c3
-
-
-def _seed_key(seed, device):
-    """The key words of ``seed``: a Python int (its low 64 bits) or a one-element int64 / uint64 tensor."""
-    if isinstance(seed, torch.Tensor):
-        if seed.numel() != 1 or seed.dtype not in (torch.int64, torch.uint64):
-            raise ValueError("seed must be a Python int or a one-element int64 / uint64 tensor")
-        w = seed.reshape(1).view(torch.int64).to(device)
-        return w & _M32, (w >> 32) & _M32
-    s = int(seed) & 0xFFFFFFFFFFFFFFFF
-    return s & _M32, s >> 32
-
-
-def sample_uniforms(n_samples: int, shape, seed=0, offset: int = 0, device=None) -> torch.Tensor:
-    """The uniforms of ``nb_sample`` for elements of ``shape`` (row-major index e): fp64 ``[n_samples, *shape]``,
-    ``u[s, e] = (word + 0.5) 2^-32`` with ``word`` output ``s & 3`` of Philox4x32-10 at counter
-    ``(e & 0xffffffff, e >> 32, s >> 2, offset)`` and key ``(seed & 0xffffffff, seed >> 32)``.  Strictly inside
-    (0, 1); draws ``s < S1`` of a longer call are those of the ``S1`` call."""
-    S = int(n_samples)
-    if S < 1:
-        raise ValueError(f"sample_uniforms: n_samples={n_samples}")
-    if not 0 <= int(offset) <= _M32:
-        raise ValueError(f"sample_uniforms: offset={offset} is not a 32-bit word")
-    shape = tuple(int(v) for v in shape)
-    dev = torch.device(device) if device is not None else (seed.device if isinstance(seed, torch.Tensor)
-                                                           else torch.device("cpu"))
-    n = 1
-    for v in shape:
-        n *= v
-    e = torch.arange(n, dtype=torch.int64, device=dev)
-    key = _seed_key(seed, dev)
-    words = []
-    for blk in range((S + 3) // 4):
-        words.extend(philox4x32((e & _M32, e >> 32, blk, int(offset)), key))
-    w = torch.stack([t.expand(n) for t in words[:S]])
-    return ((w.to(torch.float64) + 0.5) * 2.0 ** -32).reshape((S,) + shape)
-
-
-def _nb_invert_torch(q, rate, dispersion, eps):
-    """The smallest integer k >= 0 with F(k) >= q for a level per element: ``q`` fp64 ``[S, *rate.shape]`` strictly
-    inside (0, 1).  The search of ``_nb_quantiles_torch`` with the kernel's start (k_nb_sample): from the known point
-    (0, p^r, p^r) where p^r has not underflowed and the Cornish-Fisher guess is within the walk of 0, else from the
-    guess.  Evaluations are made for the elements that still search only.  ``(out fp32, flag)``."""
-    shape = tuple(q.shape)
-    par = _nbq_params(rate, dispersion, eps)
-    r, t, p, omp, lp, lomp, valid = (v.expand(shape).reshape(-1) for v in par)
-    q = q.reshape(-1)
-    g = _nbq_guess(torch.special.ndtri(q), r, t, omp, p)
-    pm0 = torch.exp(r * lp)
-    k = torch.zeros_like(r)
-    F, pm = pm0.clone(), pm0.clone()
-    lo, hi = torch.zeros_like(r), torch.full_like(r, NBQ_KLIM)
-    need = ~((pm0 > 0.0) & (g <= float(_NBQ_WALK)))
-    k = torch.where(need, g, k)
-    done = ~valid
-    for it in range(_NBQ_EVALS):
-        i = (need & ~done).nonzero().squeeze(1)
-        if i.numel():
-            Fe, pe, ok = _nb_cdf_pmf(k[i], r[i], p[i], omp[i], lp[i], lomp[i])
-            F[i], pm[i] = Fe, pe
-            done[i[~ok]] = True                                 # the fraction's cap: lo < hi stays, so NaN below
-        for _ in range(_NBQ_WALK):
-            act = ~done
-            down = act & (F >= q) & (k > lo) & (F - pm >= q)
-            up = act & (F < q) & (k + 1.0 < NBQ_KLIM)
-            if not bool((down | up).any()):
-                break
-            Fd, pd = F - pm, pm * k / ((k - 1.0 + r) * omp)
-            pu = pm * (k + r) / (k + 1.0) * omp
-            F = torch.where(down, Fd, torch.where(up, F + pu, F))
-            pm = torch.where(down, pd, torch.where(up, pu, pm))
-            lo = torch.where(up, k + 1.0, lo)
-            k = torch.where(down, k - 1.0, torch.where(up, k + 1.0, k))
-        ge = F >= q
-        hi = torch.where(~done & ge, torch.minimum(hi, k), hi)
-        lo = torch.where(~done & ~ge, k + 1.0, lo)
-        found = ~done & ge & ((k <= lo) | (F - pm < q))
-        lo = torch.where(found, k, lo)
-        hi = torch.where(found, k, hi)
-        done = done | found | (lo >= hi)
-        kn = torch.floor(k + (q - F) / pm + 0.5)
-        newton = (it < _NBQ_NEWTON) & (kn >= lo) & (kn < hi)
-        kn = torch.where(newton, kn, torch.floor(0.5 * (lo + hi)))
-        need = ~done
-        k = torch.where(need, kn.clamp(max=NBQ_KLIM - 1.0), k)
-        if bool(done.all()):
-            break
-    ans_ok = valid & (lo >= hi) & (hi < NBQ_KLIM)
-    out = torch.where(ans_ok, hi, torch.full_like(hi, float("nan"))).to(torch.float32).reshape(shape)
-    return out, (valid & ~ans_ok).any().to(torch.int32) * NBQ_FLAG_RANGE
+# ``hip``: k_nb_sample (csrc/sample.hip).  ``torch``: the same Philox in int64 ops and the same search at a level per
+# element, started as the kernel starts it (nbdist.py).
 
 
 def nb_sample(rate: torch.Tensor, dispersion: torch.Tensor, n_samples: int = 1, seed=0, offset: int = 0,
@@ -743,17 +483,13 @@ def nb_sample(rate: torch.Tensor, dispersion: torch.Tensor, n_samples: int = 1, 
     S = int(n_samples)
     if S < 1:
         raise ValueError(f"nb_sample: n_samples={n_samples}")
-    if backend not in (None, "hip", "torch"):
-        raise ValueError(f"nb_sample: backend {backend!r} is not 'hip', 'torch' or None")
     if not 0 <= int(offset) <= _M32:
         raise ValueError(f"nb_sample: offset={offset} is not a 32-bit word")
     if tuple(rate.shape) != tuple(dispersion.shape) or rate.dim() != 3:
         raise ValueError(f"nb_sample takes rate and dispersion of one shape [B, H, N], got {tuple(rate.shape)} "
                          f"{tuple(dispersion.shape)}")
-    eligible = _hip_eligible(rate, dispersion)
-    if backend == "hip" and not eligible:
-        raise ValueError("nb_sample: backend 'hip' takes fp32 [B, H, N] tensors on one ROCm device, without autograd")
-    if eligible and backend != "torch":
+    if _use_hip("nb_sample", backend, _hip_eligible(rate, dispersion),
+                "fp32 [B, H, N] tensors on one ROCm device, without autograd"):
         from . import runtime as rt
 
         out, _, u = rt.nb_sample(_rows(rate), _rows(dispersion), S, seed, offset, eps, flag=flag,
@@ -801,14 +537,6 @@ def path_quantiles(samples: torch.Tensor, levels, window: Optional[int] = None) 
 PATHS_MAX = 1024             # paths of one ftn_path_summary call (FTN_PATHS_MAX)
 
 
-def _path_levels(levels, who: str) -> List[float]:
-    lv = [float(q) for q in levels]
-    for q in lv:
-        if not 0.0 < q < 1.0:
-            raise ValueError(f"{who}: level {q} is not strictly inside (0, 1)")
-    return lv
-
-
 def _path_window(x: torch.Tensor, w: int, reduce: str) -> torch.Tensor:
     """``x`` [..., H, N] fp32 -> [..., H / w, N] fp32: window sums in fp64 rounded once, or window maxima."""
     H, N = x.shape[-2], x.shape[-1]
@@ -836,15 +564,6 @@ def _path_summary_torch(samples, ranks, w, reduce, y, want_sorted):
     return out
 
 
-def _path_rows(t: torch.Tensor) -> torch.Tensor:
-    """``t`` [P,B,H,N] as the kernel takes it: rows contiguous and N apart, batch and path strides of its own."""
-    P, B, H, N = t.shape
-    s = t.stride()
-    ok = ((N == 1 or s[3] == 1) and (H == 1 or s[2] == N) and (B == 1 or s[1] >= H * N)
-          and (P == 1 or s[0] >= (B - 1) * (s[1] if B > 1 else 0) + H * N))
-    return t if ok else t.contiguous()
-
-
 def path_summary(samples: torch.Tensor, levels=(), y: torch.Tensor | None = None, window: Optional[int] = None,
                  reduce: str = "sum", want_sorted: bool = False, backend: Optional[str] = None
                  ) -> Dict[str, torch.Tensor]:
@@ -861,9 +580,7 @@ def path_summary(samples: torch.Tensor, levels=(), y: torch.Tensor | None = None
     import math
 
     global _last_backend
-    lv = _path_levels(levels, "path_summary")
-    if backend not in (None, "hip", "torch"):
-        raise ValueError(f"path_summary: backend {backend!r} is not 'hip', 'torch' or None")
+    lv = _check_levels(levels, "path_summary", allow_empty=True)
     if reduce not in ("sum", "max"):
         raise ValueError(f"path_summary: reduce {reduce!r} is not 'sum' or 'max'")
     if not isinstance(samples, torch.Tensor) or samples.dim() != 4 or samples.numel() == 0:
@@ -879,16 +596,14 @@ def path_summary(samples: torch.Tensor, levels=(), y: torch.Tensor | None = None
     ranks = [min(max(math.ceil(q * P), 1), P) for q in lv]
     eligible = (samples.is_cuda and samples.dtype == torch.float32 and P <= PATHS_MAX
                 and not (torch.is_grad_enabled() and (samples.requires_grad or (y is not None and y.requires_grad))))
-    if backend == "hip" and not eligible:
-        raise ValueError(f"path_summary: backend 'hip' takes fp32 [P, B, H, N] samples on a ROCm device, without "
-                         f"autograd, P <= {PATHS_MAX}")
-    if eligible and backend != "torch":
+    if _use_hip("path_summary", backend, eligible,
+                f"fp32 [P, B, H, N] samples on a ROCm device, without autograd, P <= {PATHS_MAX}"):
         from . import runtime as rt
 
         yk = None
         if y is not None:
             yk = _rows(y.detach().to(device=samples.device, dtype=torch.float32))
-        res = rt.path_summary(_path_rows(samples.detach()), ranks, w, reduce, y=yk, want_mean=True,
+        res = rt.path_summary(_rows(samples.detach()), ranks, w, reduce, y=yk, want_mean=True,
                               want_sorted=want_sorted)
         if res["quantiles"] is None:
             res["quantiles"] = torch.empty((0, B, H // w, N), dtype=torch.float32, device=samples.device)
@@ -910,9 +625,7 @@ def path_metrics(samples: torch.Tensor, y: torch.Tensor, levels, window: Optiona
     ``max(q (yw - Q), (q - 1) (yw - Q))``; ``crps``, the mean sample CRPS; ``count``, the valid elements (int64).
     An element is valid where ``yw``, its quantiles and its CRPS are finite and, with ``mask`` [B,H,N], every step
     of its window is inside the mask."""
-    lv = _path_levels(levels, "path_metrics")
-    if not lv:
-        raise ValueError("path_metrics: no levels")
+    lv = _check_levels(levels, "path_metrics")
     s = path_summary(samples, lv, y, window, reduce)
     Q, crps = s["quantiles"], s["crps"]
     P, B, H, N = samples.shape
@@ -923,16 +636,8 @@ def path_metrics(samples: torch.Tensor, y: torch.Tensor, levels, window: Optiona
         if tuple(mask.shape) != (B, H, N):
             raise ValueError(f"path_metrics: mask must be [B, H, N] = {(B, H, N)}, got {tuple(mask.shape)}")
         valid = valid & mask.to(device=Q.device).to(torch.bool).reshape(B, H // w, w, N).all(2)
-    wgt = valid.to(torch.float32)
-    den = wgt.sum().clamp(min=1.0)
-    zero = torch.zeros((), dtype=torch.float32, device=Q.device)
-    yv = torch.where(valid, yw, zero)
-    Qv = torch.where(valid, Q, zero)
-    diff = yv - Qv
-    pin = torch.stack([torch.maximum(q * diff[i], (q - 1.0) * diff[i]) for i, q in enumerate(lv)]) * wgt
-    return {"coverage": ((yv <= Qv).to(torch.float32) * wgt).sum((1, 2, 3)) / den,
-            "pinball": pin.sum((1, 2, 3)) / den,
-            "crps": torch.where(valid, crps, zero).sum() / den,
+    coverage, pinball, den = _calibration(valid, yw, Q, lv)
+    return {"coverage": coverage, "pinball": pinball, "crps": torch.where(valid, crps, crps.new_zeros(())).sum() / den,
             "count": valid.sum()}
 
 
@@ -1099,8 +804,6 @@ def group_sums(x: torch.Tensor, groups: SeriesGroups, backend: Optional[str] = N
     passed as a view, anything else is copied), ``"torch"`` (the same additions in torch ops, any device, bit-equal;
     other dtypes are converted to fp32 first), or None: ``hip`` where it can run.  Never synchronises on ``hip``."""
     global _last_backend
-    if backend not in (None, "hip", "torch"):
-        raise ValueError(f"group_sums: backend {backend!r} is not 'hip', 'torch' or None")
     if not isinstance(groups, SeriesGroups):
         raise ValueError(f"group_sums: groups must be a SeriesGroups, got {type(groups)}")
     if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != groups.n_series or x.numel() == 0:
@@ -1109,12 +812,11 @@ def group_sums(x: torch.Tensor, groups: SeriesGroups, backend: Optional[str] = N
     eligible = (x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)
                 and groups.n_series <= GROUP_NMAX and groups.n_groups <= GROUP_GMAX
                 and groups.n_chunks <= GROUP_CHUNKS_MAX)
-    if backend == "hip" and not eligible:
-        raise ValueError(f"group_sums: backend 'hip' takes fp32 [..., N] on a ROCm device, without autograd, "
-                         f"N <= {GROUP_NMAX}, at most {GROUP_GMAX} groups and {GROUP_CHUNKS_MAX} chunks of "
-                         f"{GROUP_CHUNK} members")
+    use_hip = _use_hip("group_sums", backend, eligible,
+                       f"fp32 [..., N] on a ROCm device, without autograd, N <= {GROUP_NMAX}, at most {GROUP_GMAX} "
+                       f"groups and {GROUP_CHUNKS_MAX} chunks of {GROUP_CHUNK} members")
     groups = groups.to(x.device)
-    if eligible and backend != "torch":
+    if use_hip:
         from . import runtime as rt
 
         out = rt.group_sum(_group_rows(x.detach()), groups.order, groups.offsets, groups.offsets_host)

@@ -110,3 +110,39 @@ def test_interval_metrics_against_numpy(ftn):
         tol = n * 2.0 ** -23
         assert np.all(np.abs(got["pinball"].numpy() - pin) <= tol * np.maximum(pin, 1.0) + ties / n)
         assert abs(float(got["pit_mean"]) - pit) <= tol
+
+
+def _same_bits(got, want):
+    return got.dtype == want.dtype == np.float32 and got.shape == want.shape and \
+        np.array_equal(got.view(np.int32), want.view(np.int32))
+
+
+def test_one_search_reproduces_the_two_it_replaced(ftn):
+    """``nb_quantiles`` and ``nb_sample`` on the torch backend against tests/golden/nb_torch_parent.npz, the outputs of
+    the two search loops that ``nbdist._nb_search`` replaced (tests/golden/make_golden_nb_torch.py): every fp32 word,
+    NaN positions included, and the flags."""
+    import nbs_checks as ns
+
+    sc = ftn.score
+    with np.load(nq.GOLDEN / "nb_torch_parent.npz") as z:
+        pin = {k: z[k] for k in z.files}
+    edge = (torch.from_numpy(pin["edge_rate"]), torch.from_numpy(pin["edge_disp"]))
+    q_cases = [(n, *_t(nq.load(n), "rate", "disp"), list(nq.load(n)["levels"]))
+               for n in ("scalar", "pipeline", "large", "tiny")]
+    q_cases.append(("edge", *edge, [0.025, 0.5, 0.975]))
+    for name, rate, disp, levels in q_cases:
+        out = sc.nb_quantiles(rate, disp, levels)
+        assert sc._last_backend == "torch" and _same_bits(out.numpy(), pin[f"q_{name}"]), name
+        out2, flag = sc._nb_quantiles_torch(rate, disp, [float(q) for q in levels], 1e-8)
+        assert torch.equal(out2.view(torch.int32), out.view(torch.int32)), name
+        assert int(flag) == int(pin[f"qflag_{name}"]), name
+    s_cases = [(n, *_t(ns.load(n), "rate", "disp"), *(int(ns.load(n)[k]) for k in ("S", "seed", "offset")))
+               for n in ("std_scalar", "tiny", "large")]
+    s_cases.append(("edge", *edge, 5, 11, 2))
+    for name, rate, disp, S, seed, offset in s_cases:
+        flag = torch.zeros(1, dtype=torch.int32)
+        out = sc.nb_sample(rate, disp, S, seed, offset, backend="torch", flag=flag)
+        assert sc._last_backend == "torch" and _same_bits(out.numpy(), pin[f"s_{name}"]), name
+        assert int(flag) == int(pin[f"sflag_{name}"]), name
+    assert int(pin["qflag_edge"]) == int(pin["sflag_edge"]) == sc.NBQ_FLAG_RANGE       # the pin holds a raised flag too
+    assert np.isnan(pin["q_edge"]).any() and np.isnan(pin["s_edge"]).any()
