@@ -81,6 +81,17 @@ __device__ __forceinline__ f4 chain_bf(const bf8 (&ap)[PxFmt<NS>::NW], const bf8
   }
 }
 
+// the same chain on weight fragments held as dwords (stagec_pos.hip's prefetch path): the operand type exists only
+// at the MFMA, so no __bf16 vector crosses a basic-block boundary
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+template <int NS>
+__device__ __forceinline__ f4 chain_u(const u4 (&au)[PxFmt<NS>::NW], const bf8 (&bp)[NS], f4 c) {
+  bf8 ap[PxFmt<NS>::NW];
+#pragma unroll
+  for (int pz = 0; pz < PxFmt<NS>::NW; ++pz) ap[pz] = __builtin_bit_cast(bf8, au[pz]);
+  return chain_bf<NS>(ap, bp, c);
+}
+
 // eight fp32 values -> NS pieces of 8 (bf16: exact truncation split; fp16: hi + scaled remainder, ftn_common.h)
 template <int NS>
 __device__ __forceinline__ void split_pieces(const float (&v)[8], bf8 (&out)[NS]) {

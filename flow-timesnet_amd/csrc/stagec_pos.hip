@@ -197,27 +197,33 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
 #pragma unroll
         for (int pz = 0; pz < NWP; ++pz) ap[pz] = *(const bf8*)(wlb + wl_off + (size_t)(f * 3 + pz) * 1024);
       };
+      // the prefetch path carries its fragments as dwords: a bf8 that crosses the `if (i < gcnt)` block boundary is
+      // rebuilt half by half (v_lshrrev_b32 + v_perm_b32 per dword, 72 VALU per chunk that compute nothing)
+      auto ldfrag_u = [&](int f, u4 (&ap)[NWP]) {
+#pragma unroll
+        for (int pz = 0; pz < NWP; ++pz) ap[pz] = *(const u4*)(wlb + wl_off + (size_t)(f * 3 + pz) * 1024);
+      };
 #pragma unroll
       for (int t = 0; t < 2; ++t)                                 // (needed after the res1 products, which cover the load)
         bo_t[t] = (hc * 2 + t) * 16 < a.FP ? *(const f4*)(a.bo + 16 * (hc * 2 + t) + 4 * qa) : f4{0.f, 0.f, 0.f, 0.f};
       if constexpr (PF == 1) {
         if (gcnt > 0) {
           constexpr int NFG = 2 * SKM + NOA;                      // fragments one group walks: layer 1, then layer 2a
-          bf8 fr[2][NWP];
+          u4 fr[2][NWP];
           // res1(x) + b, once for all groups of the pass
           {
             bf8 xp[SCP][NS];
-            ldfrag(2 * SKM, fr[0]);
+            ldfrag_u(2 * SKM, fr[0]);
 #pragma unroll
             for (int s = 0; s < SCP; ++s)
 #pragma unroll
               for (int pz = 0; pz < NS; ++pz) xp[s][pz] = *(const bf8*)(xl + (size_t)(s * NS + pz) * 1024);
 #pragma unroll
             for (int k = 0; k < 2 * SCP; ++k) {
-              if (k + 1 < 2 * SCP) ldfrag(2 * SKM + k + 1, fr[(k + 1) & 1]);
-              else ldfrag(0, fr[(k + 1) & 1]);                    // the first group's first fragment
+              if (k + 1 < 2 * SCP) ldfrag_u(2 * SKM + k + 1, fr[(k + 1) & 1]);
+              else ldfrag_u(0, fr[(k + 1) & 1]);                    // the first group's first fragment
               __builtin_amdgcn_sched_barrier(0);
-              res1[k / SCP] = chain_bf<NS>(fr[k & 1], xp[k % SCP], res1[k / SCP]);
+              res1[k / SCP] = chain_u<NS>(fr[k & 1], xp[k % SCP], res1[k / SCP]);
             }
           }
           static_assert((2 * SCP) % 2 == 0, "group 0 starts on fragment buffer 0");
@@ -235,10 +241,10 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
                 const int cur = (i * NFG + k) & 1;
                 // the next fragment of this group, or - behind the last one - the first fragment of the next group (the
                 // same weights for every group; after the pass's last group the read is simply not used)
-                ldfrag(k + 1 < 2 * SKM ? k + 1 : (k + 1 < NFG ? NL1 + (k + 1 - 2 * SKM) : 0), fr[cur ^ 1]);
+                ldfrag_u(k + 1 < 2 * SKM ? k + 1 : (k + 1 < NFG ? NL1 + (k + 1 - 2 * SKM) : 0), fr[cur ^ 1]);
                 __builtin_amdgcn_sched_barrier(0);
-                if (k < 2 * SKM) h[k / SKM] = chain_bf<NS>(fr[cur], mp[i][k % SKM], h[k / SKM]);
-                else aacc[i][k - 2 * SKM] = chain_bf<NS>(fr[cur], hp, aacc[i][k - 2 * SKM]);
+                if (k < 2 * SKM) h[k / SKM] = chain_u<NS>(fr[cur], mp[i][k % SKM], h[k / SKM]);
+                else aacc[i][k - 2 * SKM] = chain_u<NS>(fr[cur], hp, aacc[i][k - 2 * SKM]);
                 if (k == 2 * SKM - 1) {
                   // g_g = act(act(W_out1 m_g + b) + res1(x))  (:652-654, then TimesBlock's mid activation :757)
 #pragma unroll
@@ -254,8 +260,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
             }
           }
           if (!tail_blk) {
-            bf8 sp[NS], f2[2][NWP];
-            ldfrag(NL1 + NOA, f2[0]);
+            bf8 sp[NS];
+            u4 f2[2][NWP];
+            ldfrag_u(NL1 + NOA, f2[0]);
             const float sv[8] = {sacc[0][0], sacc[0][1], sacc[0][2], sacc[0][3], sacc[1][0], sacc[1][1], sacc[1][2], sacc[1][3]};
             split_pieces<NS>(sv, sp);
             // all NOR accumulator tiles come back from the slab in ONE round trip (the groups' h / hp / fragment
@@ -265,9 +272,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_mlp_pos(MlpPosArgs pa) {
             for (int o = 0; o < NOR; ++o) rr[o] = *(const f4*)(rl + o * 1024);
 #pragma unroll
             for (int o = 0; o < NOR; ++o) {
-              if (o + 1 < NOR) ldfrag(NL1 + NOA + o + 1, f2[(o + 1) & 1]);
+              if (o + 1 < NOR) ldfrag_u(NL1 + NOA + o + 1, f2[(o + 1) & 1]);
               __builtin_amdgcn_sched_barrier(0);
-              rr[o] = chain_bf<NS>(f2[o & 1], sp, rr[o]);
+              rr[o] = chain_u<NS>(f2[o & 1], sp, rr[o]);
             }
 #pragma unroll
             for (int o = 0; o < NOR; ++o) *(f4*)(rl + o * 1024) = rr[o];
