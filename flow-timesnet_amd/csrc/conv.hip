@@ -2,10 +2,81 @@
 // (k_conv) and on the split 16-bit engines (k_conv_bf, k_conv_bf_fast), with their launch geometry.
 #include <stdlib.h>
 #include "ftn_conv.h"
+#include "ftn_conv_split.h"
 #include "ftn_mlp.h"
 
 static const bool g_conv_generic = [] { const char* e = getenv("FTN_CONV_GENERIC"); return e != nullptr && e[0] == '1'; }();  // experiment switch
-static const bool g_conv_quant = [] { const char* e = getenv("FTN_CONV_QUANT"); return e == nullptr || e[0] != '0'; }();
+
+// ---------------------------------------------------------------- tile and pixel bookkeeping of the three kernels
+// One conv tile of the per-row tile list: its period group, the group's grid, the tile inside it and the staged
+// region = tile + halo, clipped to the grid.
+struct ConvTile {
+  int g;                                 // period group
+  int p, cycles, P;                      // grid: columns (the period), rows, pixels
+  int r0, c0, th, tw, npx, nunits;       // tile: origin, size, pixels, 16-pixel units
+  int R0, C0, RW, RH;                    // staged region: origin, width, height
+  // staged-region pixel sp (row-major) -> grid pixel = window position t (fold, :1041-1046); sp / RW by reciprocal
+  __device__ __forceinline__ int grid_px(int sp, float inv_rw) const {
+    const int rr = (int)(((float)sp + 0.5f) * inv_rw), cx = sp - rr * RW;
+    return (R0 + rr) * p + C0 + cx;
+  }
+};
+
+// tile bx of the descriptor's tile list for a kernel with halo (hy, hx).  G = d->n_groups, which the split-engine
+// kernels read once in front of their tile loops (inside, behind the output stores, it is a vector load per tile)
+__device__ __forceinline__ ConvTile conv_tile(const FtnDesc* __restrict__ d, int G, int bx, int hy, int hx) {
+  ConvTile t;
+  t.g = 0;
+  for (int gg = 1; gg < G; ++gg)
+    if (bx >= d->g_tile_off[gg]) t.g = gg;
+  const int tix = bx - d->g_tile_off[t.g];
+  const int ntx = d->g_ntx[t.g];
+  const int ty = tix / ntx, tx = tix - ty * ntx;
+  t.p = d->g_period[t.g]; t.cycles = d->g_cycles[t.g];
+  t.P = d->g_px_off[t.g + 1] - d->g_px_off[t.g];
+  t.r0 = ty * d->g_th[t.g]; t.c0 = tx * d->g_tw[t.g];
+  t.th = min(d->g_th[t.g], t.cycles - t.r0); t.tw = min(d->g_tw[t.g], t.p - t.c0);
+  t.npx = t.th * t.tw; t.nunits = (t.npx + 15) >> 4;
+  const int R1 = min(t.cycles, t.r0 + t.th + hy), C1 = min(t.p, t.c0 + t.tw + hx);
+  t.R0 = max(0, t.r0 - hy); t.C0 = max(0, t.c0 - hx);
+  t.RW = C1 - t.C0; t.RH = R1 - t.R0;
+  return t;
+}
+
+// grid pixel tpx of an input with one row per window position (bt_L > 0, ConvArgs.bt_L) is the shared pad row
+__device__ __forceinline__ bool conv_pad_row(int bt_L, int tpx) { return bt_L > 0 && tpx >= bt_L; }
+
+// Pixel idx of a tile (row-major; a lane's idx may lie past the tile: ok = false, it then stands on pixel 0 with
+// empty masks): grid position (ri, ci) and the kernel taps that fall inside the grid, as a row and a column mask.
+struct ConvPixel { int ri, ci; bool ok; unsigned rm, cm; };
+
+__device__ __forceinline__ ConvPixel conv_pixel(const ConvTile& t, int idx, float inv_tw, int kh, int kw) {
+  ConvPixel px;
+  px.ok = idx < t.npx;
+  if (!px.ok) idx = 0;
+  // idx / tw by reciprocal: exact for idx < 2^20 because (idx + 0.5) / tw is never an integer
+  const int r = (int)(((float)idx + 0.5f) * inv_tw), c = idx - r * t.tw;
+  px.ri = t.r0 + r; px.ci = t.c0 + c;
+  const int hy = kh >> 1, hx = kw >> 1;
+  const unsigned kmh = (1u << kh) - 1u, kmw = (1u << kw) - 1u;
+  // taps dy with 0 <= ri + dy - hy < cycles are the bits [lo, hi) of the row mask (same for columns)
+  const int rlo = max(0, hy - px.ri), rhi = min(kh, t.cycles + hy - px.ri);
+  const int clo = max(0, hx - px.ci), chi = min(kw, t.p + hx - px.ci);
+  const unsigned rm = (rhi > rlo) ? ((kmh >> (kh - rhi)) & (kmh << rlo)) & kmh : 0u;
+  const unsigned cm = (chi > clo) ? ((kmw >> (kw - chi)) & (kmw << clo)) & kmw : 0u;
+  px.rm = px.ok ? rm : 0u;
+  px.cm = px.ok ? cm : 0u;
+  return px;
+}
+
+// zero blocks of every plane of both region buffers of the split engines (never overwritten by the DMA)
+template <int NS>
+__device__ __forceinline__ void zero_blocks(char* __restrict__ rbuf0, int region_bytes, int plane, int zbase) {
+  if (threadIdx.x < 2 * NS * 16) {
+    const int pl = threadIdx.x >> 4;                             // (buffer, piece) plane index
+    *(f4*)(rbuf0 + (size_t)(pl / NS) * region_bytes + (size_t)(pl % NS) * plane + zbase + (threadIdx.x & 15) * 16) = f4{0.f, 0.f, 0.f, 0.f};
+  }
+}
 
 // ---------------------------------------------------------------- stages B / D
 // Grouped k x k convolution as an im2col GEMM.  One workgroup = one conv tile
@@ -78,7 +149,7 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
   const FtnDesc* __restrict__ d = a.desc;
   const size_t wgid = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
   stamp(a.dbg, a.dbg_cap, wgid, 0);
-  if (a.dbg != nullptr && threadIdx.x == 0 && wgid * 8 + 7 < a.dbg_cap) a.dbg[wgid * 8 + 6] = __builtin_amdgcn_s_memrealtime();
+  stamp_realtime(a.dbg, a.dbg_cap, wgid, 6);
   // grid.x = max_groups (one tile per group is the common case); a workgroup walks the
   // data-dependent tile list with that stride, so no workgroup is dispatched empty unless
   // groups merged (interleaved empty workgroups skew the round-robin XCD placement)
@@ -88,58 +159,33 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
   const int b = blockIdx.y;
   const int zb = blockIdx.z / a.nchunk, chunk = blockIdx.z - zb * a.nchunk;
   const int br = a.order[zb];
-  const int G = d->n_groups;
-  int g = 0;
-  for (int gg = 1; gg < G; ++gg)
-    if (bx >= d->g_tile_off[gg]) g = gg;
-  const int tix = bx - d->g_tile_off[g];
-  const int ntx = d->g_ntx[g];
-  const int ty = tix / ntx, tx = tix - ty * ntx;
-  const int p = d->g_period[g], cycles = d->g_cycles[g];
-  const int P = d->g_px_off[g + 1] - d->g_px_off[g];
-  const int r0 = ty * d->g_th[g], c0 = tx * d->g_tw[g];
-  const int th = min(d->g_th[g], cycles - r0), tw = min(d->g_tw[g], p - c0);
-  const int kh = a.kh[br], kw = a.kw[br], hy = kh >> 1, hx = kw >> 1;
-  // staged region = tile + halo, clipped to the grid
-  const int R0 = max(0, r0 - hy), R1 = min(cycles, r0 + th + hy);
-  const int C0 = max(0, c0 - hx), C1 = min(p, c0 + tw + hx);
-  const int RW = C1 - C0, RH = R1 - R0;
+  const int kh = a.kh[br], kw = a.kw[br];
+  const ConvTile t = conv_tile(d, d->n_groups, bx, kh >> 1, kw >> 1);
   float* __restrict__ tile = lds;
   float* __restrict__ wl = lds + a.region_floats;
   const int zoff = a.region_floats - 16;                 // 16 zero floats at the end of the region area
-  const size_t nimg = (size_t)a.B * d->g_px_off[g] + (size_t)b * P;
+  const size_t nimg = (size_t)a.B * d->g_px_off[t.g] + (size_t)b * t.P;
   const int btL = a.bt_L;
   const float* __restrict__ in = a.in + (btL > 0 ? (size_t)b * btL : nimg) * a.INC + br * a.in_stride_br;
   const float* __restrict__ in_pad = a.in + (size_t)a.B * btL * a.INC + br * a.in_stride_br;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
-  const int npx = th * tw, nunits = (npx + 15) >> 4;
   const int wrot = (wave + b) & 3;                                 // rotate so co-resident workgroups balance the SIMDs
-  const int nu = nunits > wrot ? (nunits - wrot + 3) >> 2 : 0;   // units of this wave: wrot, wrot+4, ...
+  const int nu = t.nunits > wrot ? (t.nunits - wrot + 3) >> 2 : 0;   // units of this wave: wrot, wrot+4, ...
   const int nco_tot = a.cout >> 4, co0 = chunk * NCO;
   const int ncc = a.cin >> 4, ntaps = kh * kw;
 
   int lbase[CONV_NU], oidx[CONV_NU];
   unsigned rmask[CONV_NU], cmask[CONV_NU];
   bool pok[CONV_NU];
-  // idx / tw by reciprocal: exact for idx < 2^20 because (idx + 0.5) / tw is never an integer
-  const float inv_tw = 1.0f / (float)tw;
-  const unsigned kmh = (1u << kh) - 1u, kmw = (1u << kw) - 1u;
+  const float inv_tw = 1.0f / (float)t.tw;
 #pragma unroll
   for (int u = 0; u < CONV_NU; ++u) {
-    int idx = (wrot + 4 * u) * 16 + j;
-    pok[u] = idx < npx;
-    if (!pok[u]) idx = 0;
-    const int r = (int)(((float)idx + 0.5f) * inv_tw), c = idx - r * tw;
-    const int ri = r0 + r, ci = c0 + c;
-    lbase[u] = ((ri - R0) * RW + (ci - C0)) * LDS_PX_STRIDE + 4 * q;
-    oidx[u] = ri * p + ci;
-    // taps dy with 0 <= ri + dy - hy < cycles are the bits [lo, hi) of the row mask (same for columns)
-    const int rlo = max(0, hy - ri), rhi = min(kh, cycles + hy - ri);
-    const int clo = max(0, hx - ci), chi = min(kw, p + hx - ci);
-    const unsigned rm = (rhi > rlo) ? ((kmh >> (kh - rhi)) & (kmh << rlo)) & kmh : 0u;
-    const unsigned cm = (chi > clo) ? ((kmw >> (kw - chi)) & (kmw << clo)) & kmw : 0u;
-    rmask[u] = pok[u] ? rm : 0u;
-    cmask[u] = pok[u] ? cm : 0u;
+    const ConvPixel px = conv_pixel(t, (wrot + 4 * u) * 16 + j, inv_tw, kh, kw);
+    pok[u] = px.ok;
+    lbase[u] = ((px.ri - t.R0) * t.RW + (px.ci - t.C0)) * LDS_PX_STRIDE + 4 * q;
+    oidx[u] = px.ri * t.p + px.ci;
+    rmask[u] = px.rm;
+    cmask[u] = px.cm;
   }
   f4 acc[NCO][CONV_NU];
 #pragma unroll
@@ -151,8 +197,8 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
   }
   if (threadIdx.x < 4) *(f4*)(tile + zoff + 4 * threadIdx.x) = f4{0.f, 0.f, 0.f, 0.f};
   const float* __restrict__ Wb = a.W[br];
-  const int nstage = RH * RW * 4;
-  const float inv_rw = 1.0f / (float)RW;
+  const int nstage = t.RH * t.RW * 4;                    // four 16-byte quarters per region pixel
+  const float inv_rw = 1.0f / (float)t.RW;
   for (int cc = 0; cc < ncc; ++cc) {
     if (cc > 0) __syncthreads();
     // weight fragments: LDS-DMA (global_load_lds_dwordx4), one 1-KiB fragment per wave
@@ -177,10 +223,9 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         const int s = s0 + 256 * k;
-        const int sp = s >> 2, qq = s & 3;
-        const int rr = (int)(((float)sp + 0.5f) * inv_rw), cx = sp - rr * RW;
-        const int tpx = (R0 + rr) * p + C0 + cx;               // grid pixel = window position t (fold, :1041-1046)
-        const float* __restrict__ row = (btL > 0 && tpx >= btL) ? in_pad : in + (size_t)tpx * a.INC;
+        const int qq = s & 3;
+        const int tpx = t.grid_px(s >> 2, inv_rw);
+        const float* __restrict__ row = conv_pad_row(btL, tpx) ? in_pad : in + (size_t)tpx * a.INC;
         v[k] = s < nstage ? *(const f4*)(row + 16 * cc + 4 * qq) : f4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
@@ -192,20 +237,18 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
     __syncthreads();
     if (cc == 0) stamp(a.dbg, a.dbg_cap, wgid, 1);
     switch (nu) {
-      case 6: conv_taps<NCO, 6>(acc, tile, wl, lbase, rmask, cmask, kh, kw, RW, zoff, lane); break;
-      case 5: conv_taps<NCO, 5>(acc, tile, wl, lbase, rmask, cmask, kh, kw, RW, zoff, lane); break;
-      case 4: conv_taps<NCO, 4>(acc, tile, wl, lbase, rmask, cmask, kh, kw, RW, zoff, lane); break;
-      case 3: conv_taps<NCO, 3>(acc, tile, wl, lbase, rmask, cmask, kh, kw, RW, zoff, lane); break;
-      case 2: conv_taps<NCO, 2>(acc, tile, wl, lbase, rmask, cmask, kh, kw, RW, zoff, lane); break;
-      case 1: conv_taps<NCO, 1>(acc, tile, wl, lbase, rmask, cmask, kh, kw, RW, zoff, lane); break;
+      case 6: conv_taps<NCO, 6>(acc, tile, wl, lbase, rmask, cmask, kh, kw, t.RW, zoff, lane); break;
+      case 5: conv_taps<NCO, 5>(acc, tile, wl, lbase, rmask, cmask, kh, kw, t.RW, zoff, lane); break;
+      case 4: conv_taps<NCO, 4>(acc, tile, wl, lbase, rmask, cmask, kh, kw, t.RW, zoff, lane); break;
+      case 3: conv_taps<NCO, 3>(acc, tile, wl, lbase, rmask, cmask, kh, kw, t.RW, zoff, lane); break;
+      case 2: conv_taps<NCO, 2>(acc, tile, wl, lbase, rmask, cmask, kh, kw, t.RW, zoff, lane); break;
+      case 1: conv_taps<NCO, 1>(acc, tile, wl, lbase, rmask, cmask, kh, kw, t.RW, zoff, lane); break;
       default: break;
     }
   }
   stamp(a.dbg, a.dbg_cap, wgid, 2);
-  if (a.dbg != nullptr && threadIdx.x == 0 && wgid * 8 + 7 < a.dbg_cap) {
-    a.dbg[wgid * 8 + 4] = (unsigned long long)(kh * kw);
-    a.dbg[wgid * 8 + 5] = __builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20);  // XCC_ID
-  }
+  stamp_word(a.dbg, a.dbg_cap, wgid, 4, (unsigned long long)(kh * kw));
+  stamp_word(a.dbg, a.dbg_cap, wgid, 5, __builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20));  // XCC_ID
   float* __restrict__ out = a.out + nimg * a.OUTC + br * a.out_stride_br;
 #pragma unroll
   for (int o = 0; o < NCO; ++o) {
@@ -216,7 +259,7 @@ __global__ __launch_bounds__(256) void k_conv(ConvArgs a) {
     }
   }
   stamp(a.dbg, a.dbg_cap, wgid, 3);
-  if (a.dbg != nullptr && threadIdx.x == 0 && wgid * 8 + 7 < a.dbg_cap) a.dbg[wgid * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+  stamp_realtime(a.dbg, a.dbg_cap, wgid, 7);
   }  // tile loop
 }
 
@@ -260,34 +303,18 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
   const int zbase = plane - 256;                             // 256-byte zero block at the end of every plane (256-aligned)
   const int b_begin = blockIdx.y * a.bpw, b_end = min(a.B, b_begin + a.bpw);
   const int G = d->n_groups, tiles_total = d->tiles_per_row;
-  // zero blocks of every plane of both region buffers (never overwritten by the DMA)
-  if (threadIdx.x < 2 * NS * 16) {
-    const int pl = threadIdx.x >> 4;                           // (buffer, piece) plane index
-    *(f4*)(rbuf0 + (size_t)(pl / NS) * a.region_bytes + (size_t)(pl % NS) * plane + zbase + (threadIdx.x & 15) * 16) = f4{0.f, 0.f, 0.f, 0.f};
-  }
+  zero_blocks<NS>(rbuf0, a.region_bytes, plane, zbase);
   const size_t wgid = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
   stamp(a.dbg, a.dbg_cap, wgid, 0);
-  if (a.dbg != nullptr && threadIdx.x == 0 && wgid * 8 + 7 < a.dbg_cap) { a.dbg[wgid * 8 + 6] = __builtin_amdgcn_s_memrealtime(); a.dbg[wgid * 8 + 4] = (unsigned long long)ntaps; a.dbg[wgid * 8 + 5] = 0; }
+  stamp_realtime(a.dbg, a.dbg_cap, wgid, 6);
+  stamp_word(a.dbg, a.dbg_cap, wgid, 4, (unsigned long long)ntaps);
+  stamp_word(a.dbg, a.dbg_cap, wgid, 5, 0);
 
   for (int bx = blockIdx.x; bx < tiles_total; bx += gridDim.x) {
-    int g = 0;
-    for (int gg = 1; gg < G; ++gg)
-      if (bx >= d->g_tile_off[gg]) g = gg;
-    const int tix = bx - d->g_tile_off[g];
-    const int ntx = d->g_ntx[g];
-    const int ty = tix / ntx, tx = tix - ty * ntx;
-    const int p = d->g_period[g], cycles = d->g_cycles[g];
-    const int P = d->g_px_off[g + 1] - d->g_px_off[g];
-    const int r0 = ty * d->g_th[g], c0 = tx * d->g_tw[g];
-    const int th = min(d->g_th[g], cycles - r0), tw = min(d->g_tw[g], p - c0);
-    const int R0 = max(0, r0 - hy), R1 = min(cycles, r0 + th + hy);
-    const int C0 = max(0, c0 - hx), C1 = min(p, c0 + tw + hx);
-    const int RW = C1 - C0, RH = R1 - R0;
-    const int npx = th * tw, nunits = (npx + 15) >> 4;
+    const ConvTile t = conv_tile(d, G, bx, hy, hx);
     const int in_groups = a.INC >> 4;
-    const float inv_tw = 1.0f / (float)tw, inv_rw = 1.0f / (float)RW;
-    const unsigned kmh = (1u << kh) - 1u, kmw = (1u << kw) - 1u;
-    const int nchunks16 = RH * RW * 2;                     // 16-byte chunks of one plane (two per pixel)
+    const float inv_tw = 1.0f / (float)t.tw, inv_rw = 1.0f / (float)t.RW;
+    const int nchunks16 = t.RH * t.RW * 2;                 // 16-byte chunks of one plane (two per pixel)
     const int ppp = (nchunks16 + 63) >> 6;                 // 1-KiB DMA instructions per plane
 
     // region of batch row b, channel group cc -> buffer `buf`: every lane fetches the 16 bytes (pixel, piece,
@@ -295,17 +322,16 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
     // plane split all happen in the DMA's source addresses
     const int btL = a.bt_L;
     auto dma_region = [&](int b, int cc, int buf) {
-      const __bf16* __restrict__ src = a.in + (btL > 0 ? (size_t)b * btL : (size_t)a.B * d->g_px_off[g] + (size_t)b * P) * in_groups * PXE +
+      const __bf16* __restrict__ src = a.in + (btL > 0 ? (size_t)b * btL : (size_t)a.B * d->g_px_off[t.g] + (size_t)b * t.P) * in_groups * PXE +
                                        (size_t)(br * a.in_stride_br + cc) * PXE;
       const __bf16* __restrict__ src_pad = a.in + (size_t)a.B * btL * in_groups * PXE + (size_t)(br * a.in_stride_br + cc) * PXE;
       for (int pc = wv; pc < NS * ppp; pc += 8) {
         const int pz = pc / ppp, pi = pc - pz * ppp;
         int ci = pi * 64 + lane;
         if (ci >= nchunks16) ci = nchunks16 - 1;             // tail lanes re-read the last chunk (lands in the plane's slack)
-        const int sp = ci >> 1, half = ci & 1;
-        const int rr = (int)(((float)sp + 0.5f) * inv_rw), cx = sp - rr * RW;
-        const int tpx = (R0 + rr) * p + C0 + cx;             // grid pixel = window position t (fold, :1041-1046)
-        const __bf16* __restrict__ row = (btL > 0 && tpx >= btL) ? src_pad : src + (size_t)tpx * in_groups * PXE;
+        const int half = ci & 1;
+        const int tpx = t.grid_px(ci >> 1, inv_rw);
+        const __bf16* __restrict__ row = conv_pad_row(btL, tpx) ? src_pad : src + (size_t)tpx * in_groups * PXE;
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) void*)(row + pz * 16 + half * 8),
             (__attribute__((address_space(3))) void*)(rbuf0 + (size_t)buf * a.region_bytes + (size_t)pz * plane + (size_t)pi * 1024), 16, 0, 0);
@@ -331,25 +357,18 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
     // per-lane pixel bookkeeping, once per tile (rotated by the workgroup's batch chunk so the
     // 3-unit waves spread over the SIMDs)
     const int wrot = (wave + (int)blockIdx.y) & 7;
-    const int nu = nunits > wrot ? (nunits - wrot + 7) >> 3 : 0;
+    const int nu = t.nunits > wrot ? (t.nunits - wrot + 7) >> 3 : 0;
     int lbase[CBF_NU], oidx[CBF_NU];
     unsigned rmask[CBF_NU], cmask[CBF_NU];
     bool pok[CBF_NU];
 #pragma unroll
     for (int u = 0; u < CBF_NU; ++u) {
-      int idx = (wrot + 8 * u) * 16 + j;
-      pok[u] = idx < npx;
-      if (!pok[u]) idx = 0;
-      const int r = (int)(((float)idx + 0.5f) * inv_tw), c = idx - r * tw;
-      const int ri = r0 + r, ci = c0 + c;
-      lbase[u] = ((ri - R0 - hy) * RW + (ci - C0 - hx)) * CBF_PX_BYTES + (qa & 1) * 16;
-      oidx[u] = ri * p + ci;
-      const int rlo = max(0, hy - ri), rhi = min(kh, cycles + hy - ri);
-      const int clo = max(0, hx - ci), chi = min(kw, p + hx - ci);
-      const unsigned rm = (rhi > rlo) ? ((kmh >> (kh - rhi)) & (kmh << rlo)) & kmh : 0u;
-      const unsigned cm = (chi > clo) ? ((kmw >> (kw - chi)) & (kmw << clo)) & kmw : 0u;
-      rmask[u] = pok[u] ? rm : 0u;
-      cmask[u] = pok[u] ? cm : 0u;
+      const ConvPixel px = conv_pixel(t, (wrot + 8 * u) * 16 + j, inv_tw, kh, kw);
+      pok[u] = px.ok;
+      lbase[u] = ((px.ri - t.R0 - hy) * t.RW + (px.ci - t.C0 - hx)) * CBF_PX_BYTES + (qa & 1) * 16;
+      oidx[u] = px.ri * t.p + px.ci;
+      rmask[u] = px.rm;
+      cmask[u] = px.cm;
     }
     __syncthreads();                                          // previous tile's readers are done
     if (resident) dma_weights(0, 0, S);
@@ -360,7 +379,7 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
 #pragma unroll
       for (int o = 0; o < NCO; ++o) {
         f4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (co0 + o < nco_tot) bv = *(const f4*)(a.bias + br * a.out_stride_br + 16 * (co0 + o) + 4 * (lane >> 4));
+        if (co0 + o < nco_tot) bv = *(const f4*)(a.bias + br * a.out_stride_br + 16 * (co0 + o) + 4 * qa);
 #pragma unroll
         for (int u = 0; u < CBF_NU; ++u) acc[o][u] = bv;
       }
@@ -385,7 +404,7 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
         int sload = 0, g0 = 0, g1 = SG;                       // resident slab group [g0, g1)
         auto load_slab = [&](bf8 (&bp)[CBF_NU][NS], bf8 (&ap)[NCO][NWP]) {
           const bool tapok = tl < ntaps;
-          const int toff = (dy * RW + dx) * CBF_PX_BYTES;
+          const int toff = (dy * t.RW + dx) * CBF_PX_BYTES;
 #pragma unroll
           for (int u = 0; u < CBF_NU; ++u) {
             const bool v = tapok && (((rmask[u] >> dy) & (cmask[u] >> dx) & 1u) != 0u);
@@ -440,7 +459,7 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
         }
       }
       // store this batch row's tile
-      const size_t nimg = (size_t)a.B * d->g_px_off[g] + (size_t)b * P;
+      const size_t nimg = (size_t)a.B * d->g_px_off[t.g] + (size_t)b * t.P;
       const float inv = a.inv[br];
 #pragma unroll
       for (int o = 0; o < NCO; ++o) {
@@ -451,8 +470,8 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
               const int ch = br * a.out_stride_br + 16 * (co0 + o);
               const f4 v = NS == 2 ? acc[o][u] * inv : acc[o][u];
               if (NS == 2 && a.out_p3) range_bad |= h2_bad4(v);
-              if (a.out_p3) store_px<NS == 2 ? 2 : 3>((__bf16*)a.out + ((nimg + oidx[u]) * (a.OUTC >> 4) + (ch >> 4)) * PXE, lane >> 4, v);
-              else *(f4*)((float*)a.out + (nimg + oidx[u]) * a.OUTC + ch + 4 * (lane >> 4)) = v;
+              if (a.out_p3) store_px<NS == 2 ? 2 : 3>((__bf16*)a.out + ((nimg + oidx[u]) * (a.OUTC >> 4) + (ch >> 4)) * PXE, qa, v);
+              else *(f4*)((float*)a.out + (nimg + oidx[u]) * a.OUTC + ch + 4 * qa) = v;
             }
           }
         }
@@ -460,7 +479,7 @@ __global__ __launch_bounds__(512) void k_conv_bf(ConvBfArgs a) {
     }
   }
   stamp(a.dbg, a.dbg_cap, wgid, 3);
-  if (a.dbg != nullptr && threadIdx.x == 0 && wgid * 8 + 7 < a.dbg_cap) a.dbg[wgid * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+  stamp_realtime(a.dbg, a.dbg_cap, wgid, 7);
   if (NS == 2) raise_range_flag(a.range_flag, range_bad);
 }
 
@@ -604,14 +623,13 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
   if (row_lo >= row_hi) return;
   const int kh = a.kh[br], kw = a.kw[br], hy = kh >> 1, hx = kw >> 1, ntaps = kh * kw;
   const int S = (ntaps + 1) >> 1;
-  if (a.dbg != nullptr && threadIdx.x == 0 && wgid * 8 + 7 < a.dbg_cap) { a.dbg[wgid * 8 + 6] = __builtin_amdgcn_s_memrealtime(); a.dbg[wgid * 8 + 4] = (unsigned long long)ntaps; a.dbg[wgid * 8 + 5] = ((unsigned long long)row_lo << 32) | (unsigned)row_hi; }
+  stamp_realtime(a.dbg, a.dbg_cap, wgid, 6);
+  stamp_word(a.dbg, a.dbg_cap, wgid, 4, (unsigned long long)ntaps);
+  stamp_word(a.dbg, a.dbg_cap, wgid, 5, ((unsigned long long)row_lo << 32) | (unsigned)row_hi);
   char* __restrict__ wl = ldsb;
   char* __restrict__ rbuf0 = ldsb + (size_t)NCI * S * WSTR * 1024;   // behind THIS (branch, tile)'s weight fragments
   static_assert(CBF_FAST_ZBASE % 256 == 0, "the zero block must start on a 256-byte boundary");
-  if (threadIdx.x < 2 * NS * 16) {                           // zero blocks of both region buffers
-    const int pl = threadIdx.x >> 4;
-    *(f4*)(rbuf0 + (size_t)(pl / NS) * a.region_bytes + (size_t)(pl % NS) * plane + CBF_FAST_ZBASE + (threadIdx.x & 15) * 16) = f4{0.f, 0.f, 0.f, 0.f};
-  }
+  zero_blocks<NS>(rbuf0, a.region_bytes, plane, CBF_FAST_ZBASE);
   {                                                            // every slab of the branch's one output tile, once
     // f16x2: piece 1 (A2 = A1 * 2^-11) is formed by the VALU in the slab loop, so it is neither fetched nor given
     // room in LDS (packed layout: [cin group][cout tile][slab][3 pieces] x 1 KB; LDS: [cin group][slab][WSTR])
@@ -631,7 +649,6 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
   const int in_groups = a.INC >> 4;
   const int btL = a.bt_L;
   const int h1 = qa >> 1;                                     // this lane's tap of every pair
-  const unsigned kmh = (1u << kh) - 1u, kmw = (1u << kw) - 1u;
   bool first_tile = true;
 
   for (int row = row_lo; row < row_hi;) {
@@ -639,26 +656,13 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
     const int b_begin = row - bx * a.B;
     const int b_end = min(a.B, b_begin + (row_hi - row));
     row += b_end - b_begin;
-    int g = 0;
-    for (int gg = 1; gg < G; ++gg)
-      if (bx >= d->g_tile_off[gg]) g = gg;
-    const int tix = bx - d->g_tile_off[g];
-    const int ntx = d->g_ntx[g];
-    const int ty = tix / ntx, tx = tix - ty * ntx;
-    const int p = d->g_period[g], cycles = d->g_cycles[g];
-    const int P = d->g_px_off[g + 1] - d->g_px_off[g];
-    const int r0 = ty * d->g_th[g], c0 = tx * d->g_tw[g];
-    const int th = min(d->g_th[g], cycles - r0), tw = min(d->g_tw[g], p - c0);
-    const int R0 = max(0, r0 - hy), R1 = min(cycles, r0 + th + hy);
-    const int C0 = max(0, c0 - hx), C1 = min(p, c0 + tw + hx);
-    const int RW = C1 - C0, RH = R1 - R0;
-    const int npx = th * tw, nunits = (npx + 15) >> 4;
-    const float inv_tw = 1.0f / (float)tw, inv_rw = 1.0f / (float)RW;
-    const int nchunks16 = RH * RW * 2;
+    const ConvTile t = conv_tile(d, G, bx, hy, hx);
+    const float inv_tw = 1.0f / (float)t.tw, inv_rw = 1.0f / (float)t.RW;
+    const int nchunks16 = t.RH * t.RW * 2;
     const int ppp = (nchunks16 + 63) >> 6;
     // descriptor values the row loop needs, read once per tile (a load inside the loop is a full round trip on
     // the critical path of every batch row, and its s_waitcnt vmcnt(0) also waits for everything else in flight)
-    const size_t img0 = (size_t)a.B * d->g_px_off[g];
+    const size_t img0 = (size_t)a.B * d->g_px_off[t.g];
     // Region DMA: which 16-byte chunk a lane fetches for piece k of this wave depends on the tile only, so its
     // offset (relative to the batch row's first pixel, or to the shared pad row for the live zero pixels t >= L)
     // and its LDS slot are worked out once per tile; a batch row then costs an add, a select and the load per piece
@@ -674,17 +678,16 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
       const int pz = pcc / ppp, pi = pcc - pz * ppp;
       int ci = pi * 64 + lane;
       if (ci >= nchunks16) ci = nchunks16 - 1;
-      const int sp = ci >> 1, half = ci & 1;
-      const int rr = (int)(((float)sp + 0.5f) * inv_rw), cx = sp - rr * RW;
-      const int tpx = (R0 + rr) * p + C0 + cx;
-      const bool pad = btL > 0 && tpx >= btL;
+      const int half = ci & 1;
+      const int tpx = t.grid_px(ci >> 1, inv_rw);
+      const bool pad = conv_pad_row(btL, tpx);
       poff[k] = (pad ? 0 : tpx * in_groups * PXE) + pz * 16 + half * 8;
       ppad |= (pad ? 1u : 0u) << k;
       pdst[k] = __builtin_amdgcn_readfirstlane(pz * plane + pi * 1024);
     }
     const __bf16* __restrict__ in_br = a.in + (size_t)(br * a.in_stride_br) * PXE;
     const __bf16* __restrict__ src_pad = in_br + (size_t)a.B * btL * in_groups * PXE;
-    const size_t row_stride = (size_t)(btL > 0 ? btL : P) * in_groups * PXE;
+    const size_t row_stride = (size_t)(btL > 0 ? btL : t.P) * in_groups * PXE;
     const __bf16* __restrict__ src0 = in_br + (btL > 0 ? (size_t)0 : img0 * in_groups * PXE);
     auto dma_region = [&](int b, int gi, int buf) {           // input group gi of batch row b
       const __bf16* __restrict__ src = src0 + (size_t)b * row_stride + gi * PXE;
@@ -708,44 +711,36 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
     // division-free walk over the taps (a runtime tl / kw per slab and unit cost 20 k cycles of a 7x7 tile's
     // 34 k cycle prologue, tools/stamps.py)
     const int wrot = (wave + b_begin) & 7;
-    const int nu = nunits > wrot ? (nunits - wrot + 7) >> 3 : 0;
+    const int nu = t.nunits > wrot ? (t.nunits - wrot + 7) >> 3 : 0;
     int ld[CBF_NU], oidx[CBF_NU];
     unsigned ooff[CBF_NU];
     unsigned vmask[CBF_NU];
     bool pok[CBF_NU];
 #pragma unroll
     for (int u = 0; u < CBF_NU; ++u) {
-      int idx = (wrot + 8 * u) * 16 + j;
-      pok[u] = idx < npx;
-      if (!pok[u]) idx = 0;
-      const int r = (int)(((float)idx + 0.5f) * inv_tw), c = idx - r * tw;
-      const int ri = r0 + r, ci = c0 + c;
-      ld[u] = ((ri - R0 - hy) * RW + (ci - C0 - hx)) * CBF_PX_BYTES + (qa & 1) * 16;
-      oidx[u] = ri * p + ci;
+      const ConvPixel px = conv_pixel(t, (wrot + 8 * u) * 16 + j, inv_tw, kh, kw);
+      pok[u] = px.ok;
+      ld[u] = ((px.ri - t.R0 - hy) * t.RW + (px.ci - t.C0 - hx)) * CBF_PX_BYTES + (qa & 1) * 16;
+      oidx[u] = px.ri * t.p + px.ci;
       {
         const int ch = br * a.out_stride_br + 16 * cot;
         ooff[u] = a.out_p3 ? (unsigned)((oidx[u] * (a.OUTC >> 4) + (ch >> 4)) * PXE)
                            : (unsigned)(oidx[u] * a.OUTC + ch + 4 * qa);
       }
-      // taps dy with 0 <= ri + dy - hy < cycles are the bits [lo, hi) of the row mask (same for columns)
-      const int rlo = max(0, hy - ri), rhi = min(kh, cycles + hy - ri);
-      const int clo = max(0, hx - ci), chi = min(kw, p + hx - ci);
-      const unsigned rm = (rhi > rlo) ? ((kmh >> (kh - rhi)) & (kmh << rlo)) & kmh : 0u;
-      const unsigned cm = (chi > clo) ? ((kmw >> (kw - chi)) & (kmw << clo)) & kmw : 0u;
       // bit s = tap 2s + h1 is inside the grid.  Row dy of the kernel (kw odd: its first tap has parity dy) holds the
       // taps of this lane half at dx = par, par + 2, ... with par = (dy ^ h1) & 1, i.e. every other bit of the column
       // mask, compressed, at slab (dy kw + par - h1) / 2: ~70 instructions per pixel unit instead of a 10-instruction
       // step per slab (the 7x7 prologue spent 9 k of its 25 k cycles in that loop; tools/stamps.py)
-      const unsigned ce = (cm & 1u) | ((cm >> 1) & 2u) | ((cm >> 2) & 4u) | ((cm >> 3) & 8u);
-      const unsigned co = ((cm >> 1) & 1u) | ((cm >> 2) & 2u) | ((cm >> 3) & 4u) | ((cm >> 4) & 8u);
+      const unsigned ce = (px.cm & 1u) | ((px.cm >> 1) & 2u) | ((px.cm >> 2) & 4u) | ((px.cm >> 3) & 8u);
+      const unsigned co = ((px.cm >> 1) & 1u) | ((px.cm >> 2) & 2u) | ((px.cm >> 3) & 4u) | ((px.cm >> 4) & 8u);
       unsigned m = 0u;
 #pragma unroll
       for (int dy = 0; dy < 7; ++dy) {                         // kh <= 7 here (fast path: 3x3 / 5x5 / 7x7)
         const int par = (dy ^ h1) & 1;
         const unsigned bits = par ? co : ce;
-        if (dy < kh && ((rm >> dy) & 1u)) m |= bits << ((dy * kw + par - h1) >> 1);
+        if (dy < kh && ((px.rm >> dy) & 1u)) m |= bits << ((dy * kw + par - h1) >> 1);
       }
-      vmask[u] = pok[u] ? m : 0u;
+      vmask[u] = m;                                            // (empty for a lane past the tile: its row mask is)
     }
     int it = 0;
     int keep = 0;                                             // output stores issued behind the newest region DMA
@@ -770,12 +765,12 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
         const char* __restrict__ reg = rbuf0 + (size_t)(it & 1) * a.region_bytes;
         ++it;
         const char* __restrict__ wg_ = wlane + (size_t)gi * S * WSTR * 1024;
-        if (kw == 7) conv_fast_row<NS, 7, 7>(acc, reg, wg_, ld, vmask, RW * CBF_PX_BYTES, h1 != 0);
-        else if (kw == 5) conv_fast_row<NS, 5, 5>(acc, reg, wg_, ld, vmask, RW * CBF_PX_BYTES, h1 != 0);
-        else conv_fast_row<NS, 3, 3>(acc, reg, wg_, ld, vmask, RW * CBF_PX_BYTES, h1 != 0);
+        if (kw == 7) conv_fast_row<NS, 7, 7>(acc, reg, wg_, ld, vmask, t.RW * CBF_PX_BYTES, h1 != 0);
+        else if (kw == 5) conv_fast_row<NS, 5, 5>(acc, reg, wg_, ld, vmask, t.RW * CBF_PX_BYTES, h1 != 0);
+        else conv_fast_row<NS, 3, 3>(acc, reg, wg_, ld, vmask, t.RW * CBF_PX_BYTES, h1 != 0);
       }
       // uniform row base + per-lane offsets fixed for the tile (ooff)
-      const size_t nimg = img0 + (size_t)b * P;
+      const size_t nimg = img0 + (size_t)b * t.P;
       if (a.out_p3) {
         __bf16* __restrict__ ob = (__bf16*)a.out + nimg * (size_t)(a.OUTC >> 4) * PXE;
 #pragma unroll
@@ -794,7 +789,7 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
     }
   }
   stamp(a.dbg, a.dbg_cap, wgid, 3);
-  if (a.dbg != nullptr && threadIdx.x == 0 && wgid * 8 + 7 < a.dbg_cap) a.dbg[wgid * 8 + 7] = __builtin_amdgcn_s_memrealtime();
+  stamp_realtime(a.dbg, a.dbg_cap, wgid, 7);
   if (NS == 2) raise_range_flag(a.range_flag, range_bad);
 }
 
@@ -955,73 +950,24 @@ int ftn_launch_conv_bf(ConvBfArgs& ca, const ConvBfGeom& gm, int B, int grid_x, 
     if ((long long)grid_x * ftn_cdiv(B, bp) * ca.nbr * ftn_cdiv(nco_tot, gm.NCO) >= 448) { ca.bpw = bp; break; }
   heavy_first(ca.nbr, ca.kh, ca.kw, ca.order);
   dim3 grid(grid_x, ftn_cdiv(B, ca.bpw), ca.nbr * ca.nchunk);
-  if (gm.fast && ((ca.cin == 16 && ca.cout == 16) || (ca.cin == 32 && ca.cout == 32 && nsplit == 2))) {
+  // gm.fast already says cin == cout == 16, or 32 on f16x2: the plan comes from ftn_conv_bf_geom(.., cout, nsplit), and
+  // block.hip, the only caller, fills cin = cout = the plan's mid width for both convs
+  if (gm.fast) {
     // virtual branches: (branch, 16-channel output tile); with two input groups a batch row walks two slab loops
-    const int nci = ca.cin / 16, nco = ca.cout / 16, nvb = ca.nbr * nco, wstr = nsplit == 2 ? 2 : 3;
-    // one workgroup per CU, shared out over the branches in proportion to their cost per batch row
-    // (~3.2 k cycles + 0.28 k per K-32 slab, beside a prologue worth ~17 k whatever the kernel size: fitted to
-    // tools/stamps.py after the closed-form tap masks, late round 3); every branch gets at least one
+    const int nco = ca.cout / 16, nvb = ca.nbr * nco;
     static int ncu = 0;
     if (ncu == 0) {
       int dev = 0; hipDeviceProp_t prop;
       if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-      if (ncu < 2 * FTN_MAXBR) ncu = 256;
+      if (ncu < FTN_CONV_MAXVB) ncu = 256;
     }
-    double cost[2 * FTN_MAXBR], tot = 0.0;
-    size_t lds_fast = 0;
-    for (int v = 0; v < nvb; ++v) {
-      const int k = v / nco, S = (ca.kh[k] * ca.kw[k] + 1) / 2;
-      cost[v] = 3.17 + 0.281 * S * nci; tot += cost[v];
-      const size_t need = (size_t)nci * S * wstr * 1024 + 2 * (size_t)gm.region_bytes;
-      if (need > lds_fast) lds_fast = need;
-    }
-    int used = 0, nwg[2 * FTN_MAXBR];
-    for (int k = 0; k < nvb; ++k) { nwg[k] = (int)(ncu * cost[k] / tot); if (nwg[k] < 1) nwg[k] = 1; used += nwg[k]; }
-    for (int k = 0; used < ncu; k = (k + 1) % nvb) { ++nwg[k]; ++used; }     // leftovers round-robin from the first branch
-    for (int k = 0; used > ncu && k < nvb; ++k) while (nwg[k] > 1 && used > ncu) { --nwg[k]; --used; }
-    // Rows are whole units: a 7x7 workgroup with 11 rows ends 9 % after one with 10 (tools/stamps.py: the launch
-    // ended at 79 us with the median workgroup done at 66).  With an estimate of the row count (the descriptor is on
-    // the device: groups bound x tiles of a typical grid x batch rows) pick the split that minimises
-    // max_k ceil(rows / nwg_k) * cost_k; a wrong estimate only costs balance, the kernel derives the ranges itself.
-    if (rows_est > 0 && g_conv_quant) {
-      double bestT = 1e300;
-      int best[2 * FTN_MAXBR];
-      bool found = false;
-      for (int kk = 0; kk < nvb; ++kk) {
-        for (int r = 1; r <= rows_est; ++r) {
-          const double T = r * cost[kk];                         // (the prologue is the same for every branch: it drops out)
-          if (T >= bestT) break;
-          int need[2 * FTN_MAXBR], sum = 0;
-          bool ok = true;
-          for (int k = 0; k < nvb && ok; ++k) {
-            const int per = (int)(T / cost[k] + 1e-9);
-            if (per < 1) { ok = false; break; }
-            need[k] = (rows_est + per - 1) / per;
-            sum += need[k];
-          }
-          if (ok && sum <= ncu) { bestT = T; for (int k = 0; k < nvb; ++k) best[k] = need[k]; found = true; break; }
-        }
-      }
-      if (found) {
-        int sum = 0;
-        for (int k = 0; k < nvb; ++k) sum += best[k];
-        // spare workgroups go where they shorten the longest branch next
-        while (sum < ncu) {
-          int arg = 0; double worst = -1.0;
-          for (int k = 0; k < nvb; ++k) {
-            const double t = (double)((rows_est + best[k] - 1) / best[k]) * cost[k];
-            if (t > worst) { worst = t; arg = k; }
-          }
-          ++best[arg]; ++sum;
-        }
-        for (int k = 0; k < nvb; ++k) nwg[k] = best[k];
-      }
-    }
+    int slabs[FTN_CONV_MAXVB], nwg[FTN_CONV_MAXVB];
+    for (int v = 0; v < nvb; ++v) slabs[v] = (ca.kh[v / nco] * ca.kw[v / nco] + 1) / 2;
+    ftn_conv_split(ncu, nvb, slabs, ca.cin / 16, rows_est, nwg);
     ca.nvb = nvb;
     ca.wg_off[0] = 0;
     for (int k = 0; k < nvb; ++k) ca.wg_off[k + 1] = ca.wg_off[k] + nwg[k];
-    const ConvBfGeom gmf = {gm.NCO, lds_fast, gm.plane_bytes, gm.region_bytes, gm.wbytes, gm.sgroup, true};
-    return launch_conv_bf_fast(ca, gmf, dim3((unsigned)ca.wg_off[nvb]), nsplit, st);
+    return launch_conv_bf_fast(ca, gm, dim3((unsigned)ca.wg_off[nvb]), nsplit, st);
   }
   if (nsplit == 3) return launch_conv_bf_n<3>(ca, gm, grid, st);
   if (nsplit == 2) return launch_conv_bf_n<2>(ca, gm, grid, st);

@@ -136,6 +136,17 @@ __host__ __device__ inline void ftn_build_groups(const int* periods, int K, int 
 __device__ __forceinline__ void stamp(unsigned long long* buf, size_t cap, size_t wg, int slot) {
   if (buf != nullptr && threadIdx.x == 0 && (wg * 8 + slot) < cap) buf[wg * 8 + slot] = __builtin_amdgcn_s_memtime();
 }
+// the record's extra words (slots 4-7, read by tools/stamps.py) are written only when the whole 8-word record fits
+__device__ __forceinline__ bool stamp_extra(const unsigned long long* buf, size_t cap, size_t wg) {
+  return buf != nullptr && threadIdx.x == 0 && wg * 8 + 7 < cap;
+}
+__device__ __forceinline__ void stamp_word(unsigned long long* buf, size_t cap, size_t wg, int slot, unsigned long long v) {
+  if (stamp_extra(buf, cap, wg)) buf[wg * 8 + slot] = v;
+}
+// the real-time clock (slots 6 / 7), read under the guard: as an argument of stamp_word every workgroup would read it
+__device__ __forceinline__ void stamp_realtime(unsigned long long* buf, size_t cap, size_t wg, int slot) {
+  if (stamp_extra(buf, cap, wg)) buf[wg * 8 + slot] = __builtin_amdgcn_s_memrealtime();
+}
 
 // Workgroup barrier that waits only until at most `keep` of this wave's vector-memory operations are still in
 // flight (vmcnt retires in issue order on gfx9, loads and stores alike): the conv row loop issues

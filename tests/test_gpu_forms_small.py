@@ -26,6 +26,12 @@ WIDE = 192                                                       # from here on 
 # 1 = a 50 x 1 grid, 7 = pad 6, 16 and 25 = no pad; wide blocks: 47 = pad 46, 5 = pad 2, 16 = no pad
 NATIVE = {False: dict(B=3, L=96, K=3, planted=(24, 12, 8), seed=51), True: dict(B=2, L=48, K=3, planted=(12, 8, 6), seed=52)}
 STUB = {False: dict(B=3, L=50, periods=[49, 1, 7, 16, 25], seed=53), True: dict(B=2, L=48, periods=[47, 5, 16], seed=54)}
+# selector "tiled": a stub whose grids are walked in several conv tiles.  L = 400: period 399 = a 2 x 399 grid in three
+# column tiles, 3 = 134 x 3 in two row tiles, 16 = 25 x 16 in two row tiles of 13 units (more than one per wave).  It runs
+# the forms whose multi-tile walk nothing else reaches: k_conv_bf<4,3>, k_conv_bf<1,3> with its weight groups restaged
+# (at this L the 41 slabs of k3579 do not fit beside the region buffers) and k_conv
+STUB_TILED = dict(B=2, L=400, periods=[399, 3, 16], seed=56)
+TILED_ROWS = [(96, 192, 1.5, "k3", "bf16x3"), (8, 16, 1.5, "k3579", "bf16x3"), (100, 200, 1.5, "k35", "f32")]
 
 # (d_model, d_ff, ratio, kernel set, engine, act_dtype) -> (A, conv, C, r_keeps_x, r_summed, E): a literal copy of what
 # the sweep found, not a restatement of block_forms.  Each row's shape is the cheapest of the sweep with d_ff != d_model
@@ -133,8 +139,11 @@ def _params(C, d_ff, ratio, ks, act):
     return {k: torch.from_numpy(v) for k, v in sd.items()}
 
 
-def _stub_amps(wide):
-    s = STUB[wide]
+def _stub(C, selector):
+    return STUB_TILED if selector == "tiled" else STUB[C >= WIDE]
+
+
+def _stub_amps(s):
     return np.random.RandomState(s["seed"]).standard_normal(size=(s["B"], len(s["periods"]))).astype(np.float32)
 
 
@@ -148,9 +157,9 @@ def _reference(C, d_ff, ratio, ks, act, selector):
         x = torch.from_numpy(_ftn().synth.make_input(n["B"], n["L"], C, seed=n["seed"], planted=n["planted"]))
         y, periods = oracle_fp64(x, P, act, n["K"], n["L"], ks=KSETS[ks])
     else:
-        s = STUB[wide]
+        s = _stub(C, selector)
         x = torch.from_numpy(_ftn().synth.make_input(s["B"], s["L"], C, seed=s["seed"], planted=()))
-        y, periods = oracle_fp64(x, P, act, 0, s["L"], s["periods"], _stub_amps(wide), ks=KSETS[ks])
+        y, periods = oracle_fp64(x, P, act, 0, s["L"], s["periods"], _stub_amps(s), ks=KSETS[ks])
     return P, x, y, periods
 
 
@@ -179,7 +188,7 @@ def test_small_forms_match_fp64_oracle(C, d_ff, ratio, ks, engine, act, align, s
     if selector == "native":
         blk.period_selector = T.FFTPeriodSelector(NATIVE[C >= WIDE]["K"], L)
     else:
-        object.__setattr__(blk, "period_selector", _Stub(periods, _stub_amps(C >= WIDE)))
+        object.__setattr__(blk, "period_selector", _Stub(periods, _stub_amps(_stub(C, selector))))
     xd = x.to(dev)
     if align == "misaligned":
         xd = _misaligned_copy(xd)
@@ -209,6 +218,16 @@ def test_small_forms_match_fp64_oracle(C, d_ff, ratio, ks, engine, act, align, s
     err_ln = _check(y_ln, ln_ref, engine, LN_RTOL, LN_ATOL)
     print(f"forms_small C={C} d_ff={d_ff} ratio={ratio} {ks} {engine} {act} {align} {selector}: {want['conv']} "
           f"{want['C']} {want['E']} max|y-y64|={err:.3e} ln {err_ln:.3e}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C,d_ff,ratio,ks,engine", TILED_ROWS)
+def test_small_forms_multi_tile_grids(C, d_ff, ratio, ks, engine, ftn):
+    """The same criterion on the ``STUB_TILED`` grids: every group's tile list has more than one tile."""
+    s = STUB_TILED
+    dh = ftn.lib.desc_from_periods(s["periods"], s["L"], 1, s["L"])
+    assert [int(dh.g_ntx[g]) * int(dh.g_nty[g]) for g in range(int(dh.n_groups))] == [2, 2, 3]   # periods 3, 16, 399
+    test_small_forms_match_fp64_oracle(C, d_ff, ratio, ks, engine, "gelu", "aligned", "tiled", ftn)
 
 
 @pytest.mark.gpu
