@@ -296,7 +296,11 @@ int ftn_selector_px_bound(int L, int k_periods, int pmax, int min_period_thresho
  * 0 = the worst case over any max_groups distinct periods, almost 2*L*max_groups).  A descriptor that
  * exceeds them makes the call the identity y = x; nothing is ever written past the workspace.  The
  * workspace belongs to ONE call in flight: calls that may overlap (different streams, or a captured
- * graph beside eager calls) need their own.  Returns 0 for a shape it cannot run. */
+ * graph beside eager calls) need their own.  Returns 0 for a shape it cannot run.
+ * The result of a block call does not depend on the bytes the workspace held before it, for any bit pattern (NaN
+ * and Inf encodings of fp32, bf16 and fp16 included); the call writes nothing outside
+ * [ws_dev, ws_dev + ftn_timesblock_workspace_bytes(...)).  Nothing clears a workspace: every region is written
+ * before it is read, and readers select 0 for what they mask (tests/test_gpu_workspace_hygiene.py). */
 size_t ftn_timesblock_workspace_bytes(const FtnPlan* plan, int B, int L, int max_groups, int px_bound);
 /* y = x + sum_g w[b,g] * (inception(fold_g(x)) - fold_g(x))[:L]  (:1041-1092, :818).
  * desc/weights are device pointers.  act_dtype (0 fp32, 1 bf16, 2 fp16) = dtype of the caller's activations:
