@@ -59,6 +59,7 @@ FTN_PATH_LDS = 16
 FTN_GROUP_CHUNK = 32
 FTN_GROUP_NMAX, FTN_GROUP_GMAX, FTN_GROUP_CHUNKS_MAX = 8192, 2048, 2048
 FTN_GROUP_TILE_BYTES, FTN_GROUP_TILE_ROWS = 32768, 64
+FTN_GROUP_TILE_COLS = 64
 
 
 class FtnDesc(C.Structure):
@@ -203,6 +204,9 @@ _SIGNATURES = {
                                    C.c_int, _P, C.c_longlong, C.POINTER(C.c_int), C.c_int, _P, _P, _P, _P, _P]),
     "ftn_group_sum_form": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int]),
     "ftn_group_sum": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_longlong, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "ftn_group_sum_rows_form": (C.c_int, [C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
+    "ftn_group_sum_rows": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P, _P,
+                                     C.c_int, C.c_int, _P, _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -877,6 +877,70 @@ def group_sum(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, offse
     return out
 
 
+def group_sum_rows_form_of(inner: int, member_stride: int | None = None, outer_stride: int = 0, misalign_or: int = 0,
+                           n_chunks: int = 0) -> str:
+    """The kernel form ``ftn_group_sum_rows`` takes (``ftn_group_sum_rows_form``, host-only: the launch dispatches
+    through the same function): ``"vec4/i<TI>"`` or ``"scalar/i<TI>"``, the load and store width along ``inner`` and
+    the inner columns of a tile (bits 16-27 of the word, the passes a tile takes over the chunks, are not part of the
+    name).  Strides in elements (``member_stride`` default: ``inner``; ``outer_stride`` 0 for
+    one slab), ``misalign_or`` the addresses of x and out, or-ed, modulo 16, ``n_chunks`` the chunks of 32 members
+    over all groups."""
+    f = _form("ftn_group_sum_rows_form", inner, inner if member_stride is None else member_stride, outer_stride,
+              misalign_or, n_chunks)
+    return f"{'vec4' if f & 2 else 'scalar'}/i{(f >> 8) & 255}"
+
+
+def _rows_strides(x3: torch.Tensor) -> Tuple[int, int]:
+    """``(outer_stride, member_stride)`` as ``ftn_group_sum_rows`` takes them: a stride that addresses nothing (one
+    slab, one member) is replaced by the dense one."""
+    outer, S, inner = x3.shape
+    ms = x3.stride(1) if S > 1 else inner
+    return (x3.stride(0) if outer > 1 else 0), ms
+
+
+def group_sum_rows_form(x3: torch.Tensor, offsets_host, out: torch.Tensor | None = None) -> str:
+    """``group_sum_rows_form_of`` for the tensors ``group_sum_rows(x3, order, offsets, offsets_host, out)`` is given
+    (a fresh ``out`` is 16-byte aligned)."""
+    sizes = [int(b) - int(a) for a, b in zip(offsets_host[:-1], offsets_host[1:])]
+    chunks = sum((m + _lib.FTN_GROUP_CHUNK - 1) // _lib.FTN_GROUP_CHUNK for m in sizes)
+    os_, ms = _rows_strides(x3)
+    mis = (_ptr(x3) | (0 if out is None else _ptr(out))) & 15
+    return group_sum_rows_form_of(x3.shape[2], ms, os_, mis, chunks)
+
+
+def group_sum_rows(x3: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, offsets_host,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """``ftn_group_sum_rows``: ``x3`` [outer, S, inner] fp32 on a ROCm device, ``inner`` contiguous
+    (``x3.stride(2) == 1``), members ``x3.stride(1) >= inner`` apart and slabs ``x3.stride(0) >= S x3.stride(1)``
+    apart; the groups are over the S members of dim 1: ``order`` [M] and ``offsets`` [G+1] the int32 CSR member lists
+    on that device, ``offsets_host`` the same G+1 offsets as a contiguous int32 numpy array.  Returns ``out``
+    [outer, G, inner] fp32 (default: fresh; else a contiguous one to fill).  Enqueues only."""
+    lib = _lib.load()
+    if not isinstance(x3, torch.Tensor) or x3.dim() != 3 or x3.numel() == 0:
+        raise ValueError("group_sum_rows: x3 must be a non-empty [outer, S, inner] tensor")
+    outer, S, inner = x3.shape
+    if ((inner > 1 and x3.stride(2) != 1) or (S > 1 and x3.stride(1) < inner)
+            or (outer > 1 and x3.stride(0) < S * (x3.stride(1) if S > 1 else inner))):
+        raise ValueError(f"group_sum_rows: x3 needs contiguous inner elements, members at least inner apart and slabs "
+                         f"at least S members apart, strides {x3.stride()}")
+    if x3.dtype != torch.float32 or not x3.is_cuda:
+        raise ValueError(f"group_sum_rows: x3 must be an fp32 tensor on a ROCm device, got {x3.dtype} on {x3.device}")
+    for name, t in (("order", order), ("offsets", offsets)):
+        if (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.device != x3.device
+                or not t.is_contiguous()):
+            raise ValueError(f"group_sum_rows: {name} must be a contiguous int32 vector on x3's device")
+    G, M = offsets.numel() - 1, order.numel()
+    if (getattr(offsets_host, "dtype", None) != "int32" or offsets_host.ndim != 1 or offsets_host.size != G + 1
+            or not offsets_host.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"group_sum_rows: offsets_host must be a contiguous int32 numpy array of {G + 1} offsets")
+    out = _out_or_fresh("group_sum_rows", out, (outer, G, inner), x3)
+    os_, ms = _rows_strides(x3)
+    check(lib.ftn_group_sum_rows(_ptr(x3), outer, S, inner, os_, ms, _ptr(order) if M else None, _ptr(offsets),
+                                 offsets_host.ctypes.data, G, M, _ptr(out), _stream(x3.device)),
+          "ftn_group_sum_rows")
+    return out
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch

@@ -25,10 +25,13 @@ LDS) and the same definitions in fp64 torch ops otherwise.
 
 ``SeriesGroups`` / ``group_sums`` / ``group_path_summary`` / ``group_path_metrics`` total series over groups (a store's
 items, the whole site) before summarising: a segmented sum along the series axis in a stated order,
-``ftn_group_sum`` on the ``hip`` side and the same additions in fp64 torch ops otherwise, bit for bit.
+``ftn_group_sum`` on the ``hip`` side and the same additions in fp64 torch ops otherwise, bit for bit.  With ``axis``
+the series may lie along any dim - the pipeline's one series per batch row, samples [P,B,H,1] with ``axis=1`` -
+(``ftn_group_sum_rows``, no copy), to the same bits.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -38,6 +41,7 @@ from .nbdist import (NBQ_FLAG_RANGE, NBQ_KLIM, NBQ_QMAX, _M32, _nb_cdf_torch, _n
                      _nb_quantiles_torch, philox4x32, sample_uniforms)
 
 _last_backend: Optional[str] = None
+_last_group_entry: Optional[str] = None     # the C entry the last hip ``group_sums`` ran
 
 
 def negative_binomial_mask(y: torch.Tensor, rate: torch.Tensor, dispersion: torch.Tensor,
@@ -794,7 +798,23 @@ def _group_rows(x: torch.Tensor) -> torch.Tensor:
     return v
 
 
-def group_sums(x: torch.Tensor, groups: SeriesGroups, backend: Optional[str] = None) -> torch.Tensor:
+def _group_slabs(x: torch.Tensor, axis: int) -> torch.Tensor:
+    """``x`` as [outer, S, inner] around dim ``axis`` (the ``_group_rows`` policy on both sides of it): a view where
+    the dims before ``axis`` collapse to one slab stride, the dims after it collapse with an innermost stride of 1,
+    and neither members nor slabs overlap; else one copy to contiguous."""
+    S = x.shape[axis]
+    outer, inner = math.prod(x.shape[:axis]), math.prod(x.shape[axis + 1:])
+    try:
+        v = x.view(outer, S, inner)
+    except RuntimeError:
+        return x.contiguous().view(outer, S, inner)
+    ms = v.stride(1) if S > 1 else inner
+    if ((inner > 1 and v.stride(2) != 1) or (S > 1 and ms < inner) or (outer > 1 and v.stride(0) < S * ms)):
+        v = x.contiguous().view(outer, S, inner)
+    return v
+
+
+def group_sums(x: torch.Tensor, groups: SeriesGroups, backend: Optional[str] = None, axis: int = -1) -> torch.Tensor:
     """Totals over groups of series: ``x`` [..., N] -> fp32 [..., G], ``out[.., g]`` the sum of ``x[.., i]`` over the
     members of group g in the order and precision stated above (exact for integer-valued x whose totals stay below
     2^24; NaN and inf reach only the groups that hold them; an empty group gives +0).  Works on sample paths
@@ -802,66 +822,113 @@ def group_sums(x: torch.Tensor, groups: SeriesGroups, backend: Optional[str] = N
     ``backend``: ``"hip"`` (one ``ftn_group_sum`` launch; fp32 on a ROCm device, nothing for autograd to record,
     N <= 8192, at most 2048 groups and 2048 chunks of 32 members; leading dims that collapse to one row stride are
     passed as a view, anything else is copied), ``"torch"`` (the same additions in torch ops, any device, bit-equal;
-    other dtypes are converted to fp32 first), or None: ``hip`` where it can run.  Never synchronises on ``hip``."""
-    global _last_backend
+    other dtypes are converted to fp32 first), or None: ``hip`` where it can run.  Never synchronises on ``hip``.
+
+    ``axis``: the dim the series lie along (default: the last, all of the above unchanged).  Any other dim must hold
+    ``groups.n_series`` members and the result has G in its place - the pipeline layout, one series per batch row:
+    ``group_sums(samples[P,B,H,1], groups, axis=1)`` -> [P,G,H,1], to the same bits as the totals of the transposed
+    copy.  On ``hip`` that is one ``ftn_group_sum_rows`` launch, with no limit on the number of members (groups and
+    chunks as above): the dims before ``axis`` collapse to ``outer`` and the dims after it to ``inner``, and x is
+    passed as a view when both collapses are views, the innermost stride is 1 and neither members nor slabs overlap;
+    otherwise it is copied once to contiguous.  Where the dims after ``axis`` hold one element in all, the members
+    are 1 apart and there are at most 8192 of them, that view is [outer, N] with N fastest and goes to
+    ``ftn_group_sum`` instead (``ftn_group_sum_rows`` with one column a member would be an uncoalesced gather)."""
+    global _last_backend, _last_group_entry
     if not isinstance(groups, SeriesGroups):
         raise ValueError(f"group_sums: groups must be a SeriesGroups, got {type(groups)}")
-    if not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != groups.n_series or x.numel() == 0:
+    if isinstance(x, torch.Tensor) and x.dim() >= 1:
+        if not isinstance(axis, int) or not -x.dim() <= axis < x.dim():
+            raise ValueError(f"group_sums: axis={axis!r} is not a dim of x {tuple(x.shape)}")
+        axis %= x.dim()
+    last = not isinstance(x, torch.Tensor) or x.dim() < 1 or axis == x.dim() - 1
+    if last and (not isinstance(x, torch.Tensor) or x.dim() < 1 or x.shape[-1] != groups.n_series or x.numel() == 0):
         raise ValueError(f"group_sums takes x [..., N] with N = {groups.n_series} series, got "
                          f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    if not last and (x.shape[axis] != groups.n_series or x.numel() == 0):
+        raise ValueError(f"group_sums: dim {axis} of x {tuple(x.shape)} must hold the {groups.n_series} series of the "
+                         f"groups")
     eligible = (x.is_cuda and x.dtype == torch.float32 and not (torch.is_grad_enabled() and x.requires_grad)
-                and groups.n_series <= GROUP_NMAX and groups.n_groups <= GROUP_GMAX
+                and (groups.n_series <= GROUP_NMAX or not last) and groups.n_groups <= GROUP_GMAX
                 and groups.n_chunks <= GROUP_CHUNKS_MAX)
     use_hip = _use_hip("group_sums", backend, eligible,
-                       f"fp32 [..., N] on a ROCm device, without autograd, N <= {GROUP_NMAX}, at most {GROUP_GMAX} "
-                       f"groups and {GROUP_CHUNKS_MAX} chunks of {GROUP_CHUNK} members")
+                       f"fp32 [..., N] on a ROCm device, without autograd, N <= {GROUP_NMAX} along the last dim, at most "
+                       f"{GROUP_GMAX} groups and {GROUP_CHUNKS_MAX} chunks of {GROUP_CHUNK} members")
     groups = groups.to(x.device)
     if use_hip:
         from . import runtime as rt
 
-        out = rt.group_sum(_group_rows(x.detach()), groups.order, groups.offsets, groups.offsets_host)
-        out = out.view(*x.shape[:-1], groups.n_groups)
+        if last:
+            out = rt.group_sum(_group_rows(x.detach()), groups.order, groups.offsets, groups.offsets_host)
+            out = out.view(*x.shape[:-1], groups.n_groups)
+            _last_group_entry = "ftn_group_sum"
+        else:
+            v = _group_slabs(x.detach(), axis)
+            outer, S, inner = v.shape
+            if inner == 1 and S <= GROUP_NMAX and (S == 1 or v.stride(1) == 1):
+                out = rt.group_sum(v[:, :, 0], groups.order, groups.offsets, groups.offsets_host)
+                _last_group_entry = "ftn_group_sum"
+            else:
+                out = rt.group_sum_rows(v, groups.order, groups.offsets, groups.offsets_host)
+                _last_group_entry = "ftn_group_sum_rows"
+            out = out.view(*x.shape[:axis], groups.n_groups, *x.shape[axis + 1:])
         _last_backend = "hip"
     else:
         with torch.no_grad():
-            out = _group_sums_torch(x, groups)
+            if last:
+                out = _group_sums_torch(x, groups)
+            else:
+                out = _group_sums_torch(x.movedim(axis, -1), groups).movedim(-1, axis).contiguous()
         _last_backend = "torch"
     return out
 
 
+def _group_path_axis(who: str, samples, axis) -> int:
+    """The dim of ``samples`` [P,B,H,N] the groups run along: 3 (series) or 1 (batch rows, the pipeline layout)."""
+    if not isinstance(samples, torch.Tensor) or samples.dim() != 4:
+        raise ValueError(f"{who} takes samples [P, B, H, N]")
+    if axis in (3, -1):
+        return 3
+    if axis in (1, -3):
+        return 1
+    raise ValueError(f"{who}: axis={axis!r} is neither the series axis (3 or -1) nor the batch axis (1 or -3) of "
+                     f"samples [P, B, H, N]")
+
+
 def group_path_summary(samples: torch.Tensor, groups: SeriesGroups, levels=(), y: torch.Tensor | None = None,
                        window: Optional[int] = None, reduce: str = "sum", want_sorted: bool = False,
-                       backend: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                       backend: Optional[str] = None, axis: int = -1) -> Dict[str, torch.Tensor]:
     """``path_summary`` of the group totals: ``samples`` [P,B,H,N] -> ``group_sums`` [P,B,H,G], summarised against
     ``group_sums(y)``.  The total over the group is taken first and the window reduce second, so ``reduce="max"``
-    is the peak of a store's total, not the total of its items' peaks.  Returns [.., B, H', G] tensors."""
-    if not isinstance(samples, torch.Tensor) or samples.dim() != 4:
-        raise ValueError("group_path_summary takes samples [P, B, H, N]")
-    totals = group_sums(samples, groups, backend)
+    is the peak of a store's total, not the total of its items' peaks.  Returns [.., B, H', G] tensors.
+    ``axis=1`` (or -3): the groups are sets of batch rows, ``groups.n_series == B`` - the pipeline layout, one series
+    per row, ``samples`` [P,B,H,1] - and ``y`` [B,H,N] is totalled along dim 0; the results are [.., G, H', N]."""
+    ax = _group_path_axis("group_path_summary", samples, axis)
+    if y is not None and (not isinstance(y, torch.Tensor) or tuple(y.shape) != tuple(samples.shape[1:])):
+        raise ValueError(f"group_path_summary: y must be [B, H, N] = {tuple(samples.shape[1:])}")
+    totals = group_sums(samples, groups, backend, axis=ax)
     yt = None
     if y is not None:
-        if not isinstance(y, torch.Tensor) or tuple(y.shape) != tuple(samples.shape[1:]):
-            raise ValueError(f"group_path_summary: y must be [B, H, N] = {tuple(samples.shape[1:])}")
-        yt = group_sums(y.detach().to(device=samples.device, dtype=torch.float32), groups, backend)
+        yt = group_sums(y.detach().to(device=samples.device, dtype=torch.float32), groups, backend, axis=ax - 1)
     return path_summary(totals, levels, yt, window, reduce, want_sorted, backend)
 
 
 def group_path_metrics(samples: torch.Tensor, y: torch.Tensor, groups: SeriesGroups, levels,
-                       window: Optional[int] = None, reduce: str = "sum", mask: torch.Tensor | None = None
-                       ) -> Dict[str, torch.Tensor]:
+                       window: Optional[int] = None, reduce: str = "sum", mask: torch.Tensor | None = None,
+                       axis: int = -1) -> Dict[str, torch.Tensor]:
     """``path_metrics`` on the group totals of ``samples`` [P,B,H,N] and ``y`` [B,H,N].  With ``mask`` [B,H,N] an
     element (b, h', g) is valid only if every member series of g is inside the mask at every step of its window: the
-    group total of the masked-out indicator is 0 there (a count, exact), formed on the device."""
-    if not isinstance(samples, torch.Tensor) or samples.dim() != 4:
-        raise ValueError("group_path_metrics takes samples [P, B, H, N]")
+    group total of the masked-out indicator is 0 there (a count, exact), formed on the device.
+    ``axis=1`` (or -3): the groups are sets of batch rows (``groups.n_series == B``); ``y`` and ``mask`` are totalled
+    along dim 0 and an element (g, h', n) is valid only if every member row is inside the mask."""
+    ax = _group_path_axis("group_path_metrics", samples, axis)
     if not isinstance(y, torch.Tensor) or tuple(y.shape) != tuple(samples.shape[1:]):
         raise ValueError(f"group_path_metrics: y must be [B, H, N] = {tuple(samples.shape[1:])}")
-    totals = group_sums(samples, groups)
-    yt = group_sums(y.detach().to(device=samples.device, dtype=torch.float32), groups)
+    if mask is not None and tuple(mask.shape) != tuple(y.shape):
+        raise ValueError(f"group_path_metrics: mask must be [B, H, N] = {tuple(y.shape)}, got {tuple(mask.shape)}")
+    totals = group_sums(samples, groups, axis=ax)
+    yt = group_sums(y.detach().to(device=samples.device, dtype=torch.float32), groups, axis=ax - 1)
     gmask = None
     if mask is not None:
-        if tuple(mask.shape) != tuple(y.shape):
-            raise ValueError(f"group_path_metrics: mask must be [B, H, N] = {tuple(y.shape)}, got {tuple(mask.shape)}")
         outside = (~mask.to(device=samples.device).to(torch.bool)).to(torch.float32)
-        gmask = group_sums(outside, groups) == 0
+        gmask = group_sums(outside, groups, axis=ax - 1) == 0
     return path_metrics(totals, yt, levels, window, reduce, gmask)

@@ -682,6 +682,47 @@ int ftn_group_sum_form(int N, long long row_stride, int misalign_or, int n_chunk
 int ftn_group_sum(const float* x_dev, long long rows, int N, long long row_stride, const int* order_dev,
                   const int* offsets_dev, const int* offsets_host, int G, int M, float* out_dev, void* stream);
 
+/* ---- series groups along an axis that is not the fastest one (groups_rows.hip) ----
+ * Additions only: FTN_ABI_VERSION stays 14.
+ *
+ * ftn_group_sum_rows (k_group_sum_rows<VEC>): x is fp32 [outer][S][inner], element (o, s, i) at
+ * x + o outer_stride + s member_stride + i (inner contiguous); out is fp32 [outer][G][inner], contiguous.  The CSR
+ * (order [M] with members in 0 .. S - 1, offsets [G + 1], offsets_host) is that of ftn_group_sum.  For every (o, i)
+ * the column x[o][.][i] is summed per group by rules 1-4 of ftn_group_sum, so the result equals ftn_group_sum on the
+ * transposed copy bit for bit, and its guarantees carry over: an empty group gives +0; NaN and inf reach only the
+ * groups that hold them; integer totals below 2^24 are exact; a group's result is a function of its member list and
+ * of its column alone - not of outer, of inner, of where the column falls in a tile, of the load width, of the grid
+ * or of the other groups.  No atomics; no loop bound depends on the data, only on the CSR.  What the kernel reads
+ * from the device CSR is clamped: offsets to 0 .. M, and a member outside 0 .. S - 1 contributes +0 and touches no
+ * memory.
+ * Limits, checked before the launch: 1 <= S < 2^31 (no FTN_GROUP_NMAX: the member axis is walked, not staged),
+ * 1 <= G <= FTN_GROUP_GMAX, at most FTN_GROUP_CHUNKS_MAX chunks; outer >= 1, inner >= 1; member_stride >= inner;
+ * outer_stride >= S member_stride unless outer == 1 (then it is ignored); S member_stride, outer outer_stride and
+ * outer G inner formed in 64 bits and rejected on overflow; offsets_host monotone from 0 to M; every pointer non-null
+ * (order may be null when M = 0) and 4-byte aligned.  Anything else is a negative return with ftn_last_error set and
+ * nothing launched.  Never allocates, never synchronises; enqueues one kernel on `stream`.
+ * A workgroup takes tiles of one o and TI consecutive inner columns, and a tile takes the chunks in passes of CP: a
+ * work item (chunk, column), columns fastest along the lanes, walks its chunk's members with an fp64 accumulator and
+ * leaves the chunk sum in LDS ([CP][TI] fp64); after a barrier one thread per (group, column) adds that group's chunk
+ * sums of the pass in ascending order and stores, columns fastest; the one group that runs past the end of a pass
+ * hands its fp64 running sum to the next pass through LDS - the same chain of additions.
+ * ftn_group_sum_rows_form (host-only; the launch dispatches through the same function):
+ *   bit 1       FTN_SHELL_VEC  16-byte loads of x and stores of out along inner, an item taking 4 columns:
+ *               inner % 4 == 0, member_stride % 4 == 0, outer_stride % 4 == 0 and misalign_or == 0; otherwise 4-byte
+ *               loads and stores.  Either way consecutive columns lie on consecutive lanes.
+ *   bits 8-15   TI, the inner columns of a tile: min(inner, FTN_GROUP_TILE_COLS), rounded down to a multiple of 4
+ *               when it is 4 or more - a member row's columns are one contiguous run, the whole row up to 64.
+ *   bits 16-27  the passes of a tile: ceil(n_chunks / CP), at least 1, with CP = FTN_GROUP_TILE_BYTES / (8 TI) chunks a
+ *               pass (the chunk sums of a pass stay within FTN_GROUP_TILE_BYTES of LDS; 512 chunks of 8 columns, 146
+ *               of 28, 64 of 64).
+ * misalign_or: ((address of x) | (address of out)) & 15.  outer_stride: 0 when outer == 1. */
+#define FTN_GROUP_TILE_COLS 64
+int ftn_group_sum_rows_form(long long inner, long long member_stride, long long outer_stride, int misalign_or,
+                            int n_chunks);
+int ftn_group_sum_rows(const float* x_dev, long long outer, int S, long long inner, long long outer_stride,
+                       long long member_stride, const int* order_dev, const int* offsets_dev, const int* offsets_host,
+                       int G, int M, float* out_dev, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
