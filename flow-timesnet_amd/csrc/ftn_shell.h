@@ -1,0 +1,65 @@
+// What the model-shell kernels of shell.hip (d_model <= 128) and shell_wide.hip (128 < d_model <= 512) share: the
+// argument blocks of the heads, the value embedding and the ring epilogue, and the heads' softplus.
+#pragma once
+#include "ftn_common.h"
+
+// softplus(beta=1, threshold=20) as torch evaluates it (x > 20 -> x, else log1p(exp(x))), in the
+// overflow-free form max(x,0) + log1p(exp(-|x|)).  exp2/log2 are the raw hardware ops (1 ulp).  Two roundings would
+// each cost more than those: t = -|x| log2(e) rounded to fp32 is a relative error of |x| 2^-24 in e (5 ulp of the
+// result at x = -10), so t is carried as hi + lo and the lo part applied to e; and 1 + e rounded is a relative error
+// of 2^-24 / e in log(1 + e) (32 ulp just above e = 2^-6), so the rounding error of the sum is handed back through
+// log(u + d) = log(u) + d / u.  Below 2^-6 the series replaces the logarithm.  |x| is clamped at 128 (e = 0 in fp32
+// from |x| = 104 on) so that an infinite x does not meet inf - inf in the lo part; a NaN stays a NaN.
+__device__ __forceinline__ float softplus20(float x) {
+  if (x > 20.f) return x;
+  const float ax = fabsf(x);
+  const float a = ax > 128.f ? -128.f : -ax;
+  const float th = a * 1.44269504088896341f;
+  const float tl = fmaf(a, 1.44269504088896341f, -th) + a * 1.925963033500011e-8f;
+  float e = __builtin_amdgcn_exp2f(th);
+  e = fmaf(e, tl * 0.69314718055994531f, e);
+  const float series = e * (1.f - e * (0.5f - e * (0.33333333333f - 0.25f * e)));
+  const float u = 1.f + e;
+  const float lg = fmaf(__builtin_amdgcn_logf(u), 0.69314718055994531f, (e - (u - 1.f)) * __builtin_amdgcn_rcpf(u));
+  return fmaxf(x, 0.f) + (e < 0.015625f ? series : lg);
+}
+
+struct HeadArgs {
+  const float* hidden;   // [rows][D]
+  const float* wmu;      // [N][D]
+  const float* bmu;      // [N]
+  const float* wsg;
+  const float* bsg;
+  const float* tail;     // element (b, s, n) at tail[b * tail_bs + min(s, hist-1) * N + n]
+  const float* late;     // optional, element (b, s, n) at late[b * late_bs + s * N + n]
+  const float* floorv;   // optional [N]
+  float* rate;           // [rows][N]
+  float* disp;
+  int* bad;              // |= 1 if a rate is not finite-positive, |= 2 for a dispersion
+  long long rows, tail_bs, late_bs;
+  int S, D, N, hist;
+  float floor_s;
+};
+
+struct EmbedArgs {
+  const float* x;
+  const float* W;        // [D][N]
+  const float* add;      // optional
+  const float* ln_g;     // optional LayerNorm epilogue ("layer" mode)
+  const float* ln_b;
+  float* out;            // row (b, l) at out + b * out_bs + l * D
+  long long x_bs, add_bs, out_bs;
+  int B, L, N, D;
+  float ln_eps;
+};
+
+struct RingArgs {
+  const float* V;        // [B][L][D]
+  const float* add;      // optional, row (b, t) at add + b * add_bs + t * D
+  const float* ln_g;
+  const float* ln_b;
+  float* out;            // [B][L][D]
+  long long add_bs;
+  int B, L, D, head;
+  float ln_eps;
+};

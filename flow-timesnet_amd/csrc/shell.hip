@@ -7,44 +7,7 @@
 #include <stdlib.h>
 #include "ftn_common.h"
 #include "ftn_mlp.h"
-
-// softplus(beta=1, threshold=20) as torch evaluates it (x > 20 -> x, else log1p(exp(x))), in the
-// overflow-free form max(x,0) + log1p(exp(-|x|)).  exp2/log2 are the raw hardware ops (1 ulp).  Two roundings would
-// each cost more than those: t = -|x| log2(e) rounded to fp32 is a relative error of |x| 2^-24 in e (5 ulp of the
-// result at x = -10), so t is carried as hi + lo and the lo part applied to e; and 1 + e rounded is a relative error
-// of 2^-24 / e in log(1 + e) (32 ulp just above e = 2^-6), so the rounding error of the sum is handed back through
-// log(u + d) = log(u) + d / u.  Below 2^-6 the series replaces the logarithm.  |x| is clamped at 128 (e = 0 in fp32
-// from |x| = 104 on) so that an infinite x does not meet inf - inf in the lo part; a NaN stays a NaN.
-__device__ __forceinline__ float softplus20(float x) {
-  if (x > 20.f) return x;
-  const float ax = fabsf(x);
-  const float a = ax > 128.f ? -128.f : -ax;
-  const float th = a * 1.44269504088896341f;
-  const float tl = fmaf(a, 1.44269504088896341f, -th) + a * 1.925963033500011e-8f;
-  float e = __builtin_amdgcn_exp2f(th);
-  e = fmaf(e, tl * 0.69314718055994531f, e);
-  const float series = e * (1.f - e * (0.5f - e * (0.33333333333f - 0.25f * e)));
-  const float u = 1.f + e;
-  const float lg = fmaf(__builtin_amdgcn_logf(u), 0.69314718055994531f, (e - (u - 1.f)) * __builtin_amdgcn_rcpf(u));
-  return fmaxf(x, 0.f) + (e < 0.015625f ? series : lg);
-}
-
-struct HeadArgs {
-  const float* hidden;   // [rows][D]
-  const float* wmu;      // [N][D]
-  const float* bmu;      // [N]
-  const float* wsg;
-  const float* bsg;
-  const float* tail;     // element (b, s, n) at tail[b * tail_bs + min(s, hist-1) * N + n]
-  const float* late;     // optional, element (b, s, n) at late[b * late_bs + s * N + n]
-  const float* floorv;   // optional [N]
-  float* rate;           // [rows][N]
-  float* disp;
-  int* bad;              // |= 1 if a rate is not finite-positive, |= 2 for a dispersion
-  long long rows, tail_bs, late_bs;
-  int S, D, N, hist;
-  float floor_s;
-};
+#include "ftn_shell.h"
 
 // One workgroup owns a 64-wide slice of the N output series: the two weight slices live in LDS in
 // MFMA A-fragment order (row i of tile o is series n0 + 16*o + i: the four q-lanes of a row cover one
@@ -379,17 +342,6 @@ extern "C" int ftn_head_forward(const float* hidden_dev, long long rows, int S, 
 // positional / time-feature term (gate * LayerNorm(aux) in "decoupled" mode), and the low-rank
 // temporal context and constant context bias pushed through W (so the [B, L, N] context tensor is
 // never materialised).  Reads x once: HBM-bound at 4*B*L*N bytes.
-struct EmbedArgs {
-  const float* x;
-  const float* W;        // [D][N]
-  const float* add;      // optional
-  const float* ln_g;     // optional LayerNorm epilogue ("layer" mode)
-  const float* ln_b;
-  float* out;            // row (b, l) at out + b * out_bs + l * D
-  long long x_bs, add_bs, out_bs;
-  int B, L, N, D;
-  float ln_eps;
-};
 
 // + add, optional LayerNorm over one row held by the four q-lanes of a 16-row tile: lane (j, q) holds columns
 // 16*o + 4*q .. +3 of row j in v[o].  Shared by the GEMM epilogue and the ring epilogue (k_embed_ring), so that a row
@@ -747,16 +699,6 @@ extern "C" int ftn_embed_rows_strided(const float* x_dev, long long x_bstride, i
 // V holds value-embedded rows x W^T (no bias, add or norm) of a sliding window as a ring: the oldest row sits in
 // slot `head`.  One memory-bound pass: reads V and add, writes the window's embedding in time order.  Lane layout,
 // add and LayerNorm are the GEMM epilogue's (embed_row_finish): 16 rows per wave, four lanes per row.
-struct RingArgs {
-  const float* V;        // [B][L][D]
-  const float* add;      // optional, row (b, t) at add + b * add_bs + t * D
-  const float* ln_g;
-  const float* ln_b;
-  float* out;            // [B][L][D]
-  long long add_bs;
-  int B, L, D, head;
-  float ln_eps;
-};
 
 template <int NO>
 __global__ __launch_bounds__(256) void k_embed_ring(RingArgs a) {

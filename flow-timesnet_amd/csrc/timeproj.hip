@@ -203,3 +203,82 @@ extern "C" int ftn_timeproj_forward(const float* seq_dev, int B, int L, int D, c
     default: return launch_timeproj_bf<6>(a, form, st);
   }
 }
+
+// ---------------------------------------------------------------------------------------------
+// 128 < d_model <= 512 (ftn_timeproj_wide_forward)
+// ---------------------------------------------------------------------------------------------
+// k_timeproj_bf tiles d_model in 64-column groups and is launched as it is.  The row form needs D / 4 <= 32 threads a
+// row group, so S == 1 gets a form of its own: a workgroup owns (batch row b, 128-column slab blockIdx.y), thread
+// (c, g) walks rows l = g, g + 16, ... of the slab's columns 4 c .. 4 c + 3 and the 16 partial sums are added in group
+// order.  The group count is fixed, so the order over l depends on L alone.
+__global__ __launch_bounds__(TP_ROW_THREADS) void k_timeproj_row_wide(TimeProjArgs a) {
+  __shared__ float wl[TP_ROW_CHUNK];
+  __shared__ f4 red[TP_ROW_THREADS];
+  constexpr int C = 32, G = TP_ROW_THREADS / C;
+  const int c = threadIdx.x % C, g = threadIdx.x / C;
+  const int d = 128 * blockIdx.y + 4 * c;
+  const bool active = d < a.D;                                  // D % 4 == 0: a quad is all inside a row or all outside
+  const float* __restrict__ sp = a.seq + (size_t)blockIdx.x * a.L * a.D + d;
+  f4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int l0 = 0; l0 < a.L; l0 += TP_ROW_CHUNK) {
+    const int n = a.L - l0 < TP_ROW_CHUNK ? a.L - l0 : TP_ROW_CHUNK;
+    for (int i = threadIdx.x; i < n; i += TP_ROW_THREADS) wl[i] = a.wt[l0 + i];
+    __syncthreads();
+    if (active) {
+#pragma unroll 4
+      for (int l = g; l < n; l += G) {
+        const f4 v = *(const f4*)(sp + (size_t)(l0 + l) * a.D);
+        const float w = wl[l];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = fmaf(w, v[k], acc[k]);
+      }
+    }
+    __syncthreads();
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x < C && active) {
+    f4 sum = red[threadIdx.x];
+    for (int gg = 1; gg < G; ++gg) sum = sum + red[gg * C + threadIdx.x];
+    const float bias = a.bt[0];
+    *(f4*)(a.hid + (size_t)blockIdx.x * a.D + d) = sum + f4{bias, bias, bias, bias};
+  }
+}
+
+static inline bool timeproj_wide_ok(int D) { return D > 128 && D <= 512 && D % 4 == 0; }
+
+// The encoding of ftn_timeproj_form: 0 is the wide row form here (k_timeproj_row_wide)
+extern "C" int ftn_timeproj_wide_form(int L, int S, int D, int wt_misalign) {
+  FTN_CHECK_ARG(L >= 1 && S >= 1 && timeproj_wide_ok(D) && wt_misalign >= 0 && wt_misalign < 16 && wt_misalign % 4 == 0,
+                "ftn_timeproj_wide_form: L=%d S=%d d_model=%d misalign=%d", L, S, D, wt_misalign);
+  return timeproj_form(L, S, (unsigned)wt_misalign);
+}
+
+extern "C" int ftn_timeproj_wide_forward(const float* seq_dev, int B, int L, int D, const float* wt_dev,
+                                         const float* bt_dev, int S, float* hidden_dev, void* stream) {
+  FTN_CHECK_ARG(seq_dev && wt_dev && bt_dev && hidden_dev, "ftn_timeproj_wide_forward: null pointer");
+  FTN_CHECK_ARG(B >= 1 && L >= 1 && S >= 1, "ftn_timeproj_wide_forward: bad shape B=%d L=%d S=%d", B, L, S);
+  FTN_CHECK_ARG(timeproj_wide_ok(D), "ftn_timeproj_wide_forward: d_model=%d must be a multiple of 4, > 128 and <= 512", D);
+  FTN_CHECK_ARG((((uintptr_t)seq_dev | (uintptr_t)hidden_dev) & 15) == 0,
+                "ftn_timeproj_wide_forward: seq and hidden must be 16-byte aligned");
+  FTN_CHECK_ARG((((uintptr_t)wt_dev | (uintptr_t)bt_dev) & 3) == 0,
+                "ftn_timeproj_wide_forward: W_t and b_t must be 4-byte aligned");
+  FTN_CHECK_ARG((long long)B * ((D + 63) / 64) <= 0x7fffffffLL && (S + 15) / 16 <= 65535,
+                "ftn_timeproj_wide_forward: B=%d S=%d exceed the launch grid", B, S);
+  TimeProjArgs a;
+  a.seq = seq_dev; a.wt = wt_dev; a.bt = bt_dev; a.hid = hidden_dev;
+  a.B = B; a.L = L; a.D = D; a.S = S;
+  const int form = timeproj_form(L, S, (unsigned)((uintptr_t)wt_dev & 15));
+  hipStream_t st = (hipStream_t)stream;
+  if (!(form & FTN_SHELL_BF)) {
+    hipLaunchKernelGGL(k_timeproj_row_wide, dim3((unsigned)B, (unsigned)((D + 127) / 128)), dim3(TP_ROW_THREADS), 0, st, a);
+    FTN_CHECK_LAUNCH();
+    return 0;
+  }
+  switch ((form >> 4) & 15) {
+    case 1: return launch_timeproj_bf<1>(a, form, st);
+    case 2: return launch_timeproj_bf<2>(a, form, st);
+    case 4: return launch_timeproj_bf<4>(a, form, st);
+    default: return launch_timeproj_bf<6>(a, form, st);
+  }
+}

@@ -19,10 +19,13 @@ flags of the blocks are collected for every step and read once after the forecas
 the whole unrolled H-step forecast as one HIP graph (every ring slot is a Python integer at capture time, so no device
 counter is needed).  Both are bit-identical to the reference loop driven over the same model on the same device.
 
-Anything else - CPU tensors, a ``direct``-mode model, autograd, ``embed_norm_mode="rms"``, d_model > 128, a foreign
-model, a ``last_seq`` whose window takes another embedding kernel than the loop's later windows (a view that is not
-16-byte aligned, or whose batch stride is not a multiple of 4, with N % 4 == 0), ``embed_norm_mode="layer"`` at a
-d_model that is not a multiple of 16 - runs the reference's loop unchanged (``forecast_recursive_batch_loop``).
+Anything else - CPU tensors, a ``direct``-mode model, autograd, ``embed_norm_mode="rms"``, d_model > 512 (> 128 under
+``FTN_SHELL_WIDE=0``), a foreign model, a ``last_seq`` whose window takes another embedding kernel than the loop's later
+windows (a view that is not 16-byte aligned, or whose batch stride is not a multiple of 4, with N % 4 == 0),
+``embed_norm_mode="layer"`` at a d_model <= 128 that is not a multiple of 16 or on a form outside
+``RING_EXACT_LAYER_FORMS`` - runs the reference's loop unchanged (``forecast_recursive_batch_loop``).  Beyond d_model 128
+the wide embedding and the wide ring share one epilogue function compiled without FMA contraction, so all four wide
+forms are in that set at every d_model.
 
 ``forecast_sample_paths`` is the same recursion fed with draws instead of rates (``score.nb_sample`` at
 ``offset = step``), P paths as one batch of P B rows; ``forecast_sample_paths_loop`` fixes its semantics.
@@ -45,7 +48,8 @@ _RANGE_WARNING = ("TimesBlock: a value left the fp16 range of engine f16x2 (|v| 
 # embedding forms whose LayerNorm epilogue is bit-identical to k_embed_ring's at d_model % 16 == 0: the default forms
 # bar the fp32-MFMA one of d_model > 64 (k_embed_in<8, *>); the forms behind FTN_EMBED_F32 / FTN_EMBED_RT are not
 # (k_embed_in_bf<8,2> differs in the last bit) or not established
-RING_EXACT_LAYER_FORMS = frozenset({"k_embed_in_bf<4,2>", "k_embed_in_bf<8,1>", "k_embed_in<4,false>"})
+_WIDE_FORMS = frozenset(f"k_embed_wide_bf<{no},4,{vec}>" for no in (4, 8) for vec in ("true", "false"))   # exact at every d_model
+RING_EXACT_LAYER_FORMS = frozenset({"k_embed_in_bf<4,2>", "k_embed_in_bf<8,1>", "k_embed_in<4,false>"}) | _WIDE_FORMS
 
 
 def _invoke_model(model, xb, x_mark=None, series_static=None, series_ids=None):
@@ -149,7 +153,7 @@ def _prepare(model, last_seq, x_mark, series_static, series_ids):
     w = model.embedding.value_embedding.weight.detach()
     B, T, N = last_seq.shape
     form = runtime.embed_form(window, w)
-    if form != runtime.embed_form_of(N, w.size(0), T * N if B > 1 else 0, 0, w.data_ptr() & 15):
+    if form != runtime.embed_form_at(N, w.size(0), T * N if B > 1 else 0, 0, w.data_ptr() & 15):
         return False
     # "layer" mode: the compiler contracts the LayerNorm epilogue of the GEMM kernels into FMAs differently from
     # k_embed_ring's on some forms, and on every form at a d_model that is not a multiple of 16 (partly masked column
@@ -157,7 +161,7 @@ def _prepare(model, last_seq, x_mark, series_static, series_ids):
     # whose bit-identity the GPU suite establishes and the loop runs for the rest
     if model.embedding.embed_norm_mode != "layer":
         return True
-    return model.d_model % 16 == 0 and form in RING_EXACT_LAYER_FORMS
+    return form in RING_EXACT_LAYER_FORMS and (model.d_model % 16 == 0 or form in _WIDE_FORMS)
 
 
 def _device_ok(model, last_seq, H, x_mark, y_mark, series_static, series_ids) -> bool:

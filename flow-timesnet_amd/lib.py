@@ -187,6 +187,19 @@ _SIGNATURES = {
     "ftn_head_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_timeproj_forward": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "ftn_timeproj_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    # 128 < d_model <= 512: the signatures of the narrow entry points above
+    "ftn_embed_wide_forward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong,
+                                         _P, _P, C.c_float, _P, _P]),
+    "ftn_embed_wide_rows_strided": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P,
+                                              C.c_longlong, _P]),
+    "ftn_embed_wide_ring": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, _P, C.c_float, _P,
+                                      _P]),
+    "ftn_head_wide_forward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_longlong,
+                                        C.c_int, _P, C.c_longlong, _P, C.c_float, _P, _P, _P, _P]),
+    "ftn_timeproj_wide_forward": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "ftn_embed_wide_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]),
+    "ftn_head_wide_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_timeproj_wide_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_score_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_score_columns": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, _P, C.c_int, C.c_float,
                                     C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -17,11 +17,14 @@ forecaster (``forecast.py``) and the series-sharded forward (``dist.SeriesSharde
 * embedding - ``_context_terms``, then ``_through_weight`` + ``_embed_epilogue`` (HIP) or ``_with_context`` (torch);
 * heads - ``_late_bias``, ``_time_projection``, ``_rate_dispersion``.
 
-``hip_width_ok`` is the one statement of the d_model these kernels take.
+``hip_shell_width_ok`` is the one statement of the d_model these kernels take (up to 512: the narrow entry points up
+to 128, the ``ftn_*_wide_*`` ones beyond, chosen in ``runtime``); ``hip_width_ok`` is the narrower limit of the
+series-sharded forward's row exchange.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
@@ -41,8 +44,17 @@ def _place(module: nn.Module, ref: torch.Tensor) -> nn.Module:
 
 
 def hip_width_ok(d_model: int) -> bool:
-    """The d_model the shell's HIP kernels (embedding, time projection, heads) take."""
+    """The d_model the narrow shell kernels and the row exchange of the series-sharded forward (``ftn_rowx_*``) take."""
     return d_model % 4 == 0 and d_model <= 128
+
+
+# FTN_SHELL_WIDE=0 (read once): the shell at d_model > 128 composes torch ops, as before the wide kernels (A/B runs)
+_SHELL_WIDE = os.environ.get("FTN_SHELL_WIDE", "1").strip() != "0"
+
+
+def hip_shell_width_ok(d_model: int) -> bool:
+    """The d_model the shell's HIP kernels (embedding, time projection, heads) take: multiples of 4 up to 512."""
+    return d_model % 4 == 0 and d_model <= (512 if _SHELL_WIDE else 128)
 
 
 # -------------------------------------------------------------------------
@@ -486,7 +498,7 @@ class TimesNet(nn.Module):
             return False
         return (window.is_cuda and window.dtype == torch.float32
                 and not (torch.is_grad_enabled() and (window.requires_grad or emb.value_embedding.weight.requires_grad))
-                and not (self.training and self.dropout > 0.0) and hip_width_ok(self.d_model)
+                and not (self.training and self.dropout > 0.0) and hip_shell_width_ok(self.d_model)
                 and window.stride(2) == 1 and window.stride(1) == window.size(2))
 
     def _context_terms(self, rows):
@@ -577,7 +589,7 @@ class TimesNet(nn.Module):
         params = (self.forecast_time_proj.weight, self.mu_head.weight, self.sigma_head.weight)
         return (seq.is_cuda and seq.dtype == torch.float32 and window.dtype == torch.float32
                 and not (torch.is_grad_enabled() and (seq.requires_grad or any(p.requires_grad for p in params)))
-                and hip_width_ok(self.d_model)
+                and hip_shell_width_ok(self.d_model)
                 and window.stride(2) == 1 and window.stride(1) == window.size(2))
 
     def _late_bias(self, rows) -> Optional[torch.Tensor]:
@@ -731,7 +743,7 @@ class TimesNet(nn.Module):
     def series_hidden(self, seq: torch.Tensor, steps: int) -> torch.Tensor:
         """``forecast_time_proj`` of the local rows: ``[B_local, steps, d_model]`` (as ``_heads``)."""
         return self._time_projection(seq, steps, seq.is_cuda and seq.dtype == torch.float32
-                                     and hip_width_ok(self.d_model))
+                                     and hip_shell_width_ok(self.d_model))
 
     def series_heads(self, hidden, window, rows, sl: dict, steps: int):
         """``(rate, dispersion, bad)`` of this rank's series from the gathered ``hidden [B, steps, D]``."""

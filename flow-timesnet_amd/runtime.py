@@ -275,6 +275,11 @@ def timesblock_forms(plan: FtnPlan, B: int, L: int, act_dtype: int = 0, x_misali
             "r_summed": bool(f.r_summed), "E": _STAGE_E[f.stage_e].format(ns=ns), "half_round": bool(f.half_round)}
 
 
+def _wide(D: int) -> bool:
+    """d_model beyond the narrow shell kernels: the ``ftn_*_wide_*`` entry points (128 < D <= 512) take the call."""
+    return int(D) > 128
+
+
 def _embed_form_name(f: int) -> str:
     no, rt = (f >> 4) & 15, (f >> 8) & 15
     return f"k_embed_in_bf<{no},{rt}>" if f & 1 else f"k_embed_in<{no},{'true' if f & 2 else 'false'}>"
@@ -283,43 +288,82 @@ def _embed_form_name(f: int) -> str:
 def embed_form_of(N: int, D: int, x_bstride: int = 0, x_misalign: int = 0, w_misalign: int = 0) -> str:
     """The kernel ``ftn_embed_forward`` / ``ftn_embed_rows_strided`` run for a window of N series into d_model D with
     this batch stride (elements) and these byte offsets of x and W from a 16-byte boundary (``ftn_embed_form``,
-    host-only: the launch dispatches through the same function, switches included)."""
+    host-only: the launch dispatches through the same function, switches included).  D <= 128."""
     f = _form("ftn_embed_form", N, D, x_bstride, x_misalign, w_misalign)
     return _embed_form_name(f)
+
+
+def embed_wide_form_of(N: int, D: int, x_bstride: int = 0, x_misalign: int = 0, w_misalign: int = 0) -> str:
+    """``embed_form_of`` for 128 < D <= 512 (``ftn_embed_wide_form``): ``k_embed_wide_bf<NO,RT,VEC>``."""
+    f = _form("ftn_embed_wide_form", N, D, x_bstride, x_misalign, w_misalign)
+    return f"k_embed_wide_bf<{(f >> 4) & 15},{(f >> 8) & 15},{'true' if f & 2 else 'false'}>"
+
+
+def embed_form_at(N: int, D: int, x_bstride: int = 0, x_misalign: int = 0, w_misalign: int = 0) -> str:
+    """The kernel ``embed_forward`` / ``embed_rows_strided`` run at any d_model they take: the narrow query up to 128,
+    the wide one beyond."""
+    return (embed_wide_form_of if _wide(D) else embed_form_of)(N, D, x_bstride, x_misalign, w_misalign)
 
 
 def embed_form(window: torch.Tensor, weight: torch.Tensor) -> str:
     """The kernel ``embed_forward(window, weight, ...)`` / ``embed_rows_strided(window, weight, ...)`` runs."""
     B, _, N = window.shape
-    return embed_form_of(N, weight.shape[0], window.stride(0) if B > 1 else 0, _ptr(window) & 15, _ptr(weight) & 15)
+    return embed_form_at(N, weight.shape[0], window.stride(0) if B > 1 else 0, _ptr(window) & 15, _ptr(weight) & 15)
 
 
 def head_form_of(N: int, D: int, tail_bstride: int = 0, late_bstride: int = 0, misalign_or: int = 0) -> Tuple[str, int]:
     """The kernel ``ftn_head_forward`` runs (``ftn_head_form``, host-only) and the cap on its ``gridDim.y``: the
-    row loop of a workgroup iterates when ``rows > 64 * cap``."""
+    row loop of a workgroup iterates when ``rows > 64 * cap``.  D <= 128."""
     f = _form("ftn_head_form", N, D, tail_bstride, late_bstride, misalign_or)
     p0, p1, cap = (f >> 4) & 15, (f >> 8) & 15, f >> 16
     return (f"k_head_bf<{p0},{p1}>" if f & 1 else f"k_head<{p0},{'true' if f & 2 else 'false'}>"), cap
 
 
+def head_wide_form_of(N: int, D: int, tail_bstride: int = 0, late_bstride: int = 0,
+                      misalign_or: int = 0) -> Tuple[str, int]:
+    """``head_form_of`` for 128 < D <= 512 (``ftn_head_wide_form``): ``k_head_wide_bf<NT>`` and its cap, or
+    ``("k_head_wide_f32", 0)`` for operands that are not vectorisable (a grid-stride kernel: no cap)."""
+    f = _form("ftn_head_wide_form", N, D, tail_bstride, late_bstride, misalign_or)
+    return (f"k_head_wide_bf<{(f >> 4) & 15}>", f >> 16) if f & 1 else ("k_head_wide_f32", 0)
+
+
+def head_form_at(N: int, D: int, tail_bstride: int = 0, late_bstride: int = 0, misalign_or: int = 0) -> Tuple[str, int]:
+    """The kernel ``head_forward`` runs at any d_model it takes."""
+    return (head_wide_form_of if _wide(D) else head_form_of)(N, D, tail_bstride, late_bstride, misalign_or)
+
+
 def head_form(hidden: torch.Tensor, w_mu: torch.Tensor, tail: torch.Tensor, late=None) -> Tuple[str, int]:
-    """``head_form_of`` for the tensors ``head_forward`` would be given (its outputs are fresh, aligned tensors)."""
+    """``head_form_at`` for the tensors ``head_forward`` would be given (its outputs are fresh, aligned tensors)."""
     B = hidden.shape[0]
     mis = (_ptr(tail) | (_ptr(late) if late is not None else 0)) & 15
-    return head_form_of(w_mu.shape[0], hidden.shape[2], tail.stride(0) if B > 1 else 0, _batch_stride(late, B), mis)
+    return head_form_at(w_mu.shape[0], hidden.shape[2], tail.stride(0) if B > 1 else 0, _batch_stride(late, B), mis)
+
+
+def _timeproj_form_name(f: int, row: str) -> str:
+    return f"k_timeproj_bf<{(f >> 4) & 15},{'true' if f & 2 else 'false'}>" if f & 1 else row
 
 
 def timeproj_form_of(L: int, S: int, D: int, wt_misalign: int = 0) -> str:
     """The kernel ``ftn_timeproj_forward`` runs for an ``L -> S`` projection at d_model D with W_t at this byte
     offset from a 16-byte boundary (``ftn_timeproj_form``, host-only: the launch dispatches through the same
-    function): ``k_timeproj_row`` for S == 1, else ``k_timeproj_bf<NST,WV>``."""
-    f = _form("ftn_timeproj_form", L, S, D, wt_misalign)
-    return f"k_timeproj_bf<{(f >> 4) & 15},{'true' if f & 2 else 'false'}>" if f & 1 else "k_timeproj_row"
+    function): ``k_timeproj_row`` for S == 1, else ``k_timeproj_bf<NST,WV>``.  D <= 128."""
+    return _timeproj_form_name(_form("ftn_timeproj_form", L, S, D, wt_misalign), "k_timeproj_row")
+
+
+def timeproj_wide_form_of(L: int, S: int, D: int, wt_misalign: int = 0) -> str:
+    """``timeproj_form_of`` for 128 < D <= 512 (``ftn_timeproj_wide_form``): ``k_timeproj_row_wide`` for S == 1, else
+    the same ``k_timeproj_bf<NST,WV>``."""
+    return _timeproj_form_name(_form("ftn_timeproj_wide_form", L, S, D, wt_misalign), "k_timeproj_row_wide")
+
+
+def timeproj_form_at(L: int, S: int, D: int, wt_misalign: int = 0) -> str:
+    """The kernel ``timeproj_forward`` runs at any d_model it takes."""
+    return (timeproj_wide_form_of if _wide(D) else timeproj_form_of)(L, S, D, wt_misalign)
 
 
 def timeproj_form(seq: torch.Tensor, wt: torch.Tensor) -> str:
     """The kernel ``timeproj_forward(seq, wt, bt)`` runs."""
-    return timeproj_form_of(seq.shape[1], wt.shape[0], seq.shape[2], _ptr(wt) & 15)
+    return timeproj_form_at(seq.shape[1], wt.shape[0], seq.shape[2], _ptr(wt) & 15)
 
 
 # ------------------------------------------------------------------ conv path
@@ -385,10 +429,11 @@ def head_forward(hidden: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor, w
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     if late is not None and (late.shape[-2:] != (S, N) or not late.is_contiguous()):
         raise ValueError("late bias must be contiguous [1|B, S, N]")
-    check(lib.ftn_head_forward(_ptr(hidden), B * S, S, D, N, _ptr(w_mu), _ptr(b_mu), _ptr(w_sigma), _ptr(b_sigma),
-                               _ptr(tail), tail.stride(0) if B > 1 else 0, int(hist),
-                               _ptr_or_null(late), _batch_stride(late, B), _ptr_or_null(floor_vec), float(floor_scalar),
-                               _ptr(rate), _ptr(disp), _ptr(bad), _stream(dev)), "ftn_head_forward")
+    entry = "ftn_head_wide_forward" if _wide(D) else "ftn_head_forward"
+    check(getattr(lib, entry)(_ptr(hidden), B * S, S, D, N, _ptr(w_mu), _ptr(b_mu), _ptr(w_sigma), _ptr(b_sigma),
+                              _ptr(tail), tail.stride(0) if B > 1 else 0, int(hist),
+                              _ptr_or_null(late), _batch_stride(late, B), _ptr_or_null(floor_vec), float(floor_scalar),
+                              _ptr(rate), _ptr(disp), _ptr(bad), _stream(dev)), entry)
     return rate, disp, bad
 
 
@@ -409,8 +454,8 @@ def timeproj_forward(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> t
             (S > 1 and bt.stride(0) != 1):
         raise ValueError("seq must be contiguous, wt rows contiguous with stride L, bt contiguous")
     hidden = torch.empty(B, S, D, dtype=torch.float32, device=seq.device)
-    check(lib.ftn_timeproj_forward(_ptr(seq), B, L, D, _ptr(wt), _ptr(bt), S, _ptr(hidden), _stream(seq.device)),
-          "ftn_timeproj_forward")
+    entry = "ftn_timeproj_wide_forward" if _wide(D) else "ftn_timeproj_forward"
+    check(getattr(lib, entry)(_ptr(seq), B, L, D, _ptr(wt), _ptr(bt), S, _ptr(hidden), _stream(seq.device)), entry)
     return hidden
 
 
@@ -425,9 +470,10 @@ def embed_forward(window: torch.Tensor, weight: torch.Tensor, add, norm=None) ->
     if add is not None and (add.shape[-2:] != (L, D) or not add.is_contiguous()):
         raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=window.device)
-    check(lib.ftn_embed_forward(_ptr(window), window.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
-                                _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
-                                _ptr(out), _stream(window.device)), "ftn_embed_forward")
+    entry = "ftn_embed_wide_forward" if _wide(D) else "ftn_embed_forward"
+    check(getattr(lib, entry)(_ptr(window), window.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
+                              _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
+                              _ptr(out), _stream(window.device)), entry)
     return out
 
 
@@ -442,9 +488,9 @@ def embed_rows_strided(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor,
     if (out.dim() != 3 or out.shape[0] != B or out.shape[2] != D or not out.is_contiguous()
             or out.dtype != torch.float32 or not 0 <= slot <= out.shape[1] - L):
         raise ValueError("out must be contiguous fp32 [B, Lr, D] with room for L rows from slot")
-    check(lib.ftn_embed_rows_strided(_ptr(x), x.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
-                                     _ptr(out) + 4 * slot * D, out.stride(0), _stream(x.device)),
-          "ftn_embed_rows_strided")
+    entry = "ftn_embed_wide_rows_strided" if _wide(D) else "ftn_embed_rows_strided"
+    check(getattr(lib, entry)(_ptr(x), x.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
+                              _ptr(out) + 4 * slot * D, out.stride(0), _stream(x.device)), entry)
 
 
 def embed_ring(V: torch.Tensor, head: int, add, norm=None) -> torch.Tensor:
@@ -458,8 +504,9 @@ def embed_ring(V: torch.Tensor, head: int, add, norm=None) -> torch.Tensor:
                             or not add.is_contiguous()):
         raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=V.device)
-    check(lib.ftn_embed_ring(_ptr(V), B, L, D, int(head), _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
-                             _ptr(out), _stream(V.device)), "ftn_embed_ring")
+    entry = "ftn_embed_wide_ring" if _wide(D) else "ftn_embed_ring"
+    check(getattr(lib, entry)(_ptr(V), B, L, D, int(head), _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
+                              _ptr(out), _stream(V.device)), entry)
     return out
 
 

@@ -488,6 +488,54 @@ int ftn_timeproj_forward(const float* seq_dev, int B, int L, int D, const float*
                          float* hidden_dev, void* stream);
 int ftn_timeproj_form(int L, int S, int D, int wt_misalign);
 
+/* ---- model shell at 128 < d_model <= 512 (csrc/shell_wide.hip, csrc/timeproj.hip) -----------------------------
+ * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.  The entry
+ * points above keep their limit (D <= 128), forms and bits; each one below takes the arguments of its narrow
+ * counterpart with the same meaning, alignment rules and "enqueue only, no hidden allocation" convention, for D a
+ * multiple of 4 with 128 < D <= 512.  Any other D is a bad argument, reported before any launch.  Products are bf16x3
+ * on the 16-bit matrix pipe.  The order of the K additions of an output element and of the LayerNorm reductions is a
+ * function of (N, D, form) alone: a row's bits do not depend on B, on its position in the batch or on which rows
+ * share the call; no atomics on outputs, no split of K across workgroups.
+ *
+ * Embedding (k_embed_wide_bf<NO, RT, VEC>): a workgroup of four waves owns 16 RT rows and sees their whole output
+ * row; wave w takes the 16 NO-column slab w of D.  x is read from HBM once (split once per workgroup, shared through
+ * LDS), W from L2 once per workgroup.  The wide rows entry writes the GEMM alone: its rows are bit-identical to what the wide forward holds
+ * before its epilogue.  The wide ring (k_embed_wide_ring) shares the epilogue function of the GEMM kernel.
+ * ftn_embed_wide_form (host-only; the launch dispatches through the same function):
+ *   bit 0      FTN_SHELL_BF   always set
+ *   bit 1      FTN_SHELL_VEC  16-byte loads of x and W: N % 4 == 0, x_bstride % 4 == 0 and both bases aligned;
+ *                             otherwise guarded 4-byte loads with the same arithmetic
+ *   bits 4-7   NO: 16-column tiles of a wave's slab (4 for D <= 256, else 8)
+ *   bits 8-11  RT: 16-row tiles of a workgroup (4)
+ *
+ * Heads: ftn_head_wide_form returns 0 for k_head_wide_f32 (operands that are not vectorisable, as FTN_SHELL_VEC of
+ * ftn_head_form: plain fp32 FMAs in k order), otherwise FTN_SHELL_BF | FTN_SHELL_VEC (k_head_wide_bf<NT>) with
+ *   bits 4-7   NT: 16-series tiles of a workgroup (2 for D <= 256, else 1); the split weights of both heads for
+ *              ceil(D / 32) K-32 slabs sit in LDS (6 KB per tile and slab)
+ *   bits 16-27 the cap on gridDim.y = ceil(256 W / ceil(N / (16 NT))) with W the workgroups whose LDS fits a CU's
+ *              160 KB; a workgroup walks more than one 64-row group of `hidden` when rows > 64 * cap
+ *
+ * Time projection: ftn_timeproj_wide_form has the encoding of ftn_timeproj_form; S > 1 runs k_timeproj_bf as it is,
+ * 0 (S == 1) is k_timeproj_row_wide (128-column slabs across gridDim.y, 16 row groups whatever D is). */
+int ftn_embed_wide_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev, int D,
+                           const float* add_dev_or_null, long long add_bstride, const float* ln_gamma_dev_or_null,
+                           const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream);
+int ftn_embed_wide_rows_strided(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
+                                int D, float* out_dev, long long out_bstride, void* stream);
+int ftn_embed_wide_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                        long long add_bstride, const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null,
+                        float ln_eps, float* out_dev, void* stream);
+int ftn_head_wide_forward(const float* hidden_dev, long long rows, int S, int D, int N, const float* w_mu_dev,
+                          const float* b_mu_dev, const float* w_sigma_dev, const float* b_sigma_dev,
+                          const float* tail_dev, long long tail_bstride, int hist, const float* late_dev_or_null,
+                          long long late_bstride, const float* floor_vec_dev_or_null, float floor_scalar,
+                          float* rate_dev, float* disp_dev, int* bad_flag_dev, void* stream);
+int ftn_timeproj_wide_forward(const float* seq_dev, int B, int L, int D, const float* wt_dev, const float* bt_dev,
+                              int S, float* hidden_dev, void* stream);
+int ftn_embed_wide_form(int N, int D, long long x_bstride, int x_misalign, int w_misalign);
+int ftn_head_wide_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or);
+int ftn_timeproj_wide_form(int L, int S, int D, int wt_misalign);
+
 /* ---- scoring a forecast (losses.py:27-58, train.py:675-765 of the reference) -------------------------
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
  *
