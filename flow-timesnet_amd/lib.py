@@ -116,6 +116,25 @@ class FtnForms(C.Structure):
         ("reserved", C.c_int32 * 3)]
 
 
+class FtnContextParams(C.Structure):
+    """Mirror of ``struct FtnContextParams`` (include/flowtimes.h): the parameters ``ftn_context_rows`` reads."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("w_s", "b_s", "sn_g", "sn_b", "emb", "cn_g", "cn_b", "w_c", "b_c", "w_p",
+                                          "b_p", "ln_g", "ln_b", "w_l", "b_l", "gate")] + [
+        (n, C.c_float) for n in ("sn_eps", "cn_eps", "ln_eps")] + [
+        (n, C.c_int32) for n in ("F", "Ws", "Ed", "V", "R", "steps", "reserved")]
+
+
+class FtnEmbedAddParams(C.Structure):
+    """Mirror of ``struct FtnEmbedAddParams`` (include/flowtimes.h): the parameters ``ftn_embed_add`` reads."""
+
+    _fields_ = [(n, C.c_void_p) for n in ("pos", "w_t", "b_t", "aux_g", "aux_b", "gate", "b_v", "basisc", "scale")] + [
+        ("aux_eps", C.c_float), ("T", C.c_int32)]
+
+
+FTN_CTX_MAX, FTN_CTX_RMAX, FTN_ADD_DMAX, FTN_ADD_TMAX = 256, 32, 512, 64
+
+
 class FtnInceptionBlockWeights(C.Structure):
     """Mirror of ``struct FtnInceptionBlockWeights`` (include/flowtimes.h): raw host pointers to the reference
     ``state_dict`` tensors of one InceptionBlock."""
@@ -220,6 +239,15 @@ _SIGNATURES = {
     "ftn_group_sum_rows_form": (C.c_int, [C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_int]),
     "ftn_group_sum_rows": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, _P, _P, _P,
                                      C.c_int, C.c_int, _P, _P]),
+    # context front end (csrc/context.hip)
+    "ftn_context_rows_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ftn_context_rows": (C.c_int, [C.POINTER(FtnContextParams), _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int,
+                                   _P, _P, _P, _P, _P]),
+    "ftn_context_through_weight": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_longlong, C.c_int, _P, _P,
+                                             _P]),
+    "ftn_embed_add_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_embed_add": (C.c_int, [C.POINTER(FtnEmbedAddParams), _P, C.c_longlong, _P, C.c_longlong, C.c_int, _P,
+                                C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

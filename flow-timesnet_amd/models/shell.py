@@ -17,6 +17,13 @@ forecaster (``forecast.py``) and the series-sharded forward (``dist.SeriesSharde
 * embedding - ``_context_terms``, then ``_through_weight`` + ``_embed_epilogue`` (HIP) or ``_with_context`` (torch);
 * heads - ``_late_bias``, ``_time_projection``, ``_rate_dispersion``.
 
+The context front end of these bodies runs in three launches of ``csrc/context.hip`` on ROCm fp32 tensors without
+autograd: ``_rows_of`` -> ``ftn_context_rows`` (the rows carry the coefficients, the constant bias and the late bias,
+which ``_context_terms`` and ``_late_bias`` hand back), ``_through_weight`` + ``_embed_epilogue`` ->
+``ftn_context_through_weight`` + ``ftn_embed_add`` (``add`` in one pass).  Anything the kernels do not take (other
+dtypes, autograd, a LayerNorm without affine parameters, sizes beyond their limits, ``FTN_CTX_HIP=0``) keeps the torch
+composition; ``_last_context_backend`` says which ran.
+
 ``hip_shell_width_ok`` is the one statement of the d_model these kernels take (up to 512: the narrow entry points up
 to 128, the ``ftn_*_wide_*`` ones beyond, chosen in ``runtime``); ``hip_width_ok`` is the narrower limit of the
 series-sharded forward's row exchange.
@@ -33,8 +40,11 @@ from torch import nn
 from torch.utils.checkpoint import checkpoint
 
 from .. import range_guard
-from .timesnet import (FFTPeriodSelector, LowRankTemporalContext, TimesBlock, _layer_norm_fp32 as _norm, _ln_params,
-                       _param_key, _safe_param_dtype)
+from .timesnet import (FFTPeriodSelector, LowRankTemporalContext, TimesBlock, _affine_layernorm,
+                       _layer_norm_fp32 as _norm, _ln_params, _param_key, _safe_param_dtype)
+
+# the limits of the context kernels (include/flowtimes.h): ctx / F / Ws / Ed, rank, time features
+_CTX_MAX, _CTX_RMAX, _ADD_TMAX = 256, 32, 64
 
 
 def _place(module: nn.Module, ref: torch.Tensor) -> nn.Module:
@@ -50,6 +60,11 @@ def hip_width_ok(d_model: int) -> bool:
 
 # FTN_SHELL_WIDE=0 (read once): the shell at d_model > 128 composes torch ops, as before the wide kernels (A/B runs)
 _SHELL_WIDE = os.environ.get("FTN_SHELL_WIDE", "1").strip() != "0"
+
+
+# FTN_CTX_HIP=0 (read once): the context front end (series rows, context terms, the embedding's `add`) composes torch
+# ops, as before its kernels (A/B runs)
+_CTX_HIP = os.environ.get("FTN_CTX_HIP", "1").strip() != "0"
 
 
 def hip_shell_width_ok(d_model: int) -> bool:
@@ -178,6 +193,21 @@ class DataEmbedding(nn.Module):
 # -------------------------------------------------------------------------
 # TimesNet                                               reference :1374-2102
 # -------------------------------------------------------------------------
+class _Aux(NamedTuple):
+    """The epilogue term of the embedding, not yet formed: ``_through_weight`` writes it and the context terms into
+    ``add`` in one pass (``ftn_embed_add``)."""
+    mark: Optional[torch.Tensor]
+    L: int
+    device: torch.device
+
+
+def _fp32_no_grad(tensors) -> bool:
+    """Every tensor is fp32, and nothing asks autograd to follow them (the HIP kernels are forward-only)."""
+    tensors = [t for t in tensors if t is not None]
+    return all(t.dtype == torch.float32 for t in tensors) and not (
+        torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
+
+
 class _Dims(NamedTuple):
     """What the lazily built layers are sized from (one call's view of the inputs)."""
     n_series: int
@@ -334,6 +364,8 @@ class TimesNet(nn.Module):
         self._last_head_backend = "torch"
         self._last_timeproj_backend = "torch"
         self._last_embed_backend = "torch"
+        self._last_context_backend = "torch"       # "hip": every piece of the last context front end ran in HIP
+        self._ctx_rows_torch = False
         self._defer_checks = False
         self._pending_bad = None
 
@@ -476,6 +508,10 @@ class TimesNet(nn.Module):
         B = window.size(0)
         shared = (static is None or static.ndim == 2) and (ids is None or ids.ndim == 1 or ids.size(0) == 1)
         Bc = 1 if shared else B
+        if self._hip_rows_ok(window, static):
+            return self._rows_hip(window, static, ids, Bc)
+        self._last_context_backend = "torch"
+        self._ctx_rows_torch = False
         cols = []
         if self.static_proj is not None and static is not None:
             st = static if static.ndim == 3 else static.unsqueeze(0).expand(Bc, -1, -1)
@@ -485,8 +521,74 @@ class TimesNet(nn.Module):
             cols.append(self.series_embedding(ids.expand(Bc, -1) if ids.size(0) != Bc else ids))
         if not cols:
             return None
+        self._ctx_rows_torch = True
         rows = cols[0] if len(cols) == 1 else torch.cat(cols, dim=-1)
         return rows if self.context_norm is None else _norm(self.context_norm, rows)
+
+    def _row_heads(self):
+        """Which maps of the series rows this model applies: ``(coefficients, constant bias, late bias)``."""
+        return (self.context_coeff is not None and self.temporal_context is not None and self.use_zero_mean_context,
+                self.context_proj is not None and self.use_constant_context_bias,
+                self.late_bias_head is not None and self.late_bias_norm is not None
+                and isinstance(self.late_bias_gate, nn.Parameter))
+
+    def _hip_rows_ok(self, window, static) -> bool:
+        """``ftn_context_rows`` takes this model's rows: ROCm fp32 tensors, no autograd, affine LayerNorms, sizes
+        inside the kernel's limits."""
+        if not (_CTX_HIP and window.is_cuda and window.dtype == torch.float32):
+            return False
+        use_static = self.static_proj is not None and static is not None
+        if not (use_static or self._uses_ids()) or not _affine_layernorm(self.context_norm, self._ctx_width(use_static)):
+            return False
+        has_coeff, has_bias, has_late = self._row_heads()
+        mods = [self.context_norm, self.context_coeff if has_coeff else None, self.context_proj if has_bias else None]
+        tensors = [self.late_bias_gate] if has_late else []
+        if use_static:
+            sn, sp = self.static_norm, self.static_proj
+            if not (sn is None or isinstance(sn, nn.Identity) or _affine_layernorm(sn, sp.out_features)):
+                return False
+            if max(sp.in_features, sp.out_features) > _CTX_MAX:
+                return False
+            mods += [sp, None if isinstance(sn, nn.Identity) else sn]
+            tensors.append(static)
+        if self._uses_ids():
+            mods.append(self.series_embedding)
+        if has_coeff and self.context_coeff.out_features > _CTX_RMAX:
+            return False
+        if has_late:
+            if not _affine_layernorm(self.late_bias_norm, self.context_norm.normalized_shape[0]):
+                return False
+            mods += [self.late_bias_norm, self.late_bias_head]
+        tensors += [p for m in mods if m is not None for p in m.parameters()]
+        return self.context_norm.normalized_shape[0] <= _CTX_MAX and _fp32_no_grad(tensors)
+
+    def _ctx_width(self, use_static: bool) -> int:
+        return ((self.static_proj.out_features if use_static else 0)
+                + (self.series_embedding.embedding_dim if self._uses_ids() else 0))
+
+    def _rows_hip(self, window, static, ids, Bc: int) -> torch.Tensor:
+        """The HIP body of ``_rows_of``: one launch gives the rows and every map of them this model applies; the rows
+        carry the maps' results (``_ftn_ctx``), which ``_context_terms`` and ``_late_bias`` hand back."""
+        from .. import runtime
+
+        has_coeff, has_bias, has_late = self._row_heads()
+        lin = lambda m: (m.weight, m.bias)
+        kw = {}
+        if self.static_proj is not None and static is not None:
+            sn = self.static_norm
+            kw.update(static=static.to(device=window.device, non_blocking=True), static_proj=lin(self.static_proj),
+                      static_norm=None if sn is None or isinstance(sn, nn.Identity) else _ln_params(sn))
+        if self._uses_ids():
+            kw.update(ids=ids, table=self.series_embedding.weight)
+        rows, coeff, cbias, late = runtime.context_rows(
+            Bc, window.size(2), _ln_params(self.context_norm),
+            coeff=lin(self.context_coeff) if has_coeff else None, proj=lin(self.context_proj) if has_bias else None,
+            late=((_ln_params(self.late_bias_norm),) + lin(self.late_bias_head) + (self.late_bias_gate.reshape(-1),)
+                  if has_late else None), **kw)
+        rows._ftn_ctx = (coeff, cbias, late)
+        self._last_context_backend = "hip"
+        self._ctx_rows_torch = False
+        return rows
 
     # ---- embedding front end ---------------------------------------------------------------
     def _hip_embed_ok(self, window: torch.Tensor) -> bool:
@@ -504,6 +606,8 @@ class TimesNet(nn.Module):
     def _context_terms(self, rows):
         """The temporal-context coefficients and the constant context bias of the series rows (None when unused)."""
         coeff = bias = None
+        if rows is not None and getattr(rows, "_ftn_ctx", None) is not None:
+            return rows._ftn_ctx[:2]
         if rows is not None:
             if self.context_coeff is not None and self.temporal_context is not None and self.use_zero_mean_context:
                 coeff = self.context_coeff(rows.to(self.context_coeff.weight.dtype))
@@ -514,7 +618,10 @@ class TimesNet(nn.Module):
     def _through_weight(self, add, coeff, bias, L: int, w):
         """``add`` (None = nothing yet) plus the two context terms pushed through the value weight ``w`` [D, N] (or a
         column slice of it): ``(add + project(coeff)) + bias @ w^T``, summed left to right - the recursive forecaster
-        and the graph tests rest on these bits.  None when there is nothing to add."""
+        and the graph tests rest on these bits.  None when there is nothing to add.  ``add`` may be the epilogue term
+        not yet formed (``_Aux``): the HIP body forms it and adds the context terms in one pass (``ftn_embed_add``)."""
+        if isinstance(add, _Aux) or (add is None and self._hip_terms_ok(coeff, bias, w)):
+            return self._hip_add(add, coeff, bias, L, w)
         terms = (None if coeff is None else self.temporal_context.project(coeff.detach().float(), L, w),
                  None if bias is None else (bias.detach().float() @ w.t()).unsqueeze(1))
         for term in terms:
@@ -522,13 +629,100 @@ class TimesNet(nn.Module):
                 add = term if add is None else add + term
         return add
 
-    def _embed_epilogue(self, window, mark):
+    def _embed_epilogue(self, window, mark, defer: bool = False):
         """What is added to ``x W^T`` once, whatever the series: value bias + positional (+ time-feature) term, gated
         and normalised in the "decoupled" mode, ``[1|B, L, D]``; and ``(gamma, beta, eps)`` of the "layer" mode's
-        LayerNorm (None otherwise)."""
+        LayerNorm (None otherwise).  ``defer``: on the HIP path the term comes back unformed (``_Aux``), for
+        ``_through_weight`` to write together with the context terms."""
         emb = self.embedding
+        ln = _ln_params(emb.norm) if emb.embed_norm_mode == "layer" else None
+        if self._hip_epilogue_ok(window, mark):
+            aux = _Aux(mark if emb.temporal_embedding is not None else None, window.size(1), window.device)
+            return (aux if defer else self._hip_add(aux, None, None, aux.L, None)), ln
+        self._last_context_backend = "torch"
         add = emb.aux_term(window[:1], mark) + emb.value_embedding.bias.detach()
-        return add, (_ln_params(emb.norm) if emb.embed_norm_mode == "layer" else None)
+        return add, ln
+
+    def _hip_epilogue_ok(self, window, mark) -> bool:
+        """``ftn_embed_add`` forms this embedding's epilogue term."""
+        emb = self.embedding
+        if not (_CTX_HIP and window.is_cuda and window.dtype == torch.float32 and hip_shell_width_ok(self.d_model)
+                and emb.embed_norm_mode in ("none", "decoupled", "layer")):
+            return False
+        mods = [emb.value_embedding]
+        tensors = []
+        if mark is not None and emb.temporal_embedding is not None:
+            if not (isinstance(emb.temporal_embedding, nn.Linear) and mark.ndim == 3 and mark.is_cuda
+                    and emb.temporal_embedding.in_features <= _ADD_TMAX):
+                return False
+            mods.append(emb.temporal_embedding)
+            tensors.append(mark)
+        if emb.aux_norm is not None:
+            if not _affine_layernorm(emb.aux_norm, self.d_model) or emb.gate is None:
+                return False
+            mods.append(emb.aux_norm)
+            tensors.append(emb.gate)
+        return _fp32_no_grad(tensors + [p for m in mods for p in m.parameters()])
+
+    def _hip_terms_ok(self, coeff, bias, w) -> bool:
+        """``ftn_context_through_weight`` + ``ftn_embed_add`` take these context terms and this weight."""
+        if not (_CTX_HIP and (coeff is not None or bias is not None) and w.is_cuda and w.ndim == 2
+                and w.size(0) % 4 == 0 and w.size(0) <= 512):
+            return False
+        if coeff is not None and not (coeff.ndim == 3 and coeff.size(2) <= _CTX_RMAX
+                                      and self.temporal_context is not None):
+            return False
+        scale = None if coeff is None else self.temporal_context.scale
+        return all(t is None or t.is_cuda for t in (coeff, bias)) and _fp32_no_grad([coeff, bias, w, scale])
+
+    def _hip_add(self, aux, coeff, bias, L: int, w) -> torch.Tensor:
+        """The HIP body of ``_embed_epilogue`` + ``_through_weight``: the context terms through ``w``
+        (``ftn_context_through_weight``, kept with the terms for the later steps of a recursive forecast), then
+        ``add`` in one pass.  Terms the kernels do not take (``_hip_terms_ok``) are added by the torch composition."""
+        from .. import runtime
+
+        emb = self.embedding
+        q_coeff = q_bias = None
+        terms_hip = (coeff is not None or bias is not None) and self._hip_terms_ok(coeff, bias, w)
+        if terms_hip:
+            holder = coeff if coeff is not None else bias
+            key = (tuple(w.shape), w.stride(0)) + _param_key((w,))
+            kept = getattr(holder, "_ftn_q", None)
+            if kept is None or kept[0] != key:
+                kept = (key,) + runtime.context_through_weight(coeff, bias, w)
+                holder._ftn_q = kept
+            q_coeff, q_bias = kept[1], kept[2]
+        kw = {}
+        device = aux.device if aux is not None else w.device
+        D = self.d_model if aux is not None else w.size(0)
+        if aux is not None:
+            kw.update(pos=emb.position_embedding.table(L, device), b_v=emb.value_embedding.bias, mark=aux.mark)
+            if aux.mark is not None:
+                kw.update(time=(emb.temporal_embedding.weight, emb.temporal_embedding.bias))
+            if emb.aux_norm is not None:
+                kw.update(aux=_ln_params(emb.aux_norm) + (emb.gate.reshape(-1),))
+        if q_coeff is not None:
+            tc = self.temporal_context
+            tc._last_backend = "fused"
+            kw.update(basisc=self._centred_basis(L, q_coeff), scale=tc.scale.reshape(1))
+        add = runtime.embed_add(L, D, device, q_coeff=q_coeff, q_bias=q_bias, **kw)
+        self._last_context_backend = "torch" if self._ctx_rows_torch else "hip"
+        if not terms_hip and (coeff is not None or bias is not None):
+            self._last_context_backend = "torch"
+            add = self._through_weight(add, coeff, bias, L, w)
+        return add
+
+    def _centred_basis(self, L: int, ref: torch.Tensor) -> torch.Tensor:
+        """The doubly centred DCT basis of ``LowRankTemporalContext.project`` [L, R]: a function of (L, rank, device),
+        kept between calls."""
+        tc = self.temporal_context
+        key = (L, tc.rank, str(ref.device))
+        kept = self.__dict__.get("_basisc")
+        if kept is None or kept[0] != key:
+            basis = tc._basis(L, ref)
+            kept = (key, (basis - basis.mean(dim=0, keepdim=True)).float().contiguous())
+            self.__dict__["_basisc"] = kept
+        return kept[1]
 
     def _hip_embed_terms(self, window, mark, coeff, bias):
         """What the HIP embedding adds to ``x W^T``: ``(w, add, ln)`` with ``w`` the value weight [D, N], ``add`` the
@@ -536,7 +730,7 @@ class TimesNet(nn.Module):
         ``_embed_epilogue``.  Shared by ``_embed`` and the recursive forecaster (``forecast.py``), which embeds its
         window row by row."""
         w = self.embedding.value_embedding.weight.detach()
-        add, ln = self._embed_epilogue(window, mark)
+        add, ln = self._embed_epilogue(window, mark, defer=True)
         add = self._through_weight(add, coeff, bias, window.size(1), w)
         return w, add.detach().float().contiguous(), ln
 
@@ -594,6 +788,8 @@ class TimesNet(nn.Module):
 
     def _late_bias(self, rows) -> Optional[torch.Tensor]:
         """The gated late-bias head of the series rows, ``[Bc, steps, N]`` (None when the model has none)."""
+        if rows is not None and getattr(rows, "_ftn_ctx", None) is not None:
+            return rows._ftn_ctx[2]
         if (rows is None or self.late_bias_head is None or self.late_bias_norm is None
                 or not isinstance(self.late_bias_gate, nn.Parameter)):
             return None

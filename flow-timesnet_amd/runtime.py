@@ -510,6 +510,209 @@ def embed_ring(V: torch.Tensor, head: int, add, norm=None) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------ context front end
+def _f32(t):
+    """An optional parameter / operand as the context kernels read it: detached, contiguous fp32."""
+    if t is None:
+        return None
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+def _rows_view(t: torch.Tensor, width: int) -> torch.Tensor:
+    """``t`` [.., n, width] with contiguous rows (any batch stride), copied only when its rows are not."""
+    ok = (width == 1 or t.stride(-1) == 1) and (t.shape[-2] == 1 or t.stride(-2) == width)
+    return t if ok else t.contiguous()
+
+
+def _out_like(who: str, out, shape, device) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if out.shape != shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous fp32 tensor of shape {tuple(shape)}")
+    return out
+
+
+def context_rows_form_of(F: int, Ws: int, Ed: int, R: int = 0, steps: int = 0) -> Tuple[int, int, int]:
+    """``(context slots of a lane, static slots of a lane, passes of the late head)`` of ``ftn_context_rows``."""
+    f = _form("ftn_context_rows_form", F, Ws, Ed, R, steps)
+    return f & 15, (f >> 4) & 15, (f >> 8) & 255
+
+
+def context_rows(Bc: int, N: int, context_norm, static=None, static_proj=None, static_norm=None, ids=None, table=None,
+                 coeff=None, proj=None, late=None, want_rows: bool = True, out=None):
+    """One launch for everything that depends on a series row only (``ftn_context_rows``).
+
+    ``static`` fp32 [N, F] or [Bc, N, F] with ``static_proj = (W_s, b_s)`` and ``static_norm = (gamma, beta, eps)``
+    or None; ``ids`` int64 [N] or [1|Bc, N] with ``table`` [V, Ed]; ``context_norm = (gamma, beta, eps)``;
+    ``coeff = (W_c, b_c)``, ``proj = (w_p, b_p)``, ``late = ((gamma, beta, eps), W_l, b_l, gate)`` select the optional
+    outputs.  Returns ``(rows [Bc, N, ctx] or None, coeff [Bc, N, R] or None, cbias [Bc, N] or None,
+    late [Bc, steps, N] or None)``; ``out``: four contiguous fp32 tensors (or None) to write these into instead of
+    fresh ones."""
+    lib = _lib.load()
+    p = _lib.FtnContextParams()
+    keep = []
+
+    def put(name, t):
+        t = _f32(t)
+        keep.append(t)
+        setattr(p, name, _ptr_or_null(t))
+        return t
+
+    dev = None
+    st_ptr = ids_ptr = None
+    st_bs = ids_bs = 0
+    if static is not None:
+        w_s = put("w_s", static_proj[0])
+        put("b_s", static_proj[1])
+        p.Ws, p.F = int(w_s.shape[0]), int(w_s.shape[1])
+        if static.dtype != torch.float32 or static.shape[-2:] != (N, p.F) or static.dim() not in (2, 3):
+            raise ValueError(f"context_rows: static must be fp32 [N, F] or [Bc, N, F], got {tuple(static.shape)}")
+        static = _rows_view(static.detach(), p.F)
+        if static.dim() == 3 and static.shape[0] not in (1, Bc):
+            raise ValueError("context_rows: static batch dimension does not match Bc")
+        st_bs = static.stride(0) if static.dim() == 3 and static.shape[0] > 1 else 0
+        st_ptr, dev = _ptr(static), static.device
+        if static_norm is not None:
+            put("sn_g", static_norm[0])
+            put("sn_b", static_norm[1])
+            p.sn_eps = float(static_norm[2])
+    if ids is not None:
+        tab = put("emb", table)
+        p.V, p.Ed = int(tab.shape[0]), int(tab.shape[1])
+        if ids.dtype != torch.int64 or ids.shape[-1] != N or ids.dim() not in (1, 2):
+            raise ValueError(f"context_rows: ids must be int64 [N] or [1|Bc, N], got {tuple(ids.shape)}")
+        ids = ids.detach()
+        if N > 1 and ids.stride(-1) != 1:
+            ids = ids.contiguous()
+        if ids.dim() == 2 and ids.shape[0] not in (1, Bc):
+            raise ValueError("context_rows: ids batch dimension does not match Bc")
+        ids_bs = ids.stride(0) if ids.dim() == 2 and ids.shape[0] > 1 else 0
+        ids_ptr, dev = _ptr(ids), ids.device
+    if dev is None:
+        raise ValueError("context_rows: neither static features nor ids")
+    ctx = p.Ws + p.Ed
+    put("cn_g", context_norm[0])
+    put("cn_b", context_norm[1])
+    p.cn_eps = float(context_norm[2])
+    outs = (None,) * 4 if out is None else tuple(out)
+    new = lambda i, *shape: _out_like("context_rows", outs[i], shape, dev)
+    rows = new(0, Bc, N, ctx) if want_rows else None
+    coeff_out = cbias_out = late_out = None
+    if coeff is not None:
+        w_c = put("w_c", coeff[0])
+        put("b_c", coeff[1])
+        p.R = int(w_c.shape[0])
+        coeff_out = new(1, Bc, N, p.R)
+    if proj is not None:
+        put("w_p", proj[0])
+        put("b_p", proj[1])
+        cbias_out = new(2, Bc, N)
+    if late is not None:
+        (g, b, eps), w_l, b_l, gate = late
+        put("ln_g", g)
+        put("ln_b", b)
+        p.ln_eps = float(eps)
+        w_l = put("w_l", w_l)
+        put("b_l", b_l)
+        put("gate", gate)
+        p.steps = int(w_l.shape[0])
+        late_out = new(3, Bc, p.steps, N)
+    check(lib.ftn_context_rows(C.byref(p), st_ptr, st_bs, ids_ptr, ids_bs, int(Bc), int(N), _ptr_or_null(rows),
+                               _ptr_or_null(coeff_out), _ptr_or_null(cbias_out), _ptr_or_null(late_out), _stream(dev)),
+          "ftn_context_rows")
+    return rows, coeff_out, cbias_out, late_out
+
+
+def context_through_weight(coeff, cbias, w: torch.Tensor, out=(None, None)):
+    """``(q_coeff [Bc, R, D] or None, q_bias [Bc, D] or None)``: ``coeff`` [Bc, N, R] and ``cbias`` [Bc, N] (either may
+    be None) contracted over the series with ``w`` [D, N], whose rows may be a column slice of a wider weight."""
+    lib = _lib.load()
+    coeff, cbias = _f32(coeff), _f32(cbias)
+    ref = coeff if coeff is not None else cbias
+    if ref is None:
+        raise ValueError("context_through_weight: neither coefficients nor bias")
+    Bc, N = int(ref.shape[0]), int(ref.shape[1])
+    R = int(coeff.shape[2]) if coeff is not None else 0
+    if w.dim() != 2 or w.shape[1] != N or w.dtype != torch.float32 or (cbias is not None and cbias.shape != (Bc, N)):
+        raise ValueError("context_through_weight: w must be fp32 [D, N] for coeff [Bc, N, R] / cbias [Bc, N]")
+    w = w.detach()
+    if N > 1 and w.stride(1) != 1:
+        w = w.contiguous()
+    D = int(w.shape[0])
+    ldw = w.stride(0) if D > 1 else N
+    q_coeff = _out_like("context_through_weight", out[0], (Bc, R, D), w.device) if coeff is not None else None
+    q_bias = _out_like("context_through_weight", out[1], (Bc, D), w.device) if cbias is not None else None
+    check(lib.ftn_context_through_weight(_ptr_or_null(coeff), _ptr_or_null(cbias), Bc, N, R, _ptr(w), max(ldw, N), D,
+                                         _ptr_or_null(q_coeff), _ptr_or_null(q_bias), _stream(w.device)),
+          "ftn_context_through_weight")
+    return q_coeff, q_bias
+
+
+def embed_add_form_of(D: int, q_coeff_bstride: int = 0, q_bias_bstride: int = 0, misalign_or: int = 0) -> str:
+    f = _form("ftn_embed_add_form", D, q_coeff_bstride, q_bias_bstride, misalign_or)
+    return f"k_embed_add<{(f >> 4) & 15},{'true' if f & 2 else 'false'}>"
+
+
+def embed_add(L: int, D: int, device, pos=None, mark=None, time=None, aux=None, b_v=None, basisc=None, scale=None,
+              q_coeff=None, q_bias=None, out=None) -> torch.Tensor:
+    """``add`` [Ba, L, D] of the embedding entry points in one pass (``ftn_embed_add``): ``pos`` [L, D] with the value
+    bias ``b_v`` (+ ``mark`` [B, L, T] through ``time = (W_t, b_t)``; ``aux = (gamma, beta, eps, gate)`` in the
+    "decoupled" mode), then ``scale * basisc @ q_coeff`` and ``q_bias`` (``context_through_weight``).  Ba is 1 when
+    nothing has more than one batch row (a mark with batch stride 0 counts as one row)."""
+    lib = _lib.load()
+    p = _lib.FtnEmbedAddParams()
+    keep = []
+
+    def put(name, t):
+        t = _f32(t)
+        keep.append(t)
+        setattr(p, name, _ptr_or_null(t))
+        return t
+
+    Bm = 1
+    mark_ptr, mark_bs = None, 0
+    if pos is not None:
+        if pos.shape != (L, D):
+            raise ValueError(f"embed_add: pos must be [L, D] = {(L, D)}, got {tuple(pos.shape)}")
+        put("pos", pos)
+        put("b_v", b_v)
+        if mark is not None:
+            w_t = put("w_t", time[0])
+            put("b_t", time[1])
+            p.T = int(w_t.shape[1])
+            if mark.dim() != 3 or mark.shape[1:] != (L, p.T) or mark.dtype != torch.float32:
+                raise ValueError(f"embed_add: mark must be fp32 [B, L, {p.T}], got {tuple(mark.shape)}")
+            mark = _rows_view(mark.detach(), p.T)
+            if mark.shape[0] > 1 and mark.stride(0) != 0:
+                Bm, mark_bs = int(mark.shape[0]), mark.stride(0)
+            mark_ptr = _ptr(mark)
+        if aux is not None:
+            put("aux_g", aux[0])
+            put("aux_b", aux[1])
+            p.aux_eps = float(aux[2])
+            put("gate", aux[3])
+    Bq = 1
+    R = 0
+    if q_coeff is not None:
+        R = int(q_coeff.shape[1])
+        Bq = int(q_coeff.shape[0])
+        put("basisc", basisc)
+        put("scale", scale)
+        if keep[-2].shape != (L, R):
+            raise ValueError("embed_add: basisc must be [L, R]")
+    if q_bias is not None:
+        Bq = int(q_bias.shape[0])
+    if Bm > 1 and Bq > 1 and Bm != Bq:
+        raise ValueError(f"embed_add: {Bm} mark rows against {Bq} context rows")
+    Ba = max(Bm, Bq)
+    out = _out_like("embed_add", out, (Ba, L, D), device)
+    check(lib.ftn_embed_add(C.byref(p), mark_ptr, mark_bs, _ptr_or_null(q_coeff), R * D if Bq > 1 else 0, R,
+                            _ptr_or_null(q_bias), D if Bq > 1 else 0, Ba, int(L), int(D), _ptr(out), _stream(device)),
+          "ftn_embed_add")
+    return out
+
+
 # ------------------------------------------------------------------ row exchange (series-sharded forward)
 def rowx_push(src: torch.Tensor, xch) -> None:
     """Store this rank's rows into every destination's buffer (``xch``: ``C.byref`` of an ``FtnRowExchange``).

@@ -771,6 +771,92 @@ int ftn_group_sum_rows(const float* x_dev, long long outer, int S, long long inn
                        long long member_stride, const int* order_dev, const int* offsets_dev, const int* offsets_host,
                        int G, int M, float* out_dev, void* stream);
 
+/* ---- context front end (csrc/context.hip) ----
+ * Additions only: FTN_ABI_VERSION stays 14.
+ *
+ * What TimesNet.forward computes from the series rows before the value embedding and the heads see it (:1883-2020,
+ * :2080-2090), as three launches.  Plain fp32 on the VALU: every sum is one chain of FMAs in index order from +0, or
+ * a fixed tree of such chains whose shape depends on the sizes alone.  No atomics, no workspace, no allocation, no
+ * synchronisation: each entry enqueues one kernel on `stream`.  A bad argument is a negative return with
+ * ftn_last_error set (the entry's name first) and nothing launched.  Every fp32 operand is 4-byte aligned unless
+ * stated otherwise.
+ *
+ * ftn_context_rows (k_context_rows): rows = Bc N, one wave a row (bc, n), ctx = Ws + Ed.
+ *   s     = static_norm(W_s static[bc][n] + b_s)         W_s [Ws][F]; no norm when sn_g is null; absent when Ws == 0
+ *   e     = E[ids[bc][n]]                                E [V][Ed], ids int64 (8-byte aligned); absent when Ed == 0
+ *   c     = context_norm(cat(s, e))                      -> rows_out [rows][ctx]
+ *   coeff = W_c c + b_c                                  W_c [R][ctx] -> coeff_out [rows][R]
+ *   cbias = w_p c + b_p                                  -> cbias_out [rows]
+ *   late  = gate[s] (W_l late_bias_norm(c) + b_l)[s]     W_l [steps][ctx] -> late_out [Bc][steps][N]
+ * Each output is optional (at least one).  static row (bc, n) is at static + bc static_bstride + n F, the id at
+ * ids + bc ids_bstride + n; both strides are ignored when Bc == 1 and may be 0 (one [N] block for every bc).  The
+ * LayerNorms are torch's: the mean, the biased variance of the centred values, 1 / sqrt(var + eps), gamma, beta.
+ * An id outside [0, V) reads nothing from the table: every output of that row is NaN, no other row changes.
+ * A row's outputs are a function of that row's inputs and the parameters alone - the same bits whatever Bc and N
+ * are and whichever rows share the call.  Limits: ctx, F, Ws, Ed <= 256, R <= 32, any steps >= 1.
+ * ftn_context_rows_form (host-only): bits 0-3 ceil(ctx / 64), the slots of a lane's share of a context vector;
+ * bits 4-7 ceil(Ws / 64); bits 8-15 min(ceil(steps / 64), 255), the passes of the late head.
+ *
+ * ftn_context_through_weight: the contraction over series of the two context terms with the value weight w [D][N]
+ * (row stride w_rstride >= N: a column slice is fine),
+ *   q_coeff[bc][r][d] = sum_n coeff[bc][n][r] w[d][n]     q_bias[bc][d] = sum_n cbias[bc][n] w[d][n]
+ * coeff [Bc][N][R], cbias [Bc][N], q_coeff [Bc][R][D], q_bias [Bc][D], all contiguous; either output optional.
+ * N <= 64 (k_through_small): one chain in n order.  N > 64 (k_through_chunks): chunks of 64 series, chunk c belongs
+ * to part c mod 4, a part adds its chunks' products in n order in one chain, and the result is
+ * (p0 + p1) + (p2 + p3).  A batch row's bits do not depend on Bc.  D a multiple of 4, <= 512; R <= 32;
+ * Bc <= 65535 when N > 64.
+ *
+ * ftn_embed_add (k_embed_add<NO, VEC>): the `add` operand of the embedding entry points, [Ba][L][D] contiguous,
+ * 16-byte aligned, one wave a row, the terms applied left to right:
+ *   aux = pos[l] (+ (mark[b][l] W_t^T + b_t));  aux = gate * LayerNorm(aux) when aux_g is given ("decoupled")
+ *   t   = aux + b_v                             (this part only when pos is given)
+ *   t   = t + scale (sum_r basisc[l][r] q_coeff[b][r])     (when q_coeff is given; scale is read from the device)
+ *   add = t + q_bias[b]                                      (when q_bias is given)
+ * pos [L][D]; mark row (b, l) at mark + b mark_bstride + l T (mark_bstride may be 0); W_t [D][T], T <= 64; basisc
+ * [L][R]; q_coeff / q_bias batch strides in elements (0: shared by the batch).  D a multiple of 4, <= 512.
+ * ftn_embed_add_form (host-only; the launch dispatches through the same function):
+ *   bit 1      FTN_SHELL_VEC  16-byte loads of the row-shaped operands (pos, b_t, gate, aux gamma / beta, b_v,
+ *                             q_coeff, q_bias): both batch strides % 4 == 0 and misalign_or == 0 (the OR of those
+ *                             operands' byte offsets from a 16-byte boundary); otherwise 4-byte loads, same arithmetic
+ *   bits 4-7   NO: 4-column groups of a lane (1 for D <= 256, else 2) */
+typedef struct FtnContextParams {
+  const float* w_s;  const float* b_s;                    /* static_proj */
+  const float* sn_g; const float* sn_b;                   /* static_norm (null: none) */
+  const float* emb;                                       /* series_embedding table */
+  const float* cn_g; const float* cn_b;                   /* context_norm */
+  const float* w_c;  const float* b_c;                    /* context_coeff */
+  const float* w_p;  const float* b_p;                    /* context_proj */
+  const float* ln_g; const float* ln_b;                   /* late_bias_norm */
+  const float* w_l;  const float* b_l; const float* gate; /* late_bias_head, late_bias_gate [steps] */
+  float sn_eps, cn_eps, ln_eps;
+  int32_t F, Ws, Ed, V, R, steps;
+  int32_t reserved;
+} FtnContextParams;
+
+typedef struct FtnEmbedAddParams {
+  const float* pos;                                       /* PositionalEmbedding table [L][D] (null: no epilogue part) */
+  const float* w_t;  const float* b_t;                    /* temporal_embedding */
+  const float* aux_g; const float* aux_b; const float* gate;   /* aux_norm and the gate [D] (null: not "decoupled") */
+  const float* b_v;                                       /* value_embedding bias */
+  const float* basisc; const float* scale;                /* centred DCT basis [L][R], temporal_context.scale [1] */
+  float aux_eps;
+  int32_t T;
+} FtnEmbedAddParams;
+
+int ftn_context_rows_form(int F, int Ws, int Ed, int R, int steps);
+int ftn_context_rows(const FtnContextParams* params, const float* static_dev_or_null, long long static_bstride,
+                     const long long* ids_dev_or_null, long long ids_bstride, int Bc, int N,
+                     float* rows_out_or_null, float* coeff_out_or_null, float* cbias_out_or_null,
+                     float* late_out_or_null, void* stream);
+int ftn_context_through_weight(const float* coeff_dev_or_null, const float* cbias_dev_or_null, int Bc, int N, int R,
+                               const float* w_dev, long long w_rstride, int D, float* q_coeff_out_or_null,
+                               float* q_bias_out_or_null, void* stream);
+int ftn_embed_add_form(int D, long long q_coeff_bstride, long long q_bias_bstride, int misalign_or);
+int ftn_embed_add(const FtnEmbedAddParams* params, const float* mark_dev_or_null, long long mark_bstride,
+                  const float* q_coeff_dev_or_null, long long q_coeff_bstride, int R,
+                  const float* q_bias_dev_or_null, long long q_bias_bstride, int Ba, int L, int D, float* out_dev,
+                  void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
