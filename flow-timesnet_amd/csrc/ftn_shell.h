@@ -41,16 +41,21 @@ struct HeadArgs {
   float floor_s;
 };
 
+// The norm over d_model that closes an embedding row: a field of the argument blocks, not a template argument - the
+// kernel forms are the same for all three.
+enum { FTN_NORM_NONE = 0, FTN_NORM_LAYER = 1, FTN_NORM_RMS = 2 };
+
 struct EmbedArgs {
   const float* x;
   const float* W;        // [D][N]
   const float* add;      // optional
-  const float* ln_g;     // optional LayerNorm epilogue ("layer" mode)
+  const float* ln_g;     // gamma / beta of the norm epilogue ("layer" and "rms" modes)
   const float* ln_b;
   float* out;            // row (b, l) at out + b * out_bs + l * D
   long long x_bs, add_bs, out_bs;
   int B, L, N, D;
   float ln_eps;
+  int norm;              // FTN_NORM_*
 };
 
 struct RingArgs {
@@ -62,4 +67,5 @@ struct RingArgs {
   long long add_bs;
   int B, L, D, head;
   float ln_eps;
+  int norm;              // FTN_NORM_*
 };

@@ -343,19 +343,38 @@ extern "C" int ftn_head_forward(const float* hidden_dev, long long rows, int S, 
 // temporal context and constant context bias pushed through W (so the [B, L, N] context tensor is
 // never materialised).  Reads x once: HBM-bound at 4*B*L*N bytes.
 
-// + add, optional LayerNorm over one row held by the four q-lanes of a 16-row tile: lane (j, q) holds columns
-// 16*o + 4*q .. +3 of row j in v[o].  Shared by the GEMM epilogue and the ring epilogue (k_embed_ring), so that a row
-// assembled from stored x W^T plus `add` comes out bit-identical to the one-pass embedding.
+// + add, optional LayerNorm or RMS norm over one row held by the four q-lanes of a 16-row tile: lane (j, q) holds
+// columns 16*o + 4*q .. +3 of row j in v[o].  Shared by the GEMM epilogue and the ring epilogue (k_embed_ring), so
+// that a row assembled from stored x W^T plus `add` comes out bit-identical to the one-pass embedding - for the RMS
+// norm on every form and at every d_model (its branch is compiled without FMA contraction, so no caller rounds it
+// differently), for LayerNorm on the forms the recursive forecaster lists.
+// RMS (FTN_NORM_RMS): the reference's fp32 formula, (v * rsqrt(mean(v^2) + eps)) * gamma + beta, the sum of squares
+// in the order of the LayerNorm mean - pair tree over the lane's valid column tiles, then the q-lanes.  Nothing is
+// pre-scaled: a row whose squares overflow gets scale = 1 / sqrt(inf) = 0 and comes out as beta.
 template <int NO>
 __device__ __forceinline__ void embed_row_finish(f4 (&v)[NO], const float* __restrict__ ap, const float* ln_g,
-                                                 const float* ln_b, float ln_eps, int D, int q) {
+                                                 const float* ln_b, float ln_eps, int D, int q, int norm) {
   const float invD = 1.0f / (float)D;
 #pragma unroll
   for (int o = 0; o < NO; ++o) {
     const int cb = 16 * o + 4 * q;
     if (ap && cb < D) v[o] = v[o] + *(const f4*)(ap + cb);      // D % 4 == 0
   }
-  if (ln_g) {
+  if (norm == FTN_NORM_RMS) {
+#pragma clang fp contract(off)
+    float ss = 0.f;
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+      if (16 * o + 4 * q < D) ss += (v[o][0] * v[o][0] + v[o][1] * v[o][1]) + (v[o][2] * v[o][2] + v[o][3] * v[o][3]);
+    ss += __shfl_xor(ss, 16);
+    ss += __shfl_xor(ss, 32);
+    const float scale = 1.0f / sqrtf(ss * invD + ln_eps);
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      const int cb = 16 * o + 4 * q;
+      if (cb < D) v[o] = (v[o] * scale) * *(const f4*)(ln_g + cb) + *(const f4*)(ln_b + cb);
+    }
+  } else if (ln_g) {
     float s = 0.f;
 #pragma unroll
     for (int o = 0; o < NO; ++o)
@@ -389,7 +408,7 @@ __device__ __forceinline__ void embed_epilogue(const EmbedArgs& a, f4 (&acc)[RT]
   for (int t = 0; t < RT; ++t) {
     const long long b = rr[t] / a.L, l = rr[t] - b * a.L;
     const float* __restrict__ ap = a.add ? a.add + b * a.add_bs + l * a.D : nullptr;
-    embed_row_finish<NO>(acc[t], ap, a.ln_g, a.ln_b, a.ln_eps, a.D, q);
+    embed_row_finish<NO>(acc[t], ap, a.ln_g, a.ln_b, a.ln_eps, a.D, q, a.norm);
     if (!rok[t]) continue;
     float* __restrict__ op = a.out + b * a.out_bs + l * a.D;
 #pragma unroll
@@ -653,23 +672,41 @@ static int embed_launch(EmbedArgs& a, hipStream_t st) {
   return launch_embed<8>(a, form, st);
 }
 
+// ftn_embed_forward and ftn_embed_forward_rms: one argument list, one set of checks.  norm: FTN_NORM_LAYER takes both
+// of gamma / beta or neither (no norm), FTN_NORM_RMS needs both.
+static int embed_forward_entry(const char* who, int norm, const float* x_dev, long long x_bstride, int B, int L, int N,
+                               const float* w_dev, int D, const float* add_dev_or_null, long long add_bstride,
+                               const float* gamma_dev, const float* beta_dev, float eps, float* out_dev,
+                               void* stream) {
+  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "%s: null pointer", who);
+  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "%s: bad shape B=%d L=%d N=%d", who, B, L, N);
+  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "%s: d_model=%d must be a multiple of 4, <= 128", who, D);
+  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
+  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
+  FTN_CHECK_ARG((((uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev | (uintptr_t)beta_dev) & 15) == 0 &&
+                    add_bstride % 4 == 0,
+                "%s: out / add / LayerNorm parameters must be 16-byte aligned", who);
+  EmbedArgs a;
+  a.x = x_dev; a.W = w_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev;
+  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.out_bs = (long long)L * D;
+  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = eps; a.norm = gamma_dev ? norm : FTN_NORM_NONE;
+  return embed_launch(a, (hipStream_t)stream);
+}
+
 extern "C" int ftn_embed_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
                                  int D, const float* add_dev_or_null, long long add_bstride,
                                  const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null, float ln_eps,
                                  float* out_dev, void* stream) {
-  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "ftn_embed_forward: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "ftn_embed_forward: bad shape B=%d L=%d N=%d", B, L, N);
-  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "ftn_embed_forward: d_model=%d must be a multiple of 4, <= 128", D);
-  FTN_CHECK_ARG((ln_gamma_dev_or_null == nullptr) == (ln_beta_dev_or_null == nullptr),
-                "ftn_embed_forward: LayerNorm needs both gamma and beta");
-  FTN_CHECK_ARG((((uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)ln_gamma_dev_or_null |
-                  (uintptr_t)ln_beta_dev_or_null) & 15) == 0 && add_bstride % 4 == 0,
-                "ftn_embed_forward: out / add / LayerNorm parameters must be 16-byte aligned");
-  EmbedArgs a;
-  a.x = x_dev; a.W = w_dev; a.add = add_dev_or_null; a.ln_g = ln_gamma_dev_or_null; a.ln_b = ln_beta_dev_or_null;
-  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.out_bs = (long long)L * D;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = ln_eps;
-  return embed_launch(a, (hipStream_t)stream);
+  return embed_forward_entry("ftn_embed_forward", FTN_NORM_LAYER, x_dev, x_bstride, B, L, N, w_dev, D, add_dev_or_null,
+                             add_bstride, ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps, out_dev, stream);
+}
+
+extern "C" int ftn_embed_forward_rms(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
+                                     int D, const float* add_dev_or_null, long long add_bstride,
+                                     const float* gamma_dev, const float* beta_dev, float eps, float* out_dev,
+                                     void* stream) {
+  return embed_forward_entry("ftn_embed_forward_rms", FTN_NORM_RMS, x_dev, x_bstride, B, L, N, w_dev, D,
+                             add_dev_or_null, add_bstride, gamma_dev, beta_dev, eps, out_dev, stream);
 }
 
 // The value-embedding GEMM alone (no add, no LayerNorm) into rows of a larger buffer: row (b, l) of x W^T lands at
@@ -689,7 +726,7 @@ extern "C" int ftn_embed_rows_strided(const float* x_dev, long long x_bstride, i
   EmbedArgs a;
   a.x = x_dev; a.W = w_dev; a.add = nullptr; a.ln_g = nullptr; a.ln_b = nullptr;
   a.out = out_dev; a.x_bs = x_bstride; a.add_bs = 0; a.out_bs = out_bstride;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = 0.f;
+  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = 0.f; a.norm = FTN_NORM_NONE;
   return embed_launch(a, (hipStream_t)stream);
 }
 
@@ -719,7 +756,7 @@ __global__ __launch_bounds__(256) void k_embed_ring(RingArgs a) {
     v[o] = cb < a.D ? *(const f4*)(vp + cb) : f4{0.f, 0.f, 0.f, 0.f};
   }
   const float* __restrict__ ap = a.add ? a.add + b * a.add_bs + (long long)t * a.D : nullptr;
-  embed_row_finish<NO>(v, ap, a.ln_g, a.ln_b, a.ln_eps, a.D, q);
+  embed_row_finish<NO>(v, ap, a.ln_g, a.ln_b, a.ln_eps, a.D, q, a.norm);
   if (!ok) return;
   float* __restrict__ op = a.out + r * a.D;
 #pragma unroll
@@ -729,22 +766,23 @@ __global__ __launch_bounds__(256) void k_embed_ring(RingArgs a) {
   }
 }
 
-extern "C" int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
-                              long long add_bstride, const float* ln_gamma_dev_or_null,
-                              const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream) {
-  FTN_CHECK_ARG(v_dev && out_dev, "ftn_embed_ring: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1, "ftn_embed_ring: bad shape B=%d L=%d", B, L);
-  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "ftn_embed_ring: d_model=%d must be a multiple of 4, <= 128", D);
-  FTN_CHECK_ARG(head >= 0 && head < L, "ftn_embed_ring: head=%d outside [0, L=%d)", head, L);
-  FTN_CHECK_ARG((ln_gamma_dev_or_null == nullptr) == (ln_beta_dev_or_null == nullptr),
-                "ftn_embed_ring: LayerNorm needs both gamma and beta");
-  FTN_CHECK_ARG((((uintptr_t)v_dev | (uintptr_t)out_dev | (uintptr_t)add_dev_or_null |
-                  (uintptr_t)ln_gamma_dev_or_null | (uintptr_t)ln_beta_dev_or_null) & 15) == 0 &&
-                add_bstride % 4 == 0 && add_bstride >= 0,
-                "ftn_embed_ring: V / out / add / LayerNorm parameters must be 16-byte aligned");
+static int embed_ring_entry(const char* who, int norm, const float* v_dev, int B, int L, int D, int head,
+                            const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
+                            const float* beta_dev, float eps, float* out_dev, void* stream) {
+  FTN_CHECK_ARG(v_dev && out_dev, "%s: null pointer", who);
+  FTN_CHECK_ARG(B >= 1 && L >= 1, "%s: bad shape B=%d L=%d", who, B, L);
+  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "%s: d_model=%d must be a multiple of 4, <= 128", who, D);
+  FTN_CHECK_ARG(head >= 0 && head < L, "%s: head=%d outside [0, L=%d)", who, head, L);
+  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
+  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
+  FTN_CHECK_ARG((((uintptr_t)v_dev | (uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev |
+                  (uintptr_t)beta_dev) & 15) == 0 &&
+                    add_bstride % 4 == 0 && add_bstride >= 0,
+                "%s: V / out / add / LayerNorm parameters must be 16-byte aligned", who);
   RingArgs a;
-  a.V = v_dev; a.add = add_dev_or_null; a.ln_g = ln_gamma_dev_or_null; a.ln_b = ln_beta_dev_or_null; a.out = out_dev;
-  a.add_bs = add_bstride; a.B = B; a.L = L; a.D = D; a.head = head; a.ln_eps = ln_eps;
+  a.V = v_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev; a.out = out_dev;
+  a.add_bs = add_bstride; a.B = B; a.L = L; a.D = D; a.head = head; a.ln_eps = eps;
+  a.norm = gamma_dev ? norm : FTN_NORM_NONE;
   const long long M = (long long)B * L;
   const dim3 grid((unsigned)((M + 63) / 64));
   hipStream_t st = (hipStream_t)stream;
@@ -752,4 +790,18 @@ extern "C" int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head,
   else hipLaunchKernelGGL(k_embed_ring<8>, grid, dim3(256), 0, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                              long long add_bstride, const float* ln_gamma_dev_or_null,
+                              const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream) {
+  return embed_ring_entry("ftn_embed_ring", FTN_NORM_LAYER, v_dev, B, L, D, head, add_dev_or_null, add_bstride,
+                          ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps, out_dev, stream);
+}
+
+extern "C" int ftn_embed_ring_rms(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                                  long long add_bstride, const float* gamma_dev, const float* beta_dev, float eps,
+                                  float* out_dev, void* stream) {
+  return embed_ring_entry("ftn_embed_ring_rms", FTN_NORM_RMS, v_dev, B, L, D, head, add_dev_or_null, add_bstride,
+                          gamma_dev, beta_dev, eps, out_dev, stream);
 }

@@ -29,10 +29,16 @@ static inline bool wide_ok(int D) { return D > 128 && D <= 512 && D % 4 == 0; }
 // through LDS (red: [2][4][16] floats) - first the mean, then the centred sum of squares; a slab past d_model adds an
 // exact zero.  Contraction into FMAs is off: the two callers must not round differently.  Every wave of the workgroup
 // calls it (two barriers with LayerNorm).
+// RMS (FTN_NORM_RMS): (v * rsqrt(mean(v^2) + eps)) * gamma + beta as embed_row_finish (shell.hip) has it, one
+// reduction - the sum of squares, slabs in slab order - and so one barrier.  With a single barrier a call may no longer
+// reuse the words its predecessor read: a wave can be writing its partial sum of the next row tile while another
+// still adds up this one's.  `half` picks the half of red[] the call goes through; successive calls of a workgroup
+// alternate it (a wave that writes half h again has passed the barrier of the call in between, which every wave
+// reaches only after its reads of h).
 template <int NO>
 __device__ __forceinline__ void embed_wide_row_finish(f4 (&v)[NO], const float* __restrict__ ap, const float* ln_g,
                                                       const float* ln_b, float ln_eps, int D, int wave, int j, int q,
-                                                      float* red) {
+                                                      float* red, int norm, int half) {
 #pragma clang fp contract(off)
   constexpr int nw = 4;
   const float invD = 1.0f / (float)D;
@@ -42,7 +48,25 @@ __device__ __forceinline__ void embed_wide_row_finish(f4 (&v)[NO], const float* 
     const int cb = c0 + 16 * o;
     if (ap && cb < D) v[o] = v[o] + *(const f4*)(ap + cb);      // D % 4 == 0
   }
-  if (ln_g) {
+  if (norm == FTN_NORM_RMS) {
+    float* rd = red + 64 * half;
+    float ss = 0.f;
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+      if (c0 + 16 * o < D) ss += (v[o][0] * v[o][0] + v[o][1] * v[o][1]) + (v[o][2] * v[o][2] + v[o][3] * v[o][3]);
+    ss += __shfl_xor(ss, 16);
+    ss += __shfl_xor(ss, 32);
+    if (q == 0) rd[16 * wave + j] = ss;
+    __syncthreads();
+    float tot = rd[j];
+    for (int w = 1; w < nw; ++w) tot += rd[16 * w + j];
+    const float scale = 1.0f / sqrtf(tot * invD + ln_eps);
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      const int cb = c0 + 16 * o;
+      if (cb < D) v[o] = (v[o] * scale) * *(const f4*)(ln_g + cb) + *(const f4*)(ln_b + cb);
+    }
+  } else if (ln_g) {
     float s = 0.f;
 #pragma unroll
     for (int o = 0; o < NO; ++o)
@@ -179,7 +203,7 @@ __global__ __launch_bounds__(256) void k_embed_wide_bf(EmbedArgs a) {
     const long long r = rok ? row : M - 1;
     const long long b = r / a.L, l = r - b * a.L;
     const float* __restrict__ ap = a.add ? a.add + b * a.add_bs + l * a.D : nullptr;
-    embed_wide_row_finish<NO>(acc[t], ap, a.ln_g, a.ln_b, a.ln_eps, a.D, wave, j, q, red);
+    embed_wide_row_finish<NO>(acc[t], ap, a.ln_g, a.ln_b, a.ln_eps, a.D, wave, j, q, red, a.norm, t & 1);
     if (!rok) continue;
     float* __restrict__ op = a.out + b * a.out_bs + l * a.D;
 #pragma unroll
@@ -220,26 +244,43 @@ static int embed_wide_launch(const EmbedArgs& a, hipStream_t st) {
   return 0;
 }
 
+// ftn_embed_wide_forward and ftn_embed_wide_forward_rms: one argument list, one set of checks (cf. shell.hip).
+static int embed_wide_forward_entry(const char* who, int norm, const float* x_dev, long long x_bstride, int B, int L,
+                                    int N, const float* w_dev, int D, const float* add_dev_or_null,
+                                    long long add_bstride, const float* gamma_dev, const float* beta_dev, float eps,
+                                    float* out_dev, void* stream) {
+  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "%s: null pointer", who);
+  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "%s: bad shape B=%d L=%d N=%d", who, B, L, N);
+  FTN_CHECK_ARG(wide_ok(D), "%s: d_model=%d must be a multiple of 4, > 128 and <= 512", who, D);
+  FTN_CHECK_ARG((long long)B * L <= 0x7fffffffLL, "%s: B=%d L=%d exceed the launch grid", who, B, L);
+  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
+  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
+  FTN_CHECK_ARG((((uintptr_t)x_dev | (uintptr_t)w_dev) & 3) == 0, "%s: x and W must be 4-byte aligned", who);
+  FTN_CHECK_ARG((((uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev | (uintptr_t)beta_dev) & 15) == 0 &&
+                    add_bstride % 4 == 0,
+                "%s: out / add / LayerNorm parameters must be 16-byte aligned", who);
+  EmbedArgs a;
+  a.x = x_dev; a.W = w_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev;
+  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.out_bs = (long long)L * D;
+  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = eps; a.norm = gamma_dev ? norm : FTN_NORM_NONE;
+  return embed_wide_launch(a, (hipStream_t)stream);
+}
+
 extern "C" int ftn_embed_wide_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
                                       int D, const float* add_dev_or_null, long long add_bstride,
                                       const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null, float ln_eps,
                                       float* out_dev, void* stream) {
-  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "ftn_embed_wide_forward: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "ftn_embed_wide_forward: bad shape B=%d L=%d N=%d", B, L, N);
-  FTN_CHECK_ARG(wide_ok(D), "ftn_embed_wide_forward: d_model=%d must be a multiple of 4, > 128 and <= 512", D);
-  FTN_CHECK_ARG((long long)B * L <= 0x7fffffffLL, "ftn_embed_wide_forward: B=%d L=%d exceed the launch grid", B, L);
-  FTN_CHECK_ARG((ln_gamma_dev_or_null == nullptr) == (ln_beta_dev_or_null == nullptr),
-                "ftn_embed_wide_forward: LayerNorm needs both gamma and beta");
-  FTN_CHECK_ARG((((uintptr_t)x_dev | (uintptr_t)w_dev) & 3) == 0,
-                "ftn_embed_wide_forward: x and W must be 4-byte aligned");
-  FTN_CHECK_ARG((((uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)ln_gamma_dev_or_null |
-                  (uintptr_t)ln_beta_dev_or_null) & 15) == 0 && add_bstride % 4 == 0,
-                "ftn_embed_wide_forward: out / add / LayerNorm parameters must be 16-byte aligned");
-  EmbedArgs a;
-  a.x = x_dev; a.W = w_dev; a.add = add_dev_or_null; a.ln_g = ln_gamma_dev_or_null; a.ln_b = ln_beta_dev_or_null;
-  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.out_bs = (long long)L * D;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = ln_eps;
-  return embed_wide_launch(a, (hipStream_t)stream);
+  return embed_wide_forward_entry("ftn_embed_wide_forward", FTN_NORM_LAYER, x_dev, x_bstride, B, L, N, w_dev, D,
+                                  add_dev_or_null, add_bstride, ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps,
+                                  out_dev, stream);
+}
+
+extern "C" int ftn_embed_wide_forward_rms(const float* x_dev, long long x_bstride, int B, int L, int N,
+                                          const float* w_dev, int D, const float* add_dev_or_null,
+                                          long long add_bstride, const float* gamma_dev, const float* beta_dev,
+                                          float eps, float* out_dev, void* stream) {
+  return embed_wide_forward_entry("ftn_embed_wide_forward_rms", FTN_NORM_RMS, x_dev, x_bstride, B, L, N, w_dev, D,
+                                  add_dev_or_null, add_bstride, gamma_dev, beta_dev, eps, out_dev, stream);
 }
 
 // The GEMM alone into rows of a larger buffer (cf. ftn_embed_rows_strided): same kernel, form and K order, so a row is
@@ -260,7 +301,7 @@ extern "C" int ftn_embed_wide_rows_strided(const float* x_dev, long long x_bstri
   EmbedArgs a;
   a.x = x_dev; a.W = w_dev; a.add = nullptr; a.ln_g = nullptr; a.ln_b = nullptr;
   a.out = out_dev; a.x_bs = x_bstride; a.add_bs = 0; a.out_bs = out_bstride;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = 0.f;
+  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = 0.f; a.norm = FTN_NORM_NONE;
   return embed_wide_launch(a, (hipStream_t)stream);
 }
 
@@ -291,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void k_embed_wide_ring(RingArgs a) {
     v[o] = *(const f4*)(vp + (cb < a.D ? cb : a.D - 4));      // (columns past d_model are never used)
   }
   const float* __restrict__ ap = a.add ? a.add + b * a.add_bs + (long long)t * a.D : nullptr;
-  embed_wide_row_finish<NO>(v, ap, a.ln_g, a.ln_b, a.ln_eps, a.D, wave, j, q, red);
+  embed_wide_row_finish<NO>(v, ap, a.ln_g, a.ln_b, a.ln_eps, a.D, wave, j, q, red, a.norm, 0);
   if (!ok) return;
   float* __restrict__ op = a.out + r * a.D;
 #pragma unroll
@@ -301,29 +342,44 @@ __global__ __launch_bounds__(256, 2) void k_embed_wide_ring(RingArgs a) {
   }
 }
 
-extern "C" int ftn_embed_wide_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
-                                   long long add_bstride, const float* ln_gamma_dev_or_null,
-                                   const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream) {
-  FTN_CHECK_ARG(v_dev && out_dev, "ftn_embed_wide_ring: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1, "ftn_embed_wide_ring: bad shape B=%d L=%d", B, L);
-  FTN_CHECK_ARG(wide_ok(D), "ftn_embed_wide_ring: d_model=%d must be a multiple of 4, > 128 and <= 512", D);
-  FTN_CHECK_ARG((long long)B * L <= 0x7fffffffLL, "ftn_embed_wide_ring: B=%d L=%d exceed the launch grid", B, L);
-  FTN_CHECK_ARG(head >= 0 && head < L, "ftn_embed_wide_ring: head=%d outside [0, L=%d)", head, L);
-  FTN_CHECK_ARG((ln_gamma_dev_or_null == nullptr) == (ln_beta_dev_or_null == nullptr),
-                "ftn_embed_wide_ring: LayerNorm needs both gamma and beta");
-  FTN_CHECK_ARG((((uintptr_t)v_dev | (uintptr_t)out_dev | (uintptr_t)add_dev_or_null |
-                  (uintptr_t)ln_gamma_dev_or_null | (uintptr_t)ln_beta_dev_or_null) & 15) == 0 &&
-                add_bstride % 4 == 0 && add_bstride >= 0,
-                "ftn_embed_wide_ring: V / out / add / LayerNorm parameters must be 16-byte aligned");
+static int embed_wide_ring_entry(const char* who, int norm, const float* v_dev, int B, int L, int D, int head,
+                                 const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
+                                 const float* beta_dev, float eps, float* out_dev, void* stream) {
+  FTN_CHECK_ARG(v_dev && out_dev, "%s: null pointer", who);
+  FTN_CHECK_ARG(B >= 1 && L >= 1, "%s: bad shape B=%d L=%d", who, B, L);
+  FTN_CHECK_ARG(wide_ok(D), "%s: d_model=%d must be a multiple of 4, > 128 and <= 512", who, D);
+  FTN_CHECK_ARG((long long)B * L <= 0x7fffffffLL, "%s: B=%d L=%d exceed the launch grid", who, B, L);
+  FTN_CHECK_ARG(head >= 0 && head < L, "%s: head=%d outside [0, L=%d)", who, head, L);
+  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
+  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
+  FTN_CHECK_ARG((((uintptr_t)v_dev | (uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev |
+                  (uintptr_t)beta_dev) & 15) == 0 &&
+                    add_bstride % 4 == 0 && add_bstride >= 0,
+                "%s: V / out / add / LayerNorm parameters must be 16-byte aligned", who);
   RingArgs a;
-  a.V = v_dev; a.add = add_dev_or_null; a.ln_g = ln_gamma_dev_or_null; a.ln_b = ln_beta_dev_or_null; a.out = out_dev;
-  a.add_bs = add_bstride; a.B = B; a.L = L; a.D = D; a.head = head; a.ln_eps = ln_eps;
+  a.V = v_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev; a.out = out_dev;
+  a.add_bs = add_bstride; a.B = B; a.L = L; a.D = D; a.head = head; a.ln_eps = eps;
+  a.norm = gamma_dev ? norm : FTN_NORM_NONE;
   const long long M = (long long)B * L;
   const dim3 grid((unsigned)((M + 15) / 16));
   if (D <= 256) hipLaunchKernelGGL(k_embed_wide_ring<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_embed_wide_ring<8>, grid, dim3(256), 0, (hipStream_t)stream, a);
   FTN_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int ftn_embed_wide_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                                   long long add_bstride, const float* ln_gamma_dev_or_null,
+                                   const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream) {
+  return embed_wide_ring_entry("ftn_embed_wide_ring", FTN_NORM_LAYER, v_dev, B, L, D, head, add_dev_or_null,
+                               add_bstride, ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps, out_dev, stream);
+}
+
+extern "C" int ftn_embed_wide_ring_rms(const float* v_dev, int B, int L, int D, int head,
+                                       const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
+                                       const float* beta_dev, float eps, float* out_dev, void* stream) {
+  return embed_wide_ring_entry("ftn_embed_wide_ring_rms", FTN_NORM_RMS, v_dev, B, L, D, head, add_dev_or_null,
+                               add_bstride, gamma_dev, beta_dev, eps, out_dev, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -19,13 +19,15 @@ flags of the blocks are collected for every step and read once after the forecas
 the whole unrolled H-step forecast as one HIP graph (every ring slot is a Python integer at capture time, so no device
 counter is needed).  Both are bit-identical to the reference loop driven over the same model on the same device.
 
-Anything else - CPU tensors, a ``direct``-mode model, autograd, ``embed_norm_mode="rms"``, d_model > 512 (> 128 under
-``FTN_SHELL_WIDE=0``), a foreign model, a ``last_seq`` whose window takes another embedding kernel than the loop's later
+Anything else - CPU tensors, a ``direct``-mode model, autograd, d_model > 512 (> 128 under ``FTN_SHELL_WIDE=0``), a
+foreign model, a ``last_seq`` whose window takes another embedding kernel than the loop's later
 windows (a view that is not 16-byte aligned, or whose batch stride is not a multiple of 4, with N % 4 == 0),
 ``embed_norm_mode="layer"`` at a d_model <= 128 that is not a multiple of 16 or on a form outside
 ``RING_EXACT_LAYER_FORMS`` - runs the reference's loop unchanged (``forecast_recursive_batch_loop``).  Beyond d_model 128
 the wide embedding and the wide ring share one epilogue function compiled without FMA contraction, so all four wide
-forms are in that set at every d_model.
+forms are in that set at every d_model.  ``embed_norm_mode="rms"`` carries no such condition: its epilogue is compiled
+without FMA contraction in the narrow kernels too, so the ring is bit-identical to the one-pass embedding on every form
+and at every d_model.
 
 ``forecast_sample_paths`` is the same recursion fed with draws instead of rates (``score.nb_sample`` at
 ``offset = step``), P paths as one batch of P B rows; ``forecast_sample_paths_loop`` fixes its semantics.
@@ -158,7 +160,8 @@ def _prepare(model, last_seq, x_mark, series_static, series_ids):
     # "layer" mode: the compiler contracts the LayerNorm epilogue of the GEMM kernels into FMAs differently from
     # k_embed_ring's on some forms, and on every form at a d_model that is not a multiple of 16 (partly masked column
     # tiles).  The ring is then equal to the loop up to rounding only, so it is used for the forms
-    # whose bit-identity the GPU suite establishes and the loop runs for the rest
+    # whose bit-identity the GPU suite establishes and the loop runs for the rest.  The "rms" epilogue is compiled
+    # without contraction in every kernel: no form condition
     if model.embedding.embed_norm_mode != "layer":
         return True
     return form in RING_EXACT_LAYER_FORMS and (model.d_model % 16 == 0 or form in _WIDE_FORMS)

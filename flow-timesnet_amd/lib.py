@@ -219,6 +219,15 @@ _SIGNATURES = {
     "ftn_embed_wide_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int]),
     "ftn_head_wide_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_timeproj_wide_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    # embed_norm_mode "rms": the signatures of the LayerNorm entry points, gamma and beta required
+    "ftn_embed_forward_rms": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong,
+                                        _P, _P, C.c_float, _P, _P]),
+    "ftn_embed_ring_rms": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, _P, C.c_float, _P,
+                                     _P]),
+    "ftn_embed_wide_forward_rms": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P,
+                                             C.c_longlong, _P, _P, C.c_float, _P, _P]),
+    "ftn_embed_wide_ring_rms": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_longlong, _P, _P, C.c_float,
+                                          _P, _P]),
     "ftn_score_form": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_score_columns": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, _P, C.c_int, C.c_float,
                                     C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -118,6 +118,12 @@ class RMSNorm(nn.Module):
         return torch.addcmul(self.bias.to(cd), v * inv_rms, self.weight.to(cd)).to(x.dtype)
 
 
+def _affine_rmsnorm(m, C: int) -> bool:
+    """``m`` is this module's ``RMSNorm`` over C columns with fp32 weight and bias, the norm the HIP epilogue takes."""
+    return (isinstance(m, RMSNorm) and all(isinstance(p, torch.Tensor) and p.dtype == torch.float32
+                                           and tuple(p.shape) == (C,) for p in (m.weight, m.bias)))
+
+
 class DataEmbedding(nn.Module):
     """value Linear(N -> d_model) + positional (+ optional time-feature Linear), with the
     reference's four normalisation modes ("decoupled" = value + gate * LayerNorm(aux))."""
@@ -593,7 +599,9 @@ class TimesNet(nn.Module):
     # ---- embedding front end ---------------------------------------------------------------
     def _hip_embed_ok(self, window: torch.Tensor) -> bool:
         emb = self.embedding
-        if emb is None or emb.embed_norm_mode not in ("decoupled", "none", "layer"):
+        if emb is None or emb.embed_norm_mode not in ("decoupled", "none", "layer", "rms"):
+            return False
+        if emb.embed_norm_mode == "rms" and not _affine_rmsnorm(emb.norm, self.d_model):
             return False
         if emb.embed_norm_mode == "layer" and not (isinstance(emb.norm, nn.LayerNorm) and emb.norm.weight is not None
                                                    and emb.norm.bias is not None):
@@ -632,10 +640,13 @@ class TimesNet(nn.Module):
     def _embed_epilogue(self, window, mark, defer: bool = False):
         """What is added to ``x W^T`` once, whatever the series: value bias + positional (+ time-feature) term, gated
         and normalised in the "decoupled" mode, ``[1|B, L, D]``; and ``(gamma, beta, eps)`` of the "layer" mode's
-        LayerNorm (None otherwise).  ``defer``: on the HIP path the term comes back unformed (``_Aux``), for
-        ``_through_weight`` to write together with the context terms."""
+        LayerNorm or ``(gamma, beta, eps, "rms")`` of the "rms" mode's norm (None otherwise).  ``defer``: on the HIP
+        path the term comes back unformed (``_Aux``), for ``_through_weight`` to write together with the context
+        terms."""
         emb = self.embedding
         ln = _ln_params(emb.norm) if emb.embed_norm_mode == "layer" else None
+        if emb.embed_norm_mode == "rms":
+            ln = _ln_params(emb.norm) + ("rms",)
         if self._hip_epilogue_ok(window, mark):
             aux = _Aux(mark if emb.temporal_embedding is not None else None, window.size(1), window.device)
             return (aux if defer else self._hip_add(aux, None, None, aux.L, None)), ln
@@ -647,7 +658,9 @@ class TimesNet(nn.Module):
         """``ftn_embed_add`` forms this embedding's epilogue term."""
         emb = self.embedding
         if not (_CTX_HIP and window.is_cuda and window.dtype == torch.float32 and hip_shell_width_ok(self.d_model)
-                and emb.embed_norm_mode in ("none", "decoupled", "layer")):
+                and emb.embed_norm_mode in ("none", "decoupled", "layer", "rms")):
+            return False
+        if emb.embed_norm_mode == "rms" and not _affine_rmsnorm(emb.norm, self.d_model):
             return False
         mods = [emb.value_embedding]
         tensors = []
@@ -932,9 +945,10 @@ class TimesNet(nn.Module):
         return F.linear(self._with_context(window, coeff, bias), w_emb.to(window.dtype))
 
     def series_embedding_epilogue(self, window, mark) -> Tuple[torch.Tensor, Optional[tuple]]:
-        """What the summed partials still need: ``_embed_epilogue`` with ``add`` as contiguous fp32."""
+        """What the summed partials still need: ``_embed_epilogue`` with ``add`` as contiguous fp32.  The norm is the
+        "layer" mode's LayerNorm or None: the series-sharded forward applies an RMS norm as a module."""
         add, ln = self._embed_epilogue(window, mark)
-        return add.detach().float().contiguous(), ln
+        return add.detach().float().contiguous(), (ln if ln is None or len(ln) == 3 else None)
 
     def series_hidden(self, seq: torch.Tensor, steps: int) -> torch.Tensor:
         """``forecast_time_proj`` of the local rows: ``[B_local, steps, d_model]`` (as ``_heads``)."""

@@ -50,6 +50,19 @@ def _norm_args(norm):
     return _ptr_or_null(g), _ptr_or_null(b), float(eps)
 
 
+def _embed_norm(norm):
+    """The norm epilogue of ``embed_forward`` / ``embed_ring``: ``(entry suffix, (gamma, beta, eps) or None)`` of
+    ``norm`` = None, ``(gamma, beta, eps)`` (LayerNorm) or ``(gamma, beta, eps, "rms")`` (the ``_rms`` entries)."""
+    if norm is None or len(norm) == 3:
+        return "", norm
+    if len(norm) != 4 or norm[3] != "rms":
+        raise ValueError(f"norm must be (gamma, beta, eps) or (gamma, beta, eps, 'rms'), got {len(norm)} elements"
+                         + (f" with kind {norm[3]!r}" if len(norm) == 4 else ""))
+    if norm[0] is None or norm[1] is None:
+        raise ValueError("the RMS norm needs gamma and beta")
+    return "_rms", tuple(norm[:3])
+
+
 def _workspace_bytes(lib, plan: FtnPlan, B: int, L: int, max_groups: int, px_bound: int) -> int:
     need = lib.ftn_timesblock_workspace_bytes(C.byref(plan), B, L, max_groups, px_bound)
     if need == 0:
@@ -461,16 +474,18 @@ def timeproj_forward(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> t
 
 def embed_forward(window: torch.Tensor, weight: torch.Tensor, add, norm=None) -> torch.Tensor:
     """``window`` [B,L,N] fp32 view with contiguous rows; ``weight`` [D,N]; ``add`` None or contiguous
-    [1|B,L,D]; ``norm`` None or ``(gamma, beta, eps)``.  Returns [B,L,D]."""
+    [1|B,L,D]; ``norm`` None, ``(gamma, beta, eps)`` of a LayerNorm or ``(gamma, beta, eps, "rms")`` of an RMS norm.
+    Returns [B,L,D]."""
     lib = _lib.load()
     B, L, N = window.shape
     D = weight.shape[0]
+    kind, norm = _embed_norm(norm)
     if window.stride(2) != 1 or window.stride(1) != N:
         raise ValueError("window rows must be contiguous")
     if add is not None and (add.shape[-2:] != (L, D) or not add.is_contiguous()):
         raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=window.device)
-    entry = "ftn_embed_wide_forward" if _wide(D) else "ftn_embed_forward"
+    entry = ("ftn_embed_wide_forward" if _wide(D) else "ftn_embed_forward") + kind
     check(getattr(lib, entry)(_ptr(window), window.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
                               _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
                               _ptr(out), _stream(window.device)), entry)
@@ -494,17 +509,19 @@ def embed_rows_strided(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor,
 
 
 def embed_ring(V: torch.Tensor, head: int, add, norm=None) -> torch.Tensor:
-    """``out[b, t] = V[b, (head + t) % L] + add[b?, t]`` (+ LayerNorm ``norm = (gamma, beta, eps)``) with
-    ``embed_forward``'s epilogue arithmetic.  ``V`` contiguous fp32 [B,L,D]; ``add`` None or contiguous [1|B,L,D]."""
+    """``out[b, t] = V[b, (head + t) % L] + add[b?, t]`` (+ LayerNorm ``norm = (gamma, beta, eps)`` or RMS norm
+    ``(gamma, beta, eps, "rms")``) with ``embed_forward``'s epilogue arithmetic.  ``V`` contiguous fp32 [B,L,D];
+    ``add`` None or contiguous [1|B,L,D]."""
     lib = _lib.load()
     B, L, D = V.shape
+    kind, norm = _embed_norm(norm)
     if not V.is_contiguous() or V.dtype != torch.float32:
         raise ValueError("V must be contiguous fp32 [B, L, D]")
     if add is not None and (add.dim() != 3 or add.shape[-2:] != (L, D) or add.shape[0] not in (1, B)
                             or not add.is_contiguous()):
         raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=V.device)
-    entry = "ftn_embed_wide_ring" if _wide(D) else "ftn_embed_ring"
+    entry = ("ftn_embed_wide_ring" if _wide(D) else "ftn_embed_ring") + kind
     check(getattr(lib, entry)(_ptr(V), B, L, D, int(head), _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
                               _ptr(out), _stream(V.device)), entry)
     return out

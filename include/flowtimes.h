@@ -536,6 +536,40 @@ int ftn_embed_wide_form(int N, int D, long long x_bstride, int x_misalign, int w
 int ftn_head_wide_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or);
 int ftn_timeproj_wide_form(int L, int S, int D, int wt_misalign);
 
+/* ---- RMS norm epilogue of the value embedding (embed_norm_mode "rms"; csrc/shell.hip, csrc/shell_wide.hip) ------
+ * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
+ *
+ * Each takes the argument list of its LayerNorm counterpart (ftn_embed_forward, ftn_embed_ring, ftn_embed_wide_forward,
+ * ftn_embed_wide_ring) with the same meaning, alignment rules, D limits (a multiple of 4; <= 128 narrow, 128 < D <= 512
+ * wide) and "enqueue only, no allocation" convention, and closes a row with the reference's RMS norm instead
+ * (models/timesnet.py:1153-1158), in fp32:
+ *   v     = x[b][l][:] W^T + add[b?][l][:]        (ring: V[b][(head + t) mod L][:] + add[b?][t][:])
+ *   ss    = sum_d v[d]^2
+ *   scale = 1 / sqrt(ss / D + eps)
+ *   out   = (v * scale) * gamma + beta
+ * gamma and beta [D] are required here: a null one is a bad argument (< 0), reported before any launch.
+ * The kernels and forms are those of the counterparts (ftn_embed_form / ftn_embed_wide_form answer for both): the
+ * norm is an argument of the kernel, not another kernel.  ss is added up in the order of the LayerNorm mean - a pair
+ * tree over the four columns of each of the lane's column tiles, the tiles in order, the four lanes of a row (xor 16,
+ * 32), and beyond d_model 128 the four column slabs in slab order through LDS with one barrier (LayerNorm: two); a slab
+ * past D adds an exact zero.  Nothing is pre-scaled against overflow: a row whose squares overflow fp32 has
+ * scale = 1 / sqrt(inf) = 0 and comes out as beta, as the reference's fp32 rsqrt(inf) gives it.  The norm is compiled
+ * without FMA contraction in the GEMM kernels and in the ring kernels alike, so a ring row is bit-identical to the row
+ * of the one-pass call on the equivalent window on every form and at every D (LayerNorm: on some narrow forms only).
+ * A row's bits do not depend on B, on its position in the batch or on which rows share the call. */
+int ftn_embed_forward_rms(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev, int D,
+                          const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
+                          const float* beta_dev, float eps, float* out_dev, void* stream);
+int ftn_embed_ring_rms(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                       long long add_bstride, const float* gamma_dev, const float* beta_dev, float eps,
+                       float* out_dev, void* stream);
+int ftn_embed_wide_forward_rms(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev, int D,
+                               const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
+                               const float* beta_dev, float eps, float* out_dev, void* stream);
+int ftn_embed_wide_ring_rms(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
+                            long long add_bstride, const float* gamma_dev, const float* beta_dev, float eps,
+                            float* out_dev, void* stream);
+
 /* ---- scoring a forecast (losses.py:27-58, train.py:675-765 of the reference) -------------------------
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
  *
