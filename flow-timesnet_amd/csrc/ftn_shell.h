@@ -1,5 +1,6 @@
-// What the model-shell kernels of shell.hip (d_model <= 128) and shell_wide.hip (128 < d_model <= 512) share: the
-// argument blocks of the heads, the value embedding and the ring epilogue, and the heads' softplus.
+// What the model-shell units share - the kernel units shell.hip (d_model <= 128), shell_wide.hip (128 < d_model <= 512)
+// and timeproj.hip, and the host entry layer shell_api.hip: the argument blocks, the heads' softplus, the two widths,
+// and the form and launch functions the kernel units define for the entry layer.
 #pragma once
 #include "ftn_common.h"
 
@@ -69,3 +70,51 @@ struct RingArgs {
   float ln_eps;
   int norm;              // FTN_NORM_*
 };
+
+struct TimeProjArgs {
+  const float* seq;      // [B][L][D]
+  const float* wt;       // [S][L], base only 4-byte aligned when it is a row slice at L % 4 != 0
+  const float* bt;       // [S]
+  float* hid;            // [B][S][D]
+  int B, L, D, S;
+};
+
+// The two widths of the shell.  An exported entry names its width and hands it to the shared body (shell_api.hip);
+// nothing picks it from d_model, so ftn_embed_forward rejects 132 and ftn_embed_wide_forward rejects 128.  The two
+// flags are checks only the wide entries make.  That is deliberate: the narrow entries accept what they accepted
+// before the wide ones existed.
+struct ShellWidth {
+  bool wide;
+  int d_min, d_max;      // d_model: a multiple of 4 in [d_min, d_max]
+  const char* range;     // how the message about d_model names the range
+  bool rows_fit_grid;    // embedding, embedding rows, ring: B * L <= 0x7fffffff
+  bool align4;           // embedding, embedding rows: x and W 4-byte aligned; heads: every operand besides hidden
+                         // and the weights (those are 16-byte aligned at either width)
+  bool d_ok(int D) const { return D >= d_min && D <= d_max && D % 4 == 0; }
+};
+inline constexpr ShellWidth kShellNarrow = {false, 4, 128, "<= 128", false, false};
+inline constexpr ShellWidth kShellWide = {true, 132, 512, "> 128 and <= 512", true, true};
+
+// gridDim.y of the head kernels: a workgroup's four waves take a 16-row tile each, up to the form's cap (form >> 16)
+static inline unsigned head_grid_y(long long rows, int form) {
+  const long long rtiles = (rows + 15) / 16, want = form >> 16;
+  const long long gy = (rtiles + 3) / 4;
+  return (unsigned)(gy > want ? want : gy);
+}
+
+// What the kernel units define for the entry layer: the form rules and one launch per operation and width, taking
+// the filled and checked argument block.  Internal to the library, so kept out of its dynamic symbol table.
+#pragma GCC visibility push(hidden)
+int head_form(int N, int D, long long tail_bs, long long late_bs, unsigned misalign);               // shell.hip
+int embed_form(int N, int D, long long x_bs, unsigned misalign);
+int head_launch(const HeadArgs& a, hipStream_t st);
+int embed_launch(const EmbedArgs& a, hipStream_t st);
+int ring_launch(const RingArgs& a, hipStream_t st);
+int head_wide_form(int N, int D, long long tail_bs, long long late_bs, unsigned misalign);          // shell_wide.hip
+int embed_wide_form(int N, int D, long long x_bs, unsigned misalign);
+int head_wide_launch(const HeadArgs& a, hipStream_t st);
+int embed_wide_launch(const EmbedArgs& a, hipStream_t st);
+int ring_wide_launch(const RingArgs& a, hipStream_t st);
+int timeproj_form(int L, int S, unsigned wt_misalign);                                               // timeproj.hip
+int timeproj_launch(const TimeProjArgs& a, const ShellWidth& w, hipStream_t st);
+#pragma GCC visibility pop

@@ -4,6 +4,7 @@
 //   k_embed_ring  the embedding of a sliding window from a ring of stored x W^T rows (recursive forecasting)
 // HBM-bound: each reads its input once and writes its outputs once; the small GEMMs run on the exact
 // fp32 MFMA (v_mfma_f32_16x16x4_f32) so no precision is traded.
+// Kernels, form rules and one launch per operation (ftn_shell.h); the C entry points are in shell_api.hip.
 #include <stdlib.h>
 #include "ftn_common.h"
 #include "ftn_mlp.h"
@@ -248,7 +249,7 @@ static const int g_head_f32 = [] { const char* e = getenv("FTN_HEAD_F32"); retur
 // below dispatches on this value and ftn_head_form exports it.  misalign: the OR of the byte offsets of tail, late,
 // rate and disp from a 16-byte boundary.  The cap on gridDim.y keeps three (16-bit forms) / four (fp32 forms)
 // workgroups per CU in flight; beyond 64 * cap rows a workgroup walks several row tiles.
-static int head_form(int N, int D, long long tail_bs, long long late_bs, unsigned misalign) {
+int head_form(int N, int D, long long tail_bs, long long late_bs, unsigned misalign) {
   const bool vec = N % 4 == 0 && tail_bs % 4 == 0 && late_bs % 4 == 0 && (misalign & 15) == 0;
   if (vec && !g_head_f32) {
     const int nt = D <= 64 ? 4 : 2, ns32 = D <= 32 ? 1 : D <= 64 ? 2 : 4;
@@ -262,23 +263,14 @@ static int head_form(int N, int D, long long tail_bs, long long late_bs, unsigne
   return (vec ? FTN_SHELL_VEC : 0) | ns << 4 | cap << 16;
 }
 
-extern "C" int ftn_head_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or) {
-  FTN_CHECK_ARG(N >= 1 && D >= 4 && D % 4 == 0 && D <= 128 && misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0,
-                "ftn_head_form: N=%d d_model=%d misalign=%d", N, D, misalign_or);
-  return head_form(N, D, tail_bstride, late_bstride, (unsigned)misalign_or);
-}
-
 template <int NT, int NS32>
 static int launch_head_bf(const HeadArgs& a, int form, hipStream_t st) {
   const int ntile = (a.N + 16 * NT - 1) / (16 * NT);
-  const long long rtiles = (a.rows + 15) / 16;
-  long long gy = (rtiles + 3) / 4;
-  const long long want = form >> 16;
-  if (gy > want) gy = want;
+  const unsigned gy = head_grid_y(a.rows, form);
   const size_t lds = (size_t)2 * NT * NS32 * 3 * 1024 + 3 * 16 * NT * sizeof(float);
   hipError_t e = hipFuncSetAttribute((const void*)k_head_bf<NT, NS32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute(k_head_bf): %s", hipGetErrorString(e)); return (int)e; }
-  hipLaunchKernelGGL((k_head_bf<NT, NS32>), dim3(ntile, (unsigned)gy), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((k_head_bf<NT, NS32>), dim3(ntile, gy), dim3(256), lds, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
 }
@@ -286,41 +278,18 @@ static int launch_head_bf(const HeadArgs& a, int form, hipStream_t st) {
 template <int NS>
 static int launch_head(const HeadArgs& a, int form, hipStream_t st) {
   const int ntile = (a.N + 63) / 64;
-  const long long rtiles = (a.rows + 15) / 16;
-  long long gy = (rtiles + 3) / 4;
-  const long long want = form >> 16;
-  if (gy > want) gy = want;
+  const unsigned gy = head_grid_y(a.rows, form);
   const size_t lds = (size_t)2 * 4 * NS * 64 * sizeof(f4) + 192 * sizeof(float);
-  if (form & FTN_SHELL_VEC) hipLaunchKernelGGL((k_head<NS, true>), dim3(ntile, (unsigned)gy), dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((k_head<NS, false>), dim3(ntile, (unsigned)gy), dim3(256), lds, st, a);
+  if (form & FTN_SHELL_VEC) hipLaunchKernelGGL((k_head<NS, true>), dim3(ntile, gy), dim3(256), lds, st, a);
+  else hipLaunchKernelGGL((k_head<NS, false>), dim3(ntile, gy), dim3(256), lds, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int ftn_head_forward(const float* hidden_dev, long long rows, int S, int D, int N, const float* w_mu_dev,
-                                const float* b_mu_dev, const float* w_sigma_dev, const float* b_sigma_dev,
-                                const float* tail_dev, long long tail_bstride, int hist,
-                                const float* late_dev_or_null, long long late_bstride,
-                                const float* floor_vec_dev_or_null, float floor_scalar, float* rate_dev,
-                                float* disp_dev, int* bad_flag_dev, void* stream) {
-  FTN_CHECK_ARG(hidden_dev && w_mu_dev && b_mu_dev && w_sigma_dev && b_sigma_dev && tail_dev && rate_dev &&
-                    disp_dev && bad_flag_dev,
-                "ftn_head_forward: null pointer");
-  FTN_CHECK_ARG(rows >= 1 && S >= 1 && rows % S == 0 && N >= 1 && hist >= 1 && hist <= S,
-                "ftn_head_forward: rows=%lld S=%d N=%d hist=%d", rows, S, N, hist);
-  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "ftn_head_forward: d_model=%d must be a multiple of 4, <= 128", D);
-  FTN_CHECK_ARG((((uintptr_t)hidden_dev | (uintptr_t)w_mu_dev | (uintptr_t)w_sigma_dev) & 15) == 0,
-                "ftn_head_forward: hidden and the head weights must be 16-byte aligned");
-  HeadArgs a;
-  a.hidden = hidden_dev; a.wmu = w_mu_dev; a.bmu = b_mu_dev; a.wsg = w_sigma_dev; a.bsg = b_sigma_dev;
-  a.tail = tail_dev; a.late = late_dev_or_null; a.floorv = floor_vec_dev_or_null;
-  a.rate = rate_dev; a.disp = disp_dev; a.bad = bad_flag_dev;
-  a.rows = rows; a.tail_bs = tail_bstride; a.late_bs = late_bstride;
-  a.S = S; a.D = D; a.N = N; a.hist = hist; a.floor_s = floor_scalar;
-  const int form = head_form(N, D, tail_bstride, late_bstride,
-                             (unsigned)(((uintptr_t)tail_dev | (uintptr_t)late_dev_or_null | (uintptr_t)rate_dev |
-                                         (uintptr_t)disp_dev) & 15));
-  hipStream_t st = (hipStream_t)stream;
+// The launch of ftn_head_forward's checked argument block.
+int head_launch(const HeadArgs& a, hipStream_t st) {
+  const int form = head_form(a.N, a.D, a.tail_bs, a.late_bs,
+                             (unsigned)(((uintptr_t)a.tail | (uintptr_t)a.late | (uintptr_t)a.rate | (uintptr_t)a.disp) & 15));
   const int p0 = (form >> 4) & 15, p1 = (form >> 8) & 15;     // NT, NS32 (16-bit forms) | NS (fp32 forms)
   if (form & FTN_SHELL_BF) {
     if (p0 == 4 && p1 == 1) return launch_head_bf<4, 1>(a, form, st);
@@ -636,7 +605,7 @@ static const int g_embed_rt = [] { const char* e = getenv("FTN_EMBED_RT"); retur
 // d_model 128: one 16-row tile per wave - at 32 rows a wave the c4 shard (46 080 rows) is 1 440 waves for 1 024 SIMDs,
 // two on some, one on others, and the launch lasts as long as the SIMDs with two (350 vs 296 us); d_model <= 64: two
 // tiles per wave share every W fragment read (51 vs 61 us at the bench shape).  FTN_EMBED_RT=1|2 forces one.
-static int embed_form(int N, int D, long long x_bs, unsigned misalign) {
+int embed_form(int N, int D, long long x_bs, unsigned misalign) {
   const bool vec = N % 4 == 0 && x_bs % 4 == 0 && (misalign & 15) == 0;
   const int no = D <= 64 ? 4 : 8;
   if (vec && !g_embed_f32) {
@@ -644,13 +613,6 @@ static int embed_form(int N, int D, long long x_bs, unsigned misalign) {
     return FTN_SHELL_BF | FTN_SHELL_VEC | no << 4 | (rt == 1 ? 1 : 2) << 8;
   }
   return (vec ? FTN_SHELL_VEC : 0) | no << 4 | 2 << 8;        // k_embed_in: two row tiles per wave
-}
-
-extern "C" int ftn_embed_form(int N, int D, long long x_bstride, int x_misalign, int w_misalign) {
-  FTN_CHECK_ARG(N >= 1 && D >= 4 && D % 4 == 0 && D <= 128 && x_misalign >= 0 && x_misalign < 16 && x_misalign % 4 == 0 &&
-                    w_misalign >= 0 && w_misalign < 16 && w_misalign % 4 == 0,
-                "ftn_embed_form: N=%d d_model=%d misalign=%d/%d", N, D, x_misalign, w_misalign);
-  return embed_form(N, D, x_bstride, (unsigned)(x_misalign | w_misalign));
 }
 
 template <int NO>
@@ -666,68 +628,10 @@ static int launch_embed(const EmbedArgs& a, int form, hipStream_t st) {
   return 0;
 }
 
-static int embed_launch(EmbedArgs& a, hipStream_t st) {
+int embed_launch(const EmbedArgs& a, hipStream_t st) {
   const int form = embed_form(a.N, a.D, a.x_bs, (unsigned)(((uintptr_t)a.x | (uintptr_t)a.W) & 15));
   if (((form >> 4) & 15) == 4) return launch_embed<4>(a, form, st);
   return launch_embed<8>(a, form, st);
-}
-
-// ftn_embed_forward and ftn_embed_forward_rms: one argument list, one set of checks.  norm: FTN_NORM_LAYER takes both
-// of gamma / beta or neither (no norm), FTN_NORM_RMS needs both.
-static int embed_forward_entry(const char* who, int norm, const float* x_dev, long long x_bstride, int B, int L, int N,
-                               const float* w_dev, int D, const float* add_dev_or_null, long long add_bstride,
-                               const float* gamma_dev, const float* beta_dev, float eps, float* out_dev,
-                               void* stream) {
-  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "%s: null pointer", who);
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "%s: bad shape B=%d L=%d N=%d", who, B, L, N);
-  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "%s: d_model=%d must be a multiple of 4, <= 128", who, D);
-  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
-  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
-  FTN_CHECK_ARG((((uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev | (uintptr_t)beta_dev) & 15) == 0 &&
-                    add_bstride % 4 == 0,
-                "%s: out / add / LayerNorm parameters must be 16-byte aligned", who);
-  EmbedArgs a;
-  a.x = x_dev; a.W = w_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev;
-  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.out_bs = (long long)L * D;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = eps; a.norm = gamma_dev ? norm : FTN_NORM_NONE;
-  return embed_launch(a, (hipStream_t)stream);
-}
-
-extern "C" int ftn_embed_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
-                                 int D, const float* add_dev_or_null, long long add_bstride,
-                                 const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null, float ln_eps,
-                                 float* out_dev, void* stream) {
-  return embed_forward_entry("ftn_embed_forward", FTN_NORM_LAYER, x_dev, x_bstride, B, L, N, w_dev, D, add_dev_or_null,
-                             add_bstride, ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps, out_dev, stream);
-}
-
-extern "C" int ftn_embed_forward_rms(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
-                                     int D, const float* add_dev_or_null, long long add_bstride,
-                                     const float* gamma_dev, const float* beta_dev, float eps, float* out_dev,
-                                     void* stream) {
-  return embed_forward_entry("ftn_embed_forward_rms", FTN_NORM_RMS, x_dev, x_bstride, B, L, N, w_dev, D,
-                             add_dev_or_null, add_bstride, gamma_dev, beta_dev, eps, out_dev, stream);
-}
-
-// The value-embedding GEMM alone (no add, no LayerNorm) into rows of a larger buffer: row (b, l) of x W^T lands at
-// out + b * out_bstride + l * D.  Same kernels, same form selection and same K order as ftn_embed_forward, so a row
-// comes out bit-identical to what the full-window call computes for it before its epilogue.  The recursive forecaster
-// (forecast.py) appends each step's B new rows (L = 1) to its ring of embedded rows with it.
-extern "C" int ftn_embed_rows_strided(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
-                                      int D, float* out_dev, long long out_bstride, void* stream) {
-  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "ftn_embed_rows_strided: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "ftn_embed_rows_strided: bad shape B=%d L=%d N=%d", B, L, N);
-  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "ftn_embed_rows_strided: d_model=%d must be a multiple of 4, <= 128",
-                D);
-  FTN_CHECK_ARG(B == 1 || out_bstride >= (long long)L * D, "ftn_embed_rows_strided: out_bstride=%lld < L*D=%lld",
-                out_bstride, (long long)L * D);
-  FTN_CHECK_ARG(((uintptr_t)out_dev & 15) == 0 && out_bstride % 4 == 0,
-                "ftn_embed_rows_strided: out must be 16-byte aligned, out_bstride a multiple of 4");
-  EmbedArgs a;
-  a.x = x_dev; a.W = w_dev; a.add = nullptr; a.ln_g = nullptr; a.ln_b = nullptr;
-  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = 0; a.out_bs = out_bstride;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = 0.f; a.norm = FTN_NORM_NONE;
-  return embed_launch(a, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -766,42 +670,11 @@ __global__ __launch_bounds__(256) void k_embed_ring(RingArgs a) {
   }
 }
 
-static int embed_ring_entry(const char* who, int norm, const float* v_dev, int B, int L, int D, int head,
-                            const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
-                            const float* beta_dev, float eps, float* out_dev, void* stream) {
-  FTN_CHECK_ARG(v_dev && out_dev, "%s: null pointer", who);
-  FTN_CHECK_ARG(B >= 1 && L >= 1, "%s: bad shape B=%d L=%d", who, B, L);
-  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "%s: d_model=%d must be a multiple of 4, <= 128", who, D);
-  FTN_CHECK_ARG(head >= 0 && head < L, "%s: head=%d outside [0, L=%d)", who, head, L);
-  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
-  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
-  FTN_CHECK_ARG((((uintptr_t)v_dev | (uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev |
-                  (uintptr_t)beta_dev) & 15) == 0 &&
-                    add_bstride % 4 == 0 && add_bstride >= 0,
-                "%s: V / out / add / LayerNorm parameters must be 16-byte aligned", who);
-  RingArgs a;
-  a.V = v_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev; a.out = out_dev;
-  a.add_bs = add_bstride; a.B = B; a.L = L; a.D = D; a.head = head; a.ln_eps = eps;
-  a.norm = gamma_dev ? norm : FTN_NORM_NONE;
-  const long long M = (long long)B * L;
+int ring_launch(const RingArgs& a, hipStream_t st) {
+  const long long M = (long long)a.B * a.L;
   const dim3 grid((unsigned)((M + 63) / 64));
-  hipStream_t st = (hipStream_t)stream;
-  if (D <= 64) hipLaunchKernelGGL(k_embed_ring<4>, grid, dim3(256), 0, st, a);
+  if (a.D <= 64) hipLaunchKernelGGL(k_embed_ring<4>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_embed_ring<8>, grid, dim3(256), 0, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
-                              long long add_bstride, const float* ln_gamma_dev_or_null,
-                              const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream) {
-  return embed_ring_entry("ftn_embed_ring", FTN_NORM_LAYER, v_dev, B, L, D, head, add_dev_or_null, add_bstride,
-                          ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps, out_dev, stream);
-}
-
-extern "C" int ftn_embed_ring_rms(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
-                                  long long add_bstride, const float* gamma_dev, const float* beta_dev, float eps,
-                                  float* out_dev, void* stream) {
-  return embed_ring_entry("ftn_embed_ring_rms", FTN_NORM_RMS, v_dev, B, L, D, head, add_dev_or_null, add_bstride,
-                          gamma_dev, beta_dev, eps, out_dev, stream);
 }

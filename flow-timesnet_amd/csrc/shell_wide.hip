@@ -6,12 +6,11 @@
 // Products are bf16x3 on the 16-bit matrix pipe (split_pieces<3> / chain_bf<3>, ftn_mlp.h), the arithmetic class of
 // the narrow forms.  No atomics on outputs, no split of K across workgroups: the bits of an output row are a function
 // of its own operands, (N, D) and the form.
+// Kernels, form rules and one launch per operation (ftn_shell.h); the C entry points are in shell_api.hip.
 #include <stdlib.h>
 #include "ftn_common.h"
 #include "ftn_mlp.h"
 #include "ftn_shell.h"
-
-static inline bool wide_ok(int D) { return D > 128 && D <= 512 && D % 4 == 0; }
 
 // ---------------------------------------------------------------------------------------------
 // Value embedding: out[b][l][:] = x[b][l][:] W^T + add[b?][l][:]   (+ optional LayerNorm over d_model)
@@ -216,19 +215,12 @@ __global__ __launch_bounds__(256) void k_embed_wide_bf(EmbedArgs a) {
 
 // The form the wide embedding entry points take (include/flowtimes.h): the one place the choice is made - the launch
 // dispatches on this value and ftn_embed_wide_form exports it.  misalign: the OR of the byte offsets of x and W.
-static int embed_wide_form(int N, int D, long long x_bs, unsigned misalign) {
+int embed_wide_form(int N, int D, long long x_bs, unsigned misalign) {
   const bool vec = N % 4 == 0 && x_bs % 4 == 0 && (misalign & 15) == 0;
   return FTN_SHELL_BF | (vec ? FTN_SHELL_VEC : 0) | (D <= 256 ? 4 : 8) << 4 | EW_RT << 8;
 }
 
-extern "C" int ftn_embed_wide_form(int N, int D, long long x_bstride, int x_misalign, int w_misalign) {
-  FTN_CHECK_ARG(N >= 1 && wide_ok(D) && x_misalign >= 0 && x_misalign < 16 && x_misalign % 4 == 0 &&
-                    w_misalign >= 0 && w_misalign < 16 && w_misalign % 4 == 0,
-                "ftn_embed_wide_form: N=%d d_model=%d misalign=%d/%d", N, D, x_misalign, w_misalign);
-  return embed_wide_form(N, D, x_bstride, (unsigned)(x_misalign | w_misalign));
-}
-
-static int embed_wide_launch(const EmbedArgs& a, hipStream_t st) {
+int embed_wide_launch(const EmbedArgs& a, hipStream_t st) {
   const int form = embed_wide_form(a.N, a.D, a.x_bs, (unsigned)(((uintptr_t)a.x | (uintptr_t)a.W) & 15));
   const long long M = (long long)a.B * a.L;
   const dim3 grid((unsigned)((M + 16 * EW_RT - 1) / (16 * EW_RT))), block(256);
@@ -242,67 +234,6 @@ static int embed_wide_launch(const EmbedArgs& a, hipStream_t st) {
   }
   FTN_CHECK_LAUNCH();
   return 0;
-}
-
-// ftn_embed_wide_forward and ftn_embed_wide_forward_rms: one argument list, one set of checks (cf. shell.hip).
-static int embed_wide_forward_entry(const char* who, int norm, const float* x_dev, long long x_bstride, int B, int L,
-                                    int N, const float* w_dev, int D, const float* add_dev_or_null,
-                                    long long add_bstride, const float* gamma_dev, const float* beta_dev, float eps,
-                                    float* out_dev, void* stream) {
-  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "%s: null pointer", who);
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "%s: bad shape B=%d L=%d N=%d", who, B, L, N);
-  FTN_CHECK_ARG(wide_ok(D), "%s: d_model=%d must be a multiple of 4, > 128 and <= 512", who, D);
-  FTN_CHECK_ARG((long long)B * L <= 0x7fffffffLL, "%s: B=%d L=%d exceed the launch grid", who, B, L);
-  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
-  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
-  FTN_CHECK_ARG((((uintptr_t)x_dev | (uintptr_t)w_dev) & 3) == 0, "%s: x and W must be 4-byte aligned", who);
-  FTN_CHECK_ARG((((uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev | (uintptr_t)beta_dev) & 15) == 0 &&
-                    add_bstride % 4 == 0,
-                "%s: out / add / LayerNorm parameters must be 16-byte aligned", who);
-  EmbedArgs a;
-  a.x = x_dev; a.W = w_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev;
-  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = add_bstride; a.out_bs = (long long)L * D;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = eps; a.norm = gamma_dev ? norm : FTN_NORM_NONE;
-  return embed_wide_launch(a, (hipStream_t)stream);
-}
-
-extern "C" int ftn_embed_wide_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev,
-                                      int D, const float* add_dev_or_null, long long add_bstride,
-                                      const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null, float ln_eps,
-                                      float* out_dev, void* stream) {
-  return embed_wide_forward_entry("ftn_embed_wide_forward", FTN_NORM_LAYER, x_dev, x_bstride, B, L, N, w_dev, D,
-                                  add_dev_or_null, add_bstride, ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps,
-                                  out_dev, stream);
-}
-
-extern "C" int ftn_embed_wide_forward_rms(const float* x_dev, long long x_bstride, int B, int L, int N,
-                                          const float* w_dev, int D, const float* add_dev_or_null,
-                                          long long add_bstride, const float* gamma_dev, const float* beta_dev,
-                                          float eps, float* out_dev, void* stream) {
-  return embed_wide_forward_entry("ftn_embed_wide_forward_rms", FTN_NORM_RMS, x_dev, x_bstride, B, L, N, w_dev, D,
-                                  add_dev_or_null, add_bstride, gamma_dev, beta_dev, eps, out_dev, stream);
-}
-
-// The GEMM alone into rows of a larger buffer (cf. ftn_embed_rows_strided): same kernel, form and K order, so a row is
-// bit-identical to what ftn_embed_wide_forward holds for it before its epilogue.
-extern "C" int ftn_embed_wide_rows_strided(const float* x_dev, long long x_bstride, int B, int L, int N,
-                                           const float* w_dev, int D, float* out_dev, long long out_bstride,
-                                           void* stream) {
-  FTN_CHECK_ARG(x_dev && w_dev && out_dev, "ftn_embed_wide_rows_strided: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && N >= 1, "ftn_embed_wide_rows_strided: bad shape B=%d L=%d N=%d", B, L, N);
-  FTN_CHECK_ARG(wide_ok(D), "ftn_embed_wide_rows_strided: d_model=%d must be a multiple of 4, > 128 and <= 512", D);
-  FTN_CHECK_ARG((long long)B * L <= 0x7fffffffLL, "ftn_embed_wide_rows_strided: B=%d L=%d exceed the launch grid", B, L);
-  FTN_CHECK_ARG(B == 1 || out_bstride >= (long long)L * D, "ftn_embed_wide_rows_strided: out_bstride=%lld < L*D=%lld",
-                out_bstride, (long long)L * D);
-  FTN_CHECK_ARG((((uintptr_t)x_dev | (uintptr_t)w_dev) & 3) == 0,
-                "ftn_embed_wide_rows_strided: x and W must be 4-byte aligned");
-  FTN_CHECK_ARG(((uintptr_t)out_dev & 15) == 0 && out_bstride % 4 == 0,
-                "ftn_embed_wide_rows_strided: out must be 16-byte aligned, out_bstride a multiple of 4");
-  EmbedArgs a;
-  a.x = x_dev; a.W = w_dev; a.add = nullptr; a.ln_g = nullptr; a.ln_b = nullptr;
-  a.out = out_dev; a.x_bs = x_bstride; a.add_bs = 0; a.out_bs = out_bstride;
-  a.B = B; a.L = L; a.N = N; a.D = D; a.ln_eps = 0.f; a.norm = FTN_NORM_NONE;
-  return embed_wide_launch(a, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -342,44 +273,13 @@ __global__ __launch_bounds__(256, 2) void k_embed_wide_ring(RingArgs a) {
   }
 }
 
-static int embed_wide_ring_entry(const char* who, int norm, const float* v_dev, int B, int L, int D, int head,
-                                 const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
-                                 const float* beta_dev, float eps, float* out_dev, void* stream) {
-  FTN_CHECK_ARG(v_dev && out_dev, "%s: null pointer", who);
-  FTN_CHECK_ARG(B >= 1 && L >= 1, "%s: bad shape B=%d L=%d", who, B, L);
-  FTN_CHECK_ARG(wide_ok(D), "%s: d_model=%d must be a multiple of 4, > 128 and <= 512", who, D);
-  FTN_CHECK_ARG((long long)B * L <= 0x7fffffffLL, "%s: B=%d L=%d exceed the launch grid", who, B, L);
-  FTN_CHECK_ARG(head >= 0 && head < L, "%s: head=%d outside [0, L=%d)", who, head, L);
-  if (norm == FTN_NORM_RMS) FTN_CHECK_ARG(gamma_dev && beta_dev, "%s: the RMS norm needs gamma and beta", who);
-  FTN_CHECK_ARG((gamma_dev == nullptr) == (beta_dev == nullptr), "%s: LayerNorm needs both gamma and beta", who);
-  FTN_CHECK_ARG((((uintptr_t)v_dev | (uintptr_t)out_dev | (uintptr_t)add_dev_or_null | (uintptr_t)gamma_dev |
-                  (uintptr_t)beta_dev) & 15) == 0 &&
-                    add_bstride % 4 == 0 && add_bstride >= 0,
-                "%s: V / out / add / LayerNorm parameters must be 16-byte aligned", who);
-  RingArgs a;
-  a.V = v_dev; a.add = add_dev_or_null; a.ln_g = gamma_dev; a.ln_b = beta_dev; a.out = out_dev;
-  a.add_bs = add_bstride; a.B = B; a.L = L; a.D = D; a.head = head; a.ln_eps = eps;
-  a.norm = gamma_dev ? norm : FTN_NORM_NONE;
-  const long long M = (long long)B * L;
+int ring_wide_launch(const RingArgs& a, hipStream_t st) {
+  const long long M = (long long)a.B * a.L;
   const dim3 grid((unsigned)((M + 15) / 16));
-  if (D <= 256) hipLaunchKernelGGL(k_embed_wide_ring<4>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(k_embed_wide_ring<8>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  if (a.D <= 256) hipLaunchKernelGGL(k_embed_wide_ring<4>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_embed_wide_ring<8>, grid, dim3(256), 0, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int ftn_embed_wide_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
-                                   long long add_bstride, const float* ln_gamma_dev_or_null,
-                                   const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream) {
-  return embed_wide_ring_entry("ftn_embed_wide_ring", FTN_NORM_LAYER, v_dev, B, L, D, head, add_dev_or_null,
-                               add_bstride, ln_gamma_dev_or_null, ln_beta_dev_or_null, ln_eps, out_dev, stream);
-}
-
-extern "C" int ftn_embed_wide_ring_rms(const float* v_dev, int B, int L, int D, int head,
-                                       const float* add_dev_or_null, long long add_bstride, const float* gamma_dev,
-                                       const float* beta_dev, float eps, float* out_dev, void* stream) {
-  return embed_wide_ring_entry("ftn_embed_wide_ring_rms", FTN_NORM_RMS, v_dev, B, L, D, head, add_dev_or_null,
-                               add_bstride, gamma_dev, beta_dev, eps, out_dev, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -576,7 +476,7 @@ static size_t head_wide_lds(int nt, int D) { return (size_t)2 * nt * ((D + 31) /
 // the byte offsets of tail, late, rate and disp from a 16-byte boundary.  The cap on gridDim.y keeps as many
 // workgroups per CU in flight as their LDS allows (160 KB a CU); beyond 64 * cap rows a workgroup walks several row
 // tiles.  0: k_head_wide_f32.
-static int head_wide_form(int N, int D, long long tail_bs, long long late_bs, unsigned misalign) {
+int head_wide_form(int N, int D, long long tail_bs, long long late_bs, unsigned misalign) {
   const bool vec = N % 4 == 0 && tail_bs % 4 == 0 && late_bs % 4 == 0 && (misalign & 15) == 0;
   if (!vec) return 0;
   const int nt = D <= 256 ? 2 : 1;
@@ -586,57 +486,23 @@ static int head_wide_form(int N, int D, long long tail_bs, long long late_bs, un
   return FTN_SHELL_BF | FTN_SHELL_VEC | nt << 4 | cap << 16;
 }
 
-extern "C" int ftn_head_wide_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or) {
-  FTN_CHECK_ARG(N >= 1 && wide_ok(D) && misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0,
-                "ftn_head_wide_form: N=%d d_model=%d misalign=%d", N, D, misalign_or);
-  return head_wide_form(N, D, tail_bstride, late_bstride, (unsigned)misalign_or);
-}
-
 template <int NT>
 static int launch_head_wide_bf(const HeadArgs& a, int form, hipStream_t st) {
   const int ntile = (a.N + 16 * NT - 1) / (16 * NT);
-  const long long rtiles = (a.rows + 15) / 16;
-  long long gy = (rtiles + 3) / 4;
-  const long long want = form >> 16;
-  if (gy > want) gy = want;
+  const unsigned gy = head_grid_y(a.rows, form);
   const size_t lds = head_wide_lds(NT, a.D);
   hipError_t e = hipFuncSetAttribute((const void*)k_head_wide_bf<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) { ftn_set_error("hipFuncSetAttribute(k_head_wide_bf): %s", hipGetErrorString(e)); return (int)e; }
-  hipLaunchKernelGGL((k_head_wide_bf<NT>), dim3(ntile, (unsigned)gy), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((k_head_wide_bf<NT>), dim3(ntile, gy), dim3(256), lds, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int ftn_head_wide_forward(const float* hidden_dev, long long rows, int S, int D, int N, const float* w_mu_dev,
-                                     const float* b_mu_dev, const float* w_sigma_dev, const float* b_sigma_dev,
-                                     const float* tail_dev, long long tail_bstride, int hist,
-                                     const float* late_dev_or_null, long long late_bstride,
-                                     const float* floor_vec_dev_or_null, float floor_scalar, float* rate_dev,
-                                     float* disp_dev, int* bad_flag_dev, void* stream) {
-  FTN_CHECK_ARG(hidden_dev && w_mu_dev && b_mu_dev && w_sigma_dev && b_sigma_dev && tail_dev && rate_dev &&
-                    disp_dev && bad_flag_dev,
-                "ftn_head_wide_forward: null pointer");
-  FTN_CHECK_ARG(rows >= 1 && S >= 1 && rows % S == 0 && N >= 1 && hist >= 1 && hist <= S,
-                "ftn_head_wide_forward: rows=%lld S=%d N=%d hist=%d", rows, S, N, hist);
-  FTN_CHECK_ARG(wide_ok(D), "ftn_head_wide_forward: d_model=%d must be a multiple of 4, > 128 and <= 512", D);
-  FTN_CHECK_ARG((((uintptr_t)hidden_dev | (uintptr_t)w_mu_dev | (uintptr_t)w_sigma_dev) & 15) == 0,
-                "ftn_head_wide_forward: hidden and the head weights must be 16-byte aligned");
-  FTN_CHECK_ARG((((uintptr_t)b_mu_dev | (uintptr_t)b_sigma_dev | (uintptr_t)tail_dev | (uintptr_t)late_dev_or_null |
-                  (uintptr_t)floor_vec_dev_or_null | (uintptr_t)rate_dev | (uintptr_t)disp_dev |
-                  (uintptr_t)bad_flag_dev) & 3) == 0,
-                "ftn_head_wide_forward: every operand must be 4-byte aligned");
-  HeadArgs a;
-  a.hidden = hidden_dev; a.wmu = w_mu_dev; a.bmu = b_mu_dev; a.wsg = w_sigma_dev; a.bsg = b_sigma_dev;
-  a.tail = tail_dev; a.late = late_dev_or_null; a.floorv = floor_vec_dev_or_null;
-  a.rate = rate_dev; a.disp = disp_dev; a.bad = bad_flag_dev;
-  a.rows = rows; a.tail_bs = tail_bstride; a.late_bs = late_bstride;
-  a.S = S; a.D = D; a.N = N; a.hist = hist; a.floor_s = floor_scalar;
-  const int form = head_wide_form(N, D, tail_bstride, late_bstride,
-                                  (unsigned)(((uintptr_t)tail_dev | (uintptr_t)late_dev_or_null | (uintptr_t)rate_dev |
-                                              (uintptr_t)disp_dev) & 15));
-  hipStream_t st = (hipStream_t)stream;
+int head_wide_launch(const HeadArgs& a, hipStream_t st) {
+  const int form = head_wide_form(a.N, a.D, a.tail_bs, a.late_bs,
+                                  (unsigned)(((uintptr_t)a.tail | (uintptr_t)a.late | (uintptr_t)a.rate | (uintptr_t)a.disp) & 15));
   if (form & FTN_SHELL_BF) return ((form >> 4) & 15) == 2 ? launch_head_wide_bf<2>(a, form, st) : launch_head_wide_bf<1>(a, form, st);
-  const long long total = rows * ((N + 3) / 4);
+  const long long total = a.rows * ((a.N + 3) / 4);
   long long nblk = (total + 255) / 256;
   if (nblk > 4096) nblk = 4096;                                 // grid-stride beyond
   hipLaunchKernelGGL(k_head_wide_f32, dim3((unsigned)nblk), dim3(256), 0, st, a);

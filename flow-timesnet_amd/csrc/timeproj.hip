@@ -5,16 +5,10 @@
 // HBM-bound by design: seq is read once (once per 96 output steps), nothing but hidden is written.  The K order of
 // every output element is a function of (L, S, D) alone - no atomics, no split of K across workgroups - so row b of
 // the result is the same bits in a batch of 1, of B, or as one rank's share of the batch.
+// Kernels, the form rule and the launch (ftn_shell.h); the C entry points are in shell_api.hip.
 #include "ftn_common.h"
 #include "ftn_mlp.h"
-
-struct TimeProjArgs {
-  const float* seq;      // [B][L][D]
-  const float* wt;       // [S][L], base only 4-byte aligned when it is a row slice at L % 4 != 0
-  const float* bt;       // [S]
-  float* hid;            // [B][S][D]
-  int B, L, D, S;
-};
+#include "ftn_shell.h"
 
 #define TP_WAVES 8       // waves of a k_timeproj_bf workgroup: the K-32 slabs of L are dealt to them round-robin
 
@@ -151,19 +145,12 @@ __global__ __launch_bounds__(TP_ROW_THREADS) void k_timeproj_row(TimeProjArgs a)
 // dispatches on this value and ftn_timeproj_form exports it.  S == 1 is the row form (0).  Otherwise NST, the 16-step
 // tiles a wave accumulates, is the smallest of 1, 2, 4, 6 that covers S (6 x 4 accumulator tiles are 96 registers:
 // two waves per SIMD); beyond 96 steps gridDim.y walks chunks of 96 and seq is read once per chunk.
-static int timeproj_form(int L, int S, unsigned wt_misalign) {
+int timeproj_form(int L, int S, unsigned wt_misalign) {
   if (S == 1) return 0;
   const int tiles = (S + 15) / 16;
   const int nst = tiles <= 1 ? 1 : tiles <= 2 ? 2 : tiles <= 4 ? 4 : 6;
   const bool wv = L % 4 == 0 && (wt_misalign & 15) == 0;
   return FTN_SHELL_BF | (wv ? FTN_SHELL_VEC : 0) | nst << 4 | TP_WAVES << 8;
-}
-
-extern "C" int ftn_timeproj_form(int L, int S, int D, int wt_misalign) {
-  FTN_CHECK_ARG(L >= 1 && S >= 1 && D >= 4 && D % 4 == 0 && D <= 128 && wt_misalign >= 0 && wt_misalign < 16 &&
-                    wt_misalign % 4 == 0,
-                "ftn_timeproj_form: L=%d S=%d d_model=%d misalign=%d", L, S, D, wt_misalign);
-  return timeproj_form(L, S, (unsigned)wt_misalign);
 }
 
 template <int NST>
@@ -173,35 +160,6 @@ static int launch_timeproj_bf(const TimeProjArgs& a, int form, hipStream_t st) {
   else hipLaunchKernelGGL((k_timeproj_bf<NST, false>), grid, dim3(64 * TP_WAVES), 0, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int ftn_timeproj_forward(const float* seq_dev, int B, int L, int D, const float* wt_dev,
-                                    const float* bt_dev, int S, float* hidden_dev, void* stream) {
-  FTN_CHECK_ARG(seq_dev && wt_dev && bt_dev && hidden_dev, "ftn_timeproj_forward: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && S >= 1, "ftn_timeproj_forward: bad shape B=%d L=%d S=%d", B, L, S);
-  FTN_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 128, "ftn_timeproj_forward: d_model=%d must be a multiple of 4, <= 128", D);
-  FTN_CHECK_ARG((((uintptr_t)seq_dev | (uintptr_t)hidden_dev) & 15) == 0,
-                "ftn_timeproj_forward: seq and hidden must be 16-byte aligned");
-  FTN_CHECK_ARG((((uintptr_t)wt_dev | (uintptr_t)bt_dev) & 3) == 0,
-                "ftn_timeproj_forward: W_t and b_t must be 4-byte aligned");
-  FTN_CHECK_ARG((long long)B * ((D + 63) / 64) <= 0x7fffffffLL && (S + 15) / 16 <= 65535,
-                "ftn_timeproj_forward: B=%d S=%d exceed the launch grid", B, S);
-  TimeProjArgs a;
-  a.seq = seq_dev; a.wt = wt_dev; a.bt = bt_dev; a.hid = hidden_dev;
-  a.B = B; a.L = L; a.D = D; a.S = S;
-  const int form = timeproj_form(L, S, (unsigned)((uintptr_t)wt_dev & 15));
-  hipStream_t st = (hipStream_t)stream;
-  if (!(form & FTN_SHELL_BF)) {
-    hipLaunchKernelGGL(k_timeproj_row, dim3((unsigned)B), dim3(TP_ROW_THREADS), 0, st, a);
-    FTN_CHECK_LAUNCH();
-    return 0;
-  }
-  switch ((form >> 4) & 15) {
-    case 1: return launch_timeproj_bf<1>(a, form, st);
-    case 2: return launch_timeproj_bf<2>(a, form, st);
-    case 4: return launch_timeproj_bf<4>(a, form, st);
-    default: return launch_timeproj_bf<6>(a, form, st);
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -245,33 +203,12 @@ __global__ __launch_bounds__(TP_ROW_THREADS) void k_timeproj_row_wide(TimeProjAr
   }
 }
 
-static inline bool timeproj_wide_ok(int D) { return D > 128 && D <= 512 && D % 4 == 0; }
-
-// The encoding of ftn_timeproj_form: 0 is the wide row form here (k_timeproj_row_wide)
-extern "C" int ftn_timeproj_wide_form(int L, int S, int D, int wt_misalign) {
-  FTN_CHECK_ARG(L >= 1 && S >= 1 && timeproj_wide_ok(D) && wt_misalign >= 0 && wt_misalign < 16 && wt_misalign % 4 == 0,
-                "ftn_timeproj_wide_form: L=%d S=%d d_model=%d misalign=%d", L, S, D, wt_misalign);
-  return timeproj_form(L, S, (unsigned)wt_misalign);
-}
-
-extern "C" int ftn_timeproj_wide_forward(const float* seq_dev, int B, int L, int D, const float* wt_dev,
-                                         const float* bt_dev, int S, float* hidden_dev, void* stream) {
-  FTN_CHECK_ARG(seq_dev && wt_dev && bt_dev && hidden_dev, "ftn_timeproj_wide_forward: null pointer");
-  FTN_CHECK_ARG(B >= 1 && L >= 1 && S >= 1, "ftn_timeproj_wide_forward: bad shape B=%d L=%d S=%d", B, L, S);
-  FTN_CHECK_ARG(timeproj_wide_ok(D), "ftn_timeproj_wide_forward: d_model=%d must be a multiple of 4, > 128 and <= 512", D);
-  FTN_CHECK_ARG((((uintptr_t)seq_dev | (uintptr_t)hidden_dev) & 15) == 0,
-                "ftn_timeproj_wide_forward: seq and hidden must be 16-byte aligned");
-  FTN_CHECK_ARG((((uintptr_t)wt_dev | (uintptr_t)bt_dev) & 3) == 0,
-                "ftn_timeproj_wide_forward: W_t and b_t must be 4-byte aligned");
-  FTN_CHECK_ARG((long long)B * ((D + 63) / 64) <= 0x7fffffffLL && (S + 15) / 16 <= 65535,
-                "ftn_timeproj_wide_forward: B=%d S=%d exceed the launch grid", B, S);
-  TimeProjArgs a;
-  a.seq = seq_dev; a.wt = wt_dev; a.bt = bt_dev; a.hid = hidden_dev;
-  a.B = B; a.L = L; a.D = D; a.S = S;
-  const int form = timeproj_form(L, S, (unsigned)((uintptr_t)wt_dev & 15));
-  hipStream_t st = (hipStream_t)stream;
+// S == 1 is the row form of the width (form 0 at either); k_timeproj_bf serves both widths.
+int timeproj_launch(const TimeProjArgs& a, const ShellWidth& w, hipStream_t st) {
+  const int form = timeproj_form(a.L, a.S, (unsigned)((uintptr_t)a.wt & 15));
   if (!(form & FTN_SHELL_BF)) {
-    hipLaunchKernelGGL(k_timeproj_row_wide, dim3((unsigned)B, (unsigned)((D + 127) / 128)), dim3(TP_ROW_THREADS), 0, st, a);
+    if (w.wide) hipLaunchKernelGGL(k_timeproj_row_wide, dim3((unsigned)a.B, (unsigned)((a.D + 127) / 128)), dim3(TP_ROW_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k_timeproj_row, dim3((unsigned)a.B), dim3(TP_ROW_THREADS), 0, st, a);
     FTN_CHECK_LAUNCH();
     return 0;
   }

@@ -293,6 +293,15 @@ def _wide(D: int) -> bool:
     return int(D) > 128
 
 
+def _shell_entry(narrow: str, D: int, kind: str = "") -> str:
+    """The shell entry point that takes d_model D: ``narrow`` (``ftn_<op>_<what>``) up to 128, its ``ftn_<op>_wide_<what>``
+    twin beyond; ``kind`` is the norm suffix of the embedding entries (``""`` or ``"_rms"``)."""
+    if _wide(D):
+        op, what = narrow[len("ftn_"):].split("_", 1)
+        narrow = f"ftn_{op}_wide_{what}"
+    return narrow + kind
+
+
 def _embed_form_name(f: int) -> str:
     no, rt = (f >> 4) & 15, (f >> 8) & 15
     return f"k_embed_in_bf<{no},{rt}>" if f & 1 else f"k_embed_in<{no},{'true' if f & 2 else 'false'}>"
@@ -442,7 +451,7 @@ def head_forward(hidden: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor, w
     bad = torch.zeros(1, dtype=torch.int32, device=dev)
     if late is not None and (late.shape[-2:] != (S, N) or not late.is_contiguous()):
         raise ValueError("late bias must be contiguous [1|B, S, N]")
-    entry = "ftn_head_wide_forward" if _wide(D) else "ftn_head_forward"
+    entry = _shell_entry("ftn_head_forward", D)
     check(getattr(lib, entry)(_ptr(hidden), B * S, S, D, N, _ptr(w_mu), _ptr(b_mu), _ptr(w_sigma), _ptr(b_sigma),
                               _ptr(tail), tail.stride(0) if B > 1 else 0, int(hist),
                               _ptr_or_null(late), _batch_stride(late, B), _ptr_or_null(floor_vec), float(floor_scalar),
@@ -467,7 +476,7 @@ def timeproj_forward(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> t
             (S > 1 and bt.stride(0) != 1):
         raise ValueError("seq must be contiguous, wt rows contiguous with stride L, bt contiguous")
     hidden = torch.empty(B, S, D, dtype=torch.float32, device=seq.device)
-    entry = "ftn_timeproj_wide_forward" if _wide(D) else "ftn_timeproj_forward"
+    entry = _shell_entry("ftn_timeproj_forward", D)
     check(getattr(lib, entry)(_ptr(seq), B, L, D, _ptr(wt), _ptr(bt), S, _ptr(hidden), _stream(seq.device)), entry)
     return hidden
 
@@ -485,7 +494,7 @@ def embed_forward(window: torch.Tensor, weight: torch.Tensor, add, norm=None) ->
     if add is not None and (add.shape[-2:] != (L, D) or not add.is_contiguous()):
         raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=window.device)
-    entry = ("ftn_embed_wide_forward" if _wide(D) else "ftn_embed_forward") + kind
+    entry = _shell_entry("ftn_embed_forward", D, kind)
     check(getattr(lib, entry)(_ptr(window), window.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
                               _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
                               _ptr(out), _stream(window.device)), entry)
@@ -503,7 +512,7 @@ def embed_rows_strided(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor,
     if (out.dim() != 3 or out.shape[0] != B or out.shape[2] != D or not out.is_contiguous()
             or out.dtype != torch.float32 or not 0 <= slot <= out.shape[1] - L):
         raise ValueError("out must be contiguous fp32 [B, Lr, D] with room for L rows from slot")
-    entry = "ftn_embed_wide_rows_strided" if _wide(D) else "ftn_embed_rows_strided"
+    entry = _shell_entry("ftn_embed_rows_strided", D)
     check(getattr(lib, entry)(_ptr(x), x.stride(0) if B > 1 else 0, B, L, N, _ptr(weight), D,
                               _ptr(out) + 4 * slot * D, out.stride(0), _stream(x.device)), entry)
 
@@ -521,7 +530,7 @@ def embed_ring(V: torch.Tensor, head: int, add, norm=None) -> torch.Tensor:
                             or not add.is_contiguous()):
         raise ValueError("add must be contiguous [1|B, L, D]")
     out = torch.empty(B, L, D, dtype=torch.float32, device=V.device)
-    entry = ("ftn_embed_wide_ring" if _wide(D) else "ftn_embed_ring") + kind
+    entry = _shell_entry("ftn_embed_ring", D, kind)
     check(getattr(lib, entry)(_ptr(V), B, L, D, int(head), _ptr_or_null(add), _batch_stride(add, B), *_norm_args(norm),
                               _ptr(out), _stream(V.device)), entry)
     return out

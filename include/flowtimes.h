@@ -412,7 +412,25 @@ int ftn_lrtc_forward(const float* coeff_dev, const float* basis_dev, const float
 #define FTN_LRTC_WIDE 4
 int ftn_lrtc_form(int N, int R, int addx, int misalign_or);
 
-/* ---- model shell around the block stack (TimesNet.forward) ------------------------ */
+/* ---- model shell around the block stack (TimesNet.forward) ------------------------
+ * Every entry point of the shell - narrow (D <= 128, declared first), wide (ftn_*_wide_*, 128 < D <= 512) and _rms -
+ * is defined in csrc/shell_api.hip: one body per operation checks the arguments, and the kernels are in
+ * csrc/shell.hip (narrow), csrc/shell_wide.hip (wide) and csrc/timeproj.hip.  The entry names its width; D outside
+ * that width's range is a bad argument, never a switch to the other width.  A bad argument returns < 0 before any
+ * launch, with a message that starts with the entry's name.  The rules, once per operation (strides in elements):
+ *   every operation   required pointers non-null; every count >= 1; D a multiple of 4 within the width's range
+ *   heads             rows % S == 0; 1 <= hist <= S; hidden, w_mu, w_sigma 16-byte aligned
+ *                     wide only: every other operand 4-byte aligned
+ *   embedding         gamma and beta both or neither (_rms: both); out, add, gamma, beta 16-byte aligned;
+ *                     add_bstride % 4 == 0.  wide only: B * L <= 0x7fffffff; x and W 4-byte aligned
+ *   embedding rows    out 16-byte aligned; out_bstride % 4 == 0, and >= L * D when B > 1
+ *                     wide only: B * L <= 0x7fffffff; x and W 4-byte aligned
+ *   ring              0 <= head < L; gamma / beta as the embedding; V, out, add, gamma, beta 16-byte aligned;
+ *                     add_bstride % 4 == 0 and >= 0.  wide only: B * L <= 0x7fffffff
+ *   time projection   seq, hidden 16-byte aligned; W_t, b_t 4-byte aligned; B * ceil(D / 64) <= 0x7fffffff and
+ *                     ceil(S / 16) <= 65535.  No difference between the widths.
+ *   form queries      N (L, S) >= 1; D as above; every misalign one of 0, 4, 8, 12
+ * The "wide only" checks are a deliberate difference: the narrow entry points accept what they always accepted. */
 /* Rate / dispersion heads (:2066-2102), one pass over hidden[rows = B*S][D] (the output of
  * forecast_time_proj, time-major):
  *   pre        = hidden W_mu^T + b_mu + tail[b, min(s, hist-1), :] (+ late[b, s, :])
@@ -422,7 +440,7 @@ int ftn_lrtc_form(int N, int R, int addx, int misalign_or);
  * (elements); late (optional) is gate * late_bias laid out [.., S, N] with batch stride late_bstride
  * (0 = shared by the batch); floor is min_sigma_vector[N] or the scalar.  *bad_flag_dev gets bit 0 / 1
  * OR-ed in when a rate / dispersion is not finite and > 0 (the reference raises RuntimeError, :2095-2098);
- * the caller zeroes it.  D must be a multiple of 4, <= 128. */
+ * the caller zeroes it. */
 int ftn_head_forward(const float* hidden_dev, long long rows, int S, int D, int N, const float* w_mu_dev,
                      const float* b_mu_dev, const float* w_sigma_dev, const float* b_sigma_dev,
                      const float* tail_dev, long long tail_bstride, int hist, const float* late_dev_or_null,
@@ -434,7 +452,7 @@ int ftn_head_forward(const float* hidden_dev, long long rows, int S, int D, int 
  * x: the [B, L, N] input window (rows contiguous, batch stride x_bstride elements); W: nn.Linear weight
  * [D][N]; add: optional [L][D] (add_bstride 0) or [B][L][D] holding bias + positional/time-feature term
  * (+ the low-rank temporal context and constant context bias pushed through W, :1958-1996, so the
- * [B, L, N] context tensor is never written).  D must be a multiple of 4, <= 128. */
+ * [B, L, N] context tensor is never written). */
 int ftn_embed_forward(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev, int D,
                       const float* add_dev_or_null, long long add_bstride, const float* ln_gamma_dev_or_null,
                       const float* ln_beta_dev_or_null, float ln_eps, float* out_dev, void* stream);
@@ -442,14 +460,14 @@ int ftn_embed_forward(const float* x_dev, long long x_bstride, int B, int L, int
 /* The GEMM of ftn_embed_forward alone (no add, no LayerNorm), row (b, l) of x W^T stored at
  * out + b * out_bstride + l * D: same kernels, form selection and K order, so each row is bit-identical to
  * the one ftn_embed_forward computes before its epilogue.  The recursive forecaster appends a step's B new
- * rows (L = 1) to its ring of embedded rows with it.  out 16-byte aligned, out_bstride % 4 == 0. */
+ * rows (L = 1) to its ring of embedded rows with it. */
 int ftn_embed_rows_strided(const float* x_dev, long long x_bstride, int B, int L, int N, const float* w_dev, int D,
                            float* out_dev, long long out_bstride, void* stream);
 
 /* Embedding of a sliding window from a ring of stored x W^T rows V [B][L][D] whose oldest row is slot `head`:
  *   out[b][t][:] = V[b][(head + t) mod L][:] + add[b?][t][:]      (+ LayerNorm over D when gamma/beta are given)
  * with ftn_embed_forward's epilogue arithmetic (bit-identical to it on the equivalent window).  add optional
- * ([L][D] with add_bstride 0, or [B][L][D]); every pointer 16-byte aligned; D a multiple of 4, <= 128. */
+ * ([L][D] with add_bstride 0, or [B][L][D]). */
 int ftn_embed_ring(const float* v_dev, int B, int L, int D, int head, const float* add_dev_or_null,
                    long long add_bstride, const float* ln_gamma_dev_or_null, const float* ln_beta_dev_or_null,
                    float ln_eps, float* out_dev, void* stream);
@@ -475,7 +493,7 @@ int ftn_head_form(int N, int D, long long tail_bstride, long long late_bstride, 
 /* Time projection between the block stack and the heads (forecast_time_proj, :2063-2066):
  *   hidden[b][s][:] = b_t[s] + sum_l W_t[s][l] seq[b][l][:]
  * seq [B][L][D] and hidden [B][S][D] contiguous fp32, 16-byte aligned; W_t [S][L] with row stride L and b_t [S]
- * need only 4-byte alignment (they may be the row slice weight[-S:]).  D a multiple of 4, <= 128; any B, L, S >= 1.
+ * need only 4-byte alignment (they may be the row slice weight[-S:]).  Any B, L, S >= 1.
  * The order in which the L terms of an output element are added depends on (L, S, D) alone: row b comes out
  * bit-identical whatever B is and whichever rows share the call.  One launch, no workspace.
  * ftn_timeproj_form (host-only; the launch dispatches through the same function): 0 = k_timeproj_row (S == 1, fp32
@@ -488,11 +506,11 @@ int ftn_timeproj_forward(const float* seq_dev, int B, int L, int D, const float*
                          float* hidden_dev, void* stream);
 int ftn_timeproj_form(int L, int S, int D, int wt_misalign);
 
-/* ---- model shell at 128 < d_model <= 512 (csrc/shell_wide.hip, csrc/timeproj.hip) -----------------------------
+/* ---- model shell at 128 < d_model <= 512 (kernels: csrc/shell_wide.hip, csrc/timeproj.hip) --------------------
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.  The entry
  * points above keep their limit (D <= 128), forms and bits; each one below takes the arguments of its narrow
- * counterpart with the same meaning, alignment rules and "enqueue only, no hidden allocation" convention, for D a
- * multiple of 4 with 128 < D <= 512.  Any other D is a bad argument, reported before any launch.  Products are bf16x3
+ * counterpart with the same meaning and "enqueue only, no hidden allocation" convention, for D a multiple of 4 with
+ * 128 < D <= 512, under the argument rules at the head of the shell section.  Products are bf16x3
  * on the 16-bit matrix pipe.  The order of the K additions of an output element and of the LayerNorm reductions is a
  * function of (N, D, form) alone: a row's bits do not depend on B, on its position in the batch or on which rows
  * share the call; no atomics on outputs, no split of K across workgroups.
@@ -536,12 +554,12 @@ int ftn_embed_wide_form(int N, int D, long long x_bstride, int x_misalign, int w
 int ftn_head_wide_form(int N, int D, long long tail_bstride, long long late_bstride, int misalign_or);
 int ftn_timeproj_wide_form(int L, int S, int D, int wt_misalign);
 
-/* ---- RMS norm epilogue of the value embedding (embed_norm_mode "rms"; csrc/shell.hip, csrc/shell_wide.hip) ------
+/* ---- RMS norm epilogue of the value embedding (embed_norm_mode "rms"; kernels: csrc/shell.hip, shell_wide.hip) --
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
  *
  * Each takes the argument list of its LayerNorm counterpart (ftn_embed_forward, ftn_embed_ring, ftn_embed_wide_forward,
- * ftn_embed_wide_ring) with the same meaning, alignment rules, D limits (a multiple of 4; <= 128 narrow, 128 < D <= 512
- * wide) and "enqueue only, no allocation" convention, and closes a row with the reference's RMS norm instead
+ * ftn_embed_wide_ring) with the same meaning, argument rules and "enqueue only, no allocation" convention, and closes
+ * a row with the reference's RMS norm instead
  * (models/timesnet.py:1153-1158), in fp32:
  *   v     = x[b][l][:] W^T + add[b?][l][:]        (ring: V[b][(head + t) mod L][:] + add[b?][t][:])
  *   ss    = sum_d v[d]^2

@@ -1,5 +1,5 @@
 """The host side of the RMS norm epilogue of the value embedding (``ftn_embed_forward_rms``, ``ftn_embed_ring_rms`` and
-their wide counterparts; csrc/shell.hip, csrc/shell_wide.hip): exports, every argument error reported with the entry's
+their wide counterparts; csrc/shell_api.hip): exports, every argument error reported with the entry's
 name before anything touches a device, the fourth element of ``runtime``'s ``norm`` tuple, and the torch path a CPU
 model keeps.  No GPU needed."""
 import pytest

@@ -1,7 +1,7 @@
-"""The host side of the model shell at 128 < d_model <= 512 (``ftn_*_wide_*``, csrc/shell_wide.hip and
-csrc/timeproj.hip): exports, the form rules restated and compared over a table, every argument error reported with the
-entry's name before anything touches a device, the width rule of ``models/shell.py`` and its ``FTN_SHELL_WIDE``
-switch.  No GPU needed."""
+"""The host side of the model shell at 128 < d_model <= 512 (``ftn_*_wide_*``: entries in csrc/shell_api.hip, form
+rules in csrc/shell_wide.hip and csrc/timeproj.hip): exports, the form rules restated and compared over a table, every
+argument error reported with the entry's name before anything touches a device, the width rule of ``models/shell.py``
+and its ``FTN_SHELL_WIDE`` switch.  No GPU needed."""
 import itertools
 import os
 import subprocess
