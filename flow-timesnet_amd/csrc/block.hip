@@ -431,13 +431,26 @@ static int forward(const float* x, float* y, int B, int L, const FtnPlan* pl, co
   return 0;
 }
 
+// rows_per_pass: 0 = the one-shot entry points (B <= 65535, one pass); >= 1 = the _rows entry points, which run stages
+// A-F for rows [r0, r0 + n) pass after pass through ONE pass-sized workspace.  Rows are independent once the selection
+// is fixed (every stage indexes a row's own pixels and its own w[b]), the descriptor is the same for every pass and no
+// stage reads workspace bytes it has not written in the same pass, so the bits are those of a single pass.
 static int forward_checked(const float* x_dev, float* y_dev, int B, int L, const FtnPlan* plan,
                            const float* wblob_dev, const FtnDesc* desc_dev, const float* weights_dev, int max_groups,
                            int px_bound, void* ws_dev, size_t ws_bytes, void* stream, const float* ln_g, const float* ln_b,
-                           float ln_eps, int act_dtype, int flags, int* range_flag) {
+                           float ln_eps, int act_dtype, int flags, int* range_flag, int rows_per_pass) {
   FTN_CHECK_ARG(x_dev && y_dev && plan && wblob_dev && desc_dev && weights_dev && ws_dev,
                 "ftn_timesblock_forward: null pointer");
-  FTN_CHECK_ARG(B >= 1 && B <= 65535 && L >= 2, "ftn_timesblock_forward: bad shape B=%d L=%d", B, L);
+  if (rows_per_pass == 0) {
+    FTN_CHECK_ARG(B >= 1 && B <= 65535 && L >= 2, "ftn_timesblock_forward: bad shape B=%d L=%d", B, L);
+  } else {
+    FTN_CHECK_ARG(B >= 1 && L >= 2, "ftn_timesblock_forward_rows: bad shape B=%d L=%d", B, L);
+    FTN_CHECK_ARG(rows_per_pass >= 1 && rows_per_pass <= 65535, "ftn_timesblock_forward_rows: rows_per_pass=%d outside [1, 65535]",
+                  rows_per_pass);
+  }
+  const int n_pass = rows_per_pass == 0 || B <= rows_per_pass ? B : rows_per_pass;        // rows of a full pass
+  FTN_CHECK_ARG(!(flags & FTN_FWD_STAGE_A_DONE) || n_pass == B,
+                "ftn_timesblock_forward_rows: FTN_FWD_STAGE_A_DONE needs a single pass (B=%d rows_per_pass=%d)", B, rows_per_pass);
   FTN_CHECK_ARG(max_groups >= 1 && max_groups <= FTN_KMAX, "ftn_timesblock_forward: max_groups=%d", max_groups);
   FTN_CHECK_ARG(plan->CP % 16 == 0 && plan->FP % 16 == 0 && plan->CP >= plan->C && plan->FP >= plan->F,
                 "ftn_timesblock_forward: plan channel padding is inconsistent");
@@ -450,13 +463,37 @@ static int forward_checked(const float* x_dev, float* y_dev, int B, int L, const
                 "ftn_timesblock_forward: flags=%d", flags);
   FTN_CHECK_ARG(act_dtype >= 0 && act_dtype <= 2 && !(act_dtype != 0 && ln_g != nullptr),
                 "ftn_timesblock_forward: act_dtype=%d (the fused LayerNorm epilogue is fp32 only)", act_dtype);
-  const size_t need = ftn_timesblock_workspace_bytes(plan, B, L, max_groups, px_bound);
-  FTN_CHECK_ARG(need > 0, "ftn_timesblock_forward: B*pixels per row exceeds 2^31 (B=%d L=%d)", B, L);
+  const size_t need = ftn_timesblock_workspace_bytes(plan, n_pass, L, max_groups, px_bound);
+  FTN_CHECK_ARG(need > 0, "ftn_timesblock_forward: B*pixels per row exceeds 2^31 (B=%d L=%d)", n_pass, L);
   FTN_CHECK_ARG(ws_bytes >= need, "ftn_timesblock_forward: workspace %zu < %zu bytes", ws_bytes, need);
   FTN_CHECK_ARG(((uintptr_t)ws_dev & 255) == 0 && ((uintptr_t)wblob_dev & 15) == 0,
                 "ftn_timesblock_forward: workspace/weights must be 256/16-byte aligned");
-  return forward(x_dev, y_dev, B, L, plan, wblob_dev, desc_dev, weights_dev, max_groups, px_bound, (char*)ws_dev,
-                 (hipStream_t)stream, ln_g, ln_b, ln_eps, act_dtype, flags, range_flag);
+  // x / y are [B][L][C] fp32 and weights [B][FTN_KMAX]: a pass starts at whole rows of each (row strides L*C floats keep
+  // the 16-byte alignment of x and y whenever the vector forms need it, C % 4 == 0).  range_flag is shared: every
+  // writer stores 1, so the word is the OR over the passes.
+  const size_t row = (size_t)L * plan->C;
+  for (int r0 = 0; r0 < B; r0 += n_pass) {
+    const int n = B - r0 < n_pass ? B - r0 : n_pass;
+    const int rc = forward(x_dev + r0 * row, y_dev + r0 * row, n, L, plan, wblob_dev, desc_dev,
+                           weights_dev + (size_t)r0 * FTN_KMAX, max_groups, px_bound, (char*)ws_dev, (hipStream_t)stream, ln_g,
+                           ln_b, ln_eps, act_dtype, flags, range_flag);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+extern "C" int ftn_timesblock_rows_per_pass(const FtnPlan* plan, int L, int max_groups, int px_bound, size_t ws_cap_bytes) {
+  auto fits = [&](int n) {
+    const size_t need = ftn_timesblock_workspace_bytes(plan, n, L, max_groups, px_bound);   // 0: bad shape or >= 2^31 pixels
+    return need > 0 && (ws_cap_bytes == 0 || need <= ws_cap_bytes);
+  };
+  if (!fits(1)) return 0;
+  int lo = 1, hi = 65535;                       // the workspace grows with the rows: largest n that fits
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (fits(mid)) lo = mid; else hi = mid - 1;
+  }
+  return lo;
 }
 
 // S3-S5 of the selector and stage A of the block in ONE launch (k_finalize_pw, stage_a.hip): see flowtimes.h
@@ -479,7 +516,8 @@ extern "C" int ftn_period_finalize_stage_a(const double* psum_dev, int nparts, i
     FTN_CHECK_ARG((((uintptr_t)amps_dev | (uintptr_t)weights_dev) & 15) == 0, "ftn_period_finalize_stage_a: amps / weights must be 16-byte aligned");
     FTN_CHECK_ARG(nparts >= 1 && Btotal >= B, "ftn_period_finalize_stage_a: bad shape");
   }
-  FTN_CHECK_ARG(B >= 1 && B <= 65535 && L >= 2, "ftn_period_finalize_stage_a: bad shape");
+  // (the row limit belongs to stage A, whose workspace holds all B rows; the finalize-only part has none)
+  FTN_CHECK_ARG(B >= 1 && (B <= 65535 || !do_a) && L >= 2, "ftn_period_finalize_stage_a: bad shape");
   FTN_CHECK_ARG(k_periods <= FTN_KMAX && act_dtype >= 0 && act_dtype <= 2, "ftn_period_finalize_stage_a: k=%d act_dtype=%d", k_periods, act_dtype);
   FTN_CHECK_ARG(plan->mode == 0 && plan->MP > 0 && plan->MP % 16 == 0, "ftn_period_finalize_stage_a: bottleneck blocks only");
   FTN_CHECK_ARG(max_groups >= 1 && max_groups <= FTN_KMAX && px_bound >= 0, "ftn_period_finalize_stage_a: bounds");
@@ -516,7 +554,16 @@ extern "C" int ftn_timesblock_forward(const float* x_dev, float* y_dev, int B, i
                                       int max_groups, int px_bound, int act_dtype, int flags, void* ws_dev,
                                       size_t ws_bytes, void* stream, int* range_flag_dev) {
   return forward_checked(x_dev, y_dev, B, L, plan, wblob_dev, desc_dev, weights_dev, max_groups, px_bound, ws_dev, ws_bytes,
-                         stream, nullptr, nullptr, 0.f, act_dtype, flags, range_flag_dev);
+                         stream, nullptr, nullptr, 0.f, act_dtype, flags, range_flag_dev, 0);
+}
+
+extern "C" int ftn_timesblock_forward_rows(const float* x_dev, float* y_dev, int B, int L, const FtnPlan* plan,
+                                           const float* wblob_dev, const FtnDesc* desc_dev, const float* weights_dev,
+                                           int max_groups, int px_bound, int act_dtype, int flags, void* ws_dev,
+                                           size_t ws_bytes, void* stream, int* range_flag_dev, int rows_per_pass) {
+  FTN_CHECK_ARG(rows_per_pass != 0, "ftn_timesblock_forward_rows: rows_per_pass=0 outside [1, 65535]");
+  return forward_checked(x_dev, y_dev, B, L, plan, wblob_dev, desc_dev, weights_dev, max_groups, px_bound, ws_dev, ws_bytes,
+                         stream, nullptr, nullptr, 0.f, act_dtype, flags, range_flag_dev, rows_per_pass);
 }
 
 extern "C" int ftn_timesblock_forward_norm(const float* x_dev, float* y_dev, int B, int L, const FtnPlan* plan,
@@ -526,7 +573,18 @@ extern "C" int ftn_timesblock_forward_norm(const float* x_dev, float* y_dev, int
                                            void* stream, int* range_flag_dev) {
   FTN_CHECK_ARG(ln_gamma_dev && ln_beta_dev && ln_eps >= 0.f, "ftn_timesblock_forward_norm: LayerNorm parameters");
   return forward_checked(x_dev, y_dev, B, L, plan, wblob_dev, desc_dev, weights_dev, max_groups, px_bound, ws_dev,
-                         ws_bytes, stream, ln_gamma_dev, ln_beta_dev, ln_eps, 0, flags, range_flag_dev);
+                         ws_bytes, stream, ln_gamma_dev, ln_beta_dev, ln_eps, 0, flags, range_flag_dev, 0);
+}
+
+extern "C" int ftn_timesblock_forward_norm_rows(const float* x_dev, float* y_dev, int B, int L, const FtnPlan* plan,
+                                                const float* wblob_dev, const FtnDesc* desc_dev, const float* weights_dev,
+                                                int max_groups, int px_bound, int flags, const float* ln_gamma_dev,
+                                                const float* ln_beta_dev, float ln_eps, void* ws_dev, size_t ws_bytes,
+                                                void* stream, int* range_flag_dev, int rows_per_pass) {
+  FTN_CHECK_ARG(ln_gamma_dev && ln_beta_dev && ln_eps >= 0.f, "ftn_timesblock_forward_norm_rows: LayerNorm parameters");
+  FTN_CHECK_ARG(rows_per_pass != 0, "ftn_timesblock_forward_norm_rows: rows_per_pass=0 outside [1, 65535]");
+  return forward_checked(x_dev, y_dev, B, L, plan, wblob_dev, desc_dev, weights_dev, max_groups, px_bound, ws_dev,
+                         ws_bytes, stream, ln_gamma_dev, ln_beta_dev, ln_eps, 0, flags, range_flag_dev, rows_per_pass);
 }
 
 extern "C" int ftn_residual_layernorm(const float* x_dev, const float* new_dev, float* out_dev, long long rows, int C,

@@ -35,7 +35,14 @@ struct FinalizeArgs {
   const unsigned long long* ready; unsigned long long ready_seq; int ready_n, psum_stride; int* xerr;
   unsigned long long* xctr; size_t xhalf;
   unsigned long long* dbg;   // diagnostic s_memtime stamps of the finalize workgroup's phases (ftn_debug_stamps which & 8), 8 words
+  int rows_outside;          // 1: the per-row section is left to k_row_weights (ftn_launch_row_weights), launched behind
 };
+
+// The per-row section (amps, w) over a grid instead of inside the finalize workgroup, once B reaches the threshold
+// (selector.hip; FTN_FIN_ROWS=<n> forces it, 0 = never).  Every finalize launch asks ftn_fin_rows_outside and, when it
+// says so, sets FinalizeArgs.rows_outside and calls ftn_launch_row_weights on the same stream right behind itself.
+bool ftn_fin_rows_outside(int B);
+int ftn_launch_row_weights(const FinalizeArgs& fa, hipStream_t st);
 
 // exchange buffer of one rank: two halves (seq parity); per half [world][F_cap] doubles, then [world][FTN_XCHG_NBLK]
 // sequence words; then one 256-byte line: the error word (int32 at +0) and the mode-1 call counter (uint64 at +8)
@@ -55,6 +62,43 @@ __device__ __forceinline__ unsigned long long ftn_xchg_seq(const unsigned long l
 // One 256-thread workgroup.  Dynamic LDS: F rounded up to a multiple of 16 floats (scores) + as many 64-bit keys
 // (ftn_finalize_lds_bytes).
 static inline size_t ftn_finalize_lds_bytes(int F) { return (size_t)((F + 15) & ~15) * (sizeof(float) + sizeof(unsigned long long)); }
+
+// Per-sample amplitudes and softmax-scatter weights of ONE batch row (:133-135, :992-1009): the row's candidate values in
+// its own LDS rows ar / wr (17-float stride: conflict-free).  The one copy of this arithmetic: finalize_body's row loop and
+// k_row_weights (selector.hip) both inline it, so the two forms agree bit for bit.  sd is the finished descriptor in LDS.
+// This runs in a single-workgroup kernel on the critical path of every block call, with a cold instruction cache:
+// what it costs is code BYTES fetched, not instructions executed - the fully unrolled, predicated 16-slot form
+// of this section (16 inlined expf, 16 divisions, a 16 x 16 select scatter) was 9 us of a 19 us launch.  So the
+// gathers are issued together (unrolled, they are one instruction each) and everything else is a rolled loop
+// over the nsel live candidates.
+__device__ __forceinline__ void finalize_row(const FtnDesc& sd, const float* __restrict__ row, float* __restrict__ ar,
+                                             float* __restrict__ wr, float* __restrict__ amps_row,
+                                             float* __restrict__ wts_row, int nsel, int G, int act_dtype) {
+  float av[FTN_KMAX];
+#pragma unroll
+  for (int j = 0; j < FTN_KMAX; ++j) av[j] = row[j < nsel ? sd.sel_freq[j] : 0];   // clamped, unconditional
+#pragma unroll
+  for (int j = 0; j < FTN_KMAX; ++j) { ar[j] = av[j]; wr[j] = 0.f; }
+  float mx = -INFINITY;
+#pragma unroll 1
+  for (int j = 0; j < FTN_KMAX; ++j) {
+    const float v = j < nsel ? rnd_act(ar[j], act_dtype) : 0.f;
+    ar[j] = v;
+    amps_row[j] = v;
+    if (j < nsel && sd.sel_group[j] >= 0) mx = fmaxf(mx, v);
+  }
+  float den = 0.f;
+#pragma unroll 1
+  for (int j = 0; j < nsel; ++j)
+    if (sd.sel_group[j] >= 0) { const float e = expf(ar[j] - mx); ar[j] = e; den += e; }
+#pragma unroll 1
+  for (int j = 0; j < nsel; ++j) {
+    const int g = sd.sel_group[j];
+    if (g >= 0) wr[g] = rnd_act(wr[g] + rnd_act(ar[j] / den, act_dtype), act_dtype);
+  }
+#pragma unroll 1
+  for (int g = 0; g < FTN_KMAX; ++g) wts_row[g] = (g < G) ? wr[g] : 0.f;
+}
 
 __device__ __forceinline__ void finalize_body(const FinalizeArgs& fa) {
   const double* __restrict__ psum = fa.psum;
@@ -451,43 +495,13 @@ __device__ __forceinline__ void finalize_body(const FinalizeArgs& fa) {
     int* dst = (int*)desc;
     for (int e = tid; e < (int)(sizeof(FtnDesc) / 4); e += 256) dst[e] = src[e];
   }
-  // per-sample amplitudes and softmax-scatter weights            (:133-135, :992-1009)
-  // One thread per batch row, its candidate values in its own LDS row (17-float stride: conflict-free).  This is a
-  // single-workgroup kernel on the critical path of every block call and it runs with a cold instruction cache:
-  // what it costs is code BYTES fetched, not instructions executed - the fully unrolled, predicated 16-slot form
-  // of this section (16 inlined expf, 16 divisions, a 16 x 16 select scatter) was 9 us of a 19 us launch.  So the
-  // gathers are issued together (unrolled, they are one instruction each) and everything else is a rolled loop
-  // over the nsel live candidates.
+  // per-sample amplitudes and softmax-scatter weights: finalize_row, one thread per batch row
   const int nsel = sd.n_sel, G = sd.n_groups;
   fstamp(4);
-  for (int b = tid; b < B; b += 256) {
-    const float* __restrict__ row = med + (size_t)b * F;
-    float* __restrict__ ar = red[tid];
-    float* __restrict__ wr = wred[tid];
-    float av[FTN_KMAX];
-#pragma unroll
-    for (int j = 0; j < FTN_KMAX; ++j) av[j] = row[j < nsel ? sd.sel_freq[j] : 0];   // clamped, unconditional
-#pragma unroll
-    for (int j = 0; j < FTN_KMAX; ++j) { ar[j] = av[j]; wr[j] = 0.f; }
-    float mx = -INFINITY;
-#pragma unroll 1
-    for (int j = 0; j < FTN_KMAX; ++j) {
-      const float v = j < nsel ? rnd_act(ar[j], act_dtype) : 0.f;
-      ar[j] = v;
-      amps[(size_t)b * FTN_KMAX + j] = v;
-      if (j < nsel && sd.sel_group[j] >= 0) mx = fmaxf(mx, v);
-    }
-    float den = 0.f;
-#pragma unroll 1
-    for (int j = 0; j < nsel; ++j)
-      if (sd.sel_group[j] >= 0) { const float e = expf(ar[j] - mx); ar[j] = e; den += e; }
-#pragma unroll 1
-    for (int j = 0; j < nsel; ++j) {
-      const int g = sd.sel_group[j];
-      if (g >= 0) wr[g] = rnd_act(wr[g] + rnd_act(ar[j] / den, act_dtype), act_dtype);
-    }
-#pragma unroll 1
-    for (int g = 0; g < FTN_KMAX; ++g) wts[(size_t)b * FTN_KMAX + g] = (g < G) ? wr[g] : 0.f;
-  }
+  // (fa.rows_outside: k_row_weights, launched behind this workgroup, runs the same section over a grid - large batches)
+  if (!fa.rows_outside)
+    for (int b = tid; b < B; b += 256)
+      finalize_row(sd, med + (size_t)b * F, red[tid], wred[tid], amps + (size_t)b * FTN_KMAX, wts + (size_t)b * FTN_KMAX, nsel, G,
+                   act_dtype);
   fstamp(5);
 }

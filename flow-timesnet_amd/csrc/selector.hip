@@ -5,11 +5,53 @@
 //   k_finalize   S3-S5  mean, DC kill, log penalty, top-k (wave arg-max),
 //                       periods, grouping, tiling, softmax weights -> FtnDesc, amps, w   (body: ftn_finalize.h)
 #include <math.h>
+#include <stdlib.h>
 #include "ftn_common.h"
 #include "ftn_exchange.h"
 
 // ---------------------------------------------------------------- S3 - S5
 __global__ __launch_bounds__(256) void k_finalize(FinalizeArgs fa) { finalize_body(fa); }
+
+// The per-row section of the finalize (amps[B][16], w[B][16]) over a grid, one thread per batch row: the finalize
+// workgroup walks the rows 256 at a time, which at B = 65 536 is 256 serial iterations on the critical path of the
+// block call.  Launched behind a finalize that ran with FinalizeArgs.rows_outside; reads the finished descriptor from
+// device memory and runs finalize_row, the very function the workgroup's loop runs, so the results agree bit for bit.
+__global__ __launch_bounds__(256) void k_row_weights(const FtnDesc* __restrict__ desc, const float* __restrict__ med, int B,
+                                                     int F, float* __restrict__ amps, float* __restrict__ wts, int act_dtype) {
+  __shared__ FtnDesc sd;
+  __shared__ float red[256][FTN_KMAX + 1];
+  __shared__ float wred[256][FTN_KMAX + 1];
+  const int tid = threadIdx.x;
+  {
+    const int* src = (const int*)desc;
+    int* dst = (int*)&sd;
+    for (int e = tid; e < (int)(sizeof(FtnDesc) / 4); e += 256) dst[e] = src[e];
+  }
+  __syncthreads();
+  const long long b = (long long)blockIdx.x * 256 + tid;
+  if (b >= B) return;
+  finalize_row(sd, med + (size_t)b * F, red[tid], wred[tid], amps + (size_t)b * FTN_KMAX, wts + (size_t)b * FTN_KMAX, sd.n_sel,
+               sd.n_groups, act_dtype);
+}
+
+// Rows from which the grid form takes the per-row section.  Measured (profiles/finalize_rows_time.json, DESIGN §4
+// "Row passes"); never below 1024, so every benchmarked configuration keeps the single launch.  FTN_FIN_ROWS=<n>
+// forces it for tests and A/B runs (read once per process): n >= 1 = rows from which the grid form runs, 0 = never.
+#define FTN_FIN_ROWS_DEFAULT 1024
+bool ftn_fin_rows_outside(int B) {
+  static const long long thr = [] {
+    const char* e = getenv("FTN_FIN_ROWS");
+    return e == nullptr || e[0] == '\0' ? (long long)FTN_FIN_ROWS_DEFAULT : atoll(e);
+  }();
+  return thr > 0 && B >= thr;
+}
+
+int ftn_launch_row_weights(const FinalizeArgs& fa, hipStream_t st) {
+  hipLaunchKernelGGL(k_row_weights, dim3((unsigned)((fa.B + 255) / 256)), dim3(256), 0, st, (const FtnDesc*)fa.desc, fa.med, fa.B,
+                     fa.F, fa.amps, fa.wts, fa.act_dtype);
+  FTN_CHECK_LAUNCH();
+  return 0;
+}
 
 extern "C" int ftn_period_finalize(const double* psum_dev, int nparts, int Btotal, const float* med_dev, int B,
                                    int L, int k_periods, int pmax, int min_period_threshold, int act_dtype,
@@ -33,9 +75,10 @@ extern "C" int ftn_period_finalize(const double* psum_dev, int nparts, int Btota
   FinalizeArgs fa = {psum_dev, nparts, Btotal, med_dev, B, L, F, k_periods, pmax, min_period_threshold, desc_dev,
                      amps_dev, weights_dev, act_dtype, max_unique > 0 ? max_unique : 0, log_base > 1.0 ? (float)log(log_base) : 0.f};
   if (xch != nullptr) ftn_xch_fill(xch, F, &fa);
+  fa.rows_outside = ftn_fin_rows_outside(B) ? 1 : 0;
   hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), lds, (hipStream_t)stream, fa);
   FTN_CHECK_LAUNCH();
-  return 0;
+  return fa.rows_outside ? ftn_launch_row_weights(fa, (hipStream_t)stream) : 0;
 }
 
 // Bound on FtnDesc.total_px / n_groups for descriptors written by ftn_period_finalize: the selector can only

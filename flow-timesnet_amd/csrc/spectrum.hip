@@ -595,6 +595,7 @@ __global__ __launch_bounds__(1024) void k_colsum(const float* __restrict__ med, 
 // ---------------------------------------------------------------- geometry and form choice
 static const size_t FTN_LDS_LIMIT = 160 * 1024;     // bytes of LDS one workgroup can be given
 static const int FTN_MAX_WAVES = 16;                // waves of a 1024-thread workgroup
+static const int FTN_GRID_YZ_MAX = 65535;           // gridDim.y / gridDim.z limit
 
 // Everything the three forms need of a shape: what the kernels index by, each form's dynamic LDS and block size, and
 // whether it fits.  The choice, the scratch query and the launch all read this one copy, so a form cannot be chosen by
@@ -630,7 +631,8 @@ static SpectrumGeom spectrum_geom(int B, int L, int C) {
   // amplitudes through the caller's scratch; batch rows ride on gridDim.y
   g.lds_tile = (size_t)4 * g.QP * 32 * sizeof(float);
   g.thr_tile = 64 * 2 * nfq;
-  g.qtile_fits = qfold_ok(L) && C > 64 && C <= 128 && B <= 65535 && 2 * nfq <= FTN_MAX_WAVES && g.lds_tile <= FTN_LDS_LIMIT;
+  // (any B: the launch takes slices of at most FTN_GRID_YZ_MAX rows)
+  g.qtile_fits = qfold_ok(L) && C > 64 && C <= 128 && 2 * nfq <= FTN_MAX_WAVES && g.lds_tile <= FTN_LDS_LIMIT;
   return g;
 }
 
@@ -684,12 +686,20 @@ extern "C" int ftn_period_spectrum(const float* x_dev, int B, int L, int C, cons
   if (form == 3) {
     // d_model > 64: (row, 32-channel tile) workgroups, amplitudes through the caller's scratch, medians in a second launch
     if ((rc = allow_lds((const void*)k_spectrum_rowq, g.lds_tile, "hipFuncSetAttribute(k_spectrum_rowq)")) != 0) return rc;
-    hipLaunchKernelGGL(k_spectrum_rowq, dim3((unsigned)g.nct, (unsigned)B), dim3(g.thr_tile), g.lds_tile, st, x_dev, B, L, C,
-                       qtab, g.F, g.QP, g.FQ, 0, med_dev, 32, (float*)scratch_dev);
-    FTN_CHECK_LAUNCH();
-    const long long rows = (long long)B * g.F;
-    hipLaunchKernelGGL(k_median_rows, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const float*)scratch_dev,
-                       rows, C, med_dev);
+    // Batch rows ride on gridDim.y, so a batch beyond its limit goes in slices of rows, each with its own part of x, of
+    // the scratch and of med: a workgroup sees only its own row, and a median is an exact selection, so every row gets
+    // the bits a single launch gives it.
+    for (int b0 = 0; b0 < B; b0 += FTN_GRID_YZ_MAX) {
+      const int nb = B - b0 < FTN_GRID_YZ_MAX ? B - b0 : FTN_GRID_YZ_MAX;
+      float* amp_g = (float*)scratch_dev + (size_t)b0 * g.F * C;
+      float* med_s = med_dev + (size_t)b0 * g.F;
+      hipLaunchKernelGGL(k_spectrum_rowq, dim3((unsigned)g.nct, (unsigned)nb), dim3(g.thr_tile), g.lds_tile, st,
+                         x_dev + (size_t)b0 * L * C, nb, L, C, qtab, g.F, g.QP, g.FQ, 0, med_s, 32, amp_g);
+      FTN_CHECK_LAUNCH();
+      const long long rows = (long long)nb * g.F;
+      hipLaunchKernelGGL(k_median_rows, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, (const float*)amp_g, rows, C, med_s);
+      if (b0 + nb < B) FTN_CHECK_LAUNCH();
+    }
   } else if (form == 2) {
     if ((rc = allow_lds((const void*)k_spectrum_rowq, g.lds_q, "hipFuncSetAttribute(k_spectrum_rowq)")) != 0) return rc;
     hipLaunchKernelGGL(k_spectrum_rowq, dim3((unsigned)B), dim3(g.thr_q), g.lds_q, st, x_dev, B, L, C, qtab, g.F, g.QP, g.FQ,

@@ -256,8 +256,14 @@ static int launch_finalize_pw(const FinalizeArgs& fa, const PwArgs& pa, int epi,
 int ftn_launch_stage_a(const PwArgs& pa, const FinalizeArgs* fa, int part, int act, int epi, bool xvec, hipStream_t st) {
   const int nblk_pw = (int)(((long long)pa.B * pa.L + 1 + 16 * NPXU * 4 - 1) / (16 * NPXU * 4));   // window rows + pad row
   if (fa == nullptr) return launch_pw_any(pa, act, 1, epi, xvec, nblk_pw, st);
-  if (act == 1) return xvec ? launch_finalize_pw<1, true>(*fa, pa, epi, nblk_pw, part, st) : launch_finalize_pw<1, false>(*fa, pa, epi, nblk_pw, part, st);
-  return xvec ? launch_finalize_pw<0, true>(*fa, pa, epi, nblk_pw, part, st) : launch_finalize_pw<0, false>(*fa, pa, epi, nblk_pw, part, st);
+  // a launch that finalizes (part 0 / 2) leaves the per-row section of a large batch to k_row_weights behind it
+  FinalizeArgs f = *fa;
+  f.rows_outside = part != 1 && ftn_fin_rows_outside(f.B) ? 1 : 0;
+  int rc;
+  if (act == 1) rc = xvec ? launch_finalize_pw<1, true>(f, pa, epi, nblk_pw, part, st) : launch_finalize_pw<1, false>(f, pa, epi, nblk_pw, part, st);
+  else rc = xvec ? launch_finalize_pw<0, true>(f, pa, epi, nblk_pw, part, st) : launch_finalize_pw<0, false>(f, pa, epi, nblk_pw, part, st);
+  if (rc == 0 && f.rows_outside) rc = ftn_launch_row_weights(f, st);
+  return rc;
 }
 
 static int launch_ew_ident(const PwArgs& pg, float* G, float* R, int CH, int mode, int act, bool xvec, hipStream_t st) {

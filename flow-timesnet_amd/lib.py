@@ -188,6 +188,13 @@ _SIGNATURES = {
                                          C.c_int, C.c_int, _P, C.c_size_t, _P, _P]),
     "ftn_timesblock_forward_norm": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(FtnPlan), _P, _P, _P, C.c_int,
                                               C.c_int, C.c_int, _P, _P, C.c_float, _P, C.c_size_t, _P, _P]),
+    # row passes: the two forwards above with rows_per_pass appended, and the host-only pass size for a workspace cap
+    "ftn_timesblock_forward_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(FtnPlan), _P, _P, _P, C.c_int,
+                                              C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, C.c_int]),
+    "ftn_timesblock_forward_norm_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(FtnPlan), _P, _P, _P, C.c_int,
+                                                   C.c_int, C.c_int, _P, _P, C.c_float, _P, C.c_size_t, _P, _P,
+                                                   C.c_int]),
+    "ftn_timesblock_rows_per_pass": (C.c_int, [C.POINTER(FtnPlan), C.c_int, C.c_int, C.c_int, C.c_size_t]),
     "ftn_period_finalize_stage_a": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, C.POINTER(FtnPlan), _P,
                                               C.c_int, C.c_int, _P, C.c_size_t, _P, _P, C.POINTER(FtnExchange)]),

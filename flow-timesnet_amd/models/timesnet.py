@@ -41,6 +41,18 @@ def _param_key(params) -> tuple:
     return tuple((p.data_ptr(), -1 if p.is_inference() else p._version) for p in params)
 
 
+_PASS_ENV = None
+
+
+def _pass_env():
+    """``(rows, cap bytes)`` of FTN_ROWS_PER_PASS / FTN_WS_CAP_MB, each None when unset; read once per process."""
+    global _PASS_ENV
+    if _PASS_ENV is None:
+        rows, cap = os.getenv("FTN_ROWS_PER_PASS"), os.getenv("FTN_WS_CAP_MB")
+        _PASS_ENV = (int(rows) if rows else None, int(float(cap) * 2 ** 20) if cap else None)
+    return _PASS_ENV
+
+
 def _env_on(name: str) -> bool:
     v = os.getenv(name)
     return bool(v) and v.strip().lower() not in {"0", "false", "off"}
@@ -329,6 +341,11 @@ class TimesBlock(nn.Module):
         self._last_loop_iterations = 0
         self._last_backend: Optional[str] = None
         self._last_forms: Optional[dict] = None      # kernel forms of the last HIP call (_forms)
+        # row passes: stages A-F of a HIP call run over its one selection in passes of rows, through a
+        # workspace of one pass.  A call is one pass unless B > 65535, or one of these asks for fewer rows:
+        self.rows_per_pass: Optional[int] = None          # rows of a pass at most (None: FTN_ROWS_PER_PASS, else no limit)
+        self.workspace_cap_bytes: Optional[int] = None    # workspace bytes at most (None: FTN_WS_CAP_MB, else no cap)
+        self._last_passes: Optional[Tuple[int, int]] = None   # (passes, rows of a full pass) of the last HIP call
         self._hip_calls = 0
         self._lazy_sel = None
         self._pack_key = None
@@ -450,7 +467,9 @@ class TimesBlock(nn.Module):
                 warnings.warn("TimesBlock: a value left the fp16 range of engine f16x2 (|v| >= 65504 or not finite); "
                               "the call was repeated on engine bf16x3", RuntimeWarning, stacklevel=3)
                 self._range_fallbacks += 1
-                y.copy_(self._run(xf, y.dtype, sel, self._packed(xf.device, "bf16x3"), norm))
+                pack3 = self._packed(xf.device, "bf16x3")
+                rows = self._pass_rows(xf.shape[0], xf.shape[1], pack3[1], lambda: (sel.max_groups, sel.px_bound))
+                y.copy_(self._run(xf, y.dtype, sel, pack3, norm, rows=rows))
                 self._last_engine_used = "bf16x3"
 
     def check_range(self) -> Optional[str]:
@@ -503,17 +522,19 @@ class TimesBlock(nn.Module):
             new = _layer_norm_fp32(post_norm, x + (new - x))
         return new
 
-    def _forms(self, plan, B: int, L: int, adt: int, xf: torch.Tensor, native: bool, fused_a: bool) -> dict:
+    def _forms(self, plan, B: int, L: int, adt: int, xf: torch.Tensor, native: bool, fused_a: bool,
+               rows: Optional[int] = None) -> dict:
         """The kernel forms of this call (``runtime.timesblock_forms``; host-only, cached per shape: the library reads
         its switches once per process).  ``A`` names ``k_finalize_pw`` when stage A rode in the selector's launch;
-        ``spectrum`` is the native selector's form (None for a host-side selector)."""
+        ``spectrum`` is the native selector's form (None for a host-side selector).  ``rows``: the call runs in passes
+        of that many rows, and the block's forms are those of a pass (the selector still sees all B rows)."""
         from .. import runtime
 
-        key = (bytes(plan), B, L, adt, xf.data_ptr() % 16, native, fused_a)
+        key = (bytes(plan), B, L, adt, xf.data_ptr() % 16, native, fused_a, rows)
         cache = self.__dict__.setdefault("_forms_cache", {})
         forms = cache.get(key)
         if forms is None:
-            forms = runtime.timesblock_forms(plan, B, L, adt, xf.data_ptr() % 16)
+            forms = runtime.timesblock_forms(plan, B if rows is None else min(B, rows), L, adt, xf.data_ptr() % 16)
             if fused_a:
                 forms["A"] = forms["A"].replace("k_pw<1,", "k_finalize_pw<")
             forms["spectrum"] = runtime.spectrum_form(B, L, xf.shape[-1], xf.data_ptr() % 16) if native else None
@@ -528,6 +549,36 @@ class TimesBlock(nn.Module):
         sel = self.period_selector
         k = getattr(sel, "k", None) if type(sel) is FFTPeriodSelector else None
         return len(self._kernel_spec) <= FTN_MAXBR and (k is None or int(k) <= FTN_KMAX)
+
+    # ---- row passes ----------------------------------------------------------------------
+    def _pass_rows(self, B: int, L: int, plan, bounds) -> Optional[int]:
+        """Rows of a pass of this call, or None for the one-shot call (whose launches are what they always were).
+        One pass unless B > 65535, or ``rows_per_pass`` / ``workspace_cap_bytes`` (FTN_ROWS_PER_PASS / FTN_WS_CAP_MB)
+        is set and asks for fewer rows than B.  ``bounds()`` -> the selection's ``(max_groups, px_bound)``."""
+        from .. import runtime
+
+        env_rows, env_cap = _pass_env()
+        rows = self.__dict__.get("rows_per_pass")
+        rows = env_rows if rows is None else rows
+        cap = self.__dict__.get("workspace_cap_bytes")
+        cap = env_cap if cap is None else cap
+        if rows is None and cap is None and B <= runtime.MAX_ROWS_PER_PASS:
+            return None
+        if rows is not None and int(rows) < 1:
+            raise ValueError(f"rows_per_pass={rows} must be at least 1")
+        if cap is not None and int(cap) < 1:
+            raise ValueError(f"workspace_cap_bytes={cap} must be positive")
+        mg, pxb = bounds()
+        fit = runtime.rows_per_pass(plan, L, mg, pxb, int(cap or 0))
+        if fit == 0:
+            one = int(runtime._lib.load().ftn_timesblock_workspace_bytes(plan, 1, L, mg, pxb))
+            if cap is not None and one > int(cap):
+                raise ValueError(f"workspace cap of {int(cap)} bytes is below the {one} bytes one row needs "
+                                 f"(L={L}, d_model={self.d_model})")
+            raise ValueError(f"the block cannot run a single row of this shape (L={L})")
+        if rows is not None:
+            fit = min(fit, int(rows))
+        return None if fit >= B else fit
 
     # ---- HIP backend: select, then run stages A-F on the selection ---------------------
     def _forward_hip(self, x: torch.Tensor, post_norm: Optional[nn.LayerNorm] = None) -> torch.Tensor:
@@ -550,7 +601,14 @@ class TimesBlock(nn.Module):
         # half inputs: the shell's LayerNorm runs outside (see forward)
         norm = _ln_params(post_norm) if post_norm is not None and adt == 0 else None
         wblob, plan = self._packed(x.device, engine)
-        sel = self._select(x, xf, plan, wblob, flag)
+        B, L = x.shape[0], x.shape[1]
+        native = type(self.period_selector) is FFTPeriodSelector
+        rows = None
+        if native:                                              # the bounds of a native selection are known up front
+            sm = self.period_selector
+            rows = self._pass_rows(B, L, plan, lambda: runtime.selector_bounds(L, sm.k, sm.pmax, sm.min_period_threshold))
+        # more than one pass: the finalize runs without the fused stage A (its workspace would be one of all B rows)
+        sel = self._select(x, xf, plan, wblob, flag, fuse_a=rows is None)
         if sel is None:
             # the reference returns x itself (:796-797); the shell then normalises x + (x - x)
             if ev is not None:
@@ -559,10 +617,12 @@ class TimesBlock(nn.Module):
                 return x
             y = runtime.residual_layernorm(xf, xf, *norm)
             return y if y.dtype == x.dtype else y.to(x.dtype)
-        native = type(self.period_selector) is FFTPeriodSelector
-        self._last_forms = self._forms(plan, B=x.shape[0], L=x.shape[1], adt=adt, xf=xf, native=native,
-                                       fused_a=getattr(sel, "stage_a", None) is not None)
-        y = self._run(xf, x.dtype, sel, (wblob, plan), norm, flag)
+        if not native:
+            rows = self._pass_rows(B, L, plan, lambda: (sel.max_groups, sel.px_bound))
+        self._last_passes = (1, B) if rows is None else (-(-B // rows), rows)
+        self._last_forms = self._forms(plan, B=B, L=L, adt=adt, xf=xf, native=native,
+                                       fused_a=getattr(sel, "stage_a", None) is not None, rows=rows)
+        y = self._run(xf, x.dtype, sel, (wblob, plan), norm, flag, rows=rows)
         if ev is not None:
             ev.record()
             self._range_pending.append((flag, ev, xf, y, norm, sel))
@@ -577,7 +637,7 @@ class TimesBlock(nn.Module):
             self._last_loop_iterations = 0
         return y
 
-    def _select(self, x: torch.Tensor, xf: torch.Tensor, plan, wblob: torch.Tensor, flag):
+    def _select(self, x: torch.Tensor, xf: torch.Tensor, plan, wblob: torch.Tensor, flag, fuse_a: bool = True):
         """This call's ``runtime.Selection``, or None when the block returns its input unchanged.  The native selector
         runs on the device, and its finalize launch also runs stage A when it can (storing into ``flag``); any other
         selector, or the env-flag grouping, groups on the host."""
@@ -592,7 +652,7 @@ class TimesBlock(nn.Module):
             max_unique = _resolve_scheduled_int(os.getenv("TIMES_PERIOD_MAX_UNIQ"), self.block_index)
             log_base = _resolve_log_binning_base(os.getenv("TIMES_PERIOD_BINNING"), self.block_index)
             sel = sel_mod.select_device(xf, act_dtype=x.dtype, max_unique=max_unique, log_base=log_base,
-                                        stage_a=(plan, wblob, flag))
+                                        stage_a=(plan, wblob, flag) if fuse_a else None)
             if sel is None:                                            # reference :796-797
                 self._last_raw_period_count = self._last_valid_period_count = self._last_group_count = 0
             else:
@@ -622,13 +682,15 @@ class TimesBlock(nn.Module):
             raise RuntimeError("host grouping and descriptor disagree")
         return runtime.selection_from_host(dh, w, x.device)
 
-    def _run(self, xf: torch.Tensor, dtype: torch.dtype, sel, pack, norm=None, flag=None) -> torch.Tensor:
+    def _run(self, xf: torch.Tensor, dtype: torch.dtype, sel, pack, norm=None, flag=None,
+             rows: Optional[int] = None) -> torch.Tensor:
         """Stages A-F of one call on a given selection and an engine's ``pack`` = ``(wblob, plan)`` (``_packed``): a
-        selection does not depend on the engine."""
+        selection does not depend on the engine.  ``rows``: in passes of that many rows (``_pass_rows``)."""
         from .. import runtime
 
         wblob, plan = pack
-        y = runtime.timesblock_forward(xf, plan, wblob, sel, norm, runtime.ACT_DTYPE.get(dtype, 0), flag)
+        y = runtime.timesblock_forward(xf, plan, wblob, sel, norm, runtime.ACT_DTYPE.get(dtype, 0), flag,
+                                       rows_per_pass=rows)
         return y if y.dtype == dtype else y.to(dtype)
 
     # ---- torch backend (generic: any inception module, autograd, CPU) ----------

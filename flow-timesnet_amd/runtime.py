@@ -389,12 +389,33 @@ def timeproj_form(seq: torch.Tensor, wt: torch.Tensor) -> str:
 
 
 # ------------------------------------------------------------------ conv path
+MAX_ROWS_PER_PASS = 65535
+
+
+def selector_bounds(L: int, k: int, pmax: int, min_thr: int) -> Tuple[int, int]:
+    """``(max_groups, px_bound)`` of the selections ``finalize`` makes for this selector configuration."""
+    return _selector_bounds(_lib.load(), L, k, pmax, min_thr)
+
+
+def rows_per_pass(plan: FtnPlan, L: int, max_groups: int, px_bound: int, ws_cap_bytes: int = 0) -> int:
+    """The largest legal ``rows_per_pass`` whose workspace is at most ``ws_cap_bytes`` (0 = no cap): host-only
+    (``ftn_timesblock_rows_per_pass``).  0 when one row does not fit."""
+    return int(_lib.load().ftn_timesblock_rows_per_pass(C.byref(plan), int(L), int(max_groups), int(px_bound),
+                                                        int(ws_cap_bytes)))
+
+
 def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel: Selection,
-                       norm=None, act_dtype: int = 0, range_flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       norm=None, act_dtype: int = 0, range_flag: Optional[torch.Tensor] = None,
+                       rows_per_pass: Optional[int] = None) -> torch.Tensor:
     """``norm=(gamma, beta, eps)`` appends the model's per-block ``LayerNorm(x + (y - x))``
-    (reference :2050-2058) to the same call.  ``range_flag``: see ``new_range_flag``."""
+    (reference :2050-2058) to the same call.  ``range_flag``: see ``new_range_flag``.
+
+    ``rows_per_pass`` (None: one pass, B <= 65535): stages A-F run in passes of that many rows over the one
+    selection, through a workspace sized for one pass (``ftn_timesblock_forward_rows``); same bits as one pass."""
     lib = _lib.load()
     B, L, _ = x.shape
+    if rows_per_pass is not None:
+        return _timesblock_forward_rows(lib, x, plan, wblob, sel, norm, act_dtype, range_flag, int(rows_per_pass))
     need = _workspace_bytes(lib, plan, B, L, sel.max_groups, sel.px_bound)
     flags = 0
     pre = getattr(sel, "stage_a", None)
@@ -417,6 +438,39 @@ def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel:
     check(lib.ftn_timesblock_forward(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
                                      _ptr(sel.weights), sel.max_groups, sel.px_bound, int(act_dtype), flags, _ptr(ws),
                                      ws.numel(), _stream(x.device), _ptr_or_null(range_flag)), "ftn_timesblock_forward")
+    return y
+
+
+def _timesblock_forward_rows(lib, x, plan, wblob, sel, norm, act_dtype, range_flag, rows: int) -> torch.Tensor:
+    """``timesblock_forward`` through the ``_rows`` entry points: the workspace is that of one pass."""
+    B, L, _ = x.shape
+    if not 1 <= rows <= MAX_ROWS_PER_PASS:
+        raise ValueError(f"rows_per_pass={rows} outside [1, {MAX_ROWS_PER_PASS}]")
+    n = min(B, rows)
+    need = _workspace_bytes(lib, plan, n, L, sel.max_groups, sel.px_bound)
+    flags = 0
+    pre = getattr(sel, "stage_a", None)
+    if pre is not None:
+        ws, x_ptr, plan_addr = pre
+        sel.stage_a = None
+        if n < B:
+            raise RuntimeError("selection carries a fused stage A, which serves a single pass only")
+        if x_ptr != x.data_ptr() or plan_addr != C.addressof(plan) or ws.numel() < need:
+            raise RuntimeError("selection carries stage A of a different input or plan")
+        flags = 1   # FTN_FWD_STAGE_A_DONE
+    else:
+        ws = _workspace(x.device, need)
+    y = torch.empty_like(x)
+    if norm is not None:
+        check(lib.ftn_timesblock_forward_norm_rows(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
+                                                   _ptr(sel.weights), sel.max_groups, sel.px_bound, flags,
+                                                   *_norm_args(norm), _ptr(ws), ws.numel(), _stream(x.device),
+                                                   _ptr_or_null(range_flag), rows), "ftn_timesblock_forward_norm_rows")
+        return y
+    check(lib.ftn_timesblock_forward_rows(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
+                                          _ptr(sel.weights), sel.max_groups, sel.px_bound, int(act_dtype), flags,
+                                          _ptr(ws), ws.numel(), _stream(x.device), _ptr_or_null(range_flag), rows),
+          "ftn_timesblock_forward_rows")
     return y
 
 

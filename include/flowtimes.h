@@ -256,7 +256,8 @@ int ftn_dft_table_init(void* table_dev, int L, void* stream);
 /* scratch_dev (ABI 10; may be NULL): ftn_period_spectrum_scratch_bytes(B, L, C) bytes of device memory.  With it,
  * 64 < C <= 128 (d_model 128) runs the quarter-folded DFT as (row, 32-channel tile) workgroups that park their
  * amplitudes [B][F][C] there, and a second launch takes the channel medians; without it (or when the function
- * returns 0) those shapes run the (row, 32-bin block) kernel. */
+ * returns 0) those shapes run the (row, 32-bin block) kernel.  The rows of that form ride on gridDim.y: a batch
+ * beyond 65535 rows is launched in slices of at most 65535, every row with the bits a single launch gives it. */
 size_t ftn_period_spectrum_scratch_bytes(int B, int L, int C);
 int ftn_period_spectrum(const float* x_dev, int B, int L, int C, const void* table_dev,
                         float* med_dev, double* psum_dev, void* stream, const FtnExchange* xch, void* scratch_dev);
@@ -271,7 +272,11 @@ int ftn_period_spectrum(const float* x_dev, int B, int L, int C, const void* tab
  * max_unique / log_base: the reference's TIMES_PERIOD_MAX_UNIQ / TIMES_PERIOD_BINNING grouping variants
  * (:350-437) with the per-depth schedule already resolved by the caller; 0 / 0.0 = unset (plain
  * duplicate-merge grouping).  log_base is a double (ABI 9): the bucket is floor(log(p) / log(base) + 1e-6) with the
- * fp32 log of the period divided by (float)log(base), base in double - torch's operand order (:352). */
+ * fp32 log of the period divided by (float)log(base), base in double - torch's operand order (:352).
+ * Any B >= 1.  The one workgroup that selects also writes amps / w, 256 rows at a time; from a measured number of rows
+ * on (FTN_FIN_ROWS=<n> in the environment forces it, 0 = never; read once per process) it leaves them to a second
+ * launch, k_row_weights, one thread per row, which runs the same per-row function on the finished descriptor: same
+ * bits.  ftn_period_finalize_stage_a does the same. */
 int ftn_period_finalize(const double* psum_dev, int nparts, int Btotal, const float* med_dev,
                         int B, int L, int k_periods, int pmax, int min_period_threshold, int act_dtype,
                         int max_unique, double log_base, FtnDesc* desc_dev, float* amps_dev, float* weights_dev,
@@ -325,7 +330,8 @@ int ftn_timesblock_forward(const float* x_dev, float* y_dev, int B, int L, const
  * follows with FTN_FWD_STAGE_A_DONE.  Bottleneck-mode plans only (mode 0).
  * The two halves can also be launched apart, on the same workspace - a batch-sharded run puts stage A between
  * issuing the exchange of the partial sums and waiting for it:  psum_dev == NULL runs stage A only (med / desc /
- * amps / weights unused),  x_dev == NULL runs S3-S5 and the descriptor copy only. */
+ * amps / weights unused),  x_dev == NULL runs S3-S5 and the descriptor copy only.  B <= 65535 whenever stage A runs
+ * (its workspace holds all B rows; a call in row passes uses ftn_period_finalize). */
 int ftn_period_finalize_stage_a(const double* psum_dev, int nparts, int Btotal, const float* med_dev, int B, int L,
                                 int k_periods, int pmax, int min_period_threshold, int act_dtype, int max_unique,
                                 double log_base, FtnDesc* desc_dev, float* amps_dev, float* weights_dev,
@@ -340,6 +346,31 @@ int ftn_timesblock_forward_norm(const float* x_dev, float* y_dev, int B, int L, 
                                 int max_groups, int px_bound, int flags, const float* ln_gamma_dev,
                                 const float* ln_beta_dev, float ln_eps, void* ws_dev, size_t ws_bytes, void* stream,
                                 int* range_flag);
+/* ---- row passes: any batch size through a bounded workspace -------------------------------------------------
+ * The two calls above for any B >= 1: stages A-F are enqueued for rows [r0, r0 + n), n = min(B, rows_per_pass), pass
+ * after pass on the one stream; x, y and weights advance by whole rows, the descriptor and the workspace are the same
+ * for every pass.  rows_per_pass is in [1, 65535]; n * pixels per row < 2^31 as for a one-shot call; and
+ *   ws_bytes >= ftn_timesblock_workspace_bytes(plan, min(B, rows_per_pass), L, max_groups, px_bound).
+ * Same bits as one pass: once the selection (descriptor + weights) is fixed a row's result depends on that row of x
+ * and of the weights only, and no stage reads workspace bytes the same pass has not written (see
+ * ftn_timesblock_workspace_bytes), so what an earlier, possibly larger pass left behind is never seen.
+ * FTN_FWD_STAGE_A_DONE is legal only when there is a single pass (ftn_period_finalize_stage_a fills a workspace of all
+ * B rows).  range_flag is shared by the passes: every writer stores 1, so the word is the OR over the passes.  No
+ * allocation and no synchronisation: a captured graph holds the unrolled passes.  With B <= rows_per_pass the launches
+ * are exactly those of ftn_timesblock_forward / _norm.  Every argument is checked before the first launch.
+ * Additions only: FTN_ABI_VERSION stays 14. */
+int ftn_timesblock_forward_rows(const float* x_dev, float* y_dev, int B, int L, const FtnPlan* plan,
+                                const float* wblob_dev, const FtnDesc* desc_dev, const float* weights_dev,
+                                int max_groups, int px_bound, int act_dtype, int flags, void* ws_dev, size_t ws_bytes,
+                                void* stream, int* range_flag, int rows_per_pass);
+int ftn_timesblock_forward_norm_rows(const float* x_dev, float* y_dev, int B, int L, const FtnPlan* plan,
+                                     const float* wblob_dev, const FtnDesc* desc_dev, const float* weights_dev,
+                                     int max_groups, int px_bound, int flags, const float* ln_gamma_dev,
+                                     const float* ln_beta_dev, float ln_eps, void* ws_dev, size_t ws_bytes,
+                                     void* stream, int* range_flag, int rows_per_pass);
+/* Host-only: the largest legal rows_per_pass (<= 65535, rows * pixels per row < 2^31) whose workspace is at most
+ * ws_cap_bytes; ws_cap_bytes = 0 means no cap.  0 when a single row does not fit (or the shape is bad). */
+int ftn_timesblock_rows_per_pass(const FtnPlan* plan, int L, int max_groups, int px_bound, size_t ws_cap_bytes);
 /* out[row][:] = LayerNorm_C( x[row][:] + (new[row][:] - x[row][:]) ) for rows x C fp32 matrices (in place
  * allowed: out == new).  Used when a block returns x unchanged (no valid period, :796-797). */
 int ftn_residual_layernorm(const float* x_dev, const float* new_dev, float* out_dev, long long rows, int C,
