@@ -19,6 +19,8 @@ Sub-modules
 ``nbdist``           the distribution's reference in torch ops, on any device: the NB CDF, the one bracketed quantile
                      search behind ``nb_quantiles`` and ``nb_sample``, Philox4x32-10 and ``sample_uniforms``; pure
                      functions without a backend choice (``score`` re-exports what callers use)
+``windows``          ``DeviceWindows``: the batches of a rolling-origin backtest formed on the device from the wide
+                     table, in the order and shapes of the reference's ``SlidingWindowDataset`` + ``DataLoader``
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401
@@ -27,6 +29,6 @@ from . import synth  # noqa: F401
 def __getattr__(name):  # lazy: keeps `import flow_timesnet_amd.synth` torch-free
     import importlib
 
-    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score", "nbdist"):
+    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score", "nbdist", "windows"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -133,6 +133,20 @@ class FtnEmbedAddParams(C.Structure):
 
 
 FTN_CTX_MAX, FTN_CTX_RMAX, FTN_ADD_DMAX, FTN_ADD_TMAX = 256, 32, 512, 64
+FTN_WIN_SERIES, FTN_WIN_WIDE = 0, 1
+FTN_WIN_TILE_SERIES, FTN_WIN_TILE_STEPS = 64, 32
+
+
+class FtnWindowArgs(C.Structure):
+    """Mirror of ``struct FtnWindowArgs`` (include/flowtimes.h): the tables, the item range and the outputs of one
+    ``ftn_window_batch`` call."""
+
+    _fields_ = [("X", C.c_void_p), ("x_stride", C.c_longlong), ("M", C.c_void_p), ("m_stride", C.c_longlong),
+                ("marks", C.c_void_p), ("marks_stride", C.c_longlong), ("statics", C.c_void_p), ("ids", C.c_void_p),
+                ("starts", C.c_void_p), ("starts_host", C.c_void_p),
+                ("T", C.c_longlong), ("item0", C.c_longlong), ("count", C.c_longlong)] + [
+        (n, C.c_int32) for n in ("N", "L", "H", "F", "Fs", "W", "layout", "reserved")] + [
+        (n, C.c_void_p) for n in ("x", "y", "mask", "x_mark", "y_mark", "static_out", "id_out")]
 
 
 class FtnInceptionBlockWeights(C.Structure):
@@ -264,6 +278,9 @@ _SIGNATURES = {
     "ftn_embed_add_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_embed_add": (C.c_int, [C.POINTER(FtnEmbedAddParams), _P, C.c_longlong, _P, C.c_longlong, C.c_int, _P,
                                 C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P]),
+    # device windows (csrc/windows.hip)
+    "ftn_window_batch_form": (C.c_int, [C.POINTER(FtnWindowArgs)]),
+    "ftn_window_batch": (C.c_int, [C.POINTER(FtnWindowArgs), _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

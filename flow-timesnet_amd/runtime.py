@@ -1271,6 +1271,137 @@ def group_sum_rows(x3: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor,
     return out
 
 
+# ------------------------------------------------------------------ device windows
+WINDOW_LAYOUTS = {"series": _lib.FTN_WIN_SERIES, "wide": _lib.FTN_WIN_WIDE}
+WINDOW_PIECES = ("x", "y", "mask", "x_mark", "y_mark", "static", "id")
+_WINDOW_FIELD = {"static": "static_out", "id": "id_out"}
+
+
+def _window_layout(who: str, layout) -> int:
+    if layout not in WINDOW_LAYOUTS:
+        raise ValueError(f"{who}: layout {layout!r} is not 'series' or 'wide'")
+    return WINDOW_LAYOUTS[layout]
+
+
+def _window_form_word(a: "_lib.FtnWindowArgs") -> dict:
+    f = _lib.load().ftn_window_batch_form(C.byref(a))
+    if f < 0:
+        check(f, "ftn_window_batch_form")
+    tile = ((f >> 8) & 255, (f >> 16) & 255)
+    return {"vec": tuple(n for b, n in enumerate(WINDOW_PIECES[:5]) if f >> b & 1), "tile": tile if tile[0] else None}
+
+
+def window_batch_form_of(layout: str, N: int, L: int, H: int, F: int = 0, Fs: int = 0, outs=("x", "y", "mask"),
+                         x_stride: int | None = None, m_stride: int | None = None, marks_stride: int | None = None,
+                         has_mask: bool = True, misalign: dict | None = None) -> dict:
+    """The kernel form ``ftn_window_batch`` takes (``ftn_window_batch_form``, host-only: the launch dispatches through
+    the same function) for the outputs named in ``outs``: ``{"vec": the pieces among x, y, mask, x_mark, y_mark that
+    move 16 bytes a lane, "tile": (series, steps) of the transposition or None}``.  Row strides in elements (default:
+    dense), ``has_mask`` whether a validity table is given, ``misalign`` the byte offsets from a 16-byte boundary of
+    the tables ``"X"``, ``"M"``, ``"marks"`` and of the outputs by name (default 0)."""
+    mis = dict(misalign or {})
+    a = _lib.FtnWindowArgs()
+    a.layout = _window_layout("window_batch_form_of", layout)
+    a.N, a.L, a.H, a.F, a.Fs = int(N), int(L), int(H), int(F), int(Fs)
+    a.x_stride = int(N if x_stride is None else x_stride)
+    a.m_stride = int(N if m_stride is None else m_stride)
+    a.marks_stride = int(F if marks_stride is None else marks_stride)
+    a.X = 0x100000 + mis.pop("X", 0)                            # stand-in addresses: the form reads their low bits only
+    a.M = 0x200000 + mis.pop("M", 0) if has_mask else None
+    a.marks = 0x300000 + mis.pop("marks", 0) if F else None
+    a.statics = 0x400000 if Fs else None
+    a.ids = 0x500000 if "id" in outs else None
+    for at, name in enumerate(outs):
+        if name not in WINDOW_PIECES:
+            raise ValueError(f"window_batch_form_of: {name!r} is not one of {WINDOW_PIECES}")
+        setattr(a, _WINDOW_FIELD.get(name, name), 0x1000000 * (at + 1) + mis.pop(name, 0))
+    if mis:
+        raise ValueError(f"window_batch_form_of: misalign names {sorted(mis)} are neither tables nor requested outputs")
+    return _window_form_word(a)
+
+
+def _window_table(who: str, name: str, t, cols: int | None, like: torch.Tensor | None, dtype=torch.float32):
+    """``(pointer, row stride, rows, columns)`` of an optional 2-D table with contiguous elements."""
+    if t is None:
+        return None, 0, 0, 0
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.numel() == 0:
+        raise ValueError(f"{who}: {name} must be a non-empty 2-D tensor")
+    if t.dtype != dtype or not t.is_cuda or (like is not None and t.device != like.device):
+        raise ValueError(f"{who}: {name} must be {dtype} on {'a ROCm device' if like is None else like.device}, got "
+                         f"{t.dtype} on {t.device}")
+    rows, c = t.shape
+    if cols is not None and c != cols:
+        raise ValueError(f"{who}: {name} has {c} columns, not {cols}")
+    if (c > 1 and t.stride(1) != 1) or (rows > 1 and t.stride(0) < c):
+        raise ValueError(f"{who}: {name} needs contiguous rows at least {c} apart, strides {t.stride()}")
+    return _ptr(t), (t.stride(0) if rows > 1 else c), rows, c
+
+
+def _window_args(who: str, X, L, H, M, marks, statics, ids, layout, outs: dict, count: int | None):
+    a = _lib.FtnWindowArgs()
+    a.layout = _window_layout(who, layout)
+    a.X, a.x_stride, T, N = _window_table(who, "X", X, None, None)
+    if X is None:
+        raise ValueError(f"{who}: X is required")
+    a.M, a.m_stride, Tm, _ = _window_table(who, "M", M, N, X)
+    a.marks, a.marks_stride, Tk, F = _window_table(who, "marks", marks, None, X)
+    if (M is not None and Tm != T) or (marks is not None and Tk != T):
+        raise ValueError(f"{who}: M and marks must have X's {T} rows")
+    for name, t in (("statics", statics), ("ids", ids)):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.device != X.device
+                              or t.shape[0] != N or t.dim() != (2 if name == "statics" else 1)
+                              or t.dtype != (torch.float32 if name == "statics" else torch.int64)):
+            raise ValueError(f"{who}: {name} must be a contiguous {'fp32 [N, Fs]' if name == 'statics' else 'int64 [N]'} "
+                             f"tensor beside X")
+    Fs = statics.shape[1] if statics is not None else 0
+    a.statics, a.ids = _ptr_or_null(statics), _ptr_or_null(ids)
+    a.T, a.N, a.L, a.H, a.F, a.Fs = T, N, int(L), int(H), F, Fs
+    wide = layout == "wide"
+    per_item = {"x": int(L) * (N if wide else 1), "y": int(H) * (N if wide else 1), "mask": int(H) * (N if wide else 1),
+                "x_mark": int(L) * F, "y_mark": int(H) * F, "static": Fs, "id": 1}
+    for name, t in outs.items():
+        if name not in WINDOW_PIECES:
+            raise ValueError(f"{who}: output {name!r} is not one of {WINDOW_PIECES}")
+        if t is None:
+            continue
+        want = torch.int64 if name == "id" else torch.float32
+        if (not isinstance(t, torch.Tensor) or t.dtype != want or t.device != X.device or not t.is_contiguous()
+                or (count is not None and (t.dim() < 1 or t.shape[0] != count or t.numel() != count * per_item[name]))):
+            raise ValueError(f"{who}: output {name!r} must be a contiguous {want} tensor beside X with {count} rows of "
+                             f"{per_item[name]} elements, got {tuple(getattr(t, 'shape', ()))}")
+        setattr(a, _WINDOW_FIELD.get(name, name), _ptr(t))
+    return a
+
+
+def window_batch_form(X: torch.Tensor, L: int, H: int, outs: dict, M=None, marks=None, statics=None, ids=None,
+                      layout: str = "series") -> dict:
+    """``window_batch_form_of`` for the tensors ``window_batch`` is given: ``outs`` maps piece names to the output
+    tensors (their addresses enter the form)."""
+    return _window_form_word(_window_args("window_batch_form", X, L, H, M, marks, statics, ids, layout, outs, None))
+
+
+def window_batch(X: torch.Tensor, starts: torch.Tensor, starts_host, L: int, H: int, item0: int, count: int,
+                 outs: dict, M=None, marks=None, statics=None, ids=None, layout: str = "series") -> None:
+    """``ftn_window_batch``: fills rows ``0 .. count - 1`` of the tensors in ``outs`` (piece name -> contiguous tensor
+    whose first dim is ``count``: ``x``, ``y``, ``mask``, ``x_mark``, ``y_mark``, ``static`` fp32, ``id`` int64) with
+    items ``item0 .. item0 + count - 1`` of the tables ``X`` [T, N], ``M`` [T, N], ``marks`` [T, F] (fp32, elements
+    contiguous, rows at least a row apart: row and column slices are fine), ``statics`` [N, Fs] and ``ids`` [N] int64,
+    all on one ROCm device.  ``starts`` [W] int32 on that device are the window start rows, ``starts_host`` the same
+    words as a contiguous int32 numpy array.  One launch on the current stream; enqueues only."""
+    who = "window_batch"
+    a = _window_args(who, X, L, H, M, marks, statics, ids, layout, outs, int(count))
+    if (not isinstance(starts, torch.Tensor) or starts.dim() != 1 or starts.dtype != torch.int32
+            or starts.device != X.device or not starts.is_contiguous()):
+        raise ValueError(f"{who}: starts must be a contiguous int32 vector on X's device")
+    W = starts.numel()
+    if (getattr(starts_host, "dtype", None) != "int32" or starts_host.ndim != 1 or starts_host.size != W
+            or not starts_host.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"{who}: starts_host must be a contiguous int32 numpy array of {W} start rows")
+    a.starts, a.starts_host, a.W = _ptr(starts), starts_host.ctypes.data, W
+    a.item0, a.count = int(item0), int(count)
+    check(_lib.load().ftn_window_batch(C.byref(a), _stream(X.device)), "ftn_window_batch")
+
+
 # ------------------------------------------------------------------ LRTC
 def lrtc_form_of(N: int, R: int, addx: bool = False, misalign_or: int = 0) -> Tuple[str, bool, int]:
     """The kernel ``ftn_lrtc_forward`` runs for N series at rank R (``ftn_lrtc_form``, host-only: the launch

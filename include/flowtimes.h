@@ -940,6 +940,85 @@ int ftn_embed_add(const FtnEmbedAddParams* params, const float* mark_dev_or_null
                   const float* q_bias_dev_or_null, long long q_bias_bstride, int Ba, int L, int D, float* out_dev,
                   void* stream);
 
+/* ---- device windows: the batches of a rolling-origin backtest (csrc/windows.hip) ----
+ * Additions only: FTN_ABI_VERSION stays 14.
+ *
+ * The wide table of a validation fold lives on the device once: X fp32 [T][N] (values), M fp32 [T][N] (validity,
+ * optional), marks fp32 [T][F] (time features, optional), statics fp32 [N][Fs] and ids int64 [N] (optional), and
+ * starts int32 [W], the first row s_w of every window (a window is rows s_w .. s_w + L + H - 1).  X, M and marks have
+ * row strides in elements (>= N, >= N, >= F), so a fold (a row slice) and a subset of series (a column slice) are
+ * passed in place; statics and ids are contiguous.
+ *
+ * ftn_window_batch (k_window_batch) enqueues ONE kernel on `stream` that writes the pieces of items
+ * item0 .. item0 + count - 1 into rows r = 0 .. count - 1 of the outputs.  It never allocates and never
+ * synchronises.  Every output is optional (a null pointer; at least one is given) and contiguous, and every value is
+ * a bit copy: NaN payloads, -0 and inf arrive unchanged.
+ *   FTN_WIN_SERIES  one series of one window per item, the order of the reference's SlidingWindowDataset
+ *                   (data/dataset.py:173-204): item k is window k / N, series i = k % N; with s = starts[k / N],
+ *                   e = s + L and r = k - item0
+ *                     x      [count][L]      x[r][l]         = X[s + l][i]
+ *                     y      [count][H]      y[r][h]         = X[e + h][i]
+ *                     mask   [count][H]      mask[r][h]      = M[e + h][i], or 1.0f when M is null (stored, not read)
+ *                     x_mark [count][L][F]   x_mark[r][l][f] = marks[s + l][f]
+ *                     y_mark [count][H][F]   y_mark[r][h][f] = marks[e + h][f]
+ *                     static [count][Fs]     static[r][:]    = statics[i][:]
+ *                     id     [count]         id[r]           = ids[i]
+ *                   A batch may start and end inside a window: it then takes a partial run of series of its first
+ *                   and last window.  item0 + count <= W N.
+ *   FTN_WIN_WIDE    one window per item (this project's [B][L][N] layout): item k is window k, s = starts[k]
+ *                     x [count][L][N]  x[r][l][n] = X[s + l][n];  y and mask [count][H][N] from rows e + h likewise;
+ *                     x_mark and y_mark as above.  Statics and ids are shared by the batch and not copied: asking
+ *                     for them is an error.  item0 + count <= W.
+ * starts_host is the same W words in host memory: the call validates them (0 <= s, s + L + H <= T) and sizes nothing
+ * from device data - the arrangement of offsets_host in ftn_group_sum.  What the kernel reads from the device copy is
+ * clamped to 0 .. T - L - H, so nothing outside the tables is ever read, not by a masked-off lane either, and
+ * nothing outside rows 0 .. count - 1 of the outputs is written.
+ * Limits, checked before the launch: 1 <= N, 1 <= L, 1 <= H, 0 <= F, 0 <= Fs, (L + H) max(N, F, Fs) < 2^31 (the words
+ * of one item's piece are counted in 32 bits), W >= 1, T >= L + H, count >= 1, 0 <= item0, item0 + count within the
+ * items; T times every row stride and count times the words of an item's piece formed in 64 bits and rejected on
+ * overflow; row strides as above; marks only with F >= 1 and statics only with Fs >= 1; x_mark / y_mark only with
+ * marks, static only with statics, id only with ids; X, starts and starts_host non-null; every pointer 4-byte
+ * aligned, ids and id 8-byte.  Anything else is a negative return with ftn_last_error set and nothing launched.
+ * No grid dimension carries count, W, L or T: a workgroup of 256 threads strides over the work units of all pieces
+ * (at most 4096 workgroups), and every address is formed in 64 bits.
+ * The kernel.  x, y and mask of FTN_WIN_SERIES are a transposition: a tile is (one window, FTN_WIN_TILE_SERIES = 64
+ * consecutive series, FTN_WIN_TILE_STEPS = 32 consecutive time steps), read along the series - the contiguous
+ * direction of the table - and written along time - the contiguous direction of an item row; consecutive series are
+ * consecutive output rows, so a tile that holds all of a row's steps is one contiguous run of the output.  The tile
+ * passes through LDS with a row stride of 65 words, which keeps both directions off shared banks.  Everything else
+ * (FTN_WIN_WIDE, the marks, statics, ids) is row copies in units of 1024 consecutive output words.
+ * ftn_window_batch_form (host-only; the launch dispatches through the same function; reads the dimensions, the row
+ * strides, which pointers are null and the low 4 bits of the addresses - starts, T, W, item0 and count are ignored):
+ *   bits 0-4    the pieces x, y, mask, x_mark, y_mark that move 16 bytes a lane (a bit is 0 for a piece that is not
+ *               requested); the others move 4 bytes a lane.  Same bits either way.  For a piece with table `tab`
+ *               (X, M or marks; none for mask when M is null), row stride `stride` and output `out`:
+ *                 x, y, mask of FTN_WIN_SERIES  N % 4 == 0, J % 4 == 0 (J = L for x, H for y and mask),
+ *                                               stride % 4 == 0, ((tab | out) & 15) == 0: quads of series are
+ *                                               loaded, quads of time steps stored
+ *                 x, y, mask of FTN_WIN_WIDE    N % 4 == 0, stride % 4 == 0, ((tab | out) & 15) == 0
+ *                 x_mark, y_mark                F % 4 == 0, stride % 4 == 0, ((tab | out) & 15) == 0
+ *               static and id always move 4 bytes a lane.
+ *   bits 8-15   FTN_WIN_TILE_SERIES and bits 16-23 FTN_WIN_TILE_STEPS when x, y or mask of FTN_WIN_SERIES is
+ *               requested (the tile of the transposition), else 0. */
+#define FTN_WIN_SERIES 0
+#define FTN_WIN_WIDE 1
+#define FTN_WIN_TILE_SERIES 64
+#define FTN_WIN_TILE_STEPS 32
+typedef struct FtnWindowArgs {
+  const float* X;        long long x_stride;              /* [T][N] values */
+  const float* M;        long long m_stride;              /* [T][N] validity (null: a mask of ones) */
+  const float* marks;    long long marks_stride;          /* [T][F] time features (null: none) */
+  const float* statics;                                   /* [N][Fs] (null: none) */
+  const long long* ids;                                   /* [N] (null: none) */
+  const int32_t* starts; const int32_t* starts_host;      /* [W] window start rows, on the device and on the host */
+  long long T, item0, count;
+  int32_t N, L, H, F, Fs, W, layout, reserved;
+  float* x; float* y; float* mask; float* x_mark; float* y_mark; float* static_out;   /* outputs, each optional */
+  long long* id_out;
+} FtnWindowArgs;
+int ftn_window_batch_form(const FtnWindowArgs* args);
+int ftn_window_batch(const FtnWindowArgs* args, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
