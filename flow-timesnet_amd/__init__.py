@@ -21,6 +21,9 @@ Sub-modules
                      functions without a backend choice (``score`` re-exports what callers use)
 ``windows``          ``DeviceWindows``: the batches of a rolling-origin backtest formed on the device from the wide
                      table, in the order and shapes of the reference's ``SlidingWindowDataset`` + ``DataLoader``
+``table``            the table's preparation on the device: ``series_features`` (the reference's static features, the
+                     full-history spectrum on the matrix pipe), ``SeriesScaler`` (fit, transform, inverse and clip),
+                     ``holdout_rows`` / ``rolling_rows``
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401
@@ -29,6 +32,7 @@ from . import synth  # noqa: F401
 def __getattr__(name):  # lazy: keeps `import flow_timesnet_amd.synth` torch-free
     import importlib
 
-    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score", "nbdist", "windows"):
+    if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score", "nbdist", "windows",
+                "table"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

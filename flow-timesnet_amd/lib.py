@@ -149,6 +149,45 @@ class FtnWindowArgs(C.Structure):
         (n, C.c_void_p) for n in ("x", "y", "mask", "x_mark", "y_mark", "static_out", "id_out")]
 
 
+FTN_TAB_CLIP, FTN_TAB_MASK, FTN_TAB_DIFF, FTN_TAB_INVERSE = 1, 2, 4, 8
+FTN_TAB_ZSCORE, FTN_TAB_MINMAX = 0, 1
+FTN_TAB_PARTIALS_MAX, FTN_TAB_SPEC_COLS, FTN_TAB_SPEC_BINS, FTN_TAB_SPEC_CHUNK = 32, 64, 128, 128
+FTN_TAB_T_MAX = 65536
+
+
+class FtnTableForm(C.Structure):
+    """Mirror of ``struct FtnTableForm`` (include/flowtimes.h): what a ``ftn_table_*_form`` query reports."""
+
+    _fields_ = [(n, C.c_int32) for n in ("load_bytes", "col_tile", "block", "chunk", "resident", "partials",
+                                         "lane_axis", "reserved")]
+
+
+class FtnTableMomentsArgs(C.Structure):
+    """Mirror of ``struct FtnTableMomentsArgs`` (include/flowtimes.h)."""
+
+    _fields_ = [("X", C.c_void_p), ("x_stride", C.c_longlong), ("M", C.c_void_p), ("m_stride", C.c_longlong),
+                ("T", C.c_longlong), ("N", C.c_int32), ("flags", C.c_int32), ("stats", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class FtnTableSpectrumArgs(C.Structure):
+    """Mirror of ``struct FtnTableSpectrumArgs`` (include/flowtimes.h)."""
+
+    _fields_ = [("X", C.c_void_p), ("x_stride", C.c_longlong), ("M", C.c_void_p), ("m_stride", C.c_longlong),
+                ("mean", C.c_void_p), ("twiddle", C.c_void_p), ("T", C.c_longlong), ("N", C.c_int32),
+                ("reserved", C.c_int32), ("f_peak", C.c_void_p), ("peak", C.c_void_p), ("total", C.c_void_p),
+                ("power_out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class FtnTableAffineArgs(C.Structure):
+    """Mirror of ``struct FtnTableAffineArgs`` (include/flowtimes.h)."""
+
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p)] + [
+        (n, C.c_longlong) for n in ("x_ostride", "x_sstride", "o_ostride", "o_sstride", "outer")] + [
+        (n, C.c_int32) for n in ("S", "inner", "n_cols", "flags")] + [
+        ("loc", C.c_void_p), ("scale", C.c_void_p), ("series", C.c_void_p)]
+
+
 class FtnInceptionBlockWeights(C.Structure):
     """Mirror of ``struct FtnInceptionBlockWeights`` (include/flowtimes.h): raw host pointers to the reference
     ``state_dict`` tensors of one InceptionBlock."""
@@ -281,6 +320,19 @@ _SIGNATURES = {
     # device windows (csrc/windows.hip)
     "ftn_window_batch_form": (C.c_int, [C.POINTER(FtnWindowArgs)]),
     "ftn_window_batch": (C.c_int, [C.POINTER(FtnWindowArgs), _P]),
+    # table preparation (csrc/table.hip)
+    "ftn_table_moments_bytes": (C.c_size_t, [C.c_longlong, C.c_int]),
+    "ftn_table_moments_form": (C.c_int, [C.POINTER(FtnTableMomentsArgs), C.POINTER(FtnTableForm)]),
+    "ftn_table_moments": (C.c_int, [C.POINTER(FtnTableMomentsArgs), _P]),
+    "ftn_table_twiddle_bytes": (C.c_size_t, [C.c_longlong]),
+    "ftn_table_twiddle_init": (C.c_int, [_P, C.c_longlong, _P]),
+    "ftn_table_spectrum_bytes": (C.c_size_t, [C.c_longlong, C.c_int]),
+    "ftn_table_spectrum_form": (C.c_int, [C.POINTER(FtnTableSpectrumArgs), C.POINTER(FtnTableForm)]),
+    "ftn_table_spectrum": (C.c_int, [C.POINTER(FtnTableSpectrumArgs), _P]),
+    "ftn_table_features": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, _P, _P]),
+    "ftn_table_scaler": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
+    "ftn_table_affine_form": (C.c_int, [C.POINTER(FtnTableAffineArgs), C.POINTER(FtnTableForm)]),
+    "ftn_table_affine": (C.c_int, [C.POINTER(FtnTableAffineArgs), _P]),
     "ftn_lrtc_basis_floats": (C.c_size_t, [C.c_int, C.c_int]),
     "ftn_lrtc_basis": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "ftn_lrtc_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

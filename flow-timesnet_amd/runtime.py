@@ -83,6 +83,7 @@ class DeviceState:
         self.device = device
         self.tables: Dict[int, torch.Tensor] = {}
         self.bases: Dict[Tuple[int, int], torch.Tensor] = {}
+        self.twiddles: Dict[int, torch.Tensor] = {}             # table spectrum: 8 T bytes per history length T
 
     def dft_table(self, L: int) -> torch.Tensor:
         t = self.tables.get(L)
@@ -92,6 +93,23 @@ class DeviceState:
             t = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
             check(lib.ftn_dft_table_init(_ptr(t), L, _stream(self.device)), "ftn_dft_table_init")
             self.tables[L] = t
+        return t
+
+    def table_twiddles(self, T: int) -> torch.Tensor:
+        """The ``T`` twiddles of ``ftn_table_spectrum`` (``ftn_table_twiddle_init``), cached per ``T``
+        (the 64 most recently built)."""
+        key = int(T)
+        t = self.twiddles.get(key)
+        if t is None:
+            lib = _lib.load()
+            nbytes = lib.ftn_table_twiddle_bytes(key)
+            if nbytes == 0:
+                raise ValueError(f"table spectrum: T={T} is outside 1..{_lib.FTN_TAB_T_MAX}")
+            if len(self.twiddles) >= 64:                        # a pipeline whose history grows by the day: keep it bounded
+                self.twiddles.pop(next(iter(self.twiddles)))
+            t = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+            check(lib.ftn_table_twiddle_init(_ptr(t), key, _stream(self.device)), "ftn_table_twiddle_init")
+            self.twiddles[key] = t
         return t
 
     def lrtc_basis(self, L: int, R: int) -> torch.Tensor:
@@ -1400,6 +1418,259 @@ def window_batch(X: torch.Tensor, starts: torch.Tensor, starts_host, L: int, H: 
     a.starts, a.starts_host, a.W = _ptr(starts), starts_host.ctypes.data, W
     a.item0, a.count = int(item0), int(count)
     check(_lib.load().ftn_window_batch(C.byref(a), _stream(X.device)), "ftn_window_batch")
+
+
+# ------------------------------------------------------------------ table preparation
+TABLE_METHODS = {"zscore": _lib.FTN_TAB_ZSCORE, "minmax": _lib.FTN_TAB_MINMAX}
+_TABLE_FORM_FIELDS = ("load_bytes", "col_tile", "block", "chunk", "resident", "partials", "lane_axis")
+
+
+def _table_form(name: str, args) -> dict:
+    f = _lib.FtnTableForm()
+    rc = getattr(_lib.load(), name)(C.byref(args), C.byref(f))
+    if rc < 0:
+        check(rc, name)
+    return {k: getattr(f, k) for k in _TABLE_FORM_FIELDS}
+
+
+def _table_flags(clip: bool, mask: bool, diffs: bool) -> int:
+    return (_lib.FTN_TAB_CLIP if clip else 0) | (_lib.FTN_TAB_MASK if mask else 0) | (_lib.FTN_TAB_DIFF if diffs else 0)
+
+
+def table_moments_form_of(T: int, N: int, x_stride: int | None = None, m_stride: int | None = None,
+                          mask: bool = False, diffs: bool = False, clip: bool = False,
+                          misalign: dict | None = None) -> dict:
+    """The form ``ftn_table_moments`` takes (``ftn_table_moments_form``, host-only: the launch dispatches through the
+    same function): ``load_bytes`` 16 or 4, ``col_tile`` columns a workgroup, ``block`` rows a row block, ``partials``
+    row blocks.  Row strides in elements (default: dense); ``misalign``: byte offsets of ``"X"`` / ``"M"`` from a
+    16-byte boundary."""
+    mis = dict(misalign or {})
+    a = _lib.FtnTableMomentsArgs()
+    a.T, a.N, a.flags = int(T), int(N), _table_flags(clip, mask, diffs)
+    a.x_stride = int(N if x_stride is None else x_stride)
+    a.m_stride = int(N if m_stride is None else m_stride)
+    a.X = 0x100000 + mis.pop("X", 0)                            # stand-in addresses: the form reads their low bits only
+    m_off = mis.pop("M", 0)
+    a.M = 0x200000 + m_off if mask else None
+    if mis:
+        raise ValueError(f"table_moments_form_of: misalign names {sorted(mis)} are not tables of the call")
+    return _table_form("ftn_table_moments_form", a)
+
+
+def _table_pair(who: str, X, M):
+    """The pointers and row strides of a table ``X`` [T, N] and its optional validity ``M``."""
+    xp, xs, T, N = _window_table(who, "X", X, None, None)
+    if X is None:
+        raise ValueError(f"{who}: X is required")
+    mp, ms, Tm, _ = _window_table(who, "M", M, N, X)
+    if M is not None and Tm != T:
+        raise ValueError(f"{who}: M must have X's {T} rows")
+    return xp, xs, mp, ms, T, N
+
+
+def table_moments(X: torch.Tensor, M: torch.Tensor | None = None, clip: bool = False, diffs: bool = False,
+                  form: bool = False, out: torch.Tensor | None = None):
+    """``ftn_table_moments``: the column statistics fp64 ``[6, N]`` (count, sum, mean, centred sum of squares, min,
+    max; ``[12, N]`` with ``diffs``: the same of the first differences) of the fp32 device table ``X`` [T, N]
+    (elements contiguous, rows at least a row apart); ``M`` given: only elements with ``M > 0`` count.  Enqueues
+    four launches on the current stream.  ``out``: the contiguous fp64 statistics tensor to fill.  ``form=True``: the
+    form dict of this call instead."""
+    who = "table_moments"
+    a = _lib.FtnTableMomentsArgs()
+    a.X, a.x_stride, a.M, a.m_stride, a.T, a.N = _table_pair(who, X, M)
+    a.flags = _table_flags(clip, M is not None, diffs)
+    if form:
+        return _table_form("ftn_table_moments_form", a)
+    lib = _lib.load()
+    rows = 12 if diffs else 6
+    stats = torch.empty(rows, a.N, dtype=torch.float64, device=X.device) if out is None else out
+    if stats.shape != (rows, a.N) or stats.dtype != torch.float64 or stats.device != X.device or not stats.is_contiguous():
+        raise ValueError(f"{who}: out must be a contiguous fp64 [{rows}, {a.N}] tensor beside X")
+    nbytes = int(lib.ftn_table_moments_bytes(a.T, a.N))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=X.device)
+    a.stats, a.workspace, a.workspace_bytes = _ptr(stats), _ptr(ws), nbytes
+    check(lib.ftn_table_moments(C.byref(a), _stream(X.device)), "ftn_table_moments")
+    return stats
+
+
+def table_spectrum_form_of(T: int, N: int, x_stride: int | None = None, m_stride: int | None = None,
+                           has_mask: bool = True, misalign: dict | None = None) -> dict:
+    """The form ``ftn_table_spectrum`` takes (``ftn_table_spectrum_form``, host-only): ``load_bytes`` of the staging
+    loads, ``col_tile`` columns and ``block`` bins a workgroup, ``chunk`` rows a staging chunk, ``resident`` whether
+    the column tile is one chunk, ``partials`` bin blocks."""
+    mis = dict(misalign or {})
+    a = _lib.FtnTableSpectrumArgs()
+    a.T, a.N = int(T), int(N)
+    a.x_stride = int(N if x_stride is None else x_stride)
+    a.m_stride = int(N if m_stride is None else m_stride)
+    a.X = 0x100000 + mis.pop("X", 0)
+    m_off = mis.pop("M", 0)
+    a.M = 0x200000 + m_off if has_mask else None
+    if mis:
+        raise ValueError(f"table_spectrum_form_of: misalign names {sorted(mis)} are not tables of the call")
+    return _table_form("ftn_table_spectrum_form", a)
+
+
+def table_spectrum(X: torch.Tensor, mean: torch.Tensor, M: torch.Tensor | None = None, power_out=None,
+                   form: bool = False, outs=None):
+    """``ftn_table_spectrum``: per column of the fp32 device table ``X`` [T, N], demeaned by ``mean`` [N] fp32 and
+    masked by ``M > 0``: ``(f_peak int32 [N], peak fp32 [N], total fp32 [N])`` of the power at bins 1 .. T // 2.
+    ``power_out``: a contiguous fp32 ``[T // 2, N]`` tensor that receives every bin (tests).  ``outs``: the three
+    output tensors to fill.  Two launches on the current stream; the twiddle table is cached per ``T``."""
+    who = "table_spectrum"
+    a = _lib.FtnTableSpectrumArgs()
+    a.X, a.x_stride, a.M, a.m_stride, a.T, a.N = _table_pair(who, X, M)
+    if form:
+        return _table_form("ftn_table_spectrum_form", a)
+    T, N, dev = a.T, a.N, X.device
+    if not isinstance(mean, torch.Tensor) or mean.shape != (N,) or mean.dtype != torch.float32 or mean.device != dev \
+            or not mean.is_contiguous():
+        raise ValueError(f"{who}: mean must be a contiguous fp32 [N] = [{N}] tensor beside X")
+    lib = _lib.load()
+    if outs is None:
+        outs = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.float32, device=dev),
+                torch.empty(N, dtype=torch.float32, device=dev))
+    f_peak, peak, total = outs
+    for t, dt in ((f_peak, torch.int32), (peak, torch.float32), (total, torch.float32)):
+        if t.shape != (N,) or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{who}: outs must be contiguous [N] tensors (int32, fp32, fp32) beside X")
+    if power_out is not None and (power_out.shape != (T // 2, N) or power_out.dtype != torch.float32
+                                  or power_out.device != dev or not power_out.is_contiguous()):
+        raise ValueError(f"{who}: power_out must be a contiguous fp32 [T // 2, N] = [{T // 2}, {N}] tensor beside X")
+    tw = state(dev).table_twiddles(T)
+    nbytes = int(lib.ftn_table_spectrum_bytes(T, N))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=dev)
+    a.mean, a.twiddle = _ptr(mean), _ptr(tw)
+    a.f_peak, a.peak, a.total = _ptr(f_peak), _ptr(peak), _ptr(total)
+    a.power_out = _ptr(power_out) if power_out is not None and power_out.numel() else None
+    a.workspace, a.workspace_bytes = _ptr(ws), nbytes
+    check(lib.ftn_table_spectrum(C.byref(a), _stream(dev)), "ftn_table_spectrum")
+    return f_peak, peak, total
+
+
+def table_features(stats: torch.Tensor, f_peak: torch.Tensor, peak: torch.Tensor, total: torch.Tensor, T: int,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """``ftn_table_features``: the five features fp32 ``[N, 5]`` from the ``[12, N]`` statistics of a masked
+    ``table_moments(..., diffs=True)`` and the outputs of ``table_spectrum``."""
+    if stats.dim() != 2 or stats.shape[0] != 12 or stats.dtype != torch.float64 or not stats.is_contiguous():
+        raise ValueError("table_features: stats must be the contiguous fp64 [12, N] statistics of table_moments")
+    N = stats.shape[1]
+    out = _out_or_fresh("table_features", out, (N, 5), peak)
+    check(_lib.load().ftn_table_features(_ptr(stats), _ptr(f_peak), _ptr(peak), _ptr(total), int(T), N, _ptr(out),
+                                         _stream(stats.device)), "ftn_table_features")
+    return out
+
+
+def table_scaler(stats: torch.Tensor, method: str, per_series: bool = True, eps: float = 1e-8):
+    """``ftn_table_scaler``: ``(loc [N], scale [N], pairs [2, N])`` fp32 from the unmasked statistics of
+    ``table_moments``; the reference's ``eps`` rule, on the device."""
+    if method not in TABLE_METHODS:
+        raise ValueError(f"table_scaler: method {method!r} is not 'zscore' or 'minmax'")
+    if stats.dim() != 2 or stats.shape[0] not in (6, 12) or stats.dtype != torch.float64 or not stats.is_contiguous():
+        raise ValueError("table_scaler: stats must be the contiguous fp64 [6, N] statistics of table_moments")
+    N, dev = stats.shape[1], stats.device
+    loc = torch.empty(N, dtype=torch.float32, device=dev)
+    scale = torch.empty(N, dtype=torch.float32, device=dev)
+    pairs = torch.empty(2, N, dtype=torch.float32, device=dev)
+    check(_lib.load().ftn_table_scaler(_ptr(stats), N, TABLE_METHODS[method], int(bool(per_series)), float(eps),
+                                       _ptr(loc), _ptr(scale), _ptr(pairs), _stream(dev)), "ftn_table_scaler")
+    return loc, scale, pairs
+
+
+def _collapse(shape, strides):
+    """``(size, stride)`` of consecutive dims read as one, or None when no single stride walks them."""
+    dims = [(n, s) for n, s in zip(shape, strides) if n != 1]
+    size = 1
+    for n, _ in dims:
+        size *= n
+    if not dims:
+        return 1, 0
+    for (_, s0), (n1, s1) in zip(dims[:-1], dims[1:]):
+        if s0 != s1 * n1:
+            return None
+    return size, dims[-1][1]
+
+
+def _affine_view(t: torch.Tensor, axis: int):
+    """``(outer, S, inner, outer stride, series stride)`` of ``t`` read as [outer][S][inner] around ``axis``, or None."""
+    shape, strides = tuple(t.shape), tuple(t.stride())
+    outer, inner = _collapse(shape[:axis], strides[:axis]), _collapse(shape[axis + 1:], strides[axis + 1:])
+    if outer is None or inner is None or (inner[0] > 1 and inner[1] != 1):
+        return None
+    S, ss = shape[axis], strides[axis]
+    if S > 1 and ss < inner[0]:
+        return None
+    if outer[0] > 1 and outer[1] < 0:
+        return None
+    return outer[0], S, inner[0], (outer[1] if outer[0] > 1 else 0), (ss if S > 1 else inner[0])
+
+
+def table_affine_form_of(outer: int, S: int, inner: int, x_strides=None, o_strides=None, n_cols: int | None = None,
+                         series: bool = False, inverse: bool = False, misalign: dict | None = None) -> dict:
+    """The form ``ftn_table_affine`` takes (``ftn_table_affine_form``, host-only) over [outer][S][inner]:
+    ``load_bytes`` 16 or 4, ``lane_axis`` 1 (four elements of one series), 2 (of four series) or 0, ``block`` elements
+    a unit.  ``x_strides`` / ``o_strides``: (outer, series) element strides (default: dense)."""
+    mis = dict(misalign or {})
+    a = _lib.FtnTableAffineArgs()
+    a.outer, a.S, a.inner = int(outer), int(S), int(inner)
+    a.x_ostride, a.x_sstride = x_strides if x_strides is not None else (a.S * a.inner, a.inner)
+    a.o_ostride, a.o_sstride = o_strides if o_strides is not None else (a.S * a.inner, a.inner)
+    a.n_cols = int(S if n_cols is None else n_cols)
+    a.flags = _lib.FTN_TAB_INVERSE if inverse else 0
+    a.x, a.out = 0x100000 + mis.pop("x", 0), 0x200000 + mis.pop("out", 0)
+    a.loc, a.scale, a.series = 0x300000, 0x400000, (0x500000 if series else None)
+    if mis:
+        raise ValueError(f"table_affine_form_of: misalign names {sorted(mis)} are not operands of the call")
+    return _table_form("ftn_table_affine_form", a)
+
+
+def table_affine(x: torch.Tensor, loc: torch.Tensor, scale: torch.Tensor, axis: int = -1, series=None,
+                 inverse: bool = False, clip: bool = False, out: torch.Tensor | None = None, form: bool = False):
+    """``ftn_table_affine``: ``(x - loc[c]) / scale[c]`` (``clip``: of ``max(x, 0)``) or, with ``inverse``,
+    ``x * scale[c] + loc[c]`` (``clip``: then ``max(., 0)``) with the series along ``axis`` of the fp32 device tensor
+    ``x``; ``c`` is the position along ``axis`` or ``series[position]`` (int64 on the device).  ``out`` may be ``x``
+    or a tensor of x's shape; a view that one outer and one series stride cannot walk is an error for ``out`` and a
+    contiguous copy for ``x``.  One launch on the current stream."""
+    who = "table_affine"
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or x.dim() < 1:
+        raise ValueError(f"{who}: x must be an fp32 tensor on a ROCm device")
+    axis = axis % x.dim()
+    dev, n_cols = x.device, loc.numel()
+    for name, t in (("loc", loc), ("scale", scale)):
+        if t.dim() != 1 or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() != n_cols:
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 vector beside x")
+    S = x.shape[axis]
+    if series is not None:
+        if (not isinstance(series, torch.Tensor) or series.shape != (S,) or series.dtype != torch.int64
+                or series.device != dev or not series.is_contiguous()):
+            raise ValueError(f"{who}: series must be a contiguous int64 [{S}] tensor beside x")
+    elif S > n_cols:
+        raise ValueError(f"{who}: {S} series along axis {axis} but loc and scale hold {n_cols}")
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.shape != x.shape or out.dtype != torch.float32 or out.device != dev:
+        raise ValueError(f"{who}: out must be an fp32 tensor of x's shape {tuple(x.shape)} beside x")
+    if x.numel() == 0:
+        return out
+    vo = _affine_view(out, axis)
+    if vo is None:
+        raise ValueError(f"{who}: out with strides {out.stride()} cannot be walked as [outer][series][inner]")
+    vx = _affine_view(x, axis)
+    if vx is None:
+        x = x.contiguous()
+        vx = _affine_view(x, axis)
+    a = _lib.FtnTableAffineArgs()
+    a.x, a.out = _ptr(x), _ptr(out)
+    a.outer, a.S, a.inner, a.x_ostride, a.x_sstride = vx
+    a.o_ostride, a.o_sstride = vo[3], vo[4]
+    if vo[0] > 1 and a.o_ostride == 0:
+        raise ValueError(f"{who}: out repeats its rows (stride 0)")
+    a.n_cols, a.flags = n_cols, (_lib.FTN_TAB_INVERSE if inverse else 0) | (_lib.FTN_TAB_CLIP if clip else 0)
+    a.loc, a.scale, a.series = _ptr(loc), _ptr(scale), _ptr_or_null(series)
+    if form:
+        return _table_form("ftn_table_affine_form", a)
+    check(_lib.load().ftn_table_affine(C.byref(a), _stream(dev)), "ftn_table_affine")
+    return out
 
 
 # ------------------------------------------------------------------ LRTC

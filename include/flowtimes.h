@@ -1019,6 +1019,123 @@ typedef struct FtnWindowArgs {
 int ftn_window_batch_form(const FtnWindowArgs* args);
 int ftn_window_batch(const FtnWindowArgs* args, void* stream);
 
+/* ---- table preparation: static features, scalers, their transform and inverse (csrc/table.hip) ----
+ * Additions only: FTN_ABI_VERSION stays 14.
+ *
+ * What the reference does to the wide table X fp32 [T][N] (validity M fp32 [T][N], optional) before the loader -
+ * compute_series_features (utils/static_features.py:17-103), fit_series_scaler (utils/io.py:548-597),
+ * _transform_dataframe (train.py:569-592) - and to the forecast after the model - inverse_transform and the clip at 0
+ * (utils/io.py:600-621, predict.py:959-961).  X and M have row strides in elements (>= N): a fold (a row slice) and a
+ * subset of series (a column slice) are passed in place.  No entry allocates, none synchronises, every limit is
+ * checked before the first launch (a violation is a negative return with ftn_last_error set and nothing launched),
+ * every address is formed in 64 bits, no grid dimension carries N or T (workgroups of 256 threads stride over the
+ * work units, at most 4096 of them), there are no floating-point atomics, and the bits do not depend on the run.
+ * A validity value counts when it is > 0; the value of an element that does not count is loaded and discarded.
+ *
+ * ftn_table_moments: per column over rows 0 .. T - 1, the statistics stats fp64 [6][N], or [12][N] with FTN_TAB_DIFF:
+ *   row 0 count   the elements that count (all T without FTN_TAB_MASK; M is ignored then and may be null)
+ *   row 1 sum     their fp64 sum (with FTN_TAB_CLIP every value is read as v < 0 ? 0 : v; nothing is written back)
+ *   row 2 mean    fp32(sum / max(count, 1)), rounded once; NaN when the sum is not finite
+ *   row 3 css     sum of double(d)^2, d = fp32(v - mean) formed in fp32, squares and sums in fp64
+ *   row 4 / 5     min and max (fp32 values; a NaN that counts is kept, as numpy keeps it; +inf / -inf when count = 0)
+ *   rows 6 - 11   the same six of the first differences fp32(v[t] - v[t-1]), t = 1 .. T - 1, where both rows count
+ * Order: a thread owns a column (the 16-byte form: four columns with one 16-byte load when N % 4 == 0, the row strides
+ * are multiples of 4 and the tables are 16-byte aligned; same bits either way) and a block of rb consecutive rows,
+ * rb = 32 doubled until at most FTN_TAB_PARTIALS_MAX = 32 blocks cover T, and adds its rows ascending; the blocks'
+ * partials are added ascending.  Two passes over the table (the centred sums need the mean), a launch between them
+ * that finishes the means once a column, and a combining launch.
+ * workspace: ftn_table_moments_bytes(T, N), 8-byte aligned, contents irrelevant before and after.
+ *
+ * ftn_table_twiddle_bytes / ftn_table_twiddle_init: the table of T twiddles (cos, sin)(2 pi m / T), m = 0 .. T - 1,
+ * evaluated in fp64 on the exactly reduced argument and rounded to fp32 - the analogue of ftn_dft_table_*.
+ *
+ * ftn_table_spectrum: with d[t][n] = (M null or M[t][n] > 0) ? fp32(X[t][n] - mean[n]) : 0 and, for f = 1 .. F =
+ * floor(T / 2), ph = 2 pi ((f t) mod T) / T, re = sum_t d cos(ph), im = sum_t d sin(ph), P[f][n] = re^2 + im^2, per
+ * column: f_peak int32 [N], the lowest f that attains the maximum of P (0 when T = 1); peak fp32 [N] = P[f_peak];
+ * total fp32 [N] = the fp64 sum of the fp32 P[f] rounded once (0, 0 when T = 1; a NaN total makes peak NaN).
+ * The sums run on v_mfma_f32_32x32x2_f32 with the twiddles as A and d as B (k_spectrum's convention); a workgroup
+ * owns FTN_TAB_SPEC_COLS = 64 columns and FTN_TAB_SPEC_BINS = 128 bins and stages d through LDS in chunks of
+ * FTN_TAB_SPEC_CHUNK = 128 rows; the phase index is carried exactly as m += 2 f mod T.  P is not written unless
+ * power_out fp32 [F][N] (contiguous, optional) is given.  The peaks and totals of the bin blocks pass through the
+ * workspace (ftn_table_spectrum_bytes(T, N), 8-byte aligned) and are combined ascending.  1 <= T <= 65536; a larger
+ * T is refused.  `twiddle` is the table of ftn_table_twiddle_init for this T; mean fp32 [N].
+ *
+ * ftn_table_features: the five features out fp32 [N][5] (mean, std, diff_std, seasonal_strength, dominant_period)
+ * from the [12][N] statistics of a FTN_TAB_MASK | FTN_TAB_DIFF call and the three spectrum outputs:
+ * std = sqrt(fp32(css / max(count, 1))), seasonal_strength = peak / max(total, 1e-6) (numpy's maximum: a NaN stays),
+ * dominant_period = total > 1e-6 ? fp32(double(T) / f_peak) : 0; diff_std, seasonal_strength and dominant_period are
+ * 0 when T = 1; a column whose mean is NaN gives (NaN, NaN, NaN, NaN, 0).
+ *
+ * ftn_table_scaler: loc fp32 [N], scale fp32 [N] and the reference's pairs fp32 [2][N] from the [6][N] statistics
+ * of a call without FTN_TAB_MASK.  FTN_TAB_ZSCORE: pairs (mean, sd), sd = sqrt(fp32(css / count)), sd < eps -> 1;
+ * FTN_TAB_MINMAX: pairs (min, max), scale = max - min, < eps -> 1.  per_series = 0 reduces the column moments to one
+ * pair in fixed-order fp64 (one workgroup: thread i adds columns i, i + 256, .. ascending, the 256 partials are added
+ * ascending) and writes it to every column.
+ *
+ * ftn_table_affine: one pass over x [outer][S][inner] (series along the middle axis; element strides x_ostride,
+ * x_sstride, and 1 along inner; the output likewise; out may be x):
+ *   transform  out = ((FTN_TAB_CLIP ? (x < 0 ? 0 : x) : x) - loc[c]) / scale[c]
+ *   inverse    (FTN_TAB_INVERSE) r = x * scale[c] + loc[c]; out = FTN_TAB_CLIP ? (r < 0 ? 0 : r) : r
+ * c = s, or series[s] (int64 [S], clamped to 0 .. n_cols - 1 when read) with a series map.  fp32 with one rounding
+ * per operation - a correctly rounded subtract and divide, a multiply and an add that are not contracted - so for
+ * the same loc and scale bits the result is numpy's bit for bit.  16-byte lanes where x and out are 16-byte aligned,
+ * the outer strides are multiples of 4 and either inner % 4 == 0 with series strides that are multiples of 4
+ * (lane_axis 1) or inner == 1, S % 4 == 0 and both series strides 1 (lane_axis 2); 4-byte lanes otherwise; the same
+ * bits either way.  S inner < 2^31 - 1024, S <= n_cols without a map.
+ *
+ * ftn_table_*_form: host-only; the launches dispatch through the same functions.  FtnTableForm: load_bytes 16 | 4;
+ * col_tile (moments: 1024 | 256 columns a workgroup; spectrum: 64); block (moments: rows a block; spectrum: bins a
+ * block; affine: elements a unit); chunk (spectrum: rows a staging chunk); resident (spectrum: 1 when the whole column
+ * tile is one chunk, 0 when it is streamed); partials (moments: row blocks; spectrum: bin blocks); lane_axis (affine). */
+#define FTN_TAB_CLIP 1
+#define FTN_TAB_MASK 2
+#define FTN_TAB_DIFF 4
+#define FTN_TAB_INVERSE 8
+#define FTN_TAB_ZSCORE 0
+#define FTN_TAB_MINMAX 1
+#define FTN_TAB_PARTIALS_MAX 32
+#define FTN_TAB_SPEC_COLS 64
+#define FTN_TAB_SPEC_BINS 128
+#define FTN_TAB_SPEC_CHUNK 128
+typedef struct FtnTableForm {
+  int32_t load_bytes, col_tile, block, chunk, resident, partials, lane_axis, reserved;
+} FtnTableForm;
+typedef struct FtnTableMomentsArgs {
+  const float* X; long long x_stride;
+  const float* M; long long m_stride;
+  long long T; int32_t N, flags;
+  double* stats;
+  void* workspace; size_t workspace_bytes;
+} FtnTableMomentsArgs;
+typedef struct FtnTableSpectrumArgs {
+  const float* X; long long x_stride;
+  const float* M; long long m_stride;
+  const float* mean; const float* twiddle;
+  long long T; int32_t N, reserved;
+  int32_t* f_peak; float* peak; float* total; float* power_out;
+  void* workspace; size_t workspace_bytes;
+} FtnTableSpectrumArgs;
+typedef struct FtnTableAffineArgs {
+  const float* x; float* out;
+  long long x_ostride, x_sstride, o_ostride, o_sstride, outer;
+  int32_t S, inner, n_cols, flags;
+  const float* loc; const float* scale; const long long* series;
+} FtnTableAffineArgs;
+size_t ftn_table_moments_bytes(long long T, int N);
+int ftn_table_moments_form(const FtnTableMomentsArgs* args, FtnTableForm* form);
+int ftn_table_moments(const FtnTableMomentsArgs* args, void* stream);
+size_t ftn_table_twiddle_bytes(long long T);
+int ftn_table_twiddle_init(void* table_dev, long long T, void* stream);
+size_t ftn_table_spectrum_bytes(long long T, int N);
+int ftn_table_spectrum_form(const FtnTableSpectrumArgs* args, FtnTableForm* form);
+int ftn_table_spectrum(const FtnTableSpectrumArgs* args, void* stream);
+int ftn_table_features(const double* stats_dev, const int32_t* f_peak_dev, const float* peak_dev,
+                       const float* total_dev, long long T, int N, float* out_dev, void* stream);
+int ftn_table_scaler(const double* stats_dev, int N, int method, int per_series, double eps, float* loc_dev,
+                     float* scale_dev, float* pairs_dev, void* stream);
+int ftn_table_affine_form(const FtnTableAffineArgs* args, FtnTableForm* form);
+int ftn_table_affine(const FtnTableAffineArgs* args, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------- */
 /* hipEvent brackets around the 6 stages (A pw-in, B conv, C fused pointwise chain,
  * D conv, E pw-out, F combine) of the following ftn_timesblock_forward calls - every
