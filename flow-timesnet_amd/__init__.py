@@ -24,6 +24,10 @@ Sub-modules
 ``table``            the table's preparation on the device: ``series_features`` (the reference's static features, the
                      full-history spectrum on the matrix pipe), ``SeriesScaler`` (fit, transform, inverse and clip),
                      ``holdout_rows`` / ``rolling_rows``
+``fit``              adapting a checkpoint to new data: ``nb_nll_grad``, the loss and its closed-form gradients with
+                     respect to rate and dispersion (fp64 inside, one kernel pass), and ``negative_binomial_nll`` as
+                     an autograd node over them; ``head_nll``, the heads with their backward on the device, and
+                     ``refit_heads``, the loop over ``TimesNet.head_inputs``
 ``graph``            HIP-graph capture / replay of an inference forward
 """
 from . import synth  # noqa: F401
@@ -33,6 +37,6 @@ def __getattr__(name):  # lazy: keeps `import flow_timesnet_amd.synth` torch-fre
     import importlib
 
     if name in ("lib", "pack", "models", "dist", "grouping", "runtime", "graph", "forecast", "score", "nbdist", "windows",
-                "table"):
+                "table", "fit"):
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

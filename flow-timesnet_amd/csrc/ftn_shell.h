@@ -25,6 +25,11 @@ __device__ __forceinline__ float softplus20(float x) {
   return fmaxf(x, 0.f) + (e < 0.015625f ? series : lg);
 }
 
+// softplus20's derivative as torch's backward takes it: sigmoid(x) up to the threshold, 1 above
+__device__ __forceinline__ float sigmoid20(float x) {
+  return x > 20.f ? 1.f : __builtin_amdgcn_rcpf(1.f + __expf(-x));
+}
+
 struct HeadArgs {
   const float* hidden;   // [rows][D]
   const float* wmu;      // [N][D]
@@ -37,6 +42,8 @@ struct HeadArgs {
   float* rate;           // [rows][N]
   float* disp;
   int* bad;              // |= 1 if a rate is not finite-positive, |= 2 for a dispersion
+  float* sig_mu;         // optional [rows][N] (both or neither, ftn_head_fit_forward): softplus' derivative at the two
+  float* sig_sg;         // pre-activations, for the heads' backward (headfit.hip)
   long long rows, tail_bs, late_bs;
   int S, D, N, hist;
   float floor_s;

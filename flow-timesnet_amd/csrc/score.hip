@@ -38,15 +38,8 @@ __device__ inline void sc_element(float y, float rate, float disp, bool m, float
   ll = 0.f;
   term = 0.f;
   if (valid) {
-    const double r = sc_rcp((double)al), t = (double)al * (double)mu;      // the product of two floats is exact
-    double xa = (double)yc + r, xr = r, xc = (double)yc + 1.0, pa = 1.0, pr = 1.0, pc = 1.0;
-    sc_shift(xa, pa);
-    sc_shift(xr, pr);
-    sc_shift(xc, pc);
-    double g = sc_stirling(xa) - sc_stirling(xr) - sc_stirling(xc);
-    if (pa != 1.0 || pr != 1.0 || pc != 1.0) g += sc_log(pr * pc * sc_rcp(pa));
-    // log alpha + log mu - log1p(alpha mu) = -log1p(1 / (alpha mu))
-    const double v = g - r * sc_log1p(t) - (double)yc * sc_log1p(sc_rcp(t));
+    double l1p;                                                 // the product of two floats is exact
+    const double v = sc_nb_ll((double)yc, sc_rcp((double)al), (double)al * (double)mu, l1p);
     ll = (float)v;
   }
   if (counts) {

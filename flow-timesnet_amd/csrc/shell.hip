@@ -132,6 +132,14 @@ __global__ __launch_bounds__(256) void k_head(HeadArgs a) {
         for (int r = 0; r < 4; ++r)
           if (nl0 + 16 * o + r < a.N) { rp[r] = rt[r]; dq[r] = dp[r]; }
       }
+      if (a.sig_mu) {                                         // the refit's forward keeps softplus' derivatives
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (nl0 + 16 * o + r < a.N) {
+            a.sig_mu[rr * a.N + nl0 + 16 * o + r] = sigmoid20(pre[r]);
+            a.sig_sg[rr * a.N + nl0 + 16 * o + r] = sigmoid20(as[o][r] + bs[r]);
+          }
+      }
     }
   }
   if (badbits) atomicOr(a.bad, badbits);
@@ -238,6 +246,13 @@ __global__ __launch_bounds__(256, 3) void k_head_bf(HeadArgs a) {
       if (!rok || nl0 + 16 * o >= a.N) continue;
       __builtin_nontemporal_store(rt, (f4*)(a.rate + rr * a.N + nl0 + 16 * o));
       __builtin_nontemporal_store(dp, (f4*)(a.disp + rr * a.N + nl0 + 16 * o));
+      if (a.sig_mu) {                                         // the refit's forward keeps softplus' derivatives
+        f4 sm, ss;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { sm[r] = sigmoid20(pre[r]); ss[r] = sigmoid20(as[o][r] + bs[r]); }
+        *(f4*)(a.sig_mu + rr * a.N + nl0 + 16 * o) = sm;
+        *(f4*)(a.sig_sg + rr * a.N + nl0 + 16 * o) = ss;
+      }
     }
   }
   if (badbits) atomicOr(a.bad, badbits);

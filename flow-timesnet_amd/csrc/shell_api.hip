@@ -34,6 +34,7 @@ static int head_entry(const char* who, const ShellWidth& w, const float* hidden,
   HeadArgs a;
   a.hidden = hidden; a.wmu = wmu; a.bmu = bmu; a.wsg = wsg; a.bsg = bsg;
   a.tail = tail; a.late = late; a.floorv = floorv; a.rate = rate; a.disp = disp; a.bad = bad;
+  a.sig_mu = a.sig_sg = nullptr;
   a.rows = rows; a.tail_bs = tail_bs; a.late_bs = late_bs;
   a.S = S; a.D = D; a.N = N; a.hist = hist; a.floor_s = floor_s;
   return (w.wide ? head_wide_launch : head_launch)(a, (hipStream_t)stream);

@@ -332,6 +332,14 @@ __device__ __forceinline__ int head_wide_finish(const HeadArgs& a, f4 mu, f4 sg,
     for (int r = 0; r < 4; ++r)
       if (n + r < a.N) { rp[r] = rt[r]; dq[r] = dp[r]; }
   }
+  if (a.sig_mu) {                                           // the refit's forward keeps softplus' derivatives
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (n + r < a.N) {
+        a.sig_mu[row * a.N + n + r] = sigmoid20(pre[r]);
+        a.sig_sg[row * a.N + n + r] = sigmoid20(sg[r] + bs[r]);
+      }
+  }
   return badbits;
 }
 

@@ -52,6 +52,8 @@ class FtnScorePart(C.Structure):
 
 SCORE_PART_BYTES = C.sizeof(FtnScorePart)
 FTN_QMAX = 8
+FTN_NBG_PARTS_MAX = 1024
+FTN_HEADFIT_COLSUM, FTN_HEADFIT_MFMA, FTN_HEADFIT_CHUNKS_MAX = 1, 2, 256
 FTN_NBQ_RANGE = 2
 FTN_PATHS_MAX = 1024
 FTN_PATH_SUM, FTN_PATH_MAX = 0, 1
@@ -292,6 +294,17 @@ _SIGNATURES = {
     "ftn_score_columns": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, _P, C.c_int, C.c_float,
                                     C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "ftn_score_fold": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P]),
+    # head refit (csrc/headfit.hip)
+    "ftn_nb_nll_grad_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
+    "ftn_nb_nll_grad_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ftn_nb_nll_grad": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, _P, C.c_int, C.c_float,
+                                  C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_size_t, C.c_int, _P]),
+    "ftn_head_backward_form": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int]),
+    "ftn_head_backward_workspace": (C.c_size_t, [C.c_longlong, C.c_int, C.c_int]),
+    "ftn_head_fit_forward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_longlong,
+                                       C.c_int, _P, C.c_longlong, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
+    "ftn_head_backward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                    _P, _P, C.c_size_t, _P]),
     "ftn_nbq_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_nb_cdf": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
                              C.c_float, _P, _P, _P, _P]),

@@ -9,9 +9,10 @@ heads - each of which calls the HIP entry point for its stage when the tensors l
 (``ftn_embed_forward``, the TimesBlock kernels with the LayerNorm epilogue, ``ftn_timeproj_forward``,
 ``ftn_head_forward``) and composes stock torch ops otherwise (CPU tensors, autograd, dropout in training).
 
-Each stage has one body, and three callers compose them: the plain forward (``_forward_once``), the device recursive
-forecaster (``forecast.py``) and the series-sharded forward (``dist.SeriesShardedTimesNet``, through the thin
-``series_*`` entry points, which hand the same bodies this rank's slices):
+Each stage has one body, and four callers compose them: the plain forward (``_forward_once``), the device recursive
+forecaster (``forecast.py``), the series-sharded forward (``dist.SeriesShardedTimesNet``, through the thin
+``series_*`` entry points, which hand the same bodies this rank's slices) and ``head_inputs``, which stops before the
+heads for a refit of them (``fit.refit_heads``):
 
 * context rows - ``_rows_of`` (``_context_rows`` / ``series_context_rows`` resolve the ids their own way);
 * embedding - ``_context_terms``, then ``_through_weight`` + ``_embed_epilogue`` (HIP) or ``_with_context`` (torch);
@@ -985,3 +986,30 @@ class TimesNet(nn.Module):
         rows = self._context_rows(window, series_static, series_ids)
         seq = self._stack(self._embed(window, mark, rows))
         return self._heads(seq, window, rows, self._out_steps)
+
+    def head_inputs(self, x: torch.Tensor, x_mark: Optional[torch.Tensor] = None,
+                    series_static: Optional[torch.Tensor] = None, series_ids: Optional[torch.Tensor] = None):
+        """What the rate / dispersion heads read, for a refit of the heads alone (``fit.refit_heads``): the stage
+        bodies of ``forward`` up to ``_time_projection`` under ``no_grad``, so the frozen backbone takes the path an
+        inference forward takes even while the head parameters require grad.  Returns ``(hidden, tail, hist, late,
+        floor)``: ``hidden [B, steps, d_model]``, ``tail`` the last ``hist`` rows of the input window (a view),
+        ``late`` the gated late bias ``[1|B, steps, N]`` or None, ``floor`` ``min_sigma_vector`` flattened or None
+        (the scalar ``min_sigma`` applies).  Nothing is recorded for autograd."""
+        def once():
+            L = self.input_len
+            if x.dim() != 3 or x.size(1) < L:
+                raise ValueError(f"TimesNet expects input shaped [B, T >= {L}, N]")
+            window = x.narrow(1, x.size(1) - L, L)
+            mark = None if x_mark is None else x_mark.narrow(1, x_mark.size(1) - L, L)
+            self._ensure_embedding(window, mark, series_static, series_ids)
+            rows = self._context_rows(window, series_static, series_ids)
+            seq = self._stack(self._embed(window, mark, rows))
+            steps = self._out_steps
+            hidden = self._time_projection(seq, steps, self._hip_heads_ok(seq, window))
+            hist = min(steps, window.size(1))
+            late, floor = self._late_bias(rows), self._floor_vector()
+            return (hidden, window[:, -hist:, :], hist, None if late is None else late.detach(),
+                    None if floor is None else floor.detach().reshape(-1))
+
+        with torch.no_grad():
+            return range_guard.repeat_on_trip(self.blocks, once, message="TimesNet: " + range_guard.MESSAGE)

@@ -988,6 +988,113 @@ def score_fold(part: torch.Tensor, B: int, N: int, acc: torch.Tensor, err: torch
           "ftn_score_fold")
 
 
+# ------------------------------------------------------------------ head refit
+def nb_nll_grad_form_of(B: int, H: int, N: int, strides=(0, 0, 0), misalign_or: int = 0) -> Tuple[str, int]:
+    """The kernel ``ftn_nb_nll_grad`` runs (``ftn_nb_nll_grad_form``, host-only) and the workgroups of its grid:
+    ``("k_nb_grad<4>" | "k_nb_grad<1>", nparts)`` - the vector form needs ``H N % 4 == 0``, batch ``strides`` that are
+    multiples of 4 and ``misalign_or == 0``."""
+    f = _form("ftn_nb_nll_grad_form", B, H, N, strides[0], strides[1], strides[2], misalign_or)
+    return f"k_nb_grad<{4 if f & 2 else 1}>", f >> 4
+
+
+def nb_nll_grad_form(y, rate, disp, mask=None, g_rate=None, g_disp=None) -> Tuple[str, int]:
+    """``nb_nll_grad_form_of`` for the tensors ``nb_nll_grad`` is given (fresh outputs are aligned)."""
+    B, H, N = y.shape
+    _, kind = _score_mask(mask, y)
+    mis = _score_misalign(y, rate, disp, mask, kind, g_rate) | ((_ptr(g_disp) & 15) if g_disp is not None else 0)
+    return nb_nll_grad_form_of(B, H, N, [t.stride(0) if B > 1 else 0 for t in (y, rate, disp)], mis)
+
+
+def nb_nll_grad(y: torch.Tensor, rate: torch.Tensor, disp: torch.Tensor, mask=None, eps: float = 1e-8,
+                scaled: bool = True, g_rate: torch.Tensor | None = None, g_disp: torch.Tensor | None = None):
+    """``ftn_nb_nll_grad`` over ``y``, ``rate``, ``disp`` [B,H,N] and an optional mask (the operands of
+    ``score_columns``).  Returns ``(words, g_rate, g_disp)``: ``words`` two fp32 on the device, the loss and the scale
+    ``-1 / max(valid, 1)``; the gradients of the loss when ``scaled``, else the raw derivatives of the log-likelihood.
+    ``g_rate`` / ``g_disp`` may be the caller's (contiguous fp32 [B,H,N]).  Enqueues only."""
+    lib = _lib.load()
+    B, H, N = _bhn_operands("nb_nll_grad", (("y", y), ("rate", rate), ("dispersion", disp)))
+    mask, kind = _score_mask(mask, y)
+    g_rate = _out_or_fresh("nb_nll_grad", g_rate, (B, H, N), y, "g_rate")
+    g_disp = _out_or_fresh("nb_nll_grad", g_disp, (B, H, N), y, "g_disp")
+    need = lib.ftn_nb_nll_grad_workspace(B, H, N)
+    if need == 0:
+        raise ValueError(f"nb_nll_grad: ftn_nb_nll_grad_workspace rejected the shape {(B, H, N)}")
+    workspace = _workspace(y.device, need)
+    words = torch.empty(2, dtype=torch.float32, device=y.device)
+    check(lib.ftn_nb_nll_grad(_ptr(y), y.stride(0), _ptr(rate), rate.stride(0), _ptr(disp), disp.stride(0),
+                              _ptr_or_null(mask), kind, float(eps), B, H, N, _ptr(g_rate), _ptr(g_disp), _ptr(words),
+                              _ptr(workspace), workspace.numel(), int(bool(scaled)), _stream(y.device)),
+          "ftn_nb_nll_grad")
+    return words, g_rate, g_disp
+
+
+def head_backward_form_of(R: int, N: int, D: int, misalign_or: int = 0) -> Tuple[str, int]:
+    """The kernel ``ftn_head_backward`` runs (``ftn_head_backward_form``, host-only) and its row chunks:
+    ``("k_headfit_colsum<N>" | "k_headfit_mfma", chunks)`` - the column sums for ``N <= 4`` and a ``hidden`` on the
+    16-byte grid."""
+    f = _form("ftn_head_backward_form", R, N, D, misalign_or)
+    return (f"k_headfit_colsum<{N}>" if f & 15 == _lib.FTN_HEADFIT_COLSUM else "k_headfit_mfma"), f >> 4
+
+
+def head_fit_forward(hidden: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor, w_sigma: torch.Tensor,
+                     b_sigma: torch.Tensor, tail: torch.Tensor, hist: int, late, floor_vec, floor_scalar: float):
+    """``head_forward``'s operands through ``ftn_head_fit_forward``: ``(rate, dispersion, sig_mu, sig_sigma, bad)``
+    with ``sig_*`` [B,S,N] softplus' derivative at the two pre-activations."""
+    lib = _lib.load()
+    B, S, D = hidden.shape
+    N = w_mu.shape[0]
+    if tail.stride(2) != 1 or tail.stride(1) != N or tail.shape != (B, hist, N):
+        raise ValueError("tail must be a [B, hist, N] view with contiguous rows")
+    if late is not None and (late.shape[-2:] != (S, N) or not late.is_contiguous()):
+        raise ValueError("late bias must be contiguous [1|B, S, N]")
+    if not hidden.is_contiguous():
+        raise ValueError("hidden must be contiguous [B, S, D]")
+    dev = hidden.device
+    rate, disp, sig_mu, sig_sg = (torch.empty(B, S, N, dtype=torch.float32, device=dev) for _ in range(4))
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib.ftn_head_fit_forward(_ptr(hidden), B * S, S, D, N, _ptr(w_mu), _ptr(b_mu), _ptr(w_sigma), _ptr(b_sigma),
+                                   _ptr(tail), tail.stride(0) if B > 1 else 0, int(hist), _ptr_or_null(late),
+                                   _batch_stride(late, B), _ptr_or_null(floor_vec), float(floor_scalar), _ptr(rate),
+                                   _ptr(disp), _ptr(sig_mu), _ptr(sig_sg), _ptr(bad), _stream(dev)),
+          "ftn_head_fit_forward")
+    return rate, disp, sig_mu, sig_sg, bad
+
+
+def head_backward(hidden: torch.Tensor, g_rate: torch.Tensor, g_disp: torch.Tensor, sig_mu: torch.Tensor,
+                  sig_sigma: torch.Tensor, scale: torch.Tensor, w_mu=None, w_sigma=None, want_hidden: bool = False):
+    """``ftn_head_backward``: ``hidden`` [R, D] (or [B,S,D]) with contiguous rows, the raw derivatives and sigmoids
+    [R, N] contiguous, ``scale`` one fp32 device word.  Returns ``(dW_mu, db_mu, dW_sigma, db_sigma, d_hidden)``
+    (``d_hidden`` None unless ``want_hidden``, which needs both weights).  Enqueues only."""
+    lib = _lib.load()
+    D = hidden.shape[-1]
+    R = hidden.numel() // D
+    N = g_rate.numel() // R
+    ops = (("g_rate", g_rate), ("g_disp", g_disp), ("sig_mu", sig_mu), ("sig_sigma", sig_sigma))
+    if hidden.dtype != torch.float32 or not hidden.is_cuda or hidden.stride(-1) != 1 or (
+            hidden.dim() > 1 and not hidden.reshape(R, D).stride(0) == D):
+        raise ValueError("head_backward: hidden must be an fp32 device tensor with contiguous rows D apart")
+    for name, t in ops:
+        if t.dtype != torch.float32 or t.device != hidden.device or not t.is_contiguous() or t.numel() != R * N:
+            raise ValueError(f"head_backward: {name} must be contiguous fp32 [{R}, {N}] beside hidden")
+    if scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != hidden.device:
+        raise ValueError("head_backward: scale must be one fp32 word beside hidden")
+    if want_hidden and (w_mu is None or w_sigma is None):
+        raise ValueError("head_backward: d_hidden needs both weights")
+    dev = hidden.device
+    dw_mu, dw_sg = (torch.empty(N, D, dtype=torch.float32, device=dev) for _ in range(2))
+    db_mu, db_sg = (torch.empty(N, dtype=torch.float32, device=dev) for _ in range(2))
+    d_hidden = torch.empty(R, D, dtype=torch.float32, device=dev).view(hidden.shape) if want_hidden else None
+    need = lib.ftn_head_backward_workspace(R, N, D)
+    if need == 0:
+        raise ValueError(f"head_backward: ftn_head_backward_workspace rejected R={R} N={N} d_model={D}")
+    ws = _workspace(dev, need)
+    check(lib.ftn_head_backward(_ptr(hidden), R, N, D, _ptr(g_rate), _ptr(g_disp), _ptr(sig_mu), _ptr(sig_sigma),
+                                _ptr(scale), _ptr_or_null(w_mu), _ptr_or_null(w_sigma), _ptr(dw_mu), _ptr(db_mu),
+                                _ptr(dw_sg), _ptr(db_sg), _ptr_or_null(d_hidden), _ptr(ws), ws.numel(), _stream(dev)),
+          "ftn_head_backward")
+    return dw_mu, db_mu, dw_sg, db_sg, d_hidden
+
+
 # ------------------------------------------------------------------ NB CDF and quantiles
 def nbq_form_of(N: int, strides=(0, 0, 0), misalign_or: int = 0) -> str:
     """The kernel form ``ftn_nb_cdf`` / ``ftn_nb_quantiles`` take (``ftn_nbq_form``, host-only: the launches dispatch

@@ -4,8 +4,9 @@ What the reference does to the wide table ``[T, N]`` between the CSV and the loa
 model, without host arithmetic: ``series_features`` (``compute_series_features``, utils/static_features.py:17-103),
 ``SeriesScaler.fit`` (``fit_series_scaler``, utils/io.py:548-597, after ``clip_negative``, train.py:834),
 ``SeriesScaler.transform`` (``_transform_dataframe``, train.py:569-592) and ``SeriesScaler.inverse``
-(``inverse_transform`` and the clip at 0, utils/io.py:600-621, predict.py:959-961).  ``holdout_rows`` and
-``rolling_rows`` are the row ranges of data/split.py:7-33: a fold is a row slice of the device table, passed in place.
+(``inverse_transform`` and the clip at 0, utils/io.py:600-621, predict.py:959-961).  ``min_sigma`` is the variability
+summary behind the dispersion floor (``_masked_std``, train.py:447-566).  ``holdout_rows`` and ``rolling_rows`` are the
+row ranges of data/split.py:7-33: a fold is a row slice of the device table, passed in place.
 Calendar features, CSV and schema I/O, pivoting and pickled artefacts stay on the host.
 
 Backends: ``torch`` is the reference's numpy restated line by line on CPU tensors (the reductions run in numpy itself,
@@ -130,6 +131,86 @@ def series_features(values, mask=None, backend: Optional[str] = None) -> torch.T
         v = X.detach().cpu().numpy()
         m = np.ones_like(v) if M is None else M.detach().cpu().numpy()
         out = torch.from_numpy(_features_numpy(v, m)).to(X.device)
+    _ran(be)
+    return out
+
+
+MIN_SIGMA_METHODS = ("global", "per_series_median")
+
+
+def _masked_std_numpy(values: np.ndarray, mask: Optional[np.ndarray], method: str):
+    """train.py:472-564 for one table, line by line: ``(std, per-series std)``; the per-series vector also for
+    ``"global"`` (the reference returns None there)."""
+    n_series = values.shape[1]
+    per_series = np.zeros(n_series, dtype=np.float64)
+    if values.size == 0:                                                             # :482, :512
+        return 0.0, per_series
+    mask_bool = np.ones(values.shape, dtype=bool) if mask is None else mask > 0.0    # :487, :521-526
+    if not np.any(mask_bool):                                                        # :488, :527
+        return 0.0, per_series
+    arr64 = values.astype(np.float64, copy=False)
+    mask_float = mask_bool.astype(np.float64, copy=False)
+    per_sum = (arr64 * mask_float).sum(axis=0)                                       # :541-543
+    per_sum_sq = (np.square(arr64) * mask_float).sum(axis=0)
+    per_count = mask_float.sum(axis=0)
+    valid_series = per_count > 0.0                                                   # :548-560
+    means = np.zeros_like(per_sum)
+    means[valid_series] = per_sum[valid_series] / per_count[valid_series]
+    variances = np.zeros_like(per_sum)
+    variances[valid_series] = np.maximum(per_sum_sq[valid_series] / per_count[valid_series] - means[valid_series] ** 2,
+                                         0.0)
+    per_series[valid_series] = np.sqrt(variances[valid_series])
+    if method == "per_series_median":
+        return float(np.median(per_series[valid_series])), per_series                # :561-564
+    values64 = arr64[mask_bool]                                                      # :490-503
+    total, total_sq, count = float(values64.sum()), float(np.square(values64).sum()), int(values64.size)
+    mean = total / count
+    return float(np.sqrt(max(total_sq / count - mean * mean, 0.0))), per_series
+
+
+def min_sigma(values, mask=None, method: str = "global", backend: Optional[str] = None):
+    """The reference's variability summary behind the dispersion floor (``_masked_std``, train.py:447-566) of the wide
+    table ``values`` [T, N] with validity ``mask`` (``> 0``; None: every element counts): ``(std, per_series)``, a
+    0-dim fp64 tensor and the per-series standard deviations fp64 ``[N]`` (0 for a series without a valid point), on
+    the table's device.  ``method``: ``"global"``, one standard deviation over all valid points, or
+    ``"per_series_median"``, the median of the per-series ones over the series that have a valid point.  The floor
+    itself is the caller's ``max(min_sigma, std * scale)`` (train.py:990-1001), and ``per_series * scale`` under the
+    same maximum refreshes ``min_sigma_vector``.  ``hip``: ``ftn_table_moments`` and a few torch ops on its [6, N]
+    statistics, no synchronisation.  Its centred sums square differences that were formed in fp32, so a standard
+    deviation is within ``2^-24`` relative of the reference's fp64 value (which subtracts ``mean^2`` from the mean
+    square)."""
+    if method not in MIN_SIGMA_METHODS:
+        raise ValueError(f"Unsupported min_sigma_method {method!r}. Expected 'global' or 'per_series_median'.")
+    X = _table(values, "values")
+    M = None if mask is None else _table(mask, "mask", X.device)
+    if M is not None and M.shape != X.shape:
+        raise ValueError("values and mask must have the same shape")
+    be = _backend(X, backend)
+    T, N = X.shape
+    if be == "torch" or T == 0 or N == 0:
+        std, per = _masked_std_numpy(X.detach().cpu().numpy(), None if M is None else M.detach().cpu().numpy(), method)
+        out = torch.tensor(std, dtype=torch.float64, device=X.device), torch.from_numpy(per).to(X.device)
+    else:
+        from . import runtime as rt
+
+        count, total, mean32, css = rt.table_moments(X, M)[:4]
+        has = count > 0
+        safe = torch.clamp(count, min=1.0)
+        zero = torch.zeros_like(css)
+        mean = torch.where(has, total / safe, zero)
+        # css is centred on the fp32 mean: sum (v - m32)^2 = sum (v - m)^2 + count (m - m32)^2
+        m2 = torch.where(has, torch.clamp(css - count * (mean - mean32) ** 2, min=0.0), zero)
+        per = torch.sqrt(m2 / safe)
+        if method == "global":
+            n = torch.clamp(count.sum(), min=1.0)
+            centre = torch.where(has, total, zero).sum() / n
+            std = torch.sqrt((m2.sum() + (count * (mean - centre) ** 2).sum()) / n)
+        else:                                                   # np.median over the k valid series, k on the device
+            ranked = torch.sort(torch.where(has, per, torch.full_like(per, float("inf")))).values
+            k = has.sum()
+            mid = torch.stack([torch.clamp(k - 1, min=0) // 2, k // 2])
+            std = torch.where(k > 0, ranked[mid].mean(), torch.zeros((), dtype=per.dtype, device=per.device))
+        out = std, per
     _ran(be)
     return out
 

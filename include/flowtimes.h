@@ -671,6 +671,78 @@ int ftn_score_fold(const FtnScorePart* part_dev, int B, int N, int ids_kind, con
                    const long long* order_dev, const long long* seg_start_dev, FtnScorePart* acc_dev, int n_slots,
                    int* err_dev, void* stream);
 
+/* ---- refitting the heads: the gradient of that likelihood (losses.py:27-58 under autograd; csrc/headfit.hip) ----
+ * Additions only: FTN_ABI_VERSION stays 14.
+ *
+ * ftn_nb_nll_grad: operands, mask, clamps and validity as ftn_score_columns.  Per element it writes the derivatives
+ * of the LOG-likelihood (contiguous fp32 [B][H][N]):
+ *   g_rate = (yc - mu) / (mu (1 + alpha mu))
+ *   g_disp = (log1p(alpha mu) - [psi(yc + 1/alpha) - psi(1/alpha)]) / alpha^2 + (yc - mu) / (alpha (1 + alpha mu))
+ * evaluated in fp64 and rounded once; the digamma difference is sc_dpsi (csrc/ftn_nbmath.h, 5e-12 relative), never
+ * two digammas subtracted.  g_rate is 0 where rate < eps and g_disp is 0 where dispersion < eps (the clamp is
+ * active); an element that is masked out or not finite gets two exact zeros and adds nothing to the sums.
+ * Two launches.  k_nb_grad<V>: a grid of nparts <= FTN_NBG_PARTS_MAX workgroups of 256 walks the elements and leaves
+ * in the workspace, per workgroup, the fp64 sums of ll and of the valid count.  k_nb_grad_fold: adds them in
+ * ascending order and writes
+ *   loss_dev[0] = -sum ll / max(count, 1)          loss_dev[1] = -1 / max(count, 1)
+ * and, with scaled = 1, multiplies g_rate and g_disp by loss_dev[1] in place: they are then the gradients of the
+ * loss.  With scaled = 0 the derivatives stay raw and a later kernel applies the device word.  Nothing synchronises,
+ * there are no atomics, and every sum's order is a function of the shape alone; the workspace may hold anything.
+ * ftn_nb_nll_grad_workspace gives its bytes (0 for a bad shape).  H N and B N must fit an int32; g_rate and g_disp
+ * are distinct buffers that overlap no operand.
+ * ftn_nb_nll_grad_form (host-only; the launch dispatches through the same function):
+ *   bit 1      FTN_SHELL_VEC  k_nb_grad<4>: 16-byte loads and stores, four elements per lane (H N % 4 == 0, every
+ *              batch stride a multiple of 4, misalign_or == 0); otherwise k_nb_grad<1>
+ *   bits 4-14  nparts
+ * misalign_or: the OR of (address & 15) of y, rate, dispersion, g_rate, g_disp and an fp32 mask, and of
+ * (address & 3) << 2 of a uint8 mask. */
+#define FTN_NBG_PARTS_MAX 1024
+int ftn_nb_nll_grad_form(int B, int H, int N, long long y_bstride, long long rate_bstride, long long disp_bstride,
+                         int misalign_or);
+size_t ftn_nb_nll_grad_workspace(int B, int H, int N);
+int ftn_nb_nll_grad(const float* y_dev, long long y_bstride, const float* rate_dev, long long rate_bstride,
+                    const float* disp_dev, long long disp_bstride, const void* mask_dev, int mask_kind, float eps,
+                    int B, int H, int N, float* g_rate_dev, float* g_disp_dev, float* loss_dev, void* workspace_dev,
+                    size_t workspace_bytes, int scaled, void* stream);
+
+/* The heads for a refit (csrc/headfit.hip; additions only).  R = B S rows of hidden [R][D], D a multiple of 4 up to 512.
+ *
+ * ftn_head_fit_forward: ftn_head_forward / ftn_head_wide_forward (whichever takes D) with two more outputs - the same
+ * kernels, form choice and rate / dispersion bits, every operand 4-byte aligned - sig_mu / sig_sigma [R][N],
+ * 16-byte aligned: softplus' derivative at both pre-activations, sigmoid(t) for t <= 20 and 1 above (torch's softplus
+ * backward).  One launch.
+ *
+ * ftn_head_backward: with G_mu = g_rate sig_mu scale and G_sg = g_disp sig_sigma scale ([R][N]; g_* the raw
+ * derivatives of ftn_nb_nll_grad with scaled = 0, scale its device word loss_dev + 1; G_mu is also the late bias'
+ * gradient),
+ *   dW_mu[n][d] = sum_r G_mu[r][n] hidden[r][d]     db_mu[n] = sum_r G_mu[r][n]       (the same pair for sigma)
+ *   d_hidden    = G_mu W_mu + G_sg W_sigma          (when d_hidden is given; it needs both weights, 16-byte aligned)
+ * Rows are cut into chunks of 256 (of ceil(R / FTN_HEADFIT_CHUNKS_MAX), made even, beyond 256 chunks); a chunk's
+ * partial [2][N][D + 1] (column D: the bias) goes to the caller's workspace (ftn_head_backward_workspace bytes, 0 for
+ * a bad shape; whatever it held before) and a second kernel adds the chunks in ascending order: the same bits on
+ * every run.  ftn_head_backward_form (host-only; the launch dispatches through the same function):
+ *   bits 0-3   FTN_HEADFIT_COLSUM  N <= 4 and hidden 16-byte aligned: lanes own float4 columns of hidden and a
+ *                                  workgroup's row lanes are added in ascending order
+ *              FTN_HEADFIT_MFMA    otherwise: [32 n x 32 d] tiles on v_mfma_f32_32x32x2_f32, K = the chunk's rows
+ *   bits 4-12  the number of chunks
+ * misalign_or: (address & 15) of hidden. */
+#define FTN_HEADFIT_COLSUM 1
+#define FTN_HEADFIT_MFMA 2
+#define FTN_HEADFIT_CHUNKS_MAX 256
+int ftn_head_backward_form(long long R, int N, int D, int misalign_or);
+size_t ftn_head_backward_workspace(long long R, int N, int D);
+int ftn_head_fit_forward(const float* hidden_dev, long long rows, int S, int D, int N, const float* w_mu_dev,
+                         const float* b_mu_dev, const float* w_sigma_dev, const float* b_sigma_dev,
+                         const float* tail_dev, long long tail_bstride, int hist, const float* late_dev_or_null,
+                         long long late_bstride, const float* floor_vec_dev_or_null, float floor_scalar,
+                         float* rate_dev, float* disp_dev, float* sig_mu_dev, float* sig_sigma_dev, int* bad_flag_dev,
+                         void* stream);
+int ftn_head_backward(const float* hidden_dev, long long R, int N, int D, const float* g_rate_dev,
+                      const float* g_disp_dev, const float* sig_mu_dev, const float* sig_sigma_dev,
+                      const float* scale_dev, const float* w_mu_dev, const float* w_sigma_dev, float* dw_mu_dev,
+                      float* db_mu_dev, float* dw_sigma_dev, float* db_sigma_dev, float* d_hidden_dev_or_null,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- using the forecast's distribution: NB CDF and quantiles (no counterpart in the reference) -----------
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
  *
