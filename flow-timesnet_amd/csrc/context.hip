@@ -439,7 +439,7 @@ static int embed_add_form(int D, long long qc_bs, long long qb_bs, unsigned misa
 }
 
 extern "C" int ftn_embed_add_form(int D, long long q_coeff_bstride, long long q_bias_bstride, int misalign_or) {
-  FTN_CHECK_ARG(D >= 4 && D <= ADD_DMAX && D % 4 == 0 && misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0,
+  FTN_CHECK_ARG(D >= 4 && D <= ADD_DMAX && D % 4 == 0 && misalign_ok(misalign_or),
                 "ftn_embed_add_form: d_model=%d misalign=%d", D, misalign_or);
   return embed_add_form(D, q_coeff_bstride, q_bias_bstride, (unsigned)misalign_or);
 }

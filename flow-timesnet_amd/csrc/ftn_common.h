@@ -31,6 +31,7 @@ unsigned long long* ftn_stamp_buf(int which_bit, size_t* cap);
 
 static inline int ftn_pad16(int v) { return (v + 15) & ~15; }
 static inline int ftn_cdiv(int a, int b) { return (a + b - 1) / b; }
+static inline bool misalign_ok(int m) { return m >= 0 && m < 16 && m % 4 == 0; }   // a *_form entry's misalign_or
 
 // The vector-load rule of the [B][H][N] scoring kernels (score.hip, quantile.hip, sample.hip): a lane may take 4
 // series with one 16-byte load when N and every batch stride are multiples of 4 and no operand is off 16 bytes.

@@ -13,18 +13,18 @@
 //            zero word that ends every staged row - a sum that starts at +0.0 is never -0.0, so adding +0.0 changes
 //            no bit and the walk has no branch;
 //   combines one thread per (row, group), group fastest: that group's chunk sums in ascending order, rounded, stored.
-// Neither the tile height, the grid nor the load width enters a group's sum.  What the kernel reads from the device
-// CSR is clamped (offsets to 0 .. M, a member outside 0 .. N - 1 to the zero word), so a CSR that disagrees with the
-// validated host copy cannot address anything outside x, order and out.
-#include "ftn_common.h"
+// Neither the tile height, the grid nor the load width enters a group's sum.  The device CSR is read through
+// ftn_groups.h alone, which clamps what it reads, and a member outside 0 .. N - 1 points at the zero word, so a CSR
+// that disagrees with the validated host copy cannot address anything outside x, order, out and the workgroup's LDS.
+#include "ftn_groups.h"
 
 #define GS_THREADS 256
 #define GS_GRID_MAX 1024
 
 struct GroupArgs {
-  const float* x;  const int* order;  const int* offsets;  float* out;
+  const float* x;  float* out;  FtnGroupCsr csr;
   long long rows, stride, tiles;
-  int N, G, M, C, T, pitch, clsh;   // C chunks in all, T rows a tile, pitch words a staged row, 2^clsh lanes along chunks
+  int N, T, pitch, clsh;            // T rows a tile, pitch words a staged row, 2^clsh lanes along chunks
 };
 
 static inline int gs_pitch(int N) { return N + (N >> 5) + 1; }
@@ -38,29 +38,12 @@ static inline int group_form(int N, long long stride, unsigned misalign, int C) 
   return (vec ? FTN_SHELL_VEC : 0) | (int)T << 8;
 }
 
-__device__ __forceinline__ int gs_offset(const GroupArgs& a, int g) {
-  const int o = a.offsets[g];
-  return o < 0 ? 0 : o > a.M ? a.M : o;
-}
-__device__ __forceinline__ int gs_chunks(const GroupArgs& a, int g) {
-  const int m = gs_offset(a, g + 1) - gs_offset(a, g);
-  return m > 0 ? (m + FTN_GROUP_CHUNK - 1) / FTN_GROUP_CHUNK : 0;
-}
-
 // the LDS words (relative to a staged row) of chunk c's members; slots beyond its end are the row's zero word
 __device__ __forceinline__ void gs_members(const GroupArgs& a, const int* cfirst, int c, int (&pos)[FTN_GROUP_CHUNK]) {
-  int lo = 0, hi = a.G;                                         // the first g with cfirst[g] > c; cfirst[0] = 0 <= c
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (cfirst[mid] <= c) lo = mid + 1;
-    else hi = mid;
-  }
-  const int g = lo - 1;
-  const int start = gs_offset(a, g) + (c - cfirst[g]) * FTN_GROUP_CHUNK;
-  const int len = gs_offset(a, g + 1) - start;
+  const FtnGroupChunk k = ftn_csr_chunk(a.csr, cfirst, c);
 #pragma unroll
   for (int j = 0; j < FTN_GROUP_CHUNK; ++j) {
-    const int i = j < len ? a.order[start + j] : -1;
+    const int i = j < k.len ? a.csr.order[k.start + j] : -1;
     pos[j] = (unsigned)i < (unsigned)a.N ? i + (i >> 5) : a.pitch - 1;
   }
 }
@@ -72,7 +55,7 @@ __device__ __forceinline__ void gs_sums(const GroupArgs& a, const float* rowsm, 
     double acc = 0.0;
 #pragma unroll
     for (int j = 0; j < FTN_GROUP_CHUNK; ++j) acc += (double)row[pos[j]];
-    csum[r * a.C + c] = acc;
+    csum[r * a.csr.C + c] = acc;
   }
 }
 
@@ -91,33 +74,18 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sum(GroupArgs a) {
   constexpr int W = VEC ? 4 : 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char gs_lds[];
   double* csum = (double*)gs_lds;                               // [T][C]
-  int* cfirst = (int*)(csum + (size_t)a.T * a.C);               // [G + 1]
-  int* part = cfirst + a.G + 1;                                 // [GS_THREADS]
+  int* cfirst = (int*)(csum + (size_t)a.T * a.csr.C);           // [G + 1]
+  int* part = cfirst + a.csr.G + 1;                             // [GS_THREADS]
   float* rowsm = (float*)(part + GS_THREADS);                   // [T][pitch]
   const int tid = threadIdx.x;
 
-  {                                                             // cfirst: thread -> `per` consecutive groups
-    const int per = (a.G + GS_THREADS - 1) / GS_THREADS;
-    const int g0 = tid * per < a.G ? tid * per : a.G, g1 = g0 + per < a.G ? g0 + per : a.G;
-    int s = 0;
-    for (int g = g0; g < g1; ++g) s += gs_chunks(a, g);
-    part[tid] = s;
-    __syncthreads();
-    int base = 0;
-    for (int u = 0; u < tid; ++u) base += part[u];
-    for (int g = g0; g < g1; ++g) {
-      cfirst[g] = base;
-      base += gs_chunks(a, g);
-    }
-    if (tid == GS_THREADS - 1) cfirst[a.G] = base;
-    for (int r = tid; r < a.T; r += GS_THREADS) rowsm[r * a.pitch + a.pitch - 1] = 0.f;
-    __syncthreads();
-  }
+  for (int r = tid; r < a.T; r += GS_THREADS) rowsm[r * a.pitch + a.pitch - 1] = 0.f;
+  ftn_csr_first_wg(a.csr, GS_THREADS, part, cfirst);
 
   const int CL = 1 << a.clsh, cl = tid & (CL - 1), rg = tid >> a.clsh, RG = GS_THREADS >> a.clsh;
-  const bool once = a.C <= CL;                                  // every chunk has its lane: the members stay in registers
+  const bool once = a.csr.C <= CL;                          // every chunk has its lane: the members stay in registers
   int pos[FTN_GROUP_CHUNK];
-  if (once && cl < a.C) gs_members(a, cfirst, cl, pos);
+  if (once && cl < a.csr.C) gs_members(a, cfirst, cl, pos);
 
   // staging: 2^lsh lanes along a row, the rows r0, r0 + RS, ..
   const int nv = VEC ? a.N >> 2 : a.N;
@@ -135,20 +103,20 @@ __global__ __launch_bounds__(GS_THREADS) void k_group_sum(GroupArgs a) {
     }
     __syncthreads();
     if (once) {
-      if (cl < a.C) gs_sums(a, rowsm, csum, cl, rg, RG, live, pos);
+      if (cl < a.csr.C) gs_sums(a, rowsm, csum, cl, rg, RG, live, pos);
     } else {
-      for (int c = cl; c < a.C; c += CL) {
+      for (int c = cl; c < a.csr.C; c += CL) {
         gs_members(a, cfirst, c, pos);
         gs_sums(a, rowsm, csum, c, rg, RG, live, pos);
       }
     }
     __syncthreads();
-    for (int w = tid; w < live * a.G; w += GS_THREADS) {
-      const int r = w / a.G, g = w - r * a.G;
-      const double* s = csum + r * a.C;
+    for (int w = tid; w < live * a.csr.G; w += GS_THREADS) {
+      const int r = w / a.csr.G, g = w - r * a.csr.G;
+      const double* s = csum + r * a.csr.C;
       double acc = 0.0;
       for (int k = cfirst[g]; k < cfirst[g + 1]; ++k) acc += s[k];
-      a.out[(row0 + r) * a.G + g] = (float)acc;
+      a.out[(row0 + r) * a.csr.G + g] = (float)acc;
     }
   }
 }
@@ -163,8 +131,7 @@ static int group_form_check(const char* who, int N, long long row_stride, int n_
 
 extern "C" int ftn_group_sum_form(int N, long long row_stride, int misalign_or, int n_chunks) {
   if (group_form_check("ftn_group_sum_form", N, row_stride, n_chunks) < 0) return -1;
-  FTN_CHECK_ARG(misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0, "ftn_group_sum_form: misalign=%d",
-                misalign_or);
+  FTN_CHECK_ARG(misalign_ok(misalign_or), "ftn_group_sum_form: misalign=%d", misalign_or);
   return group_form(N, row_stride, (unsigned)misalign_or, n_chunks);
 }
 
@@ -172,32 +139,19 @@ extern "C" int ftn_group_sum(const float* x_dev, long long rows, int N, long lon
                              const int* offsets_dev, const int* offsets_host, int G, int M, float* out_dev,
                              void* stream) {
   const char* who = "ftn_group_sum";
-  FTN_CHECK_ARG(x_dev && out_dev && offsets_dev && offsets_host, "%s: null x, out or offsets", who);
-  const uintptr_t all = (uintptr_t)x_dev | (uintptr_t)out_dev | (uintptr_t)order_dev | (uintptr_t)offsets_dev |
-                        (uintptr_t)offsets_host;
-  FTN_CHECK_ARG((all & 3) == 0, "%s: operands must be 4-byte aligned", who);
-  FTN_CHECK_ARG(G >= 1 && G <= FTN_GROUP_GMAX, "%s: G=%d is outside 1..%d", who, G, FTN_GROUP_GMAX);
-  FTN_CHECK_ARG(M >= 0 && (M == 0 || order_dev), "%s: M=%d members need order", who, M);
-  FTN_CHECK_ARG(offsets_host[0] == 0 && offsets_host[G] == M, "%s: offsets run %d..%d, not 0..M=%d", who,
-                offsets_host[0], offsets_host[G], M);
-  long long chunks = 0;
-  for (int g = 0; g < G; ++g) {
-    const long long m = (long long)offsets_host[g + 1] - offsets_host[g];
-    FTN_CHECK_ARG(m >= 0, "%s: offsets decrease at group %d", who, g);
-    chunks += (m + FTN_GROUP_CHUNK - 1) / FTN_GROUP_CHUNK;
-  }
-  FTN_CHECK_ARG(chunks <= FTN_GROUP_CHUNKS_MAX, "%s: %lld chunks are above %d", who, chunks, FTN_GROUP_CHUNKS_MAX);
-  if (group_form_check(who, N, row_stride, (int)chunks) < 0) return -1;
+  int chunks = 0;
+  if (group_csr_check(who, x_dev, out_dev, order_dev, offsets_dev, offsets_host, G, M, &chunks) < 0) return -1;
+  if (group_form_check(who, N, row_stride, chunks) < 0) return -1;
   FTN_CHECK_ARG(rows >= 1 && rows <= (1LL << 62) / (row_stride > G ? row_stride : G),
                 "%s: rows=%lld with stride %lld and G=%d", who, rows, row_stride, G);
-  const int form = group_form(N, row_stride, (unsigned)((uintptr_t)x_dev & 15), (int)chunks);
+  const int form = group_form(N, row_stride, (unsigned)((uintptr_t)x_dev & 15), chunks);
   GroupArgs a = {};
-  a.x = x_dev; a.order = order_dev; a.offsets = offsets_dev; a.out = out_dev;
+  a.x = x_dev; a.out = out_dev; a.csr = {order_dev, offsets_dev, G, M, chunks};
   a.rows = rows; a.stride = row_stride;
-  a.N = N; a.G = G; a.M = M; a.C = (int)chunks; a.T = form >> 8; a.pitch = gs_pitch(N);
+  a.N = N; a.T = form >> 8; a.pitch = gs_pitch(N);
   a.tiles = (rows + a.T - 1) / a.T;
-  while ((1 << a.clsh) < a.C && a.clsh < 8) ++a.clsh;
-  const size_t lds = (size_t)a.T * ((size_t)a.C * 8 + (size_t)a.pitch * 4) + (size_t)(G + 1 + GS_THREADS) * 4;
+  while ((1 << a.clsh) < a.csr.C && a.clsh < 8) ++a.clsh;
+  const size_t lds = (size_t)a.T * ((size_t)a.csr.C * 8 + (size_t)a.pitch * 4) + (size_t)(G + 1 + GS_THREADS) * 4;
   FTN_CHECK_ARG(lds <= 65536, "%s: a tile of %d rows takes %zu bytes of LDS", who, a.T, lds);
   const dim3 grid((unsigned)(a.tiles < GS_GRID_MAX ? a.tiles : GS_GRID_MAX));
   hipStream_t st = (hipStream_t)stream;

@@ -21,19 +21,19 @@
 //            consecutive fp64 words of one csum row (one bank pair each) and store consecutive elements of out.
 //            Lanes of different groups in one 32-lane half read rows cfirst[g] TI words apart and can meet on a bank
 //            when TI < 32; the combine reads one word per 32 loaded elements, so the rows are left unpadded.
-// Neither TI, the passes, the grid, the load width, outer nor inner enters a column's sum.  What the kernel reads from
-// the device CSR is clamped (offsets to 0 .. M, the chunks to the host's count), so a CSR that disagrees with the
-// validated host copy cannot address anything outside x, order, out and the workgroup's LDS.
-#include "ftn_common.h"
+// Neither TI, the passes, the grid, the load width, outer nor inner enters a column's sum.  The device CSR is read
+// through ftn_groups.h alone, which clamps what it reads, and a member outside 0 .. S - 1 loads nothing, so a CSR that
+// disagrees with the validated host copy cannot address anything outside x, order, out and the workgroup's LDS.
+#include "ftn_groups.h"
 
 #define RS_THREADS 1024
 #define RS_GRID_MAX 2048
 #define RS_BATCH 16
 
 struct GroupRowsArgs {
-  const float* x;  const int* order;  const int* offsets;  float* out;
+  const float* x;  float* out;  FtnGroupCsr csr;
   long long inner, outer_stride, member_stride, tiles, work;    // tiles along inner; work = outer tiles
-  int S, G, M, C, TI, CP;                                       // C chunks in all, TI columns a tile, CP chunks a pass
+  int S, TI, CP;                                                // TI columns a tile, CP chunks a pass
 };
 
 // The form every entry point takes (include/flowtimes.h): the one place the choice is made.
@@ -45,15 +45,6 @@ static inline int group_rows_form(long long inner, long long member_stride, long
   const bool vec = inner % 4 == 0 && member_stride % 4 == 0 && outer_stride % 4 == 0 && (misalign & 15) == 0;
   const int CP = group_rows_pass((int)TI);
   return (vec ? FTN_SHELL_VEC : 0) | (int)TI << 8 | (C > CP ? (C + CP - 1) / CP : 1) << 16;
-}
-
-__device__ __forceinline__ int rs_offset(const GroupRowsArgs& a, int g) {
-  const int o = a.offsets[g];
-  return o < 0 ? 0 : o > a.M ? a.M : o;
-}
-__device__ __forceinline__ int rs_chunks(const GroupRowsArgs& a, int g) {
-  const int m = rs_offset(a, g + 1) - rs_offset(a, g);
-  return m > 0 ? (m + FTN_GROUP_CHUNK - 1) / FTN_GROUP_CHUNK : 0;
 }
 
 __device__ __forceinline__ void rs_add(double (&acc)[4], f4 v) {
@@ -73,25 +64,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_group_sum_rows(GroupRowsArgs a) 
   double* csum = (double*)rs_lds;                               // [CP][TI]
   double* carry = csum + (size_t)a.CP * a.TI;                   // [2][TI]
   int* cfirst = (int*)(carry + 2 * a.TI);                       // [G + 1]
-  int* part = cfirst + a.G + 1;                                 // [RS_THREADS]
-  const int tid = threadIdx.x;
-
-  {                                                             // cfirst: thread -> `per` consecutive groups
-    const int per = (a.G + RS_THREADS - 1) / RS_THREADS;
-    const int g0 = tid * per < a.G ? tid * per : a.G, g1 = g0 + per < a.G ? g0 + per : a.G;
-    int s = 0;
-    for (int g = g0; g < g1; ++g) s += rs_chunks(a, g);
-    part[tid] = s;
-    __syncthreads();
-    int base = 0;
-    for (int u = 0; u < tid; ++u) base += part[u];
-    for (int g = g0; g < g1; ++g) {
-      cfirst[g] = base;
-      base += rs_chunks(a, g);
-    }
-    if (tid == RS_THREADS - 1) cfirst[a.G] = base;
-    __syncthreads();
-  }
+  int* part = cfirst + a.csr.G + 1;                             // [RS_THREADS]
+  const int tid = threadIdx.x, G = a.csr.G, C = a.csr.C;
+  ftn_csr_first_wg(a.csr, RS_THREADS, part, cfirst);
 
   const int QI = a.TI / W;                                      // VEC: inner % 4 == 0, so TI % 4 == 0
   for (long long work = blockIdx.x; work < a.work; work += gridDim.x) {
@@ -99,22 +74,14 @@ __global__ __launch_bounds__(RS_THREADS) void k_group_sum_rows(GroupRowsArgs a) 
     const int live = a.inner - i0 < a.TI ? (int)(a.inner - i0) : a.TI;      // VEC: live % 4 == 0
     const int QL = live / W;
     const float* xb = a.x + o * a.outer_stride + i0;
-    float* ob = a.out + o * a.G * a.inner + i0;
+    float* ob = a.out + o * G * a.inner + i0;
     int pass = 0;
-    for (int c0 = 0; c0 < a.C || pass == 0; c0 += a.CP, ++pass) {           // with no chunk at all: one pass of +0
-      const int c1 = c0 + a.CP < a.C ? c0 + a.CP : a.C;
+    for (int c0 = 0; c0 < C || pass == 0; c0 += a.CP, ++pass) {             // with no chunk at all: one pass of +0
+      const int c1 = c0 + a.CP < C ? c0 + a.CP : C;
       for (int it = tid; it < (c1 - c0) * QI; it += RS_THREADS) {
-        const int cl = it / QI, col = (it - cl * QI) * W, c = c0 + cl;
+        const int cl = it / QI, col = (it - cl * QI) * W;
         if (col >= live) continue;
-        int lo = 0, hi = a.G;                                   // the first g with cfirst[g] > c; cfirst[0] = 0 <= c
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (cfirst[mid] <= c) lo = mid + 1;
-          else hi = mid;
-        }
-        const int g = lo - 1;
-        const int start = rs_offset(a, g) + (c - cfirst[g]) * FTN_GROUP_CHUNK;
-        const int len = rs_offset(a, g + 1) - start;
+        const FtnGroupChunk k = ftn_csr_chunk(a.csr, cfirst, c0 + cl);
         double acc[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) acc[w] = 0.0;
@@ -123,7 +90,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_group_sum_rows(GroupRowsArgs a) 
           Ld v[RS_BATCH];
 #pragma unroll
           for (int j = 0; j < RS_BATCH; ++j) {
-            const int s = j0 + j < len ? a.order[start + j0 + j] : -1;
+            const int s = j0 + j < k.len ? a.csr.order[k.start + j0 + j] : -1;
             v[j] = Ld(0.f);
             if ((unsigned)s < (unsigned)a.S) v[j] = *(const Ld*)(xb + (long long)s * a.member_stride + col);
           }
@@ -136,9 +103,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_group_sum_rows(GroupRowsArgs a) 
       __syncthreads();
       const double* cin = carry + ((pass & 1) ^ 1) * a.TI;
       double* cout = carry + (pass & 1) * a.TI;
-      for (int w = tid; w < a.G * QL; w += RS_THREADS) {
+      for (int w = tid; w < G * QL; w += RS_THREADS) {
         const int g = w / QL, col = (w - g * QL) * W;
-        const int s = cfirst[g] < a.C ? cfirst[g] : a.C, e = cfirst[g + 1] < a.C ? cfirst[g + 1] : a.C;
+        const int s = cfirst[g], e = cfirst[g + 1];
         const int k0 = s > c0 ? s : c0, k1 = s == e ? k0 : e < c1 ? e : c1;
         if (s == e ? pass != 0 : k0 >= k1) continue;            // an empty group: +0, stored by the first pass
         double acc[W];
@@ -173,8 +140,7 @@ static int group_rows_form_check(const char* who, long long inner, long long mem
 extern "C" int ftn_group_sum_rows_form(long long inner, long long member_stride, long long outer_stride,
                                        int misalign_or, int n_chunks) {
   if (group_rows_form_check("ftn_group_sum_rows_form", inner, member_stride, outer_stride, n_chunks) < 0) return -1;
-  FTN_CHECK_ARG(misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0, "ftn_group_sum_rows_form: misalign=%d",
-                misalign_or);
+  FTN_CHECK_ARG(misalign_ok(misalign_or), "ftn_group_sum_rows_form: misalign=%d", misalign_or);
   return group_rows_form(inner, member_stride, outer_stride, (unsigned)misalign_or, n_chunks);
 }
 
@@ -182,25 +148,12 @@ extern "C" int ftn_group_sum_rows(const float* x_dev, long long outer, int S, lo
                                   long long member_stride, const int* order_dev, const int* offsets_dev,
                                   const int* offsets_host, int G, int M, float* out_dev, void* stream) {
   const char* who = "ftn_group_sum_rows";
-  FTN_CHECK_ARG(x_dev && out_dev && offsets_dev && offsets_host, "%s: null x, out or offsets", who);
-  const uintptr_t all = (uintptr_t)x_dev | (uintptr_t)out_dev | (uintptr_t)order_dev | (uintptr_t)offsets_dev |
-                        (uintptr_t)offsets_host;
-  FTN_CHECK_ARG((all & 3) == 0, "%s: operands must be 4-byte aligned", who);
+  int chunks = 0;
+  if (group_csr_check(who, x_dev, out_dev, order_dev, offsets_dev, offsets_host, G, M, &chunks) < 0) return -1;
   FTN_CHECK_ARG(S >= 1, "%s: S=%d is not positive", who, S);
-  FTN_CHECK_ARG(G >= 1 && G <= FTN_GROUP_GMAX, "%s: G=%d is outside 1..%d", who, G, FTN_GROUP_GMAX);
-  FTN_CHECK_ARG(M >= 0 && (M == 0 || order_dev), "%s: M=%d members need order", who, M);
-  FTN_CHECK_ARG(offsets_host[0] == 0 && offsets_host[G] == M, "%s: offsets run %d..%d, not 0..M=%d", who,
-                offsets_host[0], offsets_host[G], M);
-  long long chunks = 0;
-  for (int g = 0; g < G; ++g) {
-    const long long m = (long long)offsets_host[g + 1] - offsets_host[g];
-    FTN_CHECK_ARG(m >= 0, "%s: offsets decrease at group %d", who, g);
-    chunks += (m + FTN_GROUP_CHUNK - 1) / FTN_GROUP_CHUNK;
-  }
-  FTN_CHECK_ARG(chunks <= FTN_GROUP_CHUNKS_MAX, "%s: %lld chunks are above %d", who, chunks, FTN_GROUP_CHUNKS_MAX);
   FTN_CHECK_ARG(outer >= 1, "%s: outer=%lld is not positive", who, outer);
   if (outer == 1) outer_stride = 0;                             // one slab: its stride addresses nothing
-  if (group_rows_form_check(who, inner, member_stride, outer_stride, (int)chunks) < 0) return -1;
+  if (group_rows_form_check(who, inner, member_stride, outer_stride, chunks) < 0) return -1;
   long long span = 0, reach = 0, cells = 0;                     // every product in 64 bits
   FTN_CHECK_ARG(!__builtin_mul_overflow((long long)S, member_stride, &span),
                 "%s: S=%d members %lld apart pass 64 bits", who, S, member_stride);
@@ -212,15 +165,15 @@ extern "C" int ftn_group_sum_rows(const float* x_dev, long long outer, int S, lo
                     cells <= (1LL << 61),
                 "%s: outer=%lld G=%d inner=%lld pass 64 bits", who, outer, G, inner);
   const unsigned misalign = (unsigned)(((uintptr_t)x_dev | (uintptr_t)out_dev) & 15);
-  const int form = group_rows_form(inner, member_stride, outer_stride, misalign, (int)chunks);
+  const int form = group_rows_form(inner, member_stride, outer_stride, misalign, chunks);
   GroupRowsArgs a = {};
-  a.x = x_dev; a.order = order_dev; a.offsets = offsets_dev; a.out = out_dev;
+  a.x = x_dev; a.out = out_dev; a.csr = {order_dev, offsets_dev, G, M, chunks};
   a.inner = inner; a.outer_stride = outer_stride; a.member_stride = member_stride;
-  a.S = S; a.G = G; a.M = M; a.C = (int)chunks; a.TI = (form >> 8) & 255;
+  a.S = S; a.TI = (form >> 8) & 255;
   a.tiles = (inner + a.TI - 1) / a.TI;
   a.work = outer * a.tiles;                                     // <= outer inner, checked above
   a.CP = group_rows_pass(a.TI);
-  if (a.CP > a.C) a.CP = a.C > 1 ? a.C : 1;                     // fewer chunks than a pass holds
+  if (a.CP > chunks) a.CP = chunks > 1 ? chunks : 1;            // fewer chunks than a pass holds
   const size_t lds = (size_t)(a.CP + 2) * a.TI * 8 + (size_t)(G + 1 + RS_THREADS) * 4;
   FTN_CHECK_ARG(lds <= 65536, "%s: a tile of %d columns takes %zu bytes of LDS", who, a.TI, lds);
   const dim3 grid((unsigned)(a.work < RS_GRID_MAX ? a.work : RS_GRID_MAX));

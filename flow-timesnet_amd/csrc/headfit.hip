@@ -155,8 +155,7 @@ static bool nb_grad_shape_ok(int B, int H, int N) {
 extern "C" int ftn_nb_nll_grad_form(int B, int H, int N, long long y_bstride, long long rate_bstride,
                                     long long disp_bstride, int misalign_or) {
   FTN_CHECK_ARG(nb_grad_shape_ok(B, H, N), "ftn_nb_nll_grad_form: B=%d H=%d N=%d", B, H, N);
-  FTN_CHECK_ARG(y_bstride >= 0 && rate_bstride >= 0 && disp_bstride >= 0 && misalign_or >= 0 && misalign_or < 16 &&
-                    misalign_or % 4 == 0,
+  FTN_CHECK_ARG(y_bstride >= 0 && rate_bstride >= 0 && disp_bstride >= 0 && misalign_ok(misalign_or),
                 "ftn_nb_nll_grad_form: strides %lld %lld %lld misalign=%d", y_bstride, rate_bstride, disp_bstride,
                 misalign_or);
   return nb_grad_form(B, (long long)H * N, y_bstride, rate_bstride, disp_bstride, (unsigned)misalign_or);
@@ -379,7 +378,7 @@ static int head_bwd_form(long long R, int N, int D, unsigned misalign_or) {
 }
 
 extern "C" int ftn_head_backward_form(long long R, int N, int D, int misalign_or) {
-  FTN_CHECK_ARG(head_bwd_shape_ok(R, N, D) && misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0,
+  FTN_CHECK_ARG(head_bwd_shape_ok(R, N, D) && misalign_ok(misalign_or),
                 "ftn_head_backward_form: R=%lld N=%d d_model=%d misalign=%d", R, N, D, misalign_or);
   return head_bwd_form(R, N, D, (unsigned)misalign_or);
 }

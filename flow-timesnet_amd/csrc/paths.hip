@@ -352,8 +352,7 @@ static int path_form_check(const char* who, int P, int N, int window, long long 
 extern "C" int ftn_path_summary_form(int P, int N, int window, long long p_stride, long long b_stride,
                                      long long y_bstride, int misalign_or) {
   if (path_form_check("ftn_path_summary_form", P, N, window, p_stride, b_stride, y_bstride) < 0) return -1;
-  FTN_CHECK_ARG(misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0, "ftn_path_summary_form: misalign=%d",
-                misalign_or);
+  FTN_CHECK_ARG(misalign_ok(misalign_or), "ftn_path_summary_form: misalign=%d", misalign_or);
   return path_form(P, N, p_stride, b_stride, y_bstride, (unsigned)misalign_or);
 }
 

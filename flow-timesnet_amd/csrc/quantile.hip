@@ -103,8 +103,7 @@ __global__ __launch_bounds__(NBQ_THREADS) void k_nb_quantile(NbqArgs a) {
 extern "C" int ftn_nbq_form(int N, long long y_bstride, long long rate_bstride, long long disp_bstride,
                             int misalign_or) {
   FTN_CHECK_ARG(N >= 1, "ftn_nbq_form: N=%d", N);
-  FTN_CHECK_ARG(y_bstride >= 0 && rate_bstride >= 0 && disp_bstride >= 0 && misalign_or >= 0 && misalign_or < 16 &&
-                    misalign_or % 4 == 0,
+  FTN_CHECK_ARG(y_bstride >= 0 && rate_bstride >= 0 && disp_bstride >= 0 && misalign_ok(misalign_or),
                 "ftn_nbq_form: strides %lld %lld %lld misalign=%d", y_bstride, rate_bstride, disp_bstride, misalign_or);
   return nbq_form(N, y_bstride, rate_bstride, disp_bstride, (unsigned)misalign_or);
 }

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(NBQ_THREADS) void k_nb_sample(NbsArgs a) {
 
 extern "C" int ftn_nb_sample_form(int N, long long rate_bstride, long long disp_bstride, int misalign_or) {
   FTN_CHECK_ARG(N >= 1, "ftn_nb_sample_form: N=%d", N);
-  FTN_CHECK_ARG(rate_bstride >= 0 && disp_bstride >= 0 && misalign_or >= 0 && misalign_or < 16 && misalign_or % 4 == 0,
+  FTN_CHECK_ARG(rate_bstride >= 0 && disp_bstride >= 0 && misalign_ok(misalign_or),
                 "ftn_nb_sample_form: strides %lld %lld misalign=%d", rate_bstride, disp_bstride, misalign_or);
   return nbq_form(N, 0, rate_bstride, disp_bstride, (unsigned)misalign_or);
 }

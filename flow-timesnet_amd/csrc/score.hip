@@ -179,8 +179,7 @@ extern "C" int ftn_score_form(int H, int N, long long y_bstride, long long rate_
                               int misalign_or) {
   FTN_CHECK_ARG(H >= 1 && N >= 1 && (long long)H * N <= 0x7fffffffLL && H < (1 << 20),
                 "ftn_score_form: H=%d N=%d", H, N);
-  FTN_CHECK_ARG(y_bstride >= 0 && rate_bstride >= 0 && disp_bstride >= 0 && misalign_or >= 0 && misalign_or < 16 &&
-                    misalign_or % 4 == 0,
+  FTN_CHECK_ARG(y_bstride >= 0 && rate_bstride >= 0 && disp_bstride >= 0 && misalign_ok(misalign_or),
                 "ftn_score_form: strides %lld %lld %lld misalign=%d", y_bstride, rate_bstride, disp_bstride, misalign_or);
   return score_form(H, N, y_bstride, rate_bstride, disp_bstride, (unsigned)misalign_or);
 }

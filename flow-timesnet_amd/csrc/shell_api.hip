@@ -8,7 +8,6 @@
 
 #define FTN_CHECK_D_MODEL(who, w, D) \
   FTN_CHECK_ARG((w).d_ok(D), "%s: d_model=%d must be a multiple of 4, %s", who, D, (w).range)
-static bool misalign_ok(int m) { return m >= 0 && m < 16 && m % 4 == 0; }
 
 // --------------------------------------------------------------------------------------------------------- heads
 static int head_form_entry(const char* who, const ShellWidth& w, int N, int D, long long tail_bs, long long late_bs,

@@ -1295,12 +1295,32 @@ def group_sum_form_of(N: int, row_stride: int | None = None, misalign_or: int = 
     return f"{'vec4' if f & 2 else 'scalar'}/t{f >> 8}"
 
 
+def _csr_chunks(offsets_host) -> int:
+    """The chunks of 32 members over all groups of the CSR offsets."""
+    sizes = [int(b) - int(a) for a, b in zip(offsets_host[:-1], offsets_host[1:])]
+    return sum((m + _lib.FTN_GROUP_CHUNK - 1) // _lib.FTN_GROUP_CHUNK for m in sizes)
+
+
+def _group_csr(who: str, x: torch.Tensor, order, offsets, offsets_host) -> Tuple[int, int]:
+    """``(G, M)`` of the CSR ``order`` [M] / ``offsets`` [G+1] / ``offsets_host`` for ``x``, fp32 on a ROCm device."""
+    xn = "x3" if x.dim() == 3 else "x"
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f"{who}: {xn} must be an fp32 tensor on a ROCm device, got {x.dtype} on {x.device}")
+    for name, t in (("order", order), ("offsets", offsets)):
+        if (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.device != x.device
+                or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be a contiguous int32 vector on {xn}'s device")
+    G, M = offsets.numel() - 1, order.numel()
+    if (getattr(offsets_host, "dtype", None) != "int32" or offsets_host.ndim != 1 or offsets_host.size != G + 1
+            or not offsets_host.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"{who}: offsets_host must be a contiguous int32 numpy array of {G + 1} offsets")
+    return G, M
+
+
 def group_sum_form(x: torch.Tensor, offsets_host) -> str:
     """``group_sum_form_of`` for the tensors ``group_sum(x, order, offsets, offsets_host)`` is given."""
     rows, N = x.shape
-    sizes = [int(b) - int(a) for a, b in zip(offsets_host[:-1], offsets_host[1:])]
-    chunks = sum((m + _lib.FTN_GROUP_CHUNK - 1) // _lib.FTN_GROUP_CHUNK for m in sizes)
-    return group_sum_form_of(N, x.stride(0) if rows > 1 else N, _ptr(x) & 15, chunks)
+    return group_sum_form_of(N, x.stride(0) if rows > 1 else N, _ptr(x) & 15, _csr_chunks(offsets_host))
 
 
 def group_sum(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, offsets_host, out: torch.Tensor | None = None
@@ -1315,16 +1335,7 @@ def group_sum(x: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, offse
     rows, N = x.shape
     if (N > 1 and x.stride(1) != 1) or (rows > 1 and x.stride(0) < N):
         raise ValueError(f"group_sum: x needs contiguous rows at least N apart, strides {x.stride()}")
-    if x.dtype != torch.float32 or not x.is_cuda:
-        raise ValueError(f"group_sum: x must be an fp32 tensor on a ROCm device, got {x.dtype} on {x.device}")
-    for name, t in (("order", order), ("offsets", offsets)):
-        if (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.device != x.device
-                or not t.is_contiguous()):
-            raise ValueError(f"group_sum: {name} must be a contiguous int32 vector on x's device")
-    G, M = offsets.numel() - 1, order.numel()
-    if (getattr(offsets_host, "dtype", None) != "int32" or offsets_host.ndim != 1 or offsets_host.size != G + 1
-            or not offsets_host.flags["C_CONTIGUOUS"]):
-        raise ValueError(f"group_sum: offsets_host must be a contiguous int32 numpy array of {G + 1} offsets")
+    G, M = _group_csr("group_sum", x, order, offsets, offsets_host)
     out = _out_or_fresh("group_sum", out, (rows, G), x)
     check(lib.ftn_group_sum(_ptr(x), rows, N, x.stride(0) if rows > 1 else N, _ptr(order) if M else None,
                             _ptr(offsets), offsets_host.ctypes.data, G, M, _ptr(out), _stream(x.device)),
@@ -1356,11 +1367,9 @@ def _rows_strides(x3: torch.Tensor) -> Tuple[int, int]:
 def group_sum_rows_form(x3: torch.Tensor, offsets_host, out: torch.Tensor | None = None) -> str:
     """``group_sum_rows_form_of`` for the tensors ``group_sum_rows(x3, order, offsets, offsets_host, out)`` is given
     (a fresh ``out`` is 16-byte aligned)."""
-    sizes = [int(b) - int(a) for a, b in zip(offsets_host[:-1], offsets_host[1:])]
-    chunks = sum((m + _lib.FTN_GROUP_CHUNK - 1) // _lib.FTN_GROUP_CHUNK for m in sizes)
     os_, ms = _rows_strides(x3)
     mis = (_ptr(x3) | (0 if out is None else _ptr(out))) & 15
-    return group_sum_rows_form_of(x3.shape[2], ms, os_, mis, chunks)
+    return group_sum_rows_form_of(x3.shape[2], ms, os_, mis, _csr_chunks(offsets_host))
 
 
 def group_sum_rows(x3: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, offsets_host,
@@ -1378,16 +1387,7 @@ def group_sum_rows(x3: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor,
             or (outer > 1 and x3.stride(0) < S * (x3.stride(1) if S > 1 else inner))):
         raise ValueError(f"group_sum_rows: x3 needs contiguous inner elements, members at least inner apart and slabs "
                          f"at least S members apart, strides {x3.stride()}")
-    if x3.dtype != torch.float32 or not x3.is_cuda:
-        raise ValueError(f"group_sum_rows: x3 must be an fp32 tensor on a ROCm device, got {x3.dtype} on {x3.device}")
-    for name, t in (("order", order), ("offsets", offsets)):
-        if (not isinstance(t, torch.Tensor) or t.dim() != 1 or t.dtype != torch.int32 or t.device != x3.device
-                or not t.is_contiguous()):
-            raise ValueError(f"group_sum_rows: {name} must be a contiguous int32 vector on x3's device")
-    G, M = offsets.numel() - 1, order.numel()
-    if (getattr(offsets_host, "dtype", None) != "int32" or offsets_host.ndim != 1 or offsets_host.size != G + 1
-            or not offsets_host.flags["C_CONTIGUOUS"]):
-        raise ValueError(f"group_sum_rows: offsets_host must be a contiguous int32 numpy array of {G + 1} offsets")
+    G, M = _group_csr("group_sum_rows", x3, order, offsets, offsets_host)
     out = _out_or_fresh("group_sum_rows", out, (outer, G, inner), x3)
     os_, ms = _rows_strides(x3)
     check(lib.ftn_group_sum_rows(_ptr(x3), outer, S, inner, os_, ms, _ptr(order) if M else None, _ptr(offsets),

@@ -37,6 +37,8 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from .lib import (FTN_GROUP_CHUNK as GROUP_CHUNK, FTN_GROUP_CHUNKS_MAX as GROUP_CHUNKS_MAX,  # importing it loads nothing
+                  FTN_GROUP_GMAX as GROUP_GMAX, FTN_GROUP_NMAX as GROUP_NMAX)
 from .nbdist import (NBQ_FLAG_RANGE, NBQ_KLIM, NBQ_QMAX, _M32, _nb_cdf_torch, _nb_invert_torch,  # noqa: F401
                      _nb_quantiles_torch, philox4x32, sample_uniforms)
 
@@ -649,10 +651,7 @@ def path_metrics(samples: torch.Tensor, y: torch.Tensor, levels, window: Optiona
 # out[.., g] = the sum of x[.., i] over the members i of group g, defined to the bit (include/flowtimes.h): the members
 # in chunks of 32, a chunk's sum in fp64 left to right from +0.0, the chunk sums in ascending order in fp64, one
 # rounding to fp32.  ``hip``: ftn_group_sum (csrc/groups.hip).  ``torch``: the same additions in torch ops, anywhere.
-GROUP_CHUNK = 32             # FTN_GROUP_CHUNK
-GROUP_NMAX = 8192            # series, groups and chunks of one ftn_group_sum call (FTN_GROUP_NMAX / GMAX / CHUNKS_MAX)
-GROUP_GMAX = 2048
-GROUP_CHUNKS_MAX = 2048
+# GROUP_CHUNK, and GROUP_NMAX / GMAX / CHUNKS_MAX, the series, groups and chunks of one ftn_group_sum call: lib.py's.
 
 
 def _store_key(series_id: str) -> str:

@@ -858,8 +858,8 @@ int ftn_path_summary(const float* samples_dev, long long p_stride, long long b_s
  * An empty group gives +0.  NaN and inf behave as IEEE addition gives them and reach only the groups that hold the
  * element.  A group's result is a function of its member list and of the row alone: not of the number of rows, of
  * the other groups, of the load width or of the grid.  For integer-valued x whose totals stay below 2^24 the result
- * is exact.  No atomics; no loop bound depends on the data, only on the CSR.  A member outside 0 .. N - 1 (the
- * device words are not validated) contributes +0 and touches no memory.
+ * is exact.  No atomics; no loop bound depends on the data, only on the CSR.  What the kernel reads from the device
+ * CSR is clamped: offsets to 0 .. M, and a member outside 0 .. N - 1 contributes +0 and touches no memory.
  * Limits, checked before the launch: 1 <= N <= FTN_GROUP_NMAX, 1 <= G <= FTN_GROUP_GMAX, at most FTN_GROUP_CHUNKS_MAX
  * chunks over all groups (a group of m members has ceil(m / 32)); rows >= 1, rows row_stride and rows G formed in 64
  * bits; row_stride >= N; offsets_host monotone from 0 to M; every pointer non-null (order may be null when M = 0)
