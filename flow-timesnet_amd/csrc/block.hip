@@ -231,15 +231,39 @@ static FtnForms block_forms(const FtnPlan* pl, int L, int act_dtype, bool x_alig
   return f;
 }
 
+// The one plan check, of the forwards (whose messages these are), of ftn_timesblock_forms and of the fused stage A (which answer
+// a bad plan in their own words and add their own conditions).
+static int plan_check(const FtnPlan* plan) {
+  FTN_CHECK_ARG(plan->CP % 16 == 0 && plan->FP % 16 == 0 && plan->CP >= plan->C && plan->FP >= plan->F,
+                "ftn_timesblock_forward: plan channel padding is inconsistent");
+  FTN_CHECK_ARG(plan->nbr >= 1 && plan->nbr <= FTN_MAXBR, "ftn_timesblock_forward: nbr=%d", plan->nbr);
+  FTN_CHECK_ARG(plan->mode == 1 || (plan->MP % 16 == 0 && plan->MP > 0), "ftn_timesblock_forward: bad MP");
+  FTN_CHECK_ARG(plan->res1 || plan->CP == plan->FP, "identity res1 needs d_model == d_ff");
+  FTN_CHECK_ARG(plan->res2 || plan->CP == plan->FP, "identity res2 needs d_model == d_ff");
+  return 0;
+}
+
 extern "C" int ftn_timesblock_forms(const FtnPlan* plan, int B, int L, int act_dtype, int x_misalign, FtnForms* forms_out) {
   FTN_CHECK_ARG(plan && forms_out, "ftn_timesblock_forms: null pointer");
   FTN_CHECK_ARG(B >= 1 && B <= 65535 && L >= 2, "ftn_timesblock_forms: bad shape B=%d L=%d", B, L);
   FTN_CHECK_ARG(act_dtype >= 0 && act_dtype <= 2 && x_misalign >= 0 && x_misalign < 16,
                 "ftn_timesblock_forms: act_dtype=%d x_misalign=%d", act_dtype, x_misalign);
-  FTN_CHECK_ARG(plan->nbr >= 1 && plan->nbr <= FTN_MAXBR && (plan->mode == 1 || (plan->MP % 16 == 0 && plan->MP > 0)),
-                "ftn_timesblock_forms: bad plan");
+  FTN_CHECK_ARG(plan_check(plan) == 0, "ftn_timesblock_forms: bad plan");
   *forms_out = block_forms(plan, L, act_dtype, x_misalign == 0, true, nullptr);
   return 0;
+}
+
+// Stage A's argument block (a = W_in1 x + b into the workspace's window rows, and the sanitised copy of desc_in at its head), for
+// forward and for the fused ftn_period_finalize_stage_a.  Only the f16x2 epilogue (3) has a range to guard: any other drops the word.
+static PwArgs stage_a_args(const FtnPlan* pl, const float* wb, const float* x, char* ws, const FtnDesc* desc_in, int B, int L,
+                           int max_groups, int px_row, int epi, int* range_flag) {
+  const int CA = pl->nbr * pl->MP;
+  PwArgs pa = {};
+  pa.x = x; pa.W = wb + pl->w_in1; pa.bias = wb + pl->b_in1; pa.out = (float*)(ws + FTN_WS_HEAD); pa.desc = (const FtnDesc*)ws;   // WsLayout.offA
+  pa.B = B; pa.L = L; pa.C = pl->C; pa.KIN = pl->CP; pa.n_ot = CA / 16; pa.OUTC = CA;
+  pa.guard_src = desc_in; pa.guard_dst = (FtnDesc*)ws; pa.guard_groups = max_groups; pa.guard_px = px_row;
+  pa.range_flag = epi == 3 ? range_flag : nullptr;
+  return pa;
 }
 
 static int forward(const float* x, float* y, int B, int L, const FtnPlan* pl, const float* wb, const FtnDesc* desc_in,
@@ -269,12 +293,8 @@ static int forward(const float* x, float* y, int B, int L, const FtnPlan* pl, co
     // the split stage-C forms read m and write a' as activation pieces
     const bool c_split = fm.stage_c != FTN_FORM_C_MLP && fm.stage_c != FTN_FORM_C_GENERIC;
     // A: a = W_in1 x + b
-    PwArgs pa = {};
-    pa.x = x; pa.W = wb + pl->w_in1; pa.bias = wb + pl->b_in1; pa.out = bufA; pa.desc = desc;
-    pa.B = B; pa.L = L; pa.C = C; pa.KIN = CP; pa.n_ot = CA / 16; pa.OUTC = CA;
-    pa.guard_src = desc_in; pa.guard_dst = (FtnDesc*)ws; pa.guard_groups = max_groups; pa.guard_px = px_row;
+    const PwArgs pa = stage_a_args(pl, wb, x, ws, desc_in, B, L, max_groups, px_row, fm.stage_a_epi, range_flag);
     if (!h2) range_flag = nullptr;                              // only the f16x2 engine has a range to guard
-    pa.range_flag = range_flag;
     // (FTN_FWD_STAGE_A_DONE: ftn_period_finalize_stage_a ran stage A and published the descriptor copy)
     if (!(flags & FTN_FWD_STAGE_A_DONE) && (rc = ftn_launch_stage_a(pa, nullptr, 0, act, fm.stage_a_epi, xvec, st))) return rc;
     prof_mark(1, st);
@@ -452,12 +472,7 @@ static int forward_checked(const float* x_dev, float* y_dev, int B, int L, const
   FTN_CHECK_ARG(!(flags & FTN_FWD_STAGE_A_DONE) || n_pass == B,
                 "ftn_timesblock_forward_rows: FTN_FWD_STAGE_A_DONE needs a single pass (B=%d rows_per_pass=%d)", B, rows_per_pass);
   FTN_CHECK_ARG(max_groups >= 1 && max_groups <= FTN_KMAX, "ftn_timesblock_forward: max_groups=%d", max_groups);
-  FTN_CHECK_ARG(plan->CP % 16 == 0 && plan->FP % 16 == 0 && plan->CP >= plan->C && plan->FP >= plan->F,
-                "ftn_timesblock_forward: plan channel padding is inconsistent");
-  FTN_CHECK_ARG(plan->nbr >= 1 && plan->nbr <= FTN_MAXBR, "ftn_timesblock_forward: nbr=%d", plan->nbr);
-  FTN_CHECK_ARG(plan->mode == 1 || (plan->MP % 16 == 0 && plan->MP > 0), "ftn_timesblock_forward: bad MP");
-  FTN_CHECK_ARG(plan->res1 || plan->CP == plan->FP, "identity res1 needs d_model == d_ff");
-  FTN_CHECK_ARG(plan->res2 || plan->CP == plan->FP, "identity res2 needs d_model == d_ff");
+  if (plan_check(plan)) return -1;
   FTN_CHECK_ARG(px_bound >= 0, "ftn_timesblock_forward: px_bound=%d", px_bound);
   FTN_CHECK_ARG((flags & ~FTN_FWD_STAGE_A_DONE) == 0 && !((flags & FTN_FWD_STAGE_A_DONE) && plan->mode != 0),
                 "ftn_timesblock_forward: flags=%d", flags);
@@ -505,46 +520,31 @@ extern "C" int ftn_period_finalize_stage_a(const double* psum_dev, int nparts, i
                                            size_t ws_bytes, void* stream, int* range_flag_dev, const FtnExchange* xch) {
   // psum_dev == NULL: stage A only;  x_dev == NULL: finalize + descriptor copy only (stage A is in the workspace)
   const bool do_fin = psum_dev != nullptr || xch != nullptr, do_a = x_dev != nullptr;
-  if (xch != nullptr) {
-    FTN_CHECK_ARG(ftn_xch_ok(xch, L / 2 + 1), "ftn_period_finalize_stage_a: bad exchange (world / rank / seq / mode / F_cap)");
-    nparts = xch->world;
-  }
+  const char* who = "ftn_period_finalize_stage_a";
+  // (this entry has always looked at the exchange first; ftn_finalize_check looks again, where ftn_period_finalize does)
+  FTN_CHECK_ARG(xch == nullptr || ftn_xch_ok(xch, L / 2 + 1), "%s: bad exchange (world / rank / seq / mode / F_cap)", who);
   FTN_CHECK_ARG(do_fin || do_a, "ftn_period_finalize_stage_a: nothing to do (psum and x both null)");
   FTN_CHECK_ARG(plan && wblob_dev && ws_dev, "ftn_period_finalize_stage_a: null pointer");
-  if (do_fin) {
-    FTN_CHECK_ARG(med_dev && desc_dev && amps_dev && weights_dev, "ftn_period_finalize_stage_a: null pointer");
-    FTN_CHECK_ARG((((uintptr_t)amps_dev | (uintptr_t)weights_dev) & 15) == 0, "ftn_period_finalize_stage_a: amps / weights must be 16-byte aligned");
-    FTN_CHECK_ARG(nparts >= 1 && Btotal >= B, "ftn_period_finalize_stage_a: bad shape");
-  }
+  int rc;
+  if (do_fin && (rc = ftn_finalize_check(who, psum_dev, nparts, Btotal, med_dev, B, L, desc_dev, amps_dev, weights_dev, xch))) return rc;
   // (the row limit belongs to stage A, whose workspace holds all B rows; the finalize-only part has none)
   FTN_CHECK_ARG(B >= 1 && (B <= 65535 || !do_a) && L >= 2, "ftn_period_finalize_stage_a: bad shape");
   FTN_CHECK_ARG(k_periods <= FTN_KMAX && act_dtype >= 0 && act_dtype <= 2, "ftn_period_finalize_stage_a: k=%d act_dtype=%d", k_periods, act_dtype);
-  FTN_CHECK_ARG(plan->mode == 0 && plan->MP > 0 && plan->MP % 16 == 0, "ftn_period_finalize_stage_a: bottleneck blocks only");
+  FTN_CHECK_ARG(plan_check(plan) == 0 && plan->mode == 0, "ftn_period_finalize_stage_a: bottleneck blocks only");
   FTN_CHECK_ARG(max_groups >= 1 && max_groups <= FTN_KMAX && px_bound >= 0, "ftn_period_finalize_stage_a: bounds");
   const size_t need = ftn_timesblock_workspace_bytes(plan, B, L, max_groups, px_bound);
   FTN_CHECK_ARG(need > 0 && ws_bytes >= need && ((uintptr_t)ws_dev & 255) == 0 && ((uintptr_t)wblob_dev & 15) == 0,
                 "ftn_period_finalize_stage_a: workspace %zu < %zu bytes or misaligned", ws_bytes, need);
-  if (k_periods < 0) k_periods = 0;
-  if (pmax < 1) pmax = 1;
-  if (min_period_threshold < 1) min_period_threshold = 1;
-  if (min_period_threshold > pmax) min_period_threshold = pmax;
-  const int F = L / 2 + 1;
-  FTN_CHECK_ARG(ftn_finalize_lds_bytes(F) <= 48 * 1024, "ftn_period_finalize_stage_a: L=%d too long", L);
-  const WsLayout wl = ws_layout(plan, B, L, max_groups, px_bound);
-  const int CA = plan->nbr * plan->MP;
-  const FtnForms fm = block_forms(plan, L, act_dtype, x_dev != nullptr && ((uintptr_t)x_dev & 15) == 0, true, nullptr);
-  FinalizeArgs fa = {psum_dev, nparts, Btotal, med_dev, B, L, F, k_periods, pmax, min_period_threshold, desc_dev,
-                     amps_dev, weights_dev, act_dtype, max_unique > 0 ? max_unique : 0, log_base > 1.0 ? (float)log(log_base) : 0.f};
-  if (xch != nullptr) ftn_xch_fill(xch, F, &fa);
+  FinalizeArgs fa;
+  if ((rc = ftn_finalize_args(who, psum_dev, nparts, Btotal, med_dev, B, L, k_periods, pmax, min_period_threshold, act_dtype,
+                              max_unique, log_base, desc_dev, amps_dev, weights_dev, xch, &fa)))
+    return rc;
   size_t stamp_cap;
   fa.dbg = ftn_stamp_buf(8, &stamp_cap);
   if (stamp_cap < 8) fa.dbg = nullptr;
-  PwArgs pa = {};
-  pa.x = x_dev; pa.W = wblob_dev + plan->w_in1; pa.bias = wblob_dev + plan->b_in1; pa.out = (float*)((char*)ws_dev + wl.offA);
-  pa.desc = nullptr; pa.B = B; pa.L = L; pa.C = plan->C; pa.KIN = plan->CP; pa.n_ot = CA / 16; pa.OUTC = CA;
-  pa.guard_src = desc_dev; pa.guard_dst = (FtnDesc*)ws_dev; pa.guard_groups = max_groups;
-  pa.guard_px = worst_px_per_row(L, max_groups, px_bound);
-  pa.range_flag = fm.stage_a_epi == 3 ? range_flag_dev : nullptr;
+  const FtnForms fm = block_forms(plan, L, act_dtype, x_dev != nullptr && ((uintptr_t)x_dev & 15) == 0, true, nullptr);
+  const PwArgs pa = stage_a_args(plan, wblob_dev, x_dev, (char*)ws_dev, desc_dev, B, L, max_groups,
+                                 worst_px_per_row(L, max_groups, px_bound), fm.stage_a_epi, range_flag_dev);
   const int part = do_fin && do_a ? 0 : (do_a ? 1 : 2);
   return ftn_launch_stage_a(pa, &fa, part, fm.act, fm.stage_a_epi, fm.xvec != 0, (hipStream_t)stream);
 }

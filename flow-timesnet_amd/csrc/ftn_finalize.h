@@ -38,6 +38,24 @@ struct FinalizeArgs {
   int rows_outside;          // 1: the per-row section is left to k_row_weights (ftn_launch_row_weights), launched behind
 };
 
+// Constructor clamps of FFTPeriodSelector (:59-62): the one copy, for ftn_period_finalize[_stage_a] and ftn_selector_px_bound.
+static inline void ftn_selector_clamp(int* k, int* pmax, int* min_thr) {
+  if (*k < 0) *k = 0;
+  if (*pmax < 1) *pmax = 1;
+  if (*min_thr < 1) *min_thr = 1;
+  if (*min_thr > *pmax) *min_thr = *pmax;
+}
+
+// The finalize prologue of ftn_period_finalize and ftn_period_finalize_stage_a (selector.hip); `who` names the entry in the
+// messages.  ftn_finalize_check: operands, exchange, alignment, shape (the stage-A-only call has none of them and skips it);
+// ftn_finalize_args: the constructor clamps, the LDS limit, FinalizeArgs with the exchange's fields.  Two steps, because each
+// entry checks k / act_dtype in its own words between them, the fused one its plan and workspace too, in an order callers know.
+int ftn_finalize_check(const char* who, const double* psum, int nparts, int Btotal, const float* med, int B, int L,
+                       const FtnDesc* desc, const float* amps, const float* wts, const FtnExchange* xch);
+int ftn_finalize_args(const char* who, const double* psum, int nparts, int Btotal, const float* med, int B, int L, int k, int pmax,
+                      int min_thr, int act_dtype, int max_unique, double log_base, FtnDesc* desc, float* amps, float* wts,
+                      const FtnExchange* xch, FinalizeArgs* fa);
+
 // The per-row section (amps, w) over a grid instead of inside the finalize workgroup, once B reaches the threshold
 // (selector.hip; FTN_FIN_ROWS=<n> forces it, 0 = never).  Every finalize launch asks ftn_fin_rows_outside and, when it
 // says so, sets FinalizeArgs.rows_outside and calls ftn_launch_row_weights on the same stream right behind itself.

@@ -53,30 +53,43 @@ int ftn_launch_row_weights(const FinalizeArgs& fa, hipStream_t st) {
   return 0;
 }
 
+int ftn_finalize_check(const char* who, const double* psum, int nparts, int Btotal, const float* med, int B, int L,
+                       const FtnDesc* desc, const float* amps, const float* wts, const FtnExchange* xch) {
+  FTN_CHECK_ARG((psum || xch) && med && desc && amps && wts, "%s: null pointer", who);
+  FTN_CHECK_ARG(xch == nullptr || ftn_xch_ok(xch, L / 2 + 1), "%s: bad exchange (world / rank / seq / mode / F_cap)", who);
+  if (xch != nullptr) nparts = xch->world;
+  FTN_CHECK_ARG((((uintptr_t)amps | (uintptr_t)wts) & 15) == 0, "%s: amps / weights must be 16-byte aligned", who);
+  FTN_CHECK_ARG(B >= 1 && L >= 2 && nparts >= 1 && Btotal >= B, "%s: bad shape", who);
+  return 0;
+}
+
+int ftn_finalize_args(const char* who, const double* psum, int nparts, int Btotal, const float* med, int B, int L, int k, int pmax,
+                      int min_thr, int act_dtype, int max_unique, double log_base, FtnDesc* desc, float* amps, float* wts,
+                      const FtnExchange* xch, FinalizeArgs* fa) {
+  ftn_selector_clamp(&k, &pmax, &min_thr);
+  const int F = L / 2 + 1;
+  FTN_CHECK_ARG(ftn_finalize_lds_bytes(F) <= 48 * 1024, "%s: L=%d too long", who, L);
+  *fa = FinalizeArgs{psum, xch != nullptr ? xch->world : nparts, Btotal, med, B, L, F, k, pmax, min_thr, desc, amps, wts, act_dtype,
+                     max_unique > 0 ? max_unique : 0, log_base > 1.0 ? (float)log(log_base) : 0.f};
+  if (xch != nullptr) ftn_xch_fill(xch, F, fa);
+  return 0;
+}
+
 extern "C" int ftn_period_finalize(const double* psum_dev, int nparts, int Btotal, const float* med_dev, int B,
                                    int L, int k_periods, int pmax, int min_period_threshold, int act_dtype,
                                    int max_unique, double log_base, FtnDesc* desc_dev, float* amps_dev,
                                    float* weights_dev, void* stream, const FtnExchange* xch) {
-  FTN_CHECK_ARG((psum_dev || xch) && med_dev && desc_dev && amps_dev && weights_dev, "ftn_period_finalize: null pointer");
-  FTN_CHECK_ARG(xch == nullptr || ftn_xch_ok(xch, L / 2 + 1), "ftn_period_finalize: bad exchange (world / rank / seq / mode / F_cap)");
-  if (xch != nullptr) nparts = xch->world;
-  FTN_CHECK_ARG((((uintptr_t)amps_dev | (uintptr_t)weights_dev) & 15) == 0, "ftn_period_finalize: amps / weights must be 16-byte aligned");
-  FTN_CHECK_ARG(B >= 1 && L >= 2 && nparts >= 1 && Btotal >= B, "ftn_period_finalize: bad shape");
+  const char* who = "ftn_period_finalize";
+  int rc = ftn_finalize_check(who, psum_dev, nparts, Btotal, med_dev, B, L, desc_dev, amps_dev, weights_dev, xch);
+  if (rc) return rc;
   FTN_CHECK_ARG(k_periods <= FTN_KMAX, "ftn_period_finalize: k_periods=%d > FTN_KMAX=%d", k_periods, FTN_KMAX);
   FTN_CHECK_ARG(act_dtype >= 0 && act_dtype <= 2, "ftn_period_finalize: act_dtype=%d", act_dtype);
-  // ctor clamps of FFTPeriodSelector (:59-62)
-  if (k_periods < 0) k_periods = 0;
-  if (pmax < 1) pmax = 1;
-  if (min_period_threshold < 1) min_period_threshold = 1;
-  if (min_period_threshold > pmax) min_period_threshold = pmax;
-  const int F = L / 2 + 1;
-  const size_t lds = ftn_finalize_lds_bytes(F);
-  FTN_CHECK_ARG(lds <= 48 * 1024, "ftn_period_finalize: L=%d too long", L);
-  FinalizeArgs fa = {psum_dev, nparts, Btotal, med_dev, B, L, F, k_periods, pmax, min_period_threshold, desc_dev,
-                     amps_dev, weights_dev, act_dtype, max_unique > 0 ? max_unique : 0, log_base > 1.0 ? (float)log(log_base) : 0.f};
-  if (xch != nullptr) ftn_xch_fill(xch, F, &fa);
+  FinalizeArgs fa;
+  if ((rc = ftn_finalize_args(who, psum_dev, nparts, Btotal, med_dev, B, L, k_periods, pmax, min_period_threshold, act_dtype,
+                              max_unique, log_base, desc_dev, amps_dev, weights_dev, xch, &fa)))
+    return rc;
   fa.rows_outside = ftn_fin_rows_outside(B) ? 1 : 0;
-  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), lds, (hipStream_t)stream, fa);
+  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), ftn_finalize_lds_bytes(fa.F), (hipStream_t)stream, fa);
   FTN_CHECK_LAUNCH();
   return fa.rows_outside ? ftn_launch_row_weights(fa, (hipStream_t)stream) : 0;
 }
@@ -87,10 +100,7 @@ extern "C" int ftn_period_finalize(const double* psum_dev, int nparts, int Btota
 // i >= 2 the pad is < i, i.e. (almost) every group is L pixels plus a few; only bin 1 (period L-1) doubles.
 extern "C" int ftn_selector_px_bound(int L, int k_periods, int pmax, int min_period_threshold, int* max_groups_out) {
   FTN_CHECK_ARG(L >= 2 && k_periods <= FTN_KMAX, "ftn_selector_px_bound: L=%d k=%d", L, k_periods);
-  if (k_periods < 0) k_periods = 0;
-  if (pmax < 1) pmax = 1;
-  if (min_period_threshold < 1) min_period_threshold = 1;
-  if (min_period_threshold > pmax) min_period_threshold = pmax;
+  ftn_selector_clamp(&k_periods, &pmax, &min_period_threshold);
   const int F = L / 2 + 1;
   const int k = k_periods < F - 1 ? k_periods : F - 1;
   const int hi = pmax < (L - 1 > 1 ? L - 1 : 1) ? pmax : (L - 1 > 1 ? L - 1 : 1), lo = min_period_threshold;

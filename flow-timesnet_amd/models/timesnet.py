@@ -135,12 +135,14 @@ class FFTPeriodSelector(nn.Module):
         """Run S1-S5 on the device; returns a ``runtime.Selection`` (or ``None`` when
         the selector is degenerate, reference :89-90,140-142).  ``act_dtype`` (default: ``x.dtype``) is the
         caller's activation dtype: for bf16 / fp16 the reference's roundings of scores, amplitudes and
-        softmax weights are applied (:124-159, :1000-1009).  ``stage_a=(plan, wblob[, range_flag])`` of the TimesBlock
-        that will consume the selection lets its first stage share the finalize launch (``runtime.finalize``)."""
+        softmax weights are applied (:124-159, :1000-1009).  ``stage_a``: the ``runtime.StageA`` record of the TimesBlock
+        call that will consume the selection (its ``x`` is the tensor given here) lets its first stage share the
+        finalize launch (``runtime.finalize``)."""
         from .. import runtime
 
         if x.ndim != 3:
             raise ValueError("FFTPeriodSelector expects input shaped [B, L, C]")
+        call = runtime.StageA.checked(stage_a)
         if self._degenerate(x):
             self.last_frequency_indices = torch.zeros(0, dtype=torch.long, device=x.device)
             self.last_selected_periods = torch.zeros(0, dtype=torch.long, device=x.device)
@@ -153,47 +155,40 @@ class FFTPeriodSelector(nn.Module):
         if xf.dtype != torch.float32:
             xf = xf.float()                                   # FFT is always >= fp32 (:92-94)
         xf = xf.contiguous()
+        if call is not None and (call.x.data_ptr(), call.x.shape, call.x.dtype) != (xf.data_ptr(), xf.shape, xf.dtype):
+            raise ValueError("stage_a: the StageA record's x is not the tensor this selection is made on")
+        if self.shard_group is not None and ((max_unique or 0) > 0 or (log_base or 0.0) > 1.0):
+            # those variants rank candidate groups by batch means of the amplitudes (:374-378, :394-437); only the
+            # [F] sums are exchanged, so every rank would rank on its own rows and could keep different groups
+            raise NotImplementedError("TIMES_PERIOD_MAX_UNIQ / TIMES_PERIOD_BINNING are not supported with a "
+                                      "batch-sharded selector (shard_group): unset them or run unsharded")
         xch = None
         if self.shard_group is not None and self.shard_exchange is not None:
             xch = self.shard_exchange.next_call(L // 2 + 1)        # this call's sequence number, same on every rank
         med, psum = runtime.spectrum(xf, xch)
         b_total = B
-        pre = None
         if xch is not None:
             # k_colsum has stored this rank's sums into every peer's buffer; the finalize workgroup waits for the
             # peers' stores (bounded) while stage A runs beside it - no collective, nothing else for the host to do
-            if (max_unique or 0) > 0 or (log_base or 0.0) > 1.0:
-                raise NotImplementedError("TIMES_PERIOD_MAX_UNIQ / TIMES_PERIOD_BINNING are not supported with a "
-                                          "batch-sharded selector (shard_group): unset them or run unsharded")
             b_total = B * self.shard_exchange.world
         elif self.shard_group is not None:
             import torch.distributed as dist
 
-            if (max_unique or 0) > 0 or (log_base or 0.0) > 1.0:
-                # those variants rank candidate groups by batch means of the amplitudes (:374-378, :394-437); only the
-                # [F] sums are exchanged, so every rank would rank on its own rows and could keep different groups
-                raise NotImplementedError("TIMES_PERIOD_MAX_UNIQ / TIMES_PERIOD_BINNING are not supported with a "
-                                          "batch-sharded selector (shard_group): unset them or run unsharded")
             world = dist.get_world_size(self.shard_group)
             parts = torch.empty(world, psum.numel(), dtype=psum.dtype, device=psum.device)
-            # the block's stage A needs x only: it runs while the partial sums travel
-            overlap = stage_a is not None and runtime.fuse_stage_a(stage_a[0])
-            if dist.get_backend(self.shard_group) == "gloo":      # CPU-side rehearsal of the exchange
-                if overlap:
-                    pre = runtime.stage_a_only(xf, stage_a[0], stage_a[1], self.k, self.pmax, self.min_period_threshold,
-                                               stage_a[2] if len(stage_a) > 2 else None)
+            gloo = dist.get_backend(self.shard_group) == "gloo"   # CPU-side rehearsal of the exchange: it blocks
+            work = None if gloo else dist.all_gather_into_tensor(parts, psum, group=self.shard_group, async_op=True)
+            if call is not None and runtime.fuse_stage_a(call.plan):
+                # the block's stage A needs x only: enqueued behind the spectrum, it runs while the partial sums travel
+                runtime.stage_a_only(call, self.k, self.pmax, self.min_period_threshold)
+            if gloo:
                 dist.all_gather(list(parts.unbind(0)), psum, group=self.shard_group)
-            else:                                                  # RCCL
-                work = dist.all_gather_into_tensor(parts, psum, group=self.shard_group, async_op=True)
-                if overlap:                                        # enqueued behind the spectrum, beside the exchange
-                    pre = runtime.stage_a_only(xf, stage_a[0], stage_a[1], self.k, self.pmax, self.min_period_threshold,
-                                               stage_a[2] if len(stage_a) > 2 else None)
+            else:
                 work.wait()                                        # the compute stream waits; the host does not
             b_total = B * world          # equal shards (no host sync to learn otherwise)
             psum = parts
         sel = runtime.finalize(psum, b_total, med, L, self.k, self.pmax, self.min_period_threshold, adt,
-                               max_unique or 0, log_base or 0.0,
-                               stage_a=None if stage_a is None else (xf,) + tuple(stage_a), pre=pre, xch=xch)
+                               max_unique or 0, log_base or 0.0, stage_a=call, xch=xch)
         self._pending = sel
         return sel
 
@@ -621,7 +616,7 @@ class TimesBlock(nn.Module):
             rows = self._pass_rows(B, L, plan, lambda: (sel.max_groups, sel.px_bound))
         self._last_passes = (1, B) if rows is None else (-(-B // rows), rows)
         self._last_forms = self._forms(plan, B=B, L=L, adt=adt, xf=xf, native=native,
-                                       fused_a=getattr(sel, "stage_a", None) is not None, rows=rows)
+                                       fused_a=sel.stage_a is not None, rows=rows)
         y = self._run(xf, x.dtype, sel, (wblob, plan), norm, flag, rows=rows)
         if ev is not None:
             ev.record()
@@ -652,7 +647,7 @@ class TimesBlock(nn.Module):
             max_unique = _resolve_scheduled_int(os.getenv("TIMES_PERIOD_MAX_UNIQ"), self.block_index)
             log_base = _resolve_log_binning_base(os.getenv("TIMES_PERIOD_BINNING"), self.block_index)
             sel = sel_mod.select_device(xf, act_dtype=x.dtype, max_unique=max_unique, log_base=log_base,
-                                        stage_a=(plan, wblob, flag) if fuse_a else None)
+                                        stage_a=runtime.StageA(xf, plan, wblob, flag) if fuse_a else None)
             if sel is None:                                            # reference :796-797
                 self._last_raw_period_count = self._last_valid_period_count = self._last_group_count = 0
             else:

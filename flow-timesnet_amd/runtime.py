@@ -146,6 +146,7 @@ class Selection:
         self.weights = weights    # [B, FTN_KMAX]
         self.max_groups = max_groups     # >= desc.n_groups
         self.px_bound = px_bound         # >= desc.total_px (0: generic worst case)
+        self.stage_a = None              # StageA of the consuming block when its stage A is done (finalize .. forward)
         self._host = None
 
     def host(self) -> FtnDesc:
@@ -198,33 +199,48 @@ def fuse_stage_a(plan) -> bool:
     return plan.mode == 0 and os.getenv("FTN_FUSE_STAGE_A", "1") != "0"
 
 
-def stage_a_only(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, k: int, pmax: int, min_thr: int,
-                 range_flag: Optional[torch.Tensor] = None):
-    """Stage A of the block into a fresh workspace, without the selection (``ftn_period_finalize_stage_a`` with
-    ``psum = NULL``): a batch-sharded run launches it between issuing the exchange of the partial sums and waiting
-    for it.  Returns the token ``finalize(..., stage_a=..., pre=token)`` completes."""
+class StageA:
+    """The block call that will consume a selection: its input ``x`` (fp32, contiguous), ``plan``, ``wblob`` and
+    optional ``range_flag``.  Stage A (a = W_in1 x + b) needs nothing of the selection, so ``finalize`` runs it in
+    the selector's launch, or ``stage_a_only`` ahead of it: ``ws`` is then the block's workspace, which holds it."""
+
+    def __init__(self, x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, range_flag: Optional[torch.Tensor] = None,
+                 ws: Optional[torch.Tensor] = None) -> None:
+        self.x, self.plan, self.wblob, self.range_flag, self.ws = x, plan, wblob, range_flag, ws
+
+    @staticmethod
+    def checked(call) -> Optional["StageA"]:
+        if call is not None and not isinstance(call, StageA):
+            raise TypeError(f"stage_a must be a runtime.StageA record, not {type(call).__name__}")
+        return call
+
+
+def stage_a_only(call: StageA, k: int, pmax: int, min_thr: int) -> None:
+    """Stage A of ``call`` into a fresh workspace ``call.ws``, without the selection (``ftn_period_finalize_stage_a``
+    with ``psum = NULL``): a batch-sharded run launches it between issuing the exchange of the partial sums and
+    waiting for it.  ``finalize(..., stage_a=call)`` completes it."""
     lib = _lib.load()
-    B, L, _ = x.shape
+    B, L, _ = call.x.shape
+    dev = call.x.device
     mg, pxb = _selector_bounds(lib, L, k, pmax, min_thr)
-    ws = _workspace(x.device, _workspace_bytes(lib, plan, B, L, mg, pxb))
+    call.ws = _workspace(dev, _workspace_bytes(lib, call.plan, B, L, mg, pxb))
     check(lib.ftn_period_finalize_stage_a(None, 0, 0, None, B, L, int(k), int(pmax), int(min_thr), 0, 0, 0.0,
-                                          None, None, None, _ptr(x), C.byref(plan), _ptr(wblob), mg, pxb, _ptr(ws),
-                                          ws.numel(), _stream(x.device), _ptr_or_null(range_flag), None),
-          "ftn_period_finalize_stage_a")
-    return ws
+                                          None, None, None, _ptr(call.x), C.byref(call.plan), _ptr(call.wblob), mg, pxb,
+                                          _ptr(call.ws), call.ws.numel(), _stream(dev), _ptr_or_null(call.range_flag),
+                                          None), "ftn_period_finalize_stage_a")
 
 
 def finalize(psum: torch.Tensor, b_total: int, med: torch.Tensor, L: int, k: int, pmax: int,
              min_thr: int, act_dtype: int = 0, max_unique: int = 0, log_base: float = 0.0,
-             stage_a=None, pre=None, xch=None) -> Selection:
+             stage_a: Optional[StageA] = None, xch=None) -> Selection:
     """S3-S5 on the device.  ``psum`` is [F] or [nparts, F] (multi-GPU partial sums); ``act_dtype`` 1 / 2
     applies the reference's bf16 / fp16 roundings of scores, amplitudes and weights.
 
-    ``stage_a=(x, plan, wblob)``: the block that consumes this selection is known, so its stage A
-    (a = W_in1 x + b, independent of the selection) rides in the same launch
-    (``ftn_period_finalize_stage_a``); the returned Selection then owns the block's workspace and
-    ``timesblock_forward`` skips stage A.  ``pre`` = the workspace ``stage_a_only`` already filled: only S3-S5 and
-    the descriptor copy remain."""
+    ``stage_a``: the block call that consumes this selection is known, so its stage A rides in the same launch
+    (``ftn_period_finalize_stage_a``) when ``fuse_stage_a`` allows; after ``stage_a_only`` only S3-S5 and the
+    descriptor copy remain.  Either way the returned Selection carries the record, whose ``ws`` is the block's
+    workspace, and ``timesblock_forward`` skips stage A."""
+    call = StageA.checked(stage_a)
     lib = _lib.load()
     B = med.shape[0]
     dev = med.device
@@ -234,25 +250,18 @@ def finalize(psum: torch.Tensor, b_total: int, med: torch.Tensor, L: int, k: int
     wts = torch.empty(B, FTN_KMAX, dtype=torch.float32, device=dev)
     mg, pxb = _selector_bounds(lib, L, k, pmax, min_thr)
     sel = Selection(desc, amps, wts, mg, pxb)
-    if stage_a is not None and (pre is not None or fuse_stage_a(stage_a[1])):
-        x, plan, wblob = stage_a[:3]
-        range_flag = stage_a[3] if len(stage_a) > 3 else None
-        ws = pre
-        if pre is None:
-            ws = _workspace(dev, _workspace_bytes(lib, plan, B, L, sel.max_groups, sel.px_bound))
-        check(lib.ftn_period_finalize_stage_a(_ptr(psum), nparts, int(b_total), _ptr(med), B, L, int(k), int(pmax),
-                                              int(min_thr), int(act_dtype), int(max_unique or 0),
-                                              float(log_base or 0.0), _ptr(desc), _ptr(amps), _ptr(wts),
-                                              _ptr(x) if pre is None else None,
-                                              C.byref(plan), _ptr(wblob), sel.max_groups, sel.px_bound, _ptr(ws),
-                                              ws.numel(), _stream(dev), _ptr_or_null(range_flag), xch),
+    fin = (_ptr(psum), nparts, int(b_total), _ptr(med), B, L, int(k), int(pmax), int(min_thr), int(act_dtype),
+           int(max_unique or 0), float(log_base or 0.0), _ptr(desc), _ptr(amps), _ptr(wts))
+    if call is not None and (call.ws is not None or fuse_stage_a(call.plan)):
+        x = None                                         # stage A is in the workspace already
+        if call.ws is None:
+            x, call.ws = _ptr(call.x), _workspace(dev, _workspace_bytes(lib, call.plan, B, L, mg, pxb))
+        check(lib.ftn_period_finalize_stage_a(*fin, x, C.byref(call.plan), _ptr(call.wblob), mg, pxb, _ptr(call.ws),
+                                              call.ws.numel(), _stream(dev), _ptr_or_null(call.range_flag), xch),
               "ftn_period_finalize_stage_a")
-        sel.stage_a = (ws, x.data_ptr(), C.addressof(plan))
+        sel.stage_a = call
         return sel
-    check(lib.ftn_period_finalize(_ptr(psum), nparts, int(b_total), _ptr(med), B, L, int(k), int(pmax),
-                                  int(min_thr), int(act_dtype), int(max_unique or 0), float(log_base or 0.0), _ptr(desc),
-                                  _ptr(amps), _ptr(wts), _stream(dev), xch),
-          "ftn_period_finalize")
+    check(lib.ftn_period_finalize(*fin, _stream(dev), xch), "ftn_period_finalize")
     return sel
 
 
@@ -429,66 +438,30 @@ def timesblock_forward(x: torch.Tensor, plan: FtnPlan, wblob: torch.Tensor, sel:
     (reference :2050-2058) to the same call.  ``range_flag``: see ``new_range_flag``.
 
     ``rows_per_pass`` (None: one pass, B <= 65535): stages A-F run in passes of that many rows over the one
-    selection, through a workspace sized for one pass (``ftn_timesblock_forward_rows``); same bits as one pass."""
+    selection, through a workspace sized for one pass (the ``_rows`` entry points); same bits as one pass."""
     lib = _lib.load()
     B, L, _ = x.shape
-    if rows_per_pass is not None:
-        return _timesblock_forward_rows(lib, x, plan, wblob, sel, norm, act_dtype, range_flag, int(rows_per_pass))
-    need = _workspace_bytes(lib, plan, B, L, sel.max_groups, sel.px_bound)
-    flags = 0
-    pre = getattr(sel, "stage_a", None)
-    if pre is not None:
-        # the selector's finalize launch already ran stage A for THIS x and plan into a workspace it allocated
-        ws, x_ptr, plan_addr = pre
-        sel.stage_a = None
-        if x_ptr != x.data_ptr() or plan_addr != C.addressof(plan) or ws.numel() < need:
-            raise RuntimeError("selection carries stage A of a different input or plan")
-        flags = 1   # FTN_FWD_STAGE_A_DONE
-    else:
-        ws = _workspace(x.device, need)
-    y = torch.empty_like(x)
-    if norm is not None:
-        check(lib.ftn_timesblock_forward_norm(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
-                                              _ptr(sel.weights), sel.max_groups, sel.px_bound, flags, *_norm_args(norm),
-                                              _ptr(ws), ws.numel(), _stream(x.device), _ptr_or_null(range_flag)),
-              "ftn_timesblock_forward_norm")
-        return y
-    check(lib.ftn_timesblock_forward(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
-                                     _ptr(sel.weights), sel.max_groups, sel.px_bound, int(act_dtype), flags, _ptr(ws),
-                                     ws.numel(), _stream(x.device), _ptr_or_null(range_flag)), "ftn_timesblock_forward")
-    return y
-
-
-def _timesblock_forward_rows(lib, x, plan, wblob, sel, norm, act_dtype, range_flag, rows: int) -> torch.Tensor:
-    """``timesblock_forward`` through the ``_rows`` entry points: the workspace is that of one pass."""
-    B, L, _ = x.shape
-    if not 1 <= rows <= MAX_ROWS_PER_PASS:
+    rows = None if rows_per_pass is None else int(rows_per_pass)
+    if rows is not None and not 1 <= rows <= MAX_ROWS_PER_PASS:
         raise ValueError(f"rows_per_pass={rows} outside [1, {MAX_ROWS_PER_PASS}]")
-    n = min(B, rows)
+    n = B if rows is None else min(B, rows)                  # rows of a pass
     need = _workspace_bytes(lib, plan, n, L, sel.max_groups, sel.px_bound)
-    flags = 0
-    pre = getattr(sel, "stage_a", None)
-    if pre is not None:
-        ws, x_ptr, plan_addr = pre
-        sel.stage_a = None
+    # the selector's finalize launch may have run stage A for THIS x and plan into a workspace it allocated: that
+    # serves one forward (a second one on the same selection runs stage A itself, as the range guard's repair does)
+    call, sel.stage_a = sel.stage_a, None
+    if call is not None:
         if n < B:
             raise RuntimeError("selection carries a fused stage A, which serves a single pass only")
-        if x_ptr != x.data_ptr() or plan_addr != C.addressof(plan) or ws.numel() < need:
+        if call.x.data_ptr() != x.data_ptr() or C.addressof(call.plan) != C.addressof(plan) or call.ws.numel() < need:
             raise RuntimeError("selection carries stage A of a different input or plan")
-        flags = 1   # FTN_FWD_STAGE_A_DONE
-    else:
-        ws = _workspace(x.device, need)
+    ws = _workspace(x.device, need) if call is None else call.ws
+    flags = 0 if call is None else 1                         # FTN_FWD_STAGE_A_DONE
     y = torch.empty_like(x)
-    if norm is not None:
-        check(lib.ftn_timesblock_forward_norm_rows(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
-                                                   _ptr(sel.weights), sel.max_groups, sel.px_bound, flags,
-                                                   *_norm_args(norm), _ptr(ws), ws.numel(), _stream(x.device),
-                                                   _ptr_or_null(range_flag), rows), "ftn_timesblock_forward_norm_rows")
-        return y
-    check(lib.ftn_timesblock_forward_rows(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc),
-                                          _ptr(sel.weights), sel.max_groups, sel.px_bound, int(act_dtype), flags,
-                                          _ptr(ws), ws.numel(), _stream(x.device), _ptr_or_null(range_flag), rows),
-          "ftn_timesblock_forward_rows")
+    entry = "ftn_timesblock_forward" + ("" if norm is None else "_norm") + ("" if rows is None else "_rows")
+    mid = (int(act_dtype), flags) if norm is None else (flags, *_norm_args(norm))
+    check(getattr(lib, entry)(_ptr(x), _ptr(y), B, L, C.byref(plan), _ptr(wblob), _ptr(sel.desc), _ptr(sel.weights),
+                              sel.max_groups, sel.px_bound, *mid, _ptr(ws), ws.numel(), _stream(x.device),
+                              _ptr_or_null(range_flag), *(() if rows is None else (rows,))), entry)
     return y
 
 

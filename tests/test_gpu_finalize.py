@@ -375,8 +375,8 @@ def test_three_routes_agree_byte_for_byte(table, bound, ftn, dev):
         base = _run(ftn, dev, c)
         ref = (bytes(base[1]), base[2], base[3])
         x = torch.zeros(c["B"], c["L"], 16, device=dev)
-        fused = _run(ftn, dev, c, stage_a=(x, plan, wblob))
-        assert getattr(fused[0], "stage_a", None) is not None, c["name"]
+        fused = _run(ftn, dev, c, stage_a=ftn.runtime.StageA(x, plan, wblob))
+        assert fused[0].stage_a is not None, c["name"]
         got = (bytes(fused[1]), fused[2], fused[3])
         assert got[0] == ref[0] and torch.equal(got[1], ref[1]) and torch.equal(got[2], ref[2]), c["name"]
         if c["kind"] == "exact" and c["nparts"] == 1 and c["B"] >= 2:

@@ -289,10 +289,10 @@ def test_fused_finalize_stage_a_equals_two_launches(B, L, C, engine, ftn, dev, m
     for fuse in ("1", "0"):
         monkeypatch.setenv("FTN_FUSE_STAGE_A", fuse)
         wblob, plan = blk._packed(dev)
-        sel = blk.period_selector.select_device(x, stage_a=(plan, wblob))
-        assert (getattr(sel, "stage_a", None) is not None) == (fuse == "1")
+        sel = blk.period_selector.select_device(x, stage_a=rt.StageA(x, plan, wblob))
+        assert (sel.stage_a is not None) == (fuse == "1")
         y = rt.timesblock_forward(x, plan, wblob, sel)
-        assert getattr(sel, "stage_a", None) is None
+        assert sel.stage_a is None
         with torch.inference_mode():
             y2 = blk(x)
         assert blk._last_backend == "hip"
@@ -306,8 +306,9 @@ def test_fused_finalize_stage_a_equals_two_launches(B, L, C, engine, ftn, dev, m
     wblob, plan = blk._packed(dev)
     sm = blk.period_selector
     med, psum = rt.spectrum(x)
-    pre = rt.stage_a_only(x, plan, wblob, sm.k, sm.pmax, sm.min_period_threshold)
-    sel = rt.finalize(psum, B, med, L, sm.k, sm.pmax, sm.min_period_threshold, stage_a=(x, plan, wblob), pre=pre)
+    call = rt.StageA(x, plan, wblob)
+    rt.stage_a_only(call, sm.k, sm.pmax, sm.min_period_threshold)
+    sel = rt.finalize(psum, B, med, L, sm.k, sm.pmax, sm.min_period_threshold, stage_a=call)
     assert sel.stage_a is not None
     y = rt.timesblock_forward(x, plan, wblob, sel)
     for a, b in zip((sel.desc.cpu(), sel.amps.cpu(), sel.weights.cpu(), y.cpu()), outs[0][:4]):
@@ -321,7 +322,7 @@ def test_fused_stage_a_rejects_a_foreign_input(ftn, dev):
     blk.period_selector = ftn.models.FFTPeriodSelector(2, 48, 1)
     x = torch.from_numpy(ftn.synth.make_input(2, 48, 16, seed=1)).to(dev)
     wblob, plan = blk._packed(dev)
-    sel = blk.period_selector.select_device(x, stage_a=(plan, wblob))
+    sel = blk.period_selector.select_device(x, stage_a=rt.StageA(x, plan, wblob))
     with pytest.raises(RuntimeError, match="different input"):
         rt.timesblock_forward(x.clone(), plan, wblob, sel)
 

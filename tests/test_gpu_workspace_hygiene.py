@@ -311,7 +311,7 @@ def test_selection_buffers_ignore_their_old_content(B, L, C, K, d_ff, engine, fu
                                                  ctypes.byref(plan), wblob.data_ptr(), mg, pxb, ws.data_ptr(), ws.numel(),
                                                  st, flag.data_ptr(), None)
             ftn.lib.check(rc, "ftn_period_finalize_stage_a")
-            sel.stage_a = (ws, x.data_ptr(), ctypes.addressof(plan))
+            sel.stage_a = rt.StageA(x, plan, wblob, flag, ws)
         else:
             rc = lib.ftn_period_finalize(psum.data_ptr(), 1, B, med.data_ptr(), B, L, k, pmax, thr, 0, 0, 0.0,
                                          desc.data_ptr(), amps.data_ptr(), wts.data_ptr(), st, None)

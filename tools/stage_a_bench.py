@@ -10,10 +10,10 @@ blk.period_selector = pkg.models.FFTPeriodSelector(5, L)
 x = torch.from_numpy(pkg.synth.make_input(B, L, C, seed=0)).to(dev)
 wblob, plan = blk._packed(dev)
 sm = blk.period_selector
-for _ in range(5): rt.stage_a_only(x, plan, wblob, sm.k, sm.pmax, sm.min_period_threshold)
+for _ in range(5): rt.stage_a_only(rt.StageA(x, plan, wblob), sm.k, sm.pmax, sm.min_period_threshold)
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
-for _ in range(200): rt.stage_a_only(x, plan, wblob, sm.k, sm.pmax, sm.min_period_threshold)
+for _ in range(200): rt.stage_a_only(rt.StageA(x, plan, wblob), sm.k, sm.pmax, sm.min_period_threshold)
 e1.record(); torch.cuda.synchronize()
 print("stage A only: %.1f us" % (e0.elapsed_time(e1) / 200 * 1e3))
