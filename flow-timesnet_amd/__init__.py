@@ -20,7 +20,9 @@ Sub-modules
                      search behind ``nb_quantiles`` and ``nb_sample``, Philox4x32-10 and ``sample_uniforms``; pure
                      functions without a backend choice (``score`` re-exports what callers use)
 ``windows``          ``DeviceWindows``: the batches of a rolling-origin backtest formed on the device from the wide
-                     table, in the order and shapes of the reference's ``SlidingWindowDataset`` + ``DataLoader``
+                     table, in the order and shapes of the reference's ``SlidingWindowDataset`` + ``DataLoader``; with
+                     ``shuffle`` / ``drop_last`` / ``seed`` / ``augment`` the training loader: shuffled epochs, time
+                     shift and noise as pure functions of ``(seed, epoch)``
 ``table``            the table's preparation on the device: ``series_features`` (the reference's static features, the
                      full-history spectrum on the matrix pipe), ``SeriesScaler`` (fit, transform, inverse and clip),
                      ``holdout_rows`` / ``rolling_rows``

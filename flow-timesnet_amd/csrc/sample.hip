@@ -16,6 +16,7 @@
 // Loops: the draws (S, a launch argument) and nq_level's capped loops; no wave spins on data.  An answer >= 2^24 or
 // a cap reached gives NaN and raises FTN_NBQ_RANGE; alpha or mu not finite gives NaN and leaves the flag alone.
 #include "ftn_nbq.h"
+#include "ftn_philox.h"
 
 struct NbsArgs {
   const float* rate;  const float* disp;
@@ -30,21 +31,6 @@ struct NbsArgs {
   int S;
   unsigned offset;
 };
-
-struct NbsWords { unsigned x, y, z, w; };
-
-// Philox4x32-10 (Salmon et al., SC 2011): ten rounds, the key bumped by the Weyl constants between them
-__device__ inline NbsWords ns_philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0;  c1 = l1;
-    c2 = h0 ^ c3 ^ k1;  c3 = l0;
-    k0 += 0x9E3779B9u;  k1 += 0xBB67AE85u;
-  }
-  return {c0, c1, c2, c3};
-}
 
 template <int CPL>
 __global__ __launch_bounds__(NBQ_THREADS) void k_nb_sample(NbsArgs a) {
@@ -61,10 +47,10 @@ __global__ __launch_bounds__(NBQ_THREADS) void k_nb_sample(NbsArgs a) {
       const bool valid = nq_dist(NQ_LANE(rv, j), NQ_LANE(dv, j), a.eps, D);
       const double pm0 = nq_exp(D.r * D.lp);                    // pmf(0) = F(0) = p^r; 0 where it underflows
       const unsigned long long e = (unsigned long long)(e0 + j);
-      NbsWords wd = {0u, 0u, 0u, 0u};
+      PhiloxWords wd = {0u, 0u, 0u, 0u};
 #pragma unroll 1
       for (int s = 0; s < a.S; ++s) {
-        if ((s & 3) == 0) wd = ns_philox((unsigned)e, (unsigned)(e >> 32), (unsigned)s >> 2, a.offset, k0, k1);
+        if ((s & 3) == 0) wd = ftn_philox((unsigned)e, (unsigned)(e >> 32), (unsigned)s >> 2, a.offset, k0, k1);
         const unsigned word = (s & 3) == 0 ? wd.x : (s & 3) == 1 ? wd.y : (s & 3) == 2 ? wd.z : wd.w;
         const double u = ((double)word + 0.5) * 2.3283064365386963e-10;   // 2^-32
         NbWalk w = {0.0, pm0, pm0, 0.0, pm0 > 0.0};

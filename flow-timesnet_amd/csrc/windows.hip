@@ -22,14 +22,10 @@
 // A piece without a table (mask when M is null) stores 1.0f and reads nothing.  The start rows are read from the
 // device and clamped to 0 .. T - L - H, so a device copy that disagrees with the validated host copy cannot address
 // anything outside the tables; rows r >= count and series outside the batch's share of a window are never touched.
-#include "ftn_common.h"
+#include "ftn_win.h"
 
-#define WIN_THREADS 256
 #define WIN_LDS_STRIDE (FTN_WIN_TILE_SERIES + 1)
-#define WIN_CHUNK 1024
-#define WIN_GRID_MAX 4096
 #define WIN_PIECES 7
-#define WIN_ONE 0x3f800000u
 
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
@@ -155,12 +151,8 @@ __global__ __launch_bounds__(WIN_THREADS) void k_window_batch(WinLaunch a) {
 }
 
 // ---- host: one plan for ftn_window_batch_form and the launch ----
-static bool win_mul(long long a, long long b, long long* out) {
-  return !__builtin_mul_overflow(a, b, out) && *out <= (1LL << 61);
-}
-
-// The dimension checks both entry points share (everything but the start rows and the item range).
-static int win_check_dims(const char* who, const FtnWindowArgs* a) {
+// The dimension checks every entry point shares (everything but the start rows and the item range).
+int win_check_dims(const char* who, const FtnWindowArgs* a) {
   FTN_CHECK_ARG(a != nullptr, "%s: null arguments", who);
   FTN_CHECK_ARG(a->layout == FTN_WIN_SERIES || a->layout == FTN_WIN_WIDE, "%s: layout=%d is not FTN_WIN_SERIES or "
                 "FTN_WIN_WIDE", who, a->layout);
@@ -191,6 +183,21 @@ static int win_check_dims(const char* who, const FtnWindowArgs* a) {
   FTN_CHECK_ARG((((uintptr_t)a->ids | (uintptr_t)a->id_out) & 7) == 0, "%s: ids must be 8-byte aligned", who);
   FTN_CHECK_ARG(a->x || a->y || a->mask || a->x_mark || a->y_mark || a->static_out || a->id_out, "%s: no output "
                 "requested", who);
+  return 0;
+}
+
+int win_check_starts(const char* who, const FtnWindowArgs* a) {
+  FTN_CHECK_ARG(a->starts != nullptr && a->starts_host != nullptr, "%s: null starts or starts_host", who);
+  FTN_CHECK_ARG(a->W >= 1, "%s: W=%d windows", who, a->W);
+  const long long span = (long long)a->L + a->H;
+  FTN_CHECK_ARG(a->T >= span, "%s: T=%lld rows hold no window of L + H = %lld", who, a->T, span);
+  long long reach = 0;                                          // every product in 64 bits
+  FTN_CHECK_ARG(win_mul(a->T, a->x_stride, &reach) && (a->M == nullptr || win_mul(a->T, a->m_stride, &reach)) &&
+                    (a->marks == nullptr || win_mul(a->T, a->marks_stride, &reach)),
+                "%s: T=%lld rows at the given strides pass 64 bits", who, a->T);
+  for (int w = 0; w < a->W; ++w)
+    FTN_CHECK_ARG(a->starts_host[w] >= 0 && a->starts_host[w] + span <= a->T, "%s: window %d starts at row %d, outside "
+                  "0..T - L - H = %lld", who, w, a->starts_host[w], a->T - span);
   return 0;
 }
 
@@ -238,17 +245,9 @@ extern "C" int ftn_window_batch_form(const FtnWindowArgs* a) {
 extern "C" int ftn_window_batch(const FtnWindowArgs* a, void* stream) {
   const char* who = "ftn_window_batch";
   if (win_check_dims(who, a) < 0) return -1;
-  FTN_CHECK_ARG(a->starts != nullptr && a->starts_host != nullptr, "%s: null starts or starts_host", who);
-  FTN_CHECK_ARG(a->W >= 1, "%s: W=%d windows", who, a->W);
+  if (win_check_starts(who, a) < 0) return -1;
   const long long span = (long long)a->L + a->H;
-  FTN_CHECK_ARG(a->T >= span, "%s: T=%lld rows hold no window of L + H = %lld", who, a->T, span);
-  long long reach = 0, items = 0, words = 0;                    // every product in 64 bits
-  FTN_CHECK_ARG(win_mul(a->T, a->x_stride, &reach) && (a->M == nullptr || win_mul(a->T, a->m_stride, &reach)) &&
-                    (a->marks == nullptr || win_mul(a->T, a->marks_stride, &reach)),
-                "%s: T=%lld rows at the given strides pass 64 bits", who, a->T);
-  for (int w = 0; w < a->W; ++w)
-    FTN_CHECK_ARG(a->starts_host[w] >= 0 && a->starts_host[w] + span <= a->T, "%s: window %d starts at row %d, outside "
-                  "0..T - L - H = %lld", who, w, a->starts_host[w], a->T - span);
+  long long items = 0, words = 0;                               // every product in 64 bits
   const bool series = a->layout == FTN_WIN_SERIES;
   items = series ? (long long)a->W * a->N : a->W;               // W, N < 2^31
   FTN_CHECK_ARG(a->count >= 1, "%s: count=%lld is not positive", who, a->count);

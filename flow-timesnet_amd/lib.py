@@ -151,6 +151,15 @@ class FtnWindowArgs(C.Structure):
         (n, C.c_void_p) for n in ("x", "y", "mask", "x_mark", "y_mark", "static_out", "id_out")]
 
 
+class FtnWindowGatherArgs(C.Structure):
+    """Mirror of ``struct FtnWindowGatherArgs`` (include/flowtimes.h): an ``FtnWindowArgs`` (``item0`` is the part's
+    first global item), the series-major tables, the item list and the epoch's generator words."""
+
+    _fields_ = [("w", FtnWindowArgs), ("XT", C.c_void_p), ("xt_stride", C.c_longlong), ("MT", C.c_void_p),
+                ("mt_stride", C.c_longlong), ("items", C.c_void_p), ("seed", C.c_ulonglong),
+                ("noise_std", C.c_double), ("epoch", C.c_uint32), ("ts", C.c_int32)]
+
+
 FTN_TAB_CLIP, FTN_TAB_MASK, FTN_TAB_DIFF, FTN_TAB_INVERSE = 1, 2, 4, 8
 FTN_TAB_ZSCORE, FTN_TAB_MINMAX = 0, 1
 FTN_TAB_PARTIALS_MAX, FTN_TAB_SPEC_COLS, FTN_TAB_SPEC_BINS, FTN_TAB_SPEC_CHUNK = 32, 64, 128, 128
@@ -333,6 +342,9 @@ _SIGNATURES = {
     # device windows (csrc/windows.hip)
     "ftn_window_batch_form": (C.c_int, [C.POINTER(FtnWindowArgs)]),
     "ftn_window_batch": (C.c_int, [C.POINTER(FtnWindowArgs), _P]),
+    # training windows (csrc/windows_gather.hip)
+    "ftn_epoch_keys": (C.c_int, [C.c_longlong, C.c_ulonglong, C.c_uint, _P, _P]),
+    "ftn_window_gather": (C.c_int, [C.POINTER(FtnWindowGatherArgs), _P]),
     # table preparation (csrc/table.hip)
     "ftn_table_moments_bytes": (C.c_size_t, [C.c_longlong, C.c_int]),
     "ftn_table_moments_form": (C.c_int, [C.POINTER(FtnTableMomentsArgs), C.POINTER(FtnTableForm)]),

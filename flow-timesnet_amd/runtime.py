@@ -1488,6 +1488,12 @@ def window_batch(X: torch.Tensor, starts: torch.Tensor, starts_host, L: int, H: 
     words as a contiguous int32 numpy array.  One launch on the current stream; enqueues only."""
     who = "window_batch"
     a = _window_args(who, X, L, H, M, marks, statics, ids, layout, outs, int(count))
+    _window_starts(who, a, X, starts, starts_host)
+    a.item0, a.count = int(item0), int(count)
+    check(_lib.load().ftn_window_batch(C.byref(a), _stream(X.device)), "ftn_window_batch")
+
+
+def _window_starts(who: str, a, X, starts, starts_host) -> None:
     if (not isinstance(starts, torch.Tensor) or starts.dim() != 1 or starts.dtype != torch.int32
             or starts.device != X.device or not starts.is_contiguous()):
         raise ValueError(f"{who}: starts must be a contiguous int32 vector on X's device")
@@ -1496,8 +1502,71 @@ def window_batch(X: torch.Tensor, starts: torch.Tensor, starts_host, L: int, H: 
             or not starts_host.flags["C_CONTIGUOUS"]):
         raise ValueError(f"{who}: starts_host must be a contiguous int32 numpy array of {W} start rows")
     a.starts, a.starts_host, a.W = _ptr(starts), starts_host.ctypes.data, W
-    a.item0, a.count = int(item0), int(count)
-    check(_lib.load().ftn_window_batch(C.byref(a), _stream(X.device)), "ftn_window_batch")
+
+
+# ------------------------------------------------------------------ training windows
+WINDOW_EPOCH_MAX = 1 << 30
+
+
+def window_epoch_check(who: str, seed, epoch, ts=0, noise_std=0.0):
+    """``(seed, epoch, ts, noise_std)`` as the words the generator takes, or a ValueError: ``seed`` is taken modulo
+    2^64, ``0 <= epoch < 2^30``, ``ts >= 0`` with ``2 ts + 1 < 2^32`` (and within the int32 the C entry takes),
+    ``noise_std`` finite and not negative."""
+    epoch, ts, sd = int(epoch), int(ts), float(noise_std)
+    if not 0 <= epoch < WINDOW_EPOCH_MAX:
+        raise ValueError(f"{who}: epoch={epoch} is outside [0, 2^30)")
+    if ts < 0 or 2 * ts + 1 >= 1 << 32:
+        raise ValueError(f"{who}: time_shift={ts} must be >= 0 with 2 time_shift + 1 < 2^32")
+    if not 0.0 <= sd < float("inf"):
+        raise ValueError(f"{who}: add_noise_std={noise_std} must be finite and >= 0")
+    return int(seed) & 0xFFFFFFFFFFFFFFFF, epoch, ts, sd
+
+
+def epoch_keys(n: int, seed: int, epoch: int, device) -> torch.Tensor:
+    """``ftn_epoch_keys``: int64 ``[n]`` on ``device`` (a ROCm device), ``key64(k)`` of the epoch's order for
+    ``k < n``; the order is ``torch.argsort(keys, stable=True)``.  One launch on the current stream."""
+    who = "epoch_keys"
+    seed, epoch, _, _ = window_epoch_check(who, seed, epoch)
+    device = torch.device(device)
+    if int(n) < 1 or device.type != "cuda":
+        raise ValueError(f"{who}: n={n} keys on {device}: n must be positive and the device a ROCm device")
+    keys = torch.empty(int(n), dtype=torch.int64, device=device)
+    check(_lib.load().ftn_epoch_keys(int(n), seed, epoch, _ptr(keys), _stream(keys.device)), "ftn_epoch_keys")
+    return keys
+
+
+def window_gather(X: torch.Tensor, starts: torch.Tensor, starts_host, L: int, H: int, item_lo: int,
+                  items: torch.Tensor, outs: dict, XT=None, M=None, MT=None, marks=None, statics=None, ids=None,
+                  layout: str = "series", time_shift: int = 0, noise_std: float = 0.0, seed: int = 0,
+                  epoch: int = 0) -> None:
+    """``ftn_window_gather``: fills rows ``0 .. count - 1`` of the tensors in ``outs`` (as for ``window_batch``) with
+    the items ``items`` (contiguous int64 ``[count]`` on X's device, global indices, not read back) that belong to
+    this part, whose first item is ``item_lo``; the other rows are left untouched.  ``XT`` [N, T] (and ``MT``) are the
+    series-major copies the series layout reads (rows contiguous, at least T apart); the wide layout reads ``X`` and
+    ``M``.  ``time_shift``, ``noise_std``, ``seed`` and ``epoch`` as in include/flowtimes.h.  One launch on the
+    current stream; enqueues only."""
+    who = "window_gather"
+    seed, epoch, ts, sd = window_epoch_check(who, seed, epoch, time_shift, noise_std)
+    if (not isinstance(items, torch.Tensor) or items.dim() != 1 or items.dtype != torch.int64 or items.numel() < 1
+            or not items.is_contiguous() or not isinstance(X, torch.Tensor) or items.device != X.device):
+        raise ValueError(f"{who}: items must be a non-empty contiguous int64 vector on X's device")
+    count = items.numel()
+    g = _lib.FtnWindowGatherArgs()
+    g.w = _window_args(who, X, L, H, M, marks, statics, ids, layout, outs, count)
+    a = g.w                                                     # a view of the embedded record
+    _window_starts(who, a, X, starts, starts_host)
+    if int(item_lo) < 0:
+        raise ValueError(f"{who}: item_lo={item_lo} is negative")
+    a.item0, a.count = int(item_lo), count
+    if layout == "series":
+        if XT is None:
+            raise ValueError(f"{who}: the series layout takes XT, the series-major copy of X")
+        g.XT, g.xt_stride, Nx, Tx = _window_table(who, "XT", XT, None, X)
+        g.MT, g.mt_stride, Nm, Tm = _window_table(who, "MT", MT, None, X)
+        if (Nx, Tx) != (a.N, a.T) or (MT is not None and (Nm, Tm) != (a.N, a.T)) or (M is None) != (MT is None):
+            raise ValueError(f"{who}: XT (and MT beside M) must be [N, T] = [{a.N}, {a.T}]")
+    g.items, g.seed, g.noise_std, g.epoch, g.ts = _ptr(items), seed, sd, epoch, ts
+    check(_lib.load().ftn_window_gather(C.byref(g), _stream(X.device)), "ftn_window_gather")
 
 
 # ------------------------------------------------------------------ table preparation

@@ -1091,6 +1091,57 @@ typedef struct FtnWindowArgs {
 int ftn_window_batch_form(const FtnWindowArgs* args);
 int ftn_window_batch(const FtnWindowArgs* args, void* stream);
 
+/* ---- training windows: shuffled epochs, time shift and noise (csrc/windows_gather.hip) ----
+ * Additions only: FTN_ABI_VERSION stays 14.
+ *
+ * The reference trains on DataLoader(SlidingWindowDataset(..., augment), shuffle=True, drop_last=True) (train.py:933,
+ * data/dataset.py:181-193).  Here an epoch is a pure function of (seed, epoch) on the project's own generator,
+ * Philox4x32-10 as in ftn_nb_sample: key = (seed & 0xffffffff, seed >> 32), counter = (k & 0xffffffff, k >> 32, q,
+ * epoch << 2 | purpose), k the item's global index, 0 <= epoch < 2^30, output words (x, y, z, w).
+ *   order  (purpose 0, q = 0)  key64(k) = the signed int64 with bits (x << 32) | y; the epoch's order is the stable
+ *          ascending argsort of key64(0 .. n_items - 1).  ftn_epoch_keys writes key64(k), k < n, in one launch; the
+ *          sort is the caller's, once per epoch.
+ *   shift  (purpose 1, q = 0, ts >= 1)  delta = ((uint64) x (2 ts + 1) >> 32) - ts; the item's start row is
+ *          clamp(starts[w] + delta, 0, T - L - H) and serves x, y, mask, x_mark and y_mark together.  ts = 0: no shift
+ *          and no generator call.
+ *   noise  (purpose 2, noise_std > 0)  j = the element's index inside the item's x (l in FTN_WIN_SERIES, l N + n in
+ *          FTN_WIN_WIDE), q = j >> 2; words (x, y) serve lanes j & 3 = 0, 1 and (z, w) lanes 2, 3: for a pair (a, b),
+ *          u1 = (a + 0.5) 2^-32, u2 = (b + 0.5) 2^-32, r = sqrt(-2 ln u1), the even lane gets z = r cos(2 pi u2) and
+ *          the odd lane z = r sin(2 pi u2), all in fp64; x_out = fp32(double(x) + noise_std z), the product and the
+ *          sum rounded once each.  Only x is touched; noise_std = 0 leaves it a bit copy.
+ *
+ * ftn_window_gather (k_window_gather) enqueues ONE kernel on `stream` that writes the pieces of the items
+ * items[0 .. count - 1] (int64 on the device, global indices) into rows 0 .. count - 1 of the outputs of `w`, which
+ * are those of ftn_window_batch with the same shapes.  w.item0 is item_lo, the global index of this part's first
+ * item; a row whose item is outside item_lo .. item_lo + (W N | W) - 1 is left untouched and nothing is read for it,
+ * so a batch over several parts is one launch per part into the same outputs.  It never allocates and never
+ * synchronises; the items are not validated on the host and need not be.
+ *   FTN_WIN_SERIES  x, y and mask are read from the series-major copies XT [N][xt_stride] and MT [N][mt_stride]
+ *                   (row strides >= T; XT[i][t] = X[t][i]; MT null: a mask of ones): an item's x and y are the
+ *                   contiguous run XT[i][s .. s + L + H).  w.X and w.M are checked like ftn_window_batch's and not
+ *                   read.  statics and ids as in ftn_window_batch.
+ *   FTN_WIN_WIDE    x, y and mask are rows of w.X and w.M; XT and MT are ignored.
+ *   the marks       rows of w.marks in both layouts.
+ * The kernel is row copies: units of 1024 consecutive output words over at most 4096 workgroups of 256 threads, one
+ * indirection per row (the rows of a unit get their series and shifted start once, in LDS), consecutive lanes on
+ * consecutive words of a table row, 4 bytes a lane; every address is formed in 64 bits and no grid dimension carries
+ * count, L or T.  There is one kernel form.
+ * Limits, checked before the launch: those of ftn_window_batch on `w` (its item range aside), item_lo >= 0,
+ * count >= 1, items non-null and 8-byte aligned, ts >= 0 (so 2 ts + 1 < 2^32), noise_std finite and >= 0,
+ * epoch < 2^30, XT given with xt_stride >= T in FTN_WIN_SERIES.  Anything else is a negative return with
+ * ftn_last_error set and nothing launched. */
+typedef struct FtnWindowGatherArgs {
+  FtnWindowArgs w;                                        /* tables, starts, dimensions, outputs; item0 = item_lo */
+  const float* XT;       long long xt_stride;             /* [N][xt_stride] series-major values (FTN_WIN_SERIES) */
+  const float* MT;       long long mt_stride;             /* [N][mt_stride] series-major validity (null: ones) */
+  const long long* items;                                 /* [count] global item indices, on the device */
+  unsigned long long seed;
+  double noise_std;
+  uint32_t epoch; int32_t ts;
+} FtnWindowGatherArgs;
+int ftn_epoch_keys(long long n, unsigned long long seed, unsigned epoch, long long* keys_dev, void* stream);
+int ftn_window_gather(const FtnWindowGatherArgs* args, void* stream);
+
 /* ---- table preparation: static features, scalers, their transform and inverse (csrc/table.hip) ----
  * Additions only: FTN_ABI_VERSION stays 14.
  *
