@@ -29,6 +29,13 @@ kernels - ``ftn_head_fit_forward`` (the heads, keeping softplus' derivative at b
 sum).  On tensors those kernels do not take (CPU, other dtypes) ``head_nll`` is the torch composition of the heads
 with the loss node; ``_last_head_backend`` says which ran.
 
+``time_projection`` is ``forecast_time_proj`` as a node of its own (``ftn_timeproj_forward`` forward,
+``ftn_timeproj_backward`` in ``csrc/timeproj_bwd.hip`` backward, on the ``seq`` rows ``TimesNet.output_inputs``
+returns), ``output_nll`` that node followed by ``head_nll``, and ``refit_output`` the loop of ``refit_heads`` over the
+whole output side: the time projection and both heads, with the reference's gradient clipping when asked.  The
+backbone stays frozen on the HIP path and every gradient comes from this library's kernels, in a fixed summation
+order; ``_last_timeproj_backend`` says which path the projection took.
+
 ``backend`` follows ``score``'s rule (``_use_hip``): ``hip`` where it can run unless ``"torch"`` is asked for, and
 asking for ``"hip"`` where it cannot is an error.
 """
@@ -304,6 +311,144 @@ def refit_heads(model, batches, epochs: int = 1, lr: float = 1e-3, use_loss_mask
         raise ValueError("refit_heads: no batches")
     out, flag = torch.stack(losses), torch.cat(bads)
     host = torch.cat([out, flag.to(out.dtype)]).cpu()           # the one synchronisation
+    seen = 0
+    for v in host[len(losses):].tolist():
+        seen |= int(v)
+    for bit, name in ((1, "rate"), (2, "dispersion")):
+        if seen & bit:
+            raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
+    return host[:len(losses)]
+
+
+# ------------------------------------------------------------------ the whole output side: time projection + heads
+_last_timeproj_backend: Optional[str] = None  # which path the last ``time_projection`` took
+
+
+class _TimeProjection(torch.autograd.Function):
+    """``forecast_time_proj`` as one node: ``ftn_timeproj_forward`` (the bits of inference) forward,
+    ``ftn_timeproj_backward`` backward.  ``seq`` is a constant: no ``d_seq`` is computed."""
+
+    @staticmethod
+    def forward(ctx, seq, wt, bt):
+        from . import runtime as rt
+
+        seq = seq.detach().contiguous()
+        ctx.save_for_backward(seq)
+        return rt.timeproj_forward(seq, wt.detach(), bt.detach())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_hidden):
+        from . import runtime as rt
+
+        (seq,) = ctx.saved_tensors
+        d_hidden = d_hidden.contiguous()
+        if d_hidden.dtype != torch.float32 or d_hidden.data_ptr() % 16:     # (ftn_head_backward's own is neither)
+            d_hidden = d_hidden.float().clone()
+        dw, db = rt.timeproj_backward(seq, d_hidden)
+        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
+
+
+def time_projection(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> torch.Tensor:
+    """``hidden[b] = wt @ seq[b] + bt[:, None]``, ``[B, S, D]`` from ``seq [B, L, D]`` (``TimesNet.output_inputs``),
+    ``wt [S, L]`` and ``bt [S]``, differentiable in ``wt`` and ``bt``.  ``wt`` / ``bt`` may be the row slices
+    ``weight[-steps:]`` / ``bias[-steps:]`` of a taller projection: autograd scatters the gradient into the full
+    parameter and the other rows get exact zeros.  On fp32 ROCm tensors with d_model a multiple of 4 up to 512 and a
+    ``seq`` that does not require grad it is ``ftn_timeproj_forward`` (the bits of inference) with
+    ``ftn_timeproj_backward`` as its backward (``_last_timeproj_backend == "hip"``); otherwise - CPU tensors, other
+    dtypes, other widths, a ``seq`` that requires grad (no ``d_seq`` is computed here) - the torch composition
+    ``torch.matmul(wt, seq) + bt.view(1, -1, 1)``."""
+    if seq.dim() != 3 or wt.dim() != 2 or bt.dim() != 1 or wt.shape[1] != seq.shape[1] or bt.shape[0] != wt.shape[0]:
+        raise ValueError(f"time_projection: seq {tuple(seq.shape)}, wt {tuple(wt.shape)} and bt {tuple(bt.shape)} do "
+                         "not fit [B, L, D], [S, L] and [S]")
+    global _last_timeproj_backend
+    B, L, D = seq.shape
+    S = wt.shape[0]
+    if (seq.is_cuda and D % 4 == 0 and 4 <= D <= 512 and seq.numel() > 0 and S >= 1
+            and all(t.is_cuda and t.dtype == torch.float32 and t.device == seq.device for t in (seq, wt, bt))
+            and not (torch.is_grad_enabled() and seq.requires_grad)
+            and (S == 1 or wt.stride(0) == L) and (L == 1 or wt.stride(1) == 1) and (S == 1 or bt.stride(0) == 1)
+            and seq.data_ptr() % 16 == 0):
+        _last_timeproj_backend = "hip"
+        return _TimeProjection.apply(seq, wt, bt)
+    _last_timeproj_backend = "torch"
+    return torch.matmul(wt, seq) + bt.view(1, -1, 1)
+
+
+def output_nll(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor,
+               w_sigma: torch.Tensor, b_sigma: torch.Tensor, tail: torch.Tensor, hist: int, y: torch.Tensor,
+               mask: torch.Tensor | None = None, late: torch.Tensor | None = None, floor: torch.Tensor | None = None,
+               min_sigma: float = 1e-3):
+    """The whole output side on ``seq [B, L, D]`` (``TimesNet.output_inputs``): ``time_projection`` then ``head_nll``,
+    ``(loss, bad)``.  ``loss.backward()`` leaves gradients in ``wt``, ``bt`` and the four head tensors; on the device
+    path every one of them comes from ``ftn_head_backward`` (which also writes ``d_hidden``) and
+    ``ftn_timeproj_backward``."""
+    hidden = time_projection(seq, wt, bt)
+    return head_nll(hidden, w_mu, b_mu, w_sigma, b_sigma, tail, hist, y, mask, late, floor, min_sigma)
+
+
+def refit_output(model, batches, epochs: int = 1, lr: float = 1e-3, use_loss_mask: bool = False, optimizer=None,
+                 grad_clip: Optional[float] = None):
+    """``refit_heads`` over the whole output side of a ``TimesNet``: ``forecast_time_proj`` (its last
+    ``model._out_steps`` rows are what a step reads; the other rows of a recursive model get zero gradients),
+    ``mu_head`` and ``sigma_head``, everything else frozen.  Per batch ``model.output_inputs`` -> ``output_nll`` ->
+    ``backward()`` -> (with ``grad_clip``, the reference's ``clip_grad_norm_`` over the six tensors, train.py:1513-1515)
+    -> a step of ``optimizer`` (default: Adam with ``lr`` over the six tensors).  Losses and ``bad`` words stay on
+    the device until the one synchronisation at the end, which raises the reference's RuntimeError if a rate or
+    dispersion was not finite and > 0.  Returns the losses, fp32 ``[epochs * batches]`` on the host; mode and
+    ``requires_grad`` flags come back as they were."""
+    from .score import _unpack_batch
+
+    proj = model.forecast_time_proj
+    params = [model.mu_head.weight, model.mu_head.bias, model.sigma_head.weight, model.sigma_head.bias,
+              proj.weight, proj.bias]
+    dev = params[0].device
+    flags = [(p, p.requires_grad) for p in model.parameters()]
+    was_training = model.training
+    losses, bads = [], []
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        for p in params:
+            p.requires_grad_(True)
+        opt = optimizer if optimizer is not None else torch.optim.Adam(params, lr=lr)
+        model.eval()
+        steps = int(model._out_steps)
+        for _ in range(int(epochs)):
+            for batch in batches:
+                xb, yb, mask, x_mark, _, static, ids = _unpack_batch(batch)
+                move = lambda t: None if t is None else t.to(dev, non_blocking=True)
+                seq, tail, hist, late, floor = model.output_inputs(
+                    move(xb), move(x_mark), move(static),
+                    None if ids is None else ids.to(device=dev, dtype=torch.long, non_blocking=True))
+                yb = move(yb)[:, :steps, :]
+                if use_loss_mask and mask is None:
+                    raise ValueError("refit_output: use_loss_mask needs a mask in every batch")
+                base = (move(mask)[:, :steps, :] > 0.0) if use_loss_mask else None
+                opt.zero_grad(set_to_none=True)
+                with torch.enable_grad():
+                    loss, bad = output_nll(seq, proj.weight[-steps:], proj.bias[-steps:], *params[:4], tail, hist, yb,
+                                           base, late, floor, model.min_sigma)
+                loss.backward()
+                if grad_clip is not None:
+                    torch.nn.utils.clip_grad_norm_(params, float(grad_clip))
+                opt.step()
+                losses.append(loss.detach())
+                bads.append(bad)
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
+        model.train(was_training)
+    if not losses:
+        raise ValueError("refit_output: no batches")
+    return _losses_or_raise(losses, bads)
+
+
+def _losses_or_raise(losses, bads) -> torch.Tensor:
+    """The one synchronisation of a refit loop: the losses on the host, after the reference's RuntimeError if any
+    ``bad`` word has a bit set."""
+    out, flag = torch.stack(losses), torch.cat(bads)
+    host = torch.cat([out, flag.to(out.dtype)]).cpu()
     seen = 0
     for v in host[len(losses):].tolist():
         seen |= int(v)

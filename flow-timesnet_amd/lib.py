@@ -54,6 +54,7 @@ SCORE_PART_BYTES = C.sizeof(FtnScorePart)
 FTN_QMAX = 8
 FTN_NBG_PARTS_MAX = 1024
 FTN_HEADFIT_COLSUM, FTN_HEADFIT_MFMA, FTN_HEADFIT_CHUNKS_MAX = 1, 2, 256
+FTN_TIMEPROJ_BWD_MFMA, FTN_TIMEPROJ_BWD_CHUNKS_MAX, TIMEPROJ_BWD_CHUNK = 1, 256, 8
 FTN_NBQ_RANGE = 2
 FTN_PATHS_MAX = 1024
 FTN_PATH_SUM, FTN_PATH_MAX = 0, 1
@@ -314,6 +315,10 @@ _SIGNATURES = {
                                        C.c_int, _P, C.c_longlong, _P, C.c_float, _P, _P, _P, _P, _P, _P]),
     "ftn_head_backward": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                     _P, _P, C.c_size_t, _P]),
+    # time projection backward (csrc/timeproj_bwd.hip)
+    "ftn_timeproj_backward_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ftn_timeproj_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ftn_timeproj_backward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
     "ftn_nbq_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_nb_cdf": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
                              C.c_float, _P, _P, _P, _P]),

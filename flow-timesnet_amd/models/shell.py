@@ -995,6 +995,18 @@ class TimesNet(nn.Module):
         floor)``: ``hidden [B, steps, d_model]``, ``tail`` the last ``hist`` rows of the input window (a view),
         ``late`` the gated late bias ``[1|B, steps, N]`` or None, ``floor`` ``min_sigma_vector`` flattened or None
         (the scalar ``min_sigma`` applies).  Nothing is recorded for autograd."""
+        return self._refit_inputs(x, x_mark, series_static, series_ids, projected=True)
+
+    def output_inputs(self, x: torch.Tensor, x_mark: Optional[torch.Tensor] = None,
+                      series_static: Optional[torch.Tensor] = None, series_ids: Optional[torch.Tensor] = None):
+        """``head_inputs`` stopped one stage earlier, for a refit of the time projection and the heads
+        (``fit.refit_output``): ``(seq, tail, hist, late, floor)`` with ``seq [B, input_len, d_model]`` the block
+        stack's output, contiguous, and the rest as ``head_inputs`` returns it.  Nothing is recorded for autograd."""
+        return self._refit_inputs(x, x_mark, series_static, series_ids, projected=False)
+
+    def _refit_inputs(self, x, x_mark, series_static, series_ids, projected: bool):
+        """The body ``head_inputs`` and ``output_inputs`` share, under ``no_grad`` and the range guard: the first
+        leaves after ``_time_projection``, the second before it."""
         def once():
             L = self.input_len
             if x.dim() != 3 or x.size(1) < L:
@@ -1005,10 +1017,13 @@ class TimesNet(nn.Module):
             rows = self._context_rows(window, series_static, series_ids)
             seq = self._stack(self._embed(window, mark, rows))
             steps = self._out_steps
-            hidden = self._time_projection(seq, steps, self._hip_heads_ok(seq, window))
+            if projected:                                       # hidden [B, steps, D]
+                first = self._time_projection(seq, steps, self._hip_heads_ok(seq, window))
+            else:                                               # seq [B, L, D]
+                first = seq.contiguous()
             hist = min(steps, window.size(1))
             late, floor = self._late_bias(rows), self._floor_vector()
-            return (hidden, window[:, -hist:, :], hist, None if late is None else late.detach(),
+            return (first, window[:, -hist:, :], hist, None if late is None else late.detach(),
                     None if floor is None else floor.detach().reshape(-1))
 
         with torch.no_grad():

@@ -1068,6 +1068,37 @@ def head_backward(hidden: torch.Tensor, g_rate: torch.Tensor, g_disp: torch.Tens
     return dw_mu, db_mu, dw_sg, db_sg, d_hidden
 
 
+def timeproj_backward_form_of(B: int, L: int, S: int, D: int, misalign_or: int = 0) -> Tuple[str, int]:
+    """The kernel ``ftn_timeproj_backward`` runs (``ftn_timeproj_backward_form``, host-only) and its chunks of batch
+    rows: ``("k_timeproj_bwd_mfma", chunks)``.  ``misalign_or``: the OR of ``address & 15`` of seq and d_hidden;
+    operands off the 16-byte grid have no form (ValueError, as from the launch)."""
+    f = _form("ftn_timeproj_backward_form", B, L, S, D, misalign_or)
+    return {_lib.FTN_TIMEPROJ_BWD_MFMA: "k_timeproj_bwd_mfma"}[f & 15], f >> 4
+
+
+def timeproj_backward(seq: torch.Tensor, d_hidden: torch.Tensor, dw=None, db=None):
+    """``ftn_timeproj_backward``: ``seq`` [B,L,D] and ``d_hidden`` [B,S,D] contiguous fp32 on one device (16-byte
+    aligned, or ValueError).  Returns ``(dW_t [S,L], db_t [S])``, the gradients of ``timeproj_forward``'s ``wt`` and
+    ``bt``; ``dw`` / ``db`` may be the caller's (contiguous fp32).  Enqueues only."""
+    lib = _lib.load()
+    if seq.dim() != 3 or d_hidden.dim() != 3 or seq.shape[0] != d_hidden.shape[0] or seq.shape[2] != d_hidden.shape[2]:
+        raise ValueError("timeproj_backward takes seq [B, L, D] and d_hidden [B, S, D]")
+    for name, t in (("seq", seq), ("d_hidden", d_hidden)):
+        if t.dtype != torch.float32 or not t.is_cuda or t.device != seq.device or not t.is_contiguous():
+            raise ValueError(f"timeproj_backward: {name} must be a contiguous fp32 device tensor")
+    B, L, D = seq.shape
+    S = d_hidden.shape[1]
+    dw = _out_or_fresh("timeproj_backward", dw, (S, L), seq, "dw")
+    db = _out_or_fresh("timeproj_backward", db, (S,), seq, "db")
+    need = lib.ftn_timeproj_backward_workspace(B, L, S, D)
+    if need == 0:
+        raise ValueError(f"timeproj_backward: ftn_timeproj_backward_workspace rejected B={B} L={L} S={S} d_model={D}")
+    ws = _workspace(seq.device, need)
+    check(lib.ftn_timeproj_backward(_ptr(seq), _ptr(d_hidden), B, L, S, D, _ptr(dw), _ptr(db), _ptr(ws), ws.numel(),
+                                    _stream(seq.device)), "ftn_timeproj_backward")
+    return dw, db
+
+
 # ------------------------------------------------------------------ NB CDF and quantiles
 def nbq_form_of(N: int, strides=(0, 0, 0), misalign_or: int = 0) -> str:
     """The kernel form ``ftn_nb_cdf`` / ``ftn_nb_quantiles`` take (``ftn_nbq_form``, host-only: the launches dispatch

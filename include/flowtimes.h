@@ -743,6 +743,31 @@ int ftn_head_backward(const float* hidden_dev, long long R, int N, int D, const 
                       float* db_mu_dev, float* dw_sigma_dev, float* db_sigma_dev, float* d_hidden_dev_or_null,
                       void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The time projection's backward, for a refit of the whole output side (csrc/timeproj_bwd.hip; additions only:
+ * FTN_ABI_VERSION stays 14).  seq [B][L][D] is ftn_timeproj_forward's input, d_hidden [B][S][D] the d_hidden of
+ * ftn_head_backward (the loss scale is in it); both contiguous fp32 and 16-byte aligned (an operand off that grid is
+ * rejected before any launch), D a multiple of 4 from 4 to 512, B, L, S >= 1 (S == 1: the recursive model, whose
+ * weight is the last row of the [pred_len][L] matrix).
+ *   dW_t[s][l] = sum_b sum_d d_hidden[b][s][d] seq[b][l][d]        db_t[s] = sum_b sum_d d_hidden[b][s][d]
+ * dW_t [S][L] and db_t [S] are contiguous, 4-byte aligned, written with plain stores and nothing around them is
+ * touched.  Batch rows are cut into chunks of 8 (of ceil(B / FTN_TIMEPROJ_BWD_CHUNKS_MAX) beyond 256 chunks); a
+ * chunk's partial [S][L + 1] (column L: the bias) goes to the caller's workspace (ftn_timeproj_backward_workspace
+ * bytes, 0 for a bad shape; whatever it held before) and a second kernel adds the chunks in a fixed order (chunks
+ * c, c + 16, ... ascending, then the 16 sums ascending).  No atomics and no library GEMM: every sum's order is a
+ * function of (B, L, S, D) alone, the same bits on every run, and every product is an exact fp32 fmaf step
+ * (v_mfma_f32_32x32x2_f32; no operand is split).  Two launches, enqueued only.
+ * ftn_timeproj_backward_form (host-only; the launch dispatches through the same function):
+ *   bits 0-3   FTN_TIMEPROJ_BWD_MFMA  [32 s x 32 l] tiles, K = the (b, d) pairs of the chunk's batch rows, dealt to the
+ *                                     four waves of a workgroup and added in wave order
+ *   bits 4-12  the number of chunks
+ * misalign_or: the OR of (address & 15) of seq and d_hidden; anything but 0 is an error here as in the launch. */
+#define FTN_TIMEPROJ_BWD_MFMA 1
+#define FTN_TIMEPROJ_BWD_CHUNKS_MAX 256
+int ftn_timeproj_backward_form(int B, int L, int S, int D, int misalign_or);
+size_t ftn_timeproj_backward_workspace(int B, int L, int S, int D);
+int ftn_timeproj_backward(const float* seq_dev, const float* d_hidden_dev, int B, int L, int S, int D, float* dw_t_dev,
+                          float* db_t_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ---- using the forecast's distribution: NB CDF and quantiles (no counterpart in the reference) -----------
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
  *
