@@ -3,9 +3,16 @@
 #include <stdlib.h>
 #include "ftn_conv.h"
 #include "ftn_conv_split.h"
+#include "ftn_conv_walk.h"
 #include "ftn_mlp.h"
 
 static const bool g_conv_generic = [] { const char* e = getenv("FTN_CONV_GENERIC"); return e != nullptr && e[0] == '1'; }();  // experiment switch
+// 0: the fast path shares out a branch's rows equally, tile switches uncharged (A/B runs and tests; default on)
+static const bool g_conv_walk = [] { const char* e = getenv("FTN_CONV_WALK"); return e == nullptr || e[0] != '0'; }();
+// What a workgroup of k_conv_bf_fast pays for walking on into the next tile, in the k-cycle unit of ftn_conv_split's
+// row cost: workgroups with the same rows end 9.4 k (7x7) to 12 k (3x3) cycles later when they cross a tile boundary
+// (tools/stamps.py)
+#define FTN_CONV_SWITCH_KCYC 10.0
 
 // ---------------------------------------------------------------- tile and pixel bookkeeping of the three kernels
 // One conv tile of the per-row tile list: its period group, the group's grid, the tile inside it and the staged
@@ -593,8 +600,9 @@ __device__ __forceinline__ void conv_fast_row(f4 (&acc)[CBF_NU], const char* __r
 
 // Launch shape: ONE workgroup per CU, each bound to one branch for its whole life; a branch gets a share of the
 // workgroups proportional to its cost (host: ~3.1 k + 0.35 k cycles per K-32 slab and batch row) and a workgroup
-// a contiguous range of that branch's (tile, batch row) sequence.  The branch's weight fragments (75 KB for 7x7)
-// are DMA'd once per workgroup instead of once per 8 rows, and every CU finishes at about the same time; the
+// a contiguous range of that branch's (tile, batch row) sequence (ftn_conv_walk.h: equal shares, with a step into the
+// next tile charged as rows, so the workgroups that cross a tile boundary are not the last to finish).  The branch's
+// weight fragments (75 KB for 7x7) are DMA'd once per workgroup instead of once per 8 rows, and every CU finishes at about the same time; the
 // (tile, 8-row chunk, branch) grid of k_conv_bf runs 480 unequal workgroups (49 / 25 / 9 taps) on 256 CUs in
 // roughly 1.4 rounds - 92 us for 66 us of work (tools/stamps.py).
 // NCI = 16-channel input groups per branch (mid 16: 1; mid 32: 2, late round 3).  With two, a workgroup is bound to a
@@ -616,16 +624,20 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
   const int wgi = (int)blockIdx.x - a.wg_off[vb], nwg = a.wg_off[vb + 1] - a.wg_off[vb];
   const int nco = a.cout >> 4, br = vb / nco, cot = vb - br * nco;   // branch, output tile of the branch
   const int G = d->n_groups, tiles_total = d->tiles_per_row;
-  const long long rows_total = (long long)tiles_total * a.B;
-  const int row_lo = (int)(rows_total * wgi / nwg), row_hi = (int)(rows_total * (wgi + 1) / nwg);
+  // this workgroup's positions of the branch's (tile, batch row) sequence, a tile switch charged as sw rows
+  const int sw = a.switch_rows[vb];
+  int pos[2];
+  ftn_conv_walk(tiles_total, a.B, sw, nwg, wgi, pos);
+  const int pos_hi = pos[1];
   const size_t wgid = blockIdx.x;
   stamp(a.dbg, a.dbg_cap, wgid, 0);
-  if (row_lo >= row_hi) return;
+  if (pos[0] >= pos_hi) return;
   const int kh = a.kh[br], kw = a.kw[br], hy = kh >> 1, hx = kw >> 1, ntaps = kh * kw;
   const int S = (ntaps + 1) >> 1;
   stamp_realtime(a.dbg, a.dbg_cap, wgid, 6);
   stamp_word(a.dbg, a.dbg_cap, wgid, 4, (unsigned long long)ntaps);
-  stamp_word(a.dbg, a.dbg_cap, wgid, 5, ((unsigned long long)row_lo << 32) | (unsigned)row_hi);
+  stamp_word(a.dbg, a.dbg_cap, wgid, 5, ((unsigned long long)ftn_conv_walk_row(a.B, sw, pos[0]) << 32) |   // its rows [lo, hi)
+                                        (unsigned)ftn_conv_walk_row(a.B, sw, pos_hi));
   char* __restrict__ wl = ldsb;
   char* __restrict__ rbuf0 = ldsb + (size_t)NCI * S * WSTR * 1024;   // behind THIS (branch, tile)'s weight fragments
   static_assert(CBF_FAST_ZBASE % 256 == 0, "the zero block must start on a 256-byte boundary");
@@ -651,11 +663,8 @@ __global__ __launch_bounds__(512) void k_conv_bf_fast(ConvBfArgs a) {
   const int h1 = qa >> 1;                                     // this lane's tap of every pair
   bool first_tile = true;
 
-  for (int row = row_lo; row < row_hi;) {
-    const int bx = row / a.B;                                  // tile (of the per-row tile list), then its batch rows
-    const int b_begin = row - bx * a.B;
-    const int b_end = min(a.B, b_begin + (row_hi - row));
-    row += b_end - b_begin;
+  int bx, b_begin, b_end;                                      // tile (of the per-row tile list), then its batch rows
+  for (int v = pos[0]; ftn_conv_walk_next(a.B, sw, &v, pos_hi, &bx, &b_begin, &b_end);) {
     const ConvTile t = conv_tile(d, G, bx, hy, hx);
     const float inv_tw = 1.0f / (float)t.tw, inv_rw = 1.0f / (float)t.RW;
     const int nchunks16 = t.RH * t.RW * 2;
@@ -967,6 +976,9 @@ int ftn_launch_conv_bf(ConvBfArgs& ca, const ConvBfGeom& gm, int B, int grid_x, 
     ca.nvb = nvb;
     ca.wg_off[0] = 0;
     for (int k = 0; k < nvb; ++k) ca.wg_off[k + 1] = ca.wg_off[k] + nwg[k];
+    // a tile switch in whole rows of the branch (the row cost of ftn_conv_split's model): 2 / 1 / 1 for 3x3 / 5x5 / 7x7
+    for (int v = 0; v < nvb; ++v)
+      ca.switch_rows[v] = g_conv_walk ? (int)(FTN_CONV_SWITCH_KCYC / (3.17 + 0.281 * slabs[v] * (ca.cin / 16)) + 0.5) : 0;
     return launch_conv_bf_fast(ca, gm, dim3((unsigned)ca.wg_off[nvb]), nsplit, st);
   }
   if (nsplit == 3) return launch_conv_bf_n<3>(ca, gm, grid, st);

@@ -42,6 +42,7 @@ struct ConvBfArgs {
   float inv[FTN_MAXBR];  // f16x2: 2^-s of the branch's prescaled weights (applied to the accumulators)
   int wg_off[2 * FTN_MAXBR + 1];   // k_conv_bf_fast: workgroups [wg_off[v], wg_off[v+1]) serve virtual branch v = branch * (cout / 16) + output tile
   int nvb;               // virtual branches of the fast path: nbr * (cout / 16)
+  int switch_rows[2 * FTN_MAXBR];  // k_conv_bf_fast: rows a tile switch is charged as in virtual branch v's walk (ftn_conv_walk.h)
   int* range_flag;       // f16x2 piece output (out_p3): set when an output leaves the fp16 range; may be null
   unsigned long long* dbg; size_t dbg_cap;
 };

@@ -1,6 +1,14 @@
 #!/usr/bin/env python3
 """Diagnostic: per-workgroup phase timeline of k_conv / k_mlp from s_memtime stamps
-(ftn_debug_stamps).  Usage on the GPU box: python tools/stamps.py [conv|mlp]"""
+(ftn_debug_stamps).  Usage on the GPU box: python tools/stamps.py [conv|mlp] [B] [--batch N] [--json FILE]
+(`conv` = stage D, `conv B` = stage B; --json writes the conv summary: per branch the earliest / median / latest
+workgroup end and the per-row cost by tile).
+
+Record of a k_conv_bf_fast workgroup (8 words): 0 start, 1 first row landed, 2 second row landed, 3 end (s_memtime);
+4 taps; 5 its rows [lo, hi) of the branch's (tile, batch row) sequence, lo << 32 | hi (csrc/ftn_conv_walk.h);
+6 / 7 start / end on the real-time clock (100 MHz)."""
+import argparse
+import json
 import os
 import sys
 from pathlib import Path
@@ -12,12 +20,18 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 import __graft_entry__ as ge
 
-which = sys.argv[1] if len(sys.argv) > 1 else "conv"
+ap = argparse.ArgumentParser()
+ap.add_argument("which", nargs="?", default="conv", choices=("conv", "mlp"))
+ap.add_argument("stage", nargs="?", default="D", choices=("B", "D"))
+ap.add_argument("--batch", type=int, default=int(os.environ.get("STAMP_B", "256")))
+ap.add_argument("--json", default=None)
+args = ap.parse_args()
+which = args.which
 pkg = ge.load_package()
 lib = pkg.lib.load()
 T = pkg.models.timesnet
 dev = torch.device("cuda:0")
-B, L, C, K = int(os.environ.get('STAMP_B', '256')), 336, 64, 5
+B, L, C, K = args.batch, 336, 64, 5
 ks = [(3, 3), (5, 5), (7, 7)]
 params = pkg.synth.make_inception_params(C, 4 * C, ks, 4.0, seed=0)
 blk = T.TimesBlock(C, ks, 0.0, "gelu", d_ff=4 * C, bottleneck_ratio=4.0)
@@ -31,7 +45,7 @@ with torch.inference_mode():
     torch.cuda.synchronize()
     nwg = 2_000_000
     buf = torch.zeros(nwg * 8, dtype=torch.int64, device=dev)
-    lib.ftn_debug_stamps(buf.data_ptr(), buf.numel(), (5 if len(sys.argv) > 2 and sys.argv[2] == 'B' else 1) if which == 'conv' else 2)
+    lib.ftn_debug_stamps(buf.data_ptr(), buf.numel(), (5 if args.stage == 'B' else 1) if which == 'conv' else 2)
     blk(x)
     torch.cuda.synchronize()
     lib.ftn_debug_stamps(None, 0, 0)
@@ -75,17 +89,41 @@ if which == "conv":
         e = (s[m, 7] - s[:, 6].min()) / 100
         print(f"taps {taps:3d}: end time us p10 {np.percentile(e,10):6.1f} p50 {np.median(e):6.1f} p90 {np.percentile(e,90):6.1f} max {e.max():6.1f}; start max {((s[m,6]-s[:,6].min())/100).max():5.1f}")
 
+
 if which == "conv":
     raw = buf.cpu().numpy().reshape(-1, 8)[(buf.cpu().numpy().reshape(-1, 8)[:, 6] > 0)]
     raw = raw[raw[:, 3] > 0]
     lo = (raw[:, 5] >> 32).astype(np.int64); hi = (raw[:, 5] & 0xffffffff).astype(np.int64)
     nrows = hi - lo
-    tile0 = lo // B; tile1 = (hi - 1) // B
     tot = (raw[:, 3] - raw[:, 0]).astype(np.float64)
+    t_first = raw[:, 6].min()
+    end_us = (raw[:, 7] - t_first) / 100.0
+    summary = {"batch": B, "stage": args.stage, "launch_end_us": round(float(end_us.max()), 2), "branches": {}}
     for taps in sorted(set(raw[:, 4].astype(int))):
         m = raw[:, 4] == taps
-        print(f"taps {taps}: rows/wg {nrows[m].min()}..{nrows[m].max()}")
-        for t in sorted(set(tile0[m])):
-            mm = m & (tile0 == t) & (tile1 == t)
-            if mm.sum():
-                print(f"    tile {t}: n={mm.sum():3d} cycles/row {np.mean(tot[mm]/nrows[mm]):8.0f}  total p50 {np.median(tot[mm]):9.0f}")
+        R = int(hi[m].max())
+        ntile = (R + B - 1) // B
+        # rows of every workgroup by tile, then total = prologue + sum_tile rows * cost: least squares over the branch
+        A = np.zeros((int(m.sum()), ntile + 1))
+        A[:, ntile] = 1.0
+        for i, k in enumerate(np.nonzero(m)[0]):
+            for r in range(int(lo[k]), int(hi[k])):
+                A[i, r // B] += 1.0
+        A = np.hstack([A, ((A[:, :ntile] > 0).sum(1, keepdims=True) - 1.0)])     # tile switches of the workgroup
+        sol = np.linalg.lstsq(A, tot[m], rcond=None)[0]
+        e = end_us[m]
+        first_tile = np.array([int(np.nonzero(A[i, :ntile])[0][0]) for i in range(A.shape[0])])
+        by_first = {int(t): round(float(np.median(e[first_tile == t])), 2) for t in sorted(set(first_tile))}
+        print(f"taps {taps}: rows/wg {nrows[m].min()}..{nrows[m].max()}, end us earliest {e.min():6.1f} "
+              f"median {np.median(e):6.1f} latest {e.max():6.1f}")
+        print(f"    cycles/row by tile (least squares) {[int(round(v)) for v in sol[:ntile]]}  fixed part {sol[ntile]:8.0f}  tile switch {sol[ntile + 1]:8.0f}")
+        print(f"    median end us by the workgroup's first tile {by_first}")
+        summary["branches"][str(taps)] = {
+            "workgroups": int(m.sum()), "rows_per_wg": [int(nrows[m].min()), int(nrows[m].max())],
+            "end_us": {"earliest": round(float(e.min()), 2), "median": round(float(np.median(e)), 2), "latest": round(float(e.max()), 2)},
+            "cycles_per_row_by_tile": [int(round(v)) for v in sol[:ntile]], "fixed_cycles": int(round(sol[ntile])),
+            "tile_switch_cycles": int(round(sol[ntile + 1])),
+            "median_end_us_by_first_tile": by_first}
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(json.dumps(summary, indent=1) + "\n")
