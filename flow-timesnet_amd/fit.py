@@ -36,6 +36,12 @@ whole output side: the time projection and both heads, with the reference's grad
 backbone stays frozen on the HIP path and every gradient comes from this library's kernels, in a fixed summation
 order; ``_last_timeproj_backend`` says which path the projection took.
 
+``DeviceAdamW`` is the optimizer of that loop with nothing on the host: torch's ``clip_grad_norm_`` followed by torch's
+AdamW as one call of ``ftn_refit_update`` (``csrc/refit.hip``), whose step count, learning rate, gradient norm and
+decision to skip a step are device words.  ``GraphedRefitStep`` captures a whole step of ``refit_output`` - backbone
+forward, time projection, heads, loss, both backwards, that update - in one HIP graph, and ``refit_output_graphed`` is
+the loop over it ("Refit step").
+
 ``backend`` follows ``score``'s rule (``_use_hip``): ``hip`` where it can run unless ``"torch"`` is asked for, and
 asking for ``"hip"`` where it cannot is an error.
 """
@@ -456,3 +462,426 @@ def _losses_or_raise(losses, bads) -> torch.Tensor:
         if seen & bit:
             raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
     return host[:len(losses)]
+
+
+# ------------------------------------------------------------------ the refit step on the device: clip + AdamW, one graph
+_last_optim_backend: Optional[str] = None     # which path the last ``DeviceAdamW`` update took
+
+
+def _bump_versions(tensors) -> None:
+    """What an in-place torch op does to a tensor's version counter, for tensors a kernel of ours wrote: caches keyed
+    on ``models.timesnet._param_key`` (``series_slices``, the pack caches) then see the step."""
+    for t in tensors:
+        if not t.is_inference():
+            torch.autograd.graph.increment_version(t)
+
+
+class DeviceAdamW:
+    """AdamW after a clip by the global gradient norm (torch's ``clip_grad_norm_`` then ``torch.optim.AdamW``) whose
+    step count, learning rate, norm and decision to skip live on the device: ``ftn_refit_update``
+    (``csrc/refit.hip``) on contiguous fp32 ROCm tensors (backend ``hip``), the same formulas in torch ops anywhere
+    else (backend ``torch``); ``_last_optim_backend`` says which ran.  Up to 8 parameter tensors.  Nothing is read on
+    the host, so a step can be captured in a HIP graph.
+
+    The update is skipped - parameters, moments and the step count keep every bit - when a ``skip`` word is non-zero
+    (a head's ``bad`` word, a block's f16x2 range word), the gradient norm is not finite or the loss word is not
+    finite.  Every call, skipped or not, writes ``(loss, norm before clipping, lr, flags)`` to a ring of
+    ``log_steps`` rows; ``history()`` returns the rows since its last call.  Flags: 1 rate bad, 2 dispersion bad,
+    4 range word set, 8 norm or loss not finite.
+
+    ``zero_grad`` / ``step`` read ``p.grad`` as a torch optimizer does (``refit_output(..., optimizer=...)``);
+    ``step_on`` takes caller-owned gradient buffers."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 max_norm: Optional[float] = None, log_steps: int = 4096, backend: Optional[str] = None):
+        self.params = list(params)
+        if not 1 <= len(self.params) <= 8:
+            raise ValueError(f"DeviceAdamW: {len(self.params)} parameter tensors (1..8)")
+        for p in self.params:
+            if not isinstance(p, torch.Tensor) or not p.is_floating_point() or p.numel() < 1:
+                raise ValueError("DeviceAdamW: parameters must be floating-point tensors that are not empty")
+        if len({p.device for p in self.params}) != 1:
+            raise ValueError("DeviceAdamW: parameters must be on one device")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"DeviceAdamW: betas={tuple(betas)} are not inside [0, 1)")
+        if not (lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0):
+            raise ValueError(f"DeviceAdamW: lr={lr}, eps={eps} and weight_decay={weight_decay} must be >= 0")
+        if int(log_steps) < 1:
+            raise ValueError(f"DeviceAdamW: log_steps={log_steps} must be >= 1")
+        if backend not in (None, "hip", "torch"):
+            raise ValueError(f"DeviceAdamW: backend {backend!r} is not 'hip', 'torch' or None")
+        self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.max_norm = None if max_norm is None or float(max_norm) <= 0.0 else float(max_norm)
+        self.backend = backend
+        dev = self.device = self.params[0].device
+        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self._lr = torch.full((1,), float(lr), dtype=torch.float32, device=dev)
+        self._state = torch.zeros(2, dtype=torch.int32, device=dev)      # [t, calls]
+        self._log = torch.zeros(int(log_steps), 4, dtype=torch.float32, device=dev)
+        self._calls = 0                                                   # the host's count of calls
+        self._read = 0                                                    # calls ``history()`` has returned
+
+    # ---- the torch optimizer's surface ----
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        for p in self.params:
+            if set_to_none:
+                p.grad = None
+            elif p.grad is not None:
+                p.grad.detach_().zero_()
+
+    def step(self, loss: Optional[torch.Tensor] = None, skip=()) -> None:
+        """The update from ``p.grad`` of every parameter that has one."""
+        idx = [i for i, p in enumerate(self.params) if p.grad is not None]
+        if not idx:
+            raise ValueError("DeviceAdamW.step: no parameter has a gradient")
+        self._update(idx, [self.params[i].grad for i in idx], loss, skip)
+
+    def step_on(self, grads, loss: Optional[torch.Tensor] = None, skip=()) -> None:
+        """The update from ``grads`` (one tensor per parameter, read only).  ``loss``: an optional 0-dim or one-element
+        fp32 tensor on the device, logged and checked for finiteness.  ``skip``: int32 device words; an entry may be
+        ``(word, "range")`` to mark a block's range word (flag 4), a bare word is a head's ``bad`` word."""
+        grads = list(grads)
+        if len(grads) != len(self.params):
+            raise ValueError(f"DeviceAdamW.step_on: {len(grads)} gradients for {len(self.params)} parameters")
+        self._update(list(range(len(grads))), grads, loss, skip)
+
+    def set_lr(self, value: float) -> None:
+        """An asynchronous fill of the device word: the next update, a replayed one too, uses it."""
+        self._lr.fill_(float(value))
+
+    def note_replay(self, calls: int = 1) -> None:
+        """What a replay of a captured ``step_on`` leaves to the host: the call count ``history()`` goes by and the
+        parameters' version counters."""
+        self._calls += int(calls)
+        _bump_versions(self.params)
+
+    def history(self) -> torch.Tensor:
+        """The log rows ``[calls, 4]`` = (loss, norm before clipping, lr, flags) of the calls since the last
+        ``history()`` (the last ``log_steps`` of them at most), on the host: one synchronisation."""
+        cap = self._log.shape[0]
+        first = max(self._read, self._calls - cap)
+        rows = self._log.cpu()
+        self._read = self._calls
+        return rows[[k % cap for k in range(first, self._calls)]].reshape(-1, 4)
+
+    def state_dict(self) -> dict:
+        return {"t": int(self._state[0].item()), "exp_avg": [m.detach().clone() for m in self.exp_avg],
+                "exp_avg_sq": [v.detach().clone() for v in self.exp_avg_sq]}
+
+    def load_state_dict(self, state: dict) -> None:
+        if len(state["exp_avg"]) != len(self.params) or len(state["exp_avg_sq"]) != len(self.params):
+            raise ValueError("DeviceAdamW.load_state_dict: the state is for another number of parameters")
+        for dst, src in zip(self.exp_avg + self.exp_avg_sq, list(state["exp_avg"]) + list(state["exp_avg_sq"])):
+            if tuple(dst.shape) != tuple(src.shape):
+                raise ValueError("DeviceAdamW.load_state_dict: a moment has another shape")
+        with torch.no_grad():
+            for dst, src in zip(self.exp_avg + self.exp_avg_sq, list(state["exp_avg"]) + list(state["exp_avg_sq"])):
+                dst.copy_(src)
+            self._state[0:1].fill_(int(state["t"]))
+
+    # ---- the update ----
+    def _update(self, idx, grads, loss, skip) -> None:
+        global _last_optim_backend
+        from .range_guard import _capturing
+
+        ps = [self.params[i] for i in idx]
+        ms, vs = [self.exp_avg[i] for i in idx], [self.exp_avg_sq[i] for i in idx]
+        for p, g in zip(ps, grads):
+            if not isinstance(g, torch.Tensor) or tuple(g.shape) != tuple(p.shape) or g.device != p.device:
+                raise ValueError("DeviceAdamW: a gradient does not have its parameter's shape and device")
+        words, range_mask = [], 0
+        for k, w in enumerate(skip):
+            if isinstance(w, tuple):
+                if len(w) != 2 or w[1] != "range":
+                    raise ValueError("DeviceAdamW: a skip entry is a word or (word, 'range')")
+                w, range_mask = w[0], range_mask | 1 << k
+            if not isinstance(w, torch.Tensor) or w.dtype != torch.int32 or w.numel() != 1 or w.device != self.device:
+                raise ValueError("DeviceAdamW: a skip word must be one int32 beside the parameters")
+            words.append(w)
+        if len(words) > 8:
+            raise ValueError(f"DeviceAdamW: {len(words)} skip words (at most 8)")
+        if loss is not None and (not isinstance(loss, torch.Tensor) or loss.numel() != 1
+                                 or loss.device != self.device or not loss.is_floating_point()):
+            raise ValueError("DeviceAdamW: loss must be one floating-point word beside the parameters")
+        eligible = (self.device.type == "cuda"
+                    and all(t.dtype == torch.float32 for t in ps + list(grads))
+                    and all(p.is_contiguous() for p in ps)
+                    and (loss is None or loss.dtype == torch.float32))
+        if _use_hip("DeviceAdamW", self.backend, eligible, "contiguous fp32 parameters and fp32 gradients on a ROCm device"):
+            from . import runtime as rt
+
+            rt.refit_update([p.detach() for p in ps], [g.detach().contiguous() for g in grads], ms, vs, self._lr,
+                            self._state, self.betas, self.eps, self.weight_decay, self.max_norm, words, range_mask,
+                            None if loss is None else loss.detach().reshape(1), self._log)
+            _last_optim_backend = "hip"
+            if not _capturing():
+                _bump_versions(ps)
+        else:
+            with torch.no_grad():
+                self._update_torch(ps, [g.detach() for g in grads], ms, vs, loss, words, range_mask)
+            _last_optim_backend = "torch"
+        if not _capturing():
+            self._calls += 1
+
+    def _update_torch(self, ps, grads, ms, vs, loss, words, range_mask) -> None:
+        """``ftn_refit_update`` in torch ops: fp64 for the sum of squares, the clip coefficient, the decay factor and
+        the bias corrections, each rounded once to the parameter's dtype; element arithmetic in that dtype.  The
+        decision is a device word and the update a ``torch.where``: nothing is read on the host."""
+        dev = self.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        total = torch.zeros((), **f64)
+        for g in grads:
+            total = total + g.double().square().sum()
+        norm = total.sqrt()
+        flags = torch.zeros((), dtype=torch.int32, device=dev)
+        for k, w in enumerate(words):
+            w = w.reshape(())
+            if range_mask >> k & 1:
+                flags = flags | (w != 0).to(torch.int32) * 4
+            else:
+                flags = flags | (w & 3) | ((w & ~3) != 0).to(torch.int32) * 8
+        loss_w = torch.zeros((), dtype=torch.float32, device=dev) if loss is None else loss.detach().reshape(()).float()
+        flags = flags | (~(torch.isfinite(norm) & torch.isfinite(loss_w))).to(torch.int32) * 8
+        keep = flags == 0
+        one = torch.ones((), **f64)
+        c = one if self.max_norm is None else torch.clamp(self.max_norm / (norm + 1e-6), max=1.0)
+        c = torch.where(torch.isnan(c), one, c)
+        t1 = (self._state[0] + 1).double()
+        b1, b2 = self.betas
+        bc1, bc2 = 1.0 - torch.pow(torch.tensor(b1, **f64), t1), 1.0 - torch.pow(torch.tensor(b2, **f64), t1)
+        lr = self._lr[0]
+        decay, step, rs = 1.0 - lr.double() * self.weight_decay, lr.double() / bc1, bc2.sqrt()
+        for p, g, m, v in zip(ps, grads, ms, vs):
+            dt = p.dtype
+            gc = c.to(dt) * g.to(dt)
+            m_new = b1 * m + (1.0 - b1) * gc
+            v_new = b2 * v + ((1.0 - b2) * gc) * gc
+            p_new = p * decay.to(dt) - step.to(dt) * (m_new / (v_new.sqrt() / rs.to(dt) + self.eps))
+            p.copy_(torch.where(keep, p_new, p))
+            m.copy_(torch.where(keep, m_new, m))
+            v.copy_(torch.where(keep, v_new, v))
+        row = torch.stack([loss_w, norm.float(), lr, flags.float()])
+        self._log.index_copy_(0, (self._state[1:2] % self._log.shape[0]).long(), row.reshape(1, 4))
+        self._state += torch.stack([keep.to(torch.int32), torch.ones((), dtype=torch.int32, device=dev)])
+
+
+def _refit_params(model):
+    proj = model.forecast_time_proj
+    return [model.mu_head.weight, model.mu_head.bias, model.sigma_head.weight, model.sigma_head.bias,
+            proj.weight, proj.bias]
+
+
+class GraphedRefitStep:
+    """One step of ``refit_output`` - backbone forward, time projection, heads, loss, both backwards, clip and AdamW -
+    captured once and replayed with a single graph launch: ``step(batch)`` copies the batch into the captured buffers
+    (``.inputs``: ``x, y, mask, x_mark, static, ids``, None where the captured batch had none; ``DeviceWindows`` may
+    write into them directly) and replays.  Nothing is read on the host.  The launches and their operands are the
+    ones ``_TimeProjection`` and ``_HeadNLL`` make, so a step's gradients (``.grads``, in ``refit_output``'s parameter
+    order) have the bits of the eager ``output_nll`` backward; the time projection's gradient goes into the last
+    ``steps`` rows of a zeroed full-size buffer, so the other rows of a recursive model only decay.  The update is
+    ``optimizer.step_on`` with the heads' ``bad`` word and the blocks' f16x2 range words as skip words: a replay that
+    trips one leaves parameters and moments as they were and logs the flag.  Shapes and which optional pieces exist
+    are frozen at capture; a batch that differs is a ValueError."""
+
+    def __init__(self, model, batch, optimizer: DeviceAdamW, use_loss_mask: bool = False, warmup: int = 2):
+        from .score import _unpack_batch
+
+        if not isinstance(optimizer, DeviceAdamW):
+            raise ValueError("GraphedRefitStep needs a fit.DeviceAdamW")
+        params = _refit_params(model)
+        if len(optimizer.params) != 6 or any(a is not b for a, b in zip(optimizer.params, params)):
+            raise ValueError("GraphedRefitStep: the optimizer must hold mu_head, sigma_head and forecast_time_proj "
+                             "(weight, bias each, in that order)")
+        dev = params[0].device
+        if dev.type != "cuda" or any(p.dtype != torch.float32 or not p.is_contiguous() for p in params):
+            raise ValueError("GraphedRefitStep needs a model with contiguous fp32 parameters on a ROCm device")
+        xb, yb, mask, x_mark, _, static, ids = _unpack_batch(batch)
+        if use_loss_mask and mask is None:
+            raise ValueError("GraphedRefitStep: use_loss_mask needs a mask in the batch")
+        self.model, self.optimizer, self.device = model, optimizer, dev
+        self.use_loss_mask = bool(use_loss_mask)
+        self.steps = int(model._out_steps)
+        own = lambda t, dtype=None: None if t is None else t.to(device=dev, dtype=dtype).clone()
+        self._in = (own(xb), own(yb), own(mask) if use_loss_mask else None, own(x_mark), own(static),
+                    own(ids, torch.long))
+        proj = model.forecast_time_proj
+        self._gw, self._gb = torch.zeros_like(proj.weight), torch.zeros_like(proj.bias)   # rows before -steps stay 0
+        if model.training:
+            raise ValueError("GraphedRefitStep: put the model in eval mode first (refit_output_graphed does)")
+        # warm-up on a side stream: lazy builds, packing, the allocator.  The update goes to copies of the parameters
+        # and a throw-away optimizer, so neither the model nor the moments move before the first step.
+        spare = DeviceAdamW([p.detach().clone() for p in params], backend="hip")
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(max(1, int(warmup))):
+                self._enqueue(spare)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        # a model first called on the host and then moved remembers its id row there and copies it per call, which no
+        # capture takes; given ids are checked with a host read unless the checks are deferred (graph.GraphedForward)
+        remembered = getattr(model, "_series_id_reference", None)
+        if isinstance(remembered, torch.Tensor) and remembered.device != dev:
+            model._series_id_reference = remembered.to(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        deferred = getattr(model, "_defer_checks", False)
+        model._defer_checks = True
+        try:
+            with torch.no_grad(), torch.cuda.graph(self.graph):
+                self.loss, self.bad, self.grads, self._keep = self._enqueue(optimizer)
+        finally:
+            model._defer_checks = deferred
+        self.range_words = [b._range_dev_flag for b in model.blocks if getattr(b, "_range_dev_flag", None) is not None]
+        # addresses the captured launches have baked in (as graph.GraphedForward)
+        self._packs = [m._pack for m in model.modules() if getattr(m, "_pack", None) is not None]
+
+    def _enqueue(self, optimizer: DeviceAdamW):
+        """The step's launches on the current stream, in ``refit_output``'s order."""
+        from . import runtime as rt
+
+        model, steps = self.model, self.steps
+        x, y, mask, x_mark, static, ids = self._in
+        w_mu, b_mu, w_sg, b_sg, pw, pb = (p.detach() for p in _refit_params(model))
+        seq, tail, hist, late, floor = model.output_inputs(x, x_mark, static, ids)
+        ranges = [b._range_dev_flag for b in model.blocks if getattr(b, "_range_dev_flag", None) is not None] \
+            if torch.cuda.is_current_stream_capturing() else []
+        seq = seq.detach().contiguous()
+        D = seq.shape[2]
+        if not (D % 4 == 0 and 4 <= D <= 512 and seq.dtype == torch.float32 and seq.data_ptr() % 16 == 0
+                and w_mu.data_ptr() % 16 == 0 and w_sg.data_ptr() % 16 == 0):
+            raise ValueError("GraphedRefitStep: the output side of this model does not take the HIP path (fp32, "
+                             "d_model a multiple of 4 up to 512, weights on the 16-byte grid)")
+        hidden = rt.timeproj_forward(seq, pw[-steps:], pb[-steps:])
+        tail = tail.detach()
+        if tail.stride(2) != 1 or tail.stride(1) != tail.shape[2]:
+            tail = tail.contiguous()
+        late_c = None if late is None else late.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        floor_c = None if floor is None else floor.detach().to(device=self.device,
+                                                               dtype=torch.float32).reshape(-1).contiguous()
+        rate, disp, sig_mu, sig_sg, bad = rt.head_fit_forward(hidden, w_mu, b_mu.contiguous(), w_sg, b_sg.contiguous(),
+                                                              tail, hist, late_c, floor_c, float(model.min_sigma))
+        base = (mask[:, :steps, :] > 0.0) if self.use_loss_mask else None
+        words, g_rate, g_disp = rt.nb_nll_grad(_rows(y[:, :steps, :]), rate, disp, _full_mask(base, rate),
+                                               scaled=False)
+        dw_mu, db_mu, dw_sg, db_sg, d_hidden = rt.head_backward(hidden, g_rate, g_disp, sig_mu, sig_sg,
+                                                                words[1:2], w_mu, w_sg, want_hidden=True)
+        rt.timeproj_backward(seq, d_hidden, dw=self._gw[-steps:], db=self._gb[-steps:])
+        grads = [dw_mu, db_mu, dw_sg, db_sg, self._gw, self._gb]
+        optimizer.step_on(grads, loss=words[0:1], skip=[bad] + [(w, "range") for w in ranges])
+        keep = (seq, hidden, tail, late_c, floor_c, rate, disp, sig_mu, sig_sg, base, words, g_rate, g_disp, d_hidden)
+        return words[0:1], bad, grads, keep
+
+    @property
+    def inputs(self):
+        """The captured buffers ``(x, y, mask, x_mark, static, ids)``; writing into them saves ``step``'s copy."""
+        return self._in
+
+    def replay(self) -> torch.Tensor:
+        """One replay on the buffers as they are; returns the loss word (overwritten by the next replay)."""
+        self.graph.replay()
+        self.optimizer.note_replay()
+        return self.loss
+
+    def _given(self, batch):
+        """``batch`` as ``(name, captured buffer, given tensor)`` triples, and the first name that does not fit."""
+        from .score import _unpack_batch
+
+        xb, yb, mask, x_mark, _, static, ids = _unpack_batch(batch)
+        given = (xb, yb, mask if self.use_loss_mask else None, x_mark, static, ids)
+        triples = list(zip(("x", "y", "mask", "x_mark", "static", "ids"), self._in, given))
+        odd = next((t for t in triples if (t[1] is None) != (t[2] is None)
+                    or (t[1] is not None and tuple(t[1].shape) != tuple(t[2].shape))), None)
+        return triples, odd
+
+    def fits(self, batch) -> bool:
+        """Whether ``batch`` has the captured shapes and optional pieces."""
+        return self._given(batch)[1] is None
+
+    def step(self, batch) -> torch.Tensor:
+        """Copies ``batch`` into the captured buffers (a tensor that already is its buffer is left alone) and replays;
+        returns the loss word."""
+        triples, odd = self._given(batch)
+        if odd is not None:
+            name, dst, src = odd
+            raise ValueError(f"GraphedRefitStep.step: {name} is {'absent' if src is None else tuple(src.shape)}, "
+                             f"captured {'absent' if dst is None else tuple(dst.shape)}")
+        for _, dst, src in triples:
+            if dst is not None and src.data_ptr() != dst.data_ptr():
+                dst.copy_(src, non_blocking=True)
+        return self.replay()
+
+
+_RANGE_MESSAGE = ("a value left the fp16 range of engine f16x2 inside a captured step; the steps it happened in were "
+                  "skipped: set block.engine = 'bf16x3' on the model's blocks and refit")
+
+
+def refit_output_graphed(model, batches, epochs: int = 1, lr=1e-3, weight_decay: float = 0.0,
+                         grad_clip: Optional[float] = None, use_loss_mask: bool = False):
+    """``refit_output``'s loop over a ``GraphedRefitStep`` with a ``DeviceAdamW``: one graph launch per batch, one
+    synchronisation at the end.  ``lr``: a float, or one value per epoch (``DeviceAdamW.set_lr``).  A batch whose
+    shapes differ from the first one's (a short last batch) takes the eager step of ``refit_output`` with the same
+    optimizer.  Returns the losses, fp32 ``[epochs * batches]`` on the host, after the reference's RuntimeError if a
+    logged step found a rate or dispersion not finite and > 0, and ``FloatingPointError`` if one left the fp16 range
+    of engine f16x2 (those steps were skipped; set ``block.engine = "bf16x3"`` and refit).  Mode and
+    ``requires_grad`` flags come back as they were."""
+    from .score import _unpack_batch
+
+    epochs = int(epochs)
+    rates = [float(lr)] * epochs if isinstance(lr, (int, float)) else [float(v) for v in lr]
+    if len(rates) != epochs:
+        raise ValueError(f"refit_output_graphed: {len(rates)} learning rates for {epochs} epochs")
+    params = _refit_params(model)
+    dev = params[0].device
+    flags = [(p, p.requires_grad) for p in model.parameters()]
+    was_training = model.training
+    losses = []
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        for p in params:
+            p.requires_grad_(True)
+        model.eval()
+        opt = DeviceAdamW(params, lr=rates[0] if rates else 1e-3, weight_decay=weight_decay, max_norm=grad_clip)
+        step, steps = None, int(model._out_steps)
+        for epoch in range(epochs):
+            opt.set_lr(rates[epoch])
+            for batch in batches:
+                if step is None:
+                    step = GraphedRefitStep(model, batch, opt, use_loss_mask=use_loss_mask)
+                if step.fits(batch):
+                    losses.append(step.step(batch).clone())
+                    continue
+                xb, yb, mask, x_mark, _, static, ids = _unpack_batch(batch)
+                move = lambda t: None if t is None else t.to(dev, non_blocking=True)
+                seq, tail, hist, late, floor = model.output_inputs(
+                    move(xb), move(x_mark), move(static),
+                    None if ids is None else ids.to(device=dev, dtype=torch.long, non_blocking=True))
+                if use_loss_mask and mask is None:
+                    raise ValueError("refit_output_graphed: use_loss_mask needs a mask in every batch")
+                base = (move(mask)[:, :steps, :] > 0.0) if use_loss_mask else None
+                opt.zero_grad(set_to_none=True)
+                with torch.enable_grad():
+                    proj = model.forecast_time_proj
+                    loss, bad = output_nll(seq, proj.weight[-steps:], proj.bias[-steps:], *params[:4], tail, hist,
+                                           move(yb)[:, :steps, :], base, late, floor, model.min_sigma)
+                loss.backward()
+                opt.step(loss=loss.detach(), skip=[bad])
+                opt.zero_grad(set_to_none=True)
+                losses.append(loss.detach().reshape(1))
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
+        model.train(was_training)
+    if not losses:
+        raise ValueError("refit_output_graphed: no batches")
+    host = torch.cat(losses).cpu()                               # the one synchronisation
+    seen = 0
+    for v in opt.history()[:, 3].tolist():
+        seen |= int(v)
+    for bit, name in ((1, "rate"), (2, "dispersion")):
+        if seen & bit:
+            raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
+    if seen & 4:
+        raise FloatingPointError("refit_output_graphed: " + _RANGE_MESSAGE)
+    return host

@@ -55,6 +55,21 @@ FTN_QMAX = 8
 FTN_NBG_PARTS_MAX = 1024
 FTN_HEADFIT_COLSUM, FTN_HEADFIT_MFMA, FTN_HEADFIT_CHUNKS_MAX = 1, 2, 256
 FTN_TIMEPROJ_BWD_MFMA, FTN_TIMEPROJ_BWD_CHUNKS_MAX, TIMEPROJ_BWD_CHUNK = 1, 256, 8
+FTN_REFIT_MAX_TENSORS, FTN_REFIT_MAX_SKIP, FTN_REFIT_PARTS_MAX = 8, 8, 1024
+FTN_REFIT_ONE, FTN_REFIT_GRID = 1, 2
+
+
+class FtnRefitArgs(C.Structure):
+    """Mirror of ``struct FtnRefitArgs`` (include/flowtimes.h): the operands of one clip-and-AdamW call."""
+
+    _fields_ = [("p", C.c_void_p * FTN_REFIT_MAX_TENSORS), ("g", C.c_void_p * FTN_REFIT_MAX_TENSORS),
+                ("m", C.c_void_p * FTN_REFIT_MAX_TENSORS), ("v", C.c_void_p * FTN_REFIT_MAX_TENSORS),
+                ("n", C.c_longlong * FTN_REFIT_MAX_TENSORS), ("n_tensors", C.c_int32), ("n_skip", C.c_int32),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_norm", C.c_double), ("lr", C.c_void_p), ("state", C.c_void_p),
+                ("skip", C.c_void_p * FTN_REFIT_MAX_SKIP), ("range_mask", C.c_int32), ("log_cap", C.c_int32),
+                ("loss", C.c_void_p), ("log", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("force_form", C.c_int32), ("reserved", C.c_int32)]
 FTN_NBQ_RANGE = 2
 FTN_PATHS_MAX = 1024
 FTN_PATH_SUM, FTN_PATH_MAX = 0, 1
@@ -319,6 +334,10 @@ _SIGNATURES = {
     "ftn_timeproj_backward_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_timeproj_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_timeproj_backward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    # refit step: clip and AdamW (csrc/refit.hip)
+    "ftn_refit_update_form": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "ftn_refit_update_workspace": (C.c_size_t, [C.c_int, C.POINTER(C.c_longlong)]),
+    "ftn_refit_update": (C.c_int, [C.POINTER(FtnRefitArgs), _P]),
     "ftn_nbq_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_nb_cdf": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
                              C.c_float, _P, _P, _P, _P]),

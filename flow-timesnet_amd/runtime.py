@@ -1099,6 +1099,98 @@ def timeproj_backward(seq: torch.Tensor, d_hidden: torch.Tensor, dw=None, db=Non
     return dw, db
 
 
+# ------------------------------------------------------------------ refit step: clip and AdamW
+_REFIT_FORMS = {_lib.FTN_REFIT_ONE: "k_refit_one", _lib.FTN_REFIT_GRID: "k_refit_norm+k_refit_apply"}
+
+
+def _refit_counts(counts):
+    counts = [int(c) for c in counts]
+    return len(counts), (C.c_longlong * max(len(counts), 1))(*counts)
+
+
+def refit_update_form_of(counts, misalign=None) -> Tuple[str, int, int]:
+    """The form ``ftn_refit_update`` takes for tensors of ``counts`` elements (``ftn_refit_update_form``, host-only):
+    ``("k_refit_one" | "k_refit_norm+k_refit_apply", scalar mask, chunks)``.  ``misalign``: per tensor the OR of
+    ``address & 15`` of its parameter, gradient and moments (None: all aligned); bit i of the mask says tensor i is
+    moved with scalar accesses.  More than 8 tensors or an empty one is a ValueError, as from the launch."""
+    n, arr = _refit_counts(counts)
+    mis = None
+    if misalign is not None:
+        if len(misalign) != n:
+            raise ValueError(f"refit_update_form_of: {len(misalign)} misalign values for {n} tensors")
+        mis = (C.c_int * max(n, 1))(*(int(v) for v in misalign))
+    f = _lib.load().ftn_refit_update_form(n, arr, mis)
+    if f < 0:
+        check(f, "ftn_refit_update_form")
+    return _REFIT_FORMS[f & 15], (f >> 4) & 255, f >> 12
+
+
+def refit_update(params, grads, exp_avg, exp_avg_sq, lr: torch.Tensor, state: torch.Tensor, betas=(0.9, 0.999),
+                 eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None, skip=(),
+                 range_mask: int = 0, loss: Optional[torch.Tensor] = None, log: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None, force_form: Optional[str] = None) -> None:
+    """``ftn_refit_update``: clip by the global norm of ``grads`` (``max_norm`` None or <= 0: no clip), then AdamW on
+    ``params`` with the moments ``exp_avg`` / ``exp_avg_sq``, in place; up to 8 contiguous fp32 device tensors each.
+    ``lr`` one fp32 device word, ``state`` int32 ``[t, calls]`` on the device, ``skip`` int32 device words (bit k of
+    ``range_mask``: word k is a block's range word, else a head's ``bad`` word), ``loss`` an optional fp32 word,
+    ``log`` an optional contiguous fp32 ``[cap, 4]``.  ``workspace``: uint8 storage of ``ftn_refit_update_workspace``
+    bytes (None: from the caching allocator).  ``force_form``: ``"one"`` / ``"grid"``, for tests.  Enqueues only."""
+    lib = _lib.load()
+    lists = [list(params), list(grads), list(exp_avg), list(exp_avg_sq)]
+    n = len(lists[0])
+    if any(len(l) != n for l in lists):
+        raise ValueError("refit_update: params, grads, exp_avg and exp_avg_sq must have one length")
+    if not 1 <= n <= _lib.FTN_REFIT_MAX_TENSORS:
+        raise ValueError(f"refit_update: {n} tensors (1..{_lib.FTN_REFIT_MAX_TENSORS} per call)")
+    dev = lists[0][0].device
+    a = _lib.FtnRefitArgs()
+    for i in range(n):
+        for name, l in zip(("p", "g", "m", "v"), lists):
+            t = l[i]
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != dev
+                    or not t.is_contiguous() or t.numel() != lists[0][i].numel()):
+                raise ValueError(f"refit_update: {name}[{i}] must be a contiguous fp32 device tensor of its "
+                                 "parameter's size")
+            getattr(a, name)[i] = _ptr(t)
+        a.n[i] = lists[0][i].numel()
+    words = [("lr", lr, torch.float32, 1), ("state", state, torch.int32, 2)]
+    words += [(f"skip[{k}]", w, torch.int32, 1) for k, w in enumerate(skip)]
+    if loss is not None:
+        words.append(("loss", loss, torch.float32, 1))
+    for name, t, dtype, count in words:
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or t.device != dev
+                or not t.is_contiguous()):
+            raise ValueError(f"refit_update: {name} must be {count} {dtype} word(s) beside the parameters")
+    skip = list(skip)
+    if len(skip) > _lib.FTN_REFIT_MAX_SKIP:
+        raise ValueError(f"refit_update: {len(skip)} skip words (at most {_lib.FTN_REFIT_MAX_SKIP})")
+    if log is not None and (log.dtype != torch.float32 or log.device != dev or not log.is_contiguous()
+                            or log.dim() != 2 or log.shape[1] != 4 or log.shape[0] < 1):
+        raise ValueError("refit_update: log must be contiguous fp32 [cap >= 1, 4] beside the parameters")
+    if force_form not in (None, "one", "grid"):
+        raise ValueError(f"refit_update: force_form {force_form!r} is not 'one', 'grid' or None")
+    a.n_tensors, a.n_skip = n, len(skip)
+    a.beta1, a.beta2, a.eps, a.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+    a.max_norm = 0.0 if max_norm is None else float(max_norm)
+    a.lr, a.state = _ptr(lr), _ptr(state)
+    for k, w in enumerate(skip):
+        a.skip[k] = _ptr(w)
+    a.range_mask = int(range_mask)
+    a.log_cap = 0 if log is None else log.shape[0]
+    a.loss, a.log = _ptr_or_null(loss), _ptr_or_null(log)
+    _, arr = _refit_counts(a.n[i] for i in range(n))
+    need = lib.ftn_refit_update_workspace(n, arr)
+    if need == 0:
+        raise ValueError("refit_update: ftn_refit_update_workspace rejected the counts")
+    if workspace is None:
+        workspace = _workspace(dev, need)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError("refit_update: workspace must be contiguous uint8 storage beside the parameters")
+    a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
+    a.force_form = {None: 0, "one": _lib.FTN_REFIT_ONE, "grid": _lib.FTN_REFIT_GRID}[force_form]
+    check(lib.ftn_refit_update(C.byref(a), _stream(dev)), "ftn_refit_update")
+
+
 # ------------------------------------------------------------------ NB CDF and quantiles
 def nbq_form_of(N: int, strides=(0, 0, 0), misalign_or: int = 0) -> str:
     """The kernel form ``ftn_nb_cdf`` / ``ftn_nb_quantiles`` take (``ftn_nbq_form``, host-only: the launches dispatch

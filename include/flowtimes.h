@@ -768,6 +768,65 @@ size_t ftn_timeproj_backward_workspace(int B, int L, int S, int D);
 int ftn_timeproj_backward(const float* seq_dev, const float* d_hidden_dev, int B, int L, int S, int D, float* dw_t_dev,
                           float* db_t_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* The optimiser step of a refit on the device (csrc/refit.hip; additions only: FTN_ABI_VERSION stays 14): clip by
+ * the global gradient norm, then AdamW, for n_tensors <= FTN_REFIT_MAX_TENSORS contiguous fp32 tensors of n[i] >= 1
+ * elements.  p, m, v are updated in place, g is only read (the clipped gradient is never stored).  Per element, with
+ * t' = t + 1 and lr the device word:
+ *   norm = sqrt(sum_i sum g^2)             c = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1        g' = c g
+ *   p *= 1 - lr wd        m = b1 m + (1 - b1) g'        v = b2 v + (1 - b2) g'^2
+ *   p -= (lr / (1 - b1^t')) m / (sqrt(v) / sqrt(1 - b2^t') + eps)
+ * torch's clip_grad_norm_ followed by torch's AdamW.  The sum of squares, c, the decay factor and both bias
+ * corrections are fp64, each rounded to fp32 once; element arithmetic is fp32, every operation rounded once (two are
+ * fmaf: b1 m + ., b2 v + .), so with c == 1 the result has the bits of the unclipped update.  Partial sums are added
+ * in an order that depends on the counts alone - not on the form, not on alignment, not on the run; no atomics.
+ * Device words: lr (one float), state[2] = {t, calls} (int32; t counts applied updates, calls every call), n_skip <=
+ * FTN_REFIT_MAX_SKIP int32 words passed by address, an optional fp32 loss word, an optional log float [log_cap][4].
+ * The update is skipped - p, m, v and t keep every bit - when a skip word is non-zero, the norm is not finite or the
+ * loss word is not finite.  calls advances either way, and row calls % log_cap of the log gets (loss, norm before
+ * clipping, lr, flags): flag 1 = rate bad, 2 = dispersion bad (bits 0 and 1 of a skip word whose bit in range_mask is
+ * clear: a head's `bad` word), 4 = a skip word whose bit in range_mask is set (a block's f16x2 range word) is
+ * non-zero, 8 = norm or loss not finite.  Nothing but p, m, v, state, the log row and the workspace is written.
+ * Work is dealt in units of 4 consecutive elements of one tensor.  A tensor whose p, g, m and v are all on the 16-byte
+ * grid moves whole units with 16-byte accesses and its tail with scalars; any other tensor is moved with scalars
+ * (4-byte alignment is required).  ftn_refit_update_form (host-only; the launch dispatches through the same
+ * function; misalign_or: per tensor the OR of (address & 15) of its four operands, null for all zero):
+ *   bits 0-3    FTN_REFIT_ONE   k_refit_one: one workgroup, norm and update in one launch (up to 2 chunks of 1024
+ *                               units: 8192 elements of aligned tensors)
+ *               FTN_REFIT_GRID  k_refit_norm + k_refit_apply: a workgroup per chunk writes an fp64 partial to the
+ *                               workspace, then every workgroup adds all partials in the same order
+ *   bits 4-11   the tensors moved with scalars, one bit each
+ *   bits 12-    the number of chunks (at most FTN_REFIT_PARTS_MAX; beyond that the chunk grows)
+ * The workspace (ftn_refit_update_workspace bytes, 0 for bad counts; 8-byte aligned; whatever it held before) is read
+ * only where this call wrote it; FTN_REFIT_ONE does not touch it.  force_form (0, or a form for tests) overrides the
+ * choice where the form can take the counts.  Every argument is checked before the first launch; enqueues only, all
+ * launches on the one stream. */
+#define FTN_REFIT_MAX_TENSORS 8
+#define FTN_REFIT_MAX_SKIP 8
+#define FTN_REFIT_PARTS_MAX 1024
+#define FTN_REFIT_ONE 1
+#define FTN_REFIT_GRID 2
+typedef struct FtnRefitArgs {
+  float* p[FTN_REFIT_MAX_TENSORS];
+  const float* g[FTN_REFIT_MAX_TENSORS];
+  float* m[FTN_REFIT_MAX_TENSORS];
+  float* v[FTN_REFIT_MAX_TENSORS];
+  long long n[FTN_REFIT_MAX_TENSORS];
+  int32_t n_tensors, n_skip;
+  double beta1, beta2, eps, weight_decay, max_norm;      /* max_norm <= 0: no clip */
+  const float* lr_dev;
+  int32_t* state_dev;                                     /* {t, calls} */
+  const int32_t* skip_dev[FTN_REFIT_MAX_SKIP];
+  int32_t range_mask;                                     /* bit k: skip word k is a range word (flag 4) */
+  int32_t log_cap;
+  const float* loss_dev_or_null;
+  float* log_dev_or_null;                                 /* [log_cap][4] */
+  void* workspace_dev;  size_t workspace_bytes;
+  int32_t force_form, reserved;
+} FtnRefitArgs;
+int ftn_refit_update_form(int n_tensors, const long long* counts, const int* misalign_or);
+size_t ftn_refit_update_workspace(int n_tensors, const long long* counts);
+int ftn_refit_update(const FtnRefitArgs* args, void* stream);
+
 /* ---- using the forecast's distribution: NB CDF and quantiles (no counterpart in the reference) -----------
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
  *
