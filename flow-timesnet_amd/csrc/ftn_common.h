@@ -33,6 +33,13 @@ static inline int ftn_pad16(int v) { return (v + 15) & ~15; }
 static inline int ftn_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool misalign_ok(int m) { return m >= 0 && m < 16 && m % 4 == 0; }   // a *_form entry's misalign_or
 
+// Entry b of a device row list, clamped into 0 .. n_items - 1 (timeproj.hip, timeproj_bwd.hip, refit_rows.hip: the
+// item a batch row of a cached refit reads).  No index can point outside a store of n_items >= 1 rows.
+__device__ __forceinline__ long long store_row(const long long* __restrict__ rows, long long n_items, int b) {
+  const long long r = rows[b];
+  return r < 0 ? 0 : r >= n_items ? n_items - 1 : r;
+}
+
 // The vector-load rule of the [B][H][N] scoring kernels (score.hip, quantile.hip, sample.hip): a lane may take 4
 // series with one 16-byte load when N and every batch stride are multiples of 4 and no operand is off 16 bytes.
 static inline bool ftn_vec4_ok(int N, long long s0, long long s1, long long s2, unsigned misalign_or) {

@@ -79,7 +79,9 @@ struct RingArgs {
 };
 
 struct TimeProjArgs {
-  const float* seq;      // [B][L][D]
+  const float* seq;      // [B][L][D]; with rows: the item store [n_items][L][D]
+  const long long* rows; // null, or [B]: batch row b reads item rows[b] clamped into 0 .. n_items - 1
+  long long n_items;
   const float* wt;       // [S][L], base only 4-byte aligned when it is a row slice at L % 4 != 0
   const float* bt;       // [S]
   float* hid;            // [B][S][D]

@@ -112,17 +112,21 @@ static int timeproj_form_entry(const char* who, const ShellWidth& w, int L, int 
   return timeproj_form(L, S, (unsigned)wt_misalign);
 }
 
-static int timeproj_entry(const char* who, const ShellWidth& w, const float* seq, int B, int L, int D, const float* wt,
-                          const float* bt, int S, float* hidden, void* stream) {
-  FTN_CHECK_ARG(seq && wt && bt && hidden, "%s: null pointer", who);
+// mapped (the _rows entries): seq is an item store [n_items][L][D] read through rows [B]; else rows is null.
+static int timeproj_entry(const char* who, const ShellWidth& w, bool mapped, const float* seq, long long n_items,
+                          const long long* rows, int B, int L, int D, const float* wt, const float* bt, int S,
+                          float* hidden, void* stream) {
+  FTN_CHECK_ARG(seq && wt && bt && hidden && (rows || !mapped), "%s: null pointer", who);
   FTN_CHECK_ARG(B >= 1 && L >= 1 && S >= 1, "%s: bad shape B=%d L=%d S=%d", who, B, L, S);
+  FTN_CHECK_ARG(n_items >= 1, "%s: n_items=%lld must be >= 1", who, n_items);
+  FTN_CHECK_ARG(((uintptr_t)rows & 7) == 0, "%s: rows must be 8-byte aligned", who);
   FTN_CHECK_D_MODEL(who, w, D);
   FTN_CHECK_ARG((((uintptr_t)seq | (uintptr_t)hidden) & 15) == 0, "%s: seq and hidden must be 16-byte aligned", who);
   FTN_CHECK_ARG((((uintptr_t)wt | (uintptr_t)bt) & 3) == 0, "%s: W_t and b_t must be 4-byte aligned", who);
   FTN_CHECK_ARG((long long)B * ((D + 63) / 64) <= 0x7fffffffLL && (S + 15) / 16 <= 65535,
                 "%s: B=%d S=%d exceed the launch grid", who, B, S);
   TimeProjArgs a;
-  a.seq = seq; a.wt = wt; a.bt = bt; a.hid = hidden;
+  a.seq = seq; a.rows = rows; a.n_items = n_items; a.wt = wt; a.bt = bt; a.hid = hidden;
   a.B = B; a.L = L; a.D = D; a.S = S;
   return timeproj_launch(a, w, (hipStream_t)stream);
 }
@@ -203,11 +207,23 @@ int ftn_embed_wide_form(int N, int D, long long x_bs, int x_misalign, int w_misa
 
 int ftn_timeproj_forward(const float* seq, int B, int L, int D, const float* wt, const float* bt, int S, float* hidden,
                          void* stream) {
-  return timeproj_entry("ftn_timeproj_forward", kShellNarrow, seq, B, L, D, wt, bt, S, hidden, stream);
+  return timeproj_entry("ftn_timeproj_forward", kShellNarrow, false, seq, 1, nullptr, B, L, D, wt, bt, S, hidden,
+                        stream);
+}
+int ftn_timeproj_forward_rows(const float* seq, long long n_items, const long long* rows, int B, int L, int D,
+                              const float* wt, const float* bt, int S, float* hidden, void* stream) {
+  return timeproj_entry("ftn_timeproj_forward_rows", kShellNarrow, true, seq, n_items, rows, B, L, D, wt, bt, S, hidden,
+                        stream);
 }
 int ftn_timeproj_wide_forward(const float* seq, int B, int L, int D, const float* wt, const float* bt, int S,
                               float* hidden, void* stream) {
-  return timeproj_entry("ftn_timeproj_wide_forward", kShellWide, seq, B, L, D, wt, bt, S, hidden, stream);
+  return timeproj_entry("ftn_timeproj_wide_forward", kShellWide, false, seq, 1, nullptr, B, L, D, wt, bt, S, hidden,
+                        stream);
+}
+int ftn_timeproj_wide_forward_rows(const float* seq, long long n_items, const long long* rows, int B, int L, int D,
+                                   const float* wt, const float* bt, int S, float* hidden, void* stream) {
+  return timeproj_entry("ftn_timeproj_wide_forward_rows", kShellWide, true, seq, n_items, rows, B, L, D, wt, bt, S,
+                        hidden, stream);
 }
 int ftn_timeproj_form(int L, int S, int D, int wt_misalign) {
   return timeproj_form_entry("ftn_timeproj_form", kShellNarrow, L, S, D, wt_misalign);

@@ -12,6 +12,15 @@
 
 #define TP_WAVES 8       // waves of a k_timeproj_bf workgroup: the K-32 slabs of L are dealt to them round-robin
 
+// MAP (the ftn_timeproj_*_forward_rows entries): seq is an item store [n_items][L][D] and batch row b reads item
+// rows[b], clamped into 0 .. n_items - 1.  b comes from blockIdx, so the index is one scalar load and two scalar
+// selects of a workgroup; nothing else of a kernel changes, and hidden stays [B][S][D].  The instantiations without
+// MAP are the kernels as they were.
+template <bool MAP>
+__device__ __forceinline__ const float* tp_seq_row(const TimeProjArgs& a, int b) {
+  return a.seq + (size_t)(MAP ? store_row(a.rows, a.n_items, b) : (long long)b) * a.L * a.D;
+}
+
 // The contraction runs over the ROW axis of seq, so neither operand of hidden[b] = W_t seq[b] has its K index
 // contiguous in the lane that needs it.  MFMA sums over (q, e) pairwise and does not care which l a pair stands for,
 // and a lane may feed different MFMAs from different components of one load: lane (j, q) loads the 16 bytes
@@ -24,7 +33,7 @@
 // w, w + TP_WAVES, ... of L each, keep all NST x 4 accumulator tiles in registers, split their seq slab once and
 // each W_t fragment once (W_t comes from L2: S L floats per workgroup beside the 64 L of seq), and the partial sums
 // meet in LDS, one 16-step tile at a time, summed in wave order.  WV: W_t is read with 16-byte loads.
-template <int NST, bool WV>
+template <int NST, bool WV, bool MAP>
 __global__ __launch_bounds__(64 * TP_WAVES, 2) void k_timeproj_bf(TimeProjArgs a) {
   __shared__ f4 red[TP_WAVES * 4 * 64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
@@ -33,7 +42,7 @@ __global__ __launch_bounds__(64 * TP_WAVES, 2) void k_timeproj_bf(TimeProjArgs a
   const int s0 = blockIdx.y * (16 * NST);
   const int d = 64 * g + 4 * j;
   const bool dok = d < a.D;                                     // D % 4 == 0: a quad is all inside a row or all outside
-  const float* __restrict__ sp = a.seq + (size_t)b * a.L * a.D + d;
+  const float* __restrict__ sp = tp_seq_row<MAP>(a, b) + d;
   const f4 zero = {0.f, 0.f, 0.f, 0.f};
   auto load_x = [&](int sl, f4 (&x)[8]) {
     const int l0 = 32 * sl + 8 * q;
@@ -108,13 +117,14 @@ __global__ __launch_bounds__(64 * TP_WAVES, 2) void k_timeproj_bf(TimeProjArgs a
 // group order.  G depends on D alone, so the order over l is fixed by (L, D).
 #define TP_ROW_THREADS 512
 #define TP_ROW_CHUNK 2048
+template <bool MAP>
 __global__ __launch_bounds__(TP_ROW_THREADS) void k_timeproj_row(TimeProjArgs a) {
   __shared__ float wl[TP_ROW_CHUNK];
   __shared__ f4 red[TP_ROW_THREADS];
   const int C = a.D >> 2, G = TP_ROW_THREADS / C;               // C <= 32: G >= 16
   const int c = threadIdx.x % C, g = threadIdx.x / C;
   const bool active = g < G;
-  const float* __restrict__ sp = a.seq + (size_t)blockIdx.x * a.L * a.D + 4 * c;
+  const float* __restrict__ sp = tp_seq_row<MAP>(a, (int)blockIdx.x) + 4 * c;
   f4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int l0 = 0; l0 < a.L; l0 += TP_ROW_CHUNK) {
     const int n = a.L - l0 < TP_ROW_CHUNK ? a.L - l0 : TP_ROW_CHUNK;
@@ -153,11 +163,11 @@ int timeproj_form(int L, int S, unsigned wt_misalign) {
   return FTN_SHELL_BF | (wv ? FTN_SHELL_VEC : 0) | nst << 4 | TP_WAVES << 8;
 }
 
-template <int NST>
+template <int NST, bool MAP>
 static int launch_timeproj_bf(const TimeProjArgs& a, int form, hipStream_t st) {
   const dim3 grid((unsigned)((long long)a.B * ((a.D + 63) / 64)), (unsigned)((a.S + 16 * NST - 1) / (16 * NST)));
-  if (form & FTN_SHELL_VEC) hipLaunchKernelGGL((k_timeproj_bf<NST, true>), grid, dim3(64 * TP_WAVES), 0, st, a);
-  else hipLaunchKernelGGL((k_timeproj_bf<NST, false>), grid, dim3(64 * TP_WAVES), 0, st, a);
+  if (form & FTN_SHELL_VEC) hipLaunchKernelGGL((k_timeproj_bf<NST, true, MAP>), grid, dim3(64 * TP_WAVES), 0, st, a);
+  else hipLaunchKernelGGL((k_timeproj_bf<NST, false, MAP>), grid, dim3(64 * TP_WAVES), 0, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
 }
@@ -169,6 +179,7 @@ static int launch_timeproj_bf(const TimeProjArgs& a, int form, hipStream_t st) {
 // row group, so S == 1 gets a form of its own: a workgroup owns (batch row b, 128-column slab blockIdx.y), thread
 // (c, g) walks rows l = g, g + 16, ... of the slab's columns 4 c .. 4 c + 3 and the 16 partial sums are added in group
 // order.  The group count is fixed, so the order over l depends on L alone.
+template <bool MAP>
 __global__ __launch_bounds__(TP_ROW_THREADS) void k_timeproj_row_wide(TimeProjArgs a) {
   __shared__ float wl[TP_ROW_CHUNK];
   __shared__ f4 red[TP_ROW_THREADS];
@@ -176,7 +187,7 @@ __global__ __launch_bounds__(TP_ROW_THREADS) void k_timeproj_row_wide(TimeProjAr
   const int c = threadIdx.x % C, g = threadIdx.x / C;
   const int d = 128 * blockIdx.y + 4 * c;
   const bool active = d < a.D;                                  // D % 4 == 0: a quad is all inside a row or all outside
-  const float* __restrict__ sp = a.seq + (size_t)blockIdx.x * a.L * a.D + d;
+  const float* __restrict__ sp = tp_seq_row<MAP>(a, (int)blockIdx.x) + d;
   f4 acc = {0.f, 0.f, 0.f, 0.f};
   for (int l0 = 0; l0 < a.L; l0 += TP_ROW_CHUNK) {
     const int n = a.L - l0 < TP_ROW_CHUNK ? a.L - l0 : TP_ROW_CHUNK;
@@ -203,19 +214,24 @@ __global__ __launch_bounds__(TP_ROW_THREADS) void k_timeproj_row_wide(TimeProjAr
   }
 }
 
-// S == 1 is the row form of the width (form 0 at either); k_timeproj_bf serves both widths.
-int timeproj_launch(const TimeProjArgs& a, const ShellWidth& w, hipStream_t st) {
+// S == 1 is the row form of the width (form 0 at either); k_timeproj_bf serves both widths.  MAP: a.rows is set.
+template <bool MAP>
+static int timeproj_launch_as(const TimeProjArgs& a, const ShellWidth& w, hipStream_t st) {
   const int form = timeproj_form(a.L, a.S, (unsigned)((uintptr_t)a.wt & 15));
   if (!(form & FTN_SHELL_BF)) {
-    if (w.wide) hipLaunchKernelGGL(k_timeproj_row_wide, dim3((unsigned)a.B, (unsigned)((a.D + 127) / 128)), dim3(TP_ROW_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(k_timeproj_row, dim3((unsigned)a.B), dim3(TP_ROW_THREADS), 0, st, a);
+    if (w.wide) hipLaunchKernelGGL(k_timeproj_row_wide<MAP>, dim3((unsigned)a.B, (unsigned)((a.D + 127) / 128)), dim3(TP_ROW_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(k_timeproj_row<MAP>, dim3((unsigned)a.B), dim3(TP_ROW_THREADS), 0, st, a);
     FTN_CHECK_LAUNCH();
     return 0;
   }
   switch ((form >> 4) & 15) {
-    case 1: return launch_timeproj_bf<1>(a, form, st);
-    case 2: return launch_timeproj_bf<2>(a, form, st);
-    case 4: return launch_timeproj_bf<4>(a, form, st);
-    default: return launch_timeproj_bf<6>(a, form, st);
+    case 1: return launch_timeproj_bf<1, MAP>(a, form, st);
+    case 2: return launch_timeproj_bf<2, MAP>(a, form, st);
+    case 4: return launch_timeproj_bf<4, MAP>(a, form, st);
+    default: return launch_timeproj_bf<6, MAP>(a, form, st);
   }
+}
+
+int timeproj_launch(const TimeProjArgs& a, const ShellWidth& w, hipStream_t st) {
+  return a.rows ? timeproj_launch_as<true>(a, w, st) : timeproj_launch_as<false>(a, w, st);
 }

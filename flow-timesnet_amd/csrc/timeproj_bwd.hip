@@ -10,13 +10,16 @@
 // Batch rows are cut into chunks of TPB_CHUNK, at most FTN_TIMEPROJ_BWD_CHUNKS_MAX of them (beyond that the chunk
 // grows).  No atomics; the order of every sum is a function of (B, L, S, D) alone and every word of the workspace that
 // is read was written by this call.  Kernels, the form rule, the launch and the C entry points.
+// ftn_timeproj_backward_rows reads seq through a row list (MAP below); everything else is shared.
 #include "ftn_common.h"
 
 #define TPB_CHUNK 8          // batch rows of a chunk
 #define TPB_WAVES 4          // waves of a k_timeproj_bwd_mfma workgroup: the chunk's steps are dealt to them round-robin
 
 struct TimeProjBwdArgs {
-  const float* seq;          // [B][L][D]
+  const float* seq;          // [B][L][D]; with rows: the item store [n_items][L][D]
+  const long long* rows;     // null, or [B]: batch row b reads item rows[b] clamped into 0 .. n_items - 1
+  long long n_items;
   const float* dh;           // [B][S][D]
   float* part;               // [chunks][S][L + 1]
   float* dw;  float* db;     // [S][L], [S]
@@ -31,6 +34,11 @@ struct TimeProjBwdArgs {
 // w + TPB_WAVES, ... of the chunk (the kernel waits on memory, not on the matrix pipe: four waves keep four times the
 // loads in flight), issues the next step's loads before the 16 products, and the waves' tiles meet in LDS, added in
 // wave order.
+// MAP (ftn_timeproj_backward_rows): seq is an item store and the step's batch row b reads item rows[b], clamped.  A
+// step is the same in every lane of a wave, which the compiler cannot see from threadIdx: readfirstlane says so, and
+// the index is one scalar load and two scalar selects of a step.  A step past the chunk (its loads are masked) takes
+// entry b0, so nothing is read past rows[B - 1].  The instantiation without MAP is the kernel as it was.
+template <bool MAP>
 __global__ __launch_bounds__(64 * TPB_WAVES) void k_timeproj_bwd_mfma(TimeProjBwdArgs a) {
   __shared__ float red[(TPB_WAVES - 1) * 16 * 64];
   const int W = a.L + 1, ltiles = (W + 31) >> 5, tiles = ((a.S + 31) >> 5) * ltiles;
@@ -59,6 +67,11 @@ __global__ __launch_bounds__(64 * TPB_WAVES) void k_timeproj_bwd_mfma(TimeProjBw
     const int b = b0 + t / nds, d = (t % nds) * 32 + 16 * kh;
     const float* __restrict__ ap = a.dh + ((size_t)b * a.S + (sok ? s : 0)) * a.D + d;
     const float* __restrict__ bp = a.seq + ((size_t)b * a.L + (lok ? l : 0)) * a.D + d;
+    if (MAP) {                                                  // the item's base and the step's column: scalars
+      const int tu = __builtin_amdgcn_readfirstlane(t);
+      const size_t item = (size_t)store_row(a.rows, a.n_items, tu < steps ? b0 + tu / nds : b0);
+      bp = a.seq + item * a.L * a.D + (tu % nds) * 32 + ((size_t)(lok ? l : 0) * a.D + 16 * kh);
+    }
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const bool dok = t < steps && d + 4 * m < a.D;            // D % 4 == 0: a quad is all inside a row or all outside
@@ -157,29 +170,48 @@ extern "C" size_t ftn_timeproj_backward_workspace(int B, int L, int S, int D) {
   return (size_t)(tpb_form(B) >> 4) * S * ((size_t)L + 1) * sizeof(float);
 }
 
-extern "C" int ftn_timeproj_backward(const float* seq_dev, const float* d_hidden_dev, int B, int L, int S, int D,
-                                     float* dw_t_dev, float* db_t_dev, void* workspace_dev, size_t workspace_bytes,
-                                     void* stream) {
-  const char* who = "ftn_timeproj_backward";
-  FTN_CHECK_ARG(seq_dev && d_hidden_dev && dw_t_dev && db_t_dev && workspace_dev, "%s: null pointer", who);
+// ftn_timeproj_backward (rows_dev null, n_items = B) and ftn_timeproj_backward_rows: one set of checks, one launch.
+static int tpb_entry(const char* who, bool mapped, const float* seq_dev, long long n_items, const long long* rows_dev,
+                     const float* d_hidden_dev, int B, int L, int S, int D, float* dw_t_dev, float* db_t_dev,
+                     void* workspace_dev, size_t workspace_bytes, void* stream) {
+  FTN_CHECK_ARG(seq_dev && d_hidden_dev && dw_t_dev && db_t_dev && workspace_dev && (rows_dev || !mapped),
+                "%s: null pointer", who);
   FTN_CHECK_ARG(tpb_shape_ok(B, L, S, D), "%s: B=%d L=%d S=%d d_model=%d (a multiple of 4, <= 512)", who, B, L, S, D);
+  FTN_CHECK_ARG(n_items >= 1, "%s: n_items=%lld must be >= 1", who, n_items);
+  FTN_CHECK_ARG(((uintptr_t)rows_dev & 7) == 0, "%s: rows must be 8-byte aligned", who);
   FTN_CHECK_ARG((((uintptr_t)seq_dev | (uintptr_t)d_hidden_dev) & 15) == 0,
                 "%s: seq and d_hidden must be 16-byte aligned", who);
   FTN_CHECK_ARG((((uintptr_t)dw_t_dev | (uintptr_t)db_t_dev | (uintptr_t)workspace_dev) & 3) == 0,
                 "%s: dW_t, db_t and the workspace must be 4-byte aligned", who);
   const int form = tpb_form(B);
   TimeProjBwdArgs a;
-  a.seq = seq_dev; a.dh = d_hidden_dev; a.part = (float*)workspace_dev; a.dw = dw_t_dev; a.db = db_t_dev;
+  a.seq = seq_dev; a.rows = rows_dev; a.n_items = n_items; a.dh = d_hidden_dev; a.part = (float*)workspace_dev;
+  a.dw = dw_t_dev; a.db = db_t_dev;
   a.B = B; a.L = L; a.S = S; a.D = D; a.chunk = tpb_chunk(B); a.chunks = form >> 4;
   const size_t need = (size_t)a.chunks * S * ((size_t)L + 1) * sizeof(float);
   FTN_CHECK_ARG(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed (ftn_timeproj_backward_workspace)", who,
                 workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
-  const int tiles = ((S + 31) / 32) * ((L + 1 + 31) / 32);
-  hipLaunchKernelGGL(k_timeproj_bwd_mfma, dim3((unsigned)tiles * (unsigned)a.chunks), dim3(64 * TPB_WAVES), 0, st, a);
+  const dim3 grid((unsigned)(((S + 31) / 32) * ((L + 1 + 31) / 32)) * (unsigned)a.chunks);
+  if (mapped) hipLaunchKernelGGL(k_timeproj_bwd_mfma<true>, grid, dim3(64 * TPB_WAVES), 0, st, a);
+  else hipLaunchKernelGGL(k_timeproj_bwd_mfma<false>, grid, dim3(64 * TPB_WAVES), 0, st, a);
   FTN_CHECK_LAUNCH();
   const long long per = (long long)S * (L + 1);
   hipLaunchKernelGGL(k_timeproj_bwd_reduce, dim3((unsigned)((per + 15) / 16)), dim3(256), 0, st, a);
   FTN_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int ftn_timeproj_backward(const float* seq_dev, const float* d_hidden_dev, int B, int L, int S, int D,
+                                     float* dw_t_dev, float* db_t_dev, void* workspace_dev, size_t workspace_bytes,
+                                     void* stream) {
+  return tpb_entry("ftn_timeproj_backward", false, seq_dev, B > 0 ? B : 1, nullptr, d_hidden_dev, B, L, S, D, dw_t_dev,
+                   db_t_dev, workspace_dev, workspace_bytes, stream);
+}
+
+extern "C" int ftn_timeproj_backward_rows(const float* seq_dev, long long n_items, const long long* rows_dev,
+                                          const float* d_hidden_dev, int B, int L, int S, int D, float* dw_t_dev,
+                                          float* db_t_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return tpb_entry("ftn_timeproj_backward_rows", true, seq_dev, n_items, rows_dev, d_hidden_dev, B, L, S, D, dw_t_dev,
+                   db_t_dev, workspace_dev, workspace_bytes, stream);
 }

@@ -42,6 +42,12 @@ decision to skip a step are device words.  ``GraphedRefitStep`` captures a whole
 forward, time projection, heads, loss, both backwards, that update - in one HIP graph, and ``refit_output_graphed`` is
 the loop over it ("Refit step").
 
+``OutputCache`` keeps what the output side reads of a frozen backbone - ``seq`` first of all - per item of a
+``windows.DeviceWindows``; ``GraphedCachedStep`` is ``GraphedRefitStep`` without the blocks, reading the cached ``seq``
+in place through a device row list (``time_projection(..., rows=)``, the ``_rows`` entries of ``csrc/timeproj.hip`` and
+``csrc/timeproj_bwd.hip``; ``ftn_refit_rows_gather`` for the rest of the batch), and ``refit_output_cached`` the loop
+over shuffled epochs ("Cached refit").
+
 ``backend`` follows ``score``'s rule (``_use_hip``): ``hip`` where it can run unless ``"torch"`` is asked for, and
 asking for ``"hip"`` where it cannot is an error.
 """
@@ -335,27 +341,28 @@ class _TimeProjection(torch.autograd.Function):
     ``ftn_timeproj_backward`` backward.  ``seq`` is a constant: no ``d_seq`` is computed."""
 
     @staticmethod
-    def forward(ctx, seq, wt, bt):
+    def forward(ctx, seq, wt, bt, rows=None):
         from . import runtime as rt
 
         seq = seq.detach().contiguous()
-        ctx.save_for_backward(seq)
-        return rt.timeproj_forward(seq, wt.detach(), bt.detach())
+        ctx.save_for_backward(seq, *(() if rows is None else (rows,)))
+        return rt.timeproj_forward(seq, wt.detach(), bt.detach(), rows=rows)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, d_hidden):
         from . import runtime as rt
 
-        (seq,) = ctx.saved_tensors
+        seq, *rows = ctx.saved_tensors
         d_hidden = d_hidden.contiguous()
         if d_hidden.dtype != torch.float32 or d_hidden.data_ptr() % 16:     # (ftn_head_backward's own is neither)
             d_hidden = d_hidden.float().clone()
-        dw, db = rt.timeproj_backward(seq, d_hidden)
-        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
+        dw, db = rt.timeproj_backward(seq, d_hidden, rows=rows[0] if rows else None)
+        return None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None
 
 
-def time_projection(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> torch.Tensor:
+def time_projection(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor,
+                    rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``hidden[b] = wt @ seq[b] + bt[:, None]``, ``[B, S, D]`` from ``seq [B, L, D]`` (``TimesNet.output_inputs``),
     ``wt [S, L]`` and ``bt [S]``, differentiable in ``wt`` and ``bt``.  ``wt`` / ``bt`` may be the row slices
     ``weight[-steps:]`` / ``bias[-steps:]`` of a taller projection: autograd scatters the gradient into the full
@@ -363,7 +370,15 @@ def time_projection(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> to
     ``seq`` that does not require grad it is ``ftn_timeproj_forward`` (the bits of inference) with
     ``ftn_timeproj_backward`` as its backward (``_last_timeproj_backend == "hip"``); otherwise - CPU tensors, other
     dtypes, other widths, a ``seq`` that requires grad (no ``d_seq`` is computed here) - the torch composition
-    ``torch.matmul(wt, seq) + bt.view(1, -1, 1)``."""
+    ``torch.matmul(wt, seq) + bt.view(1, -1, 1)``.
+
+    ``rows`` (an int64 vector beside ``seq``): ``seq`` is an item store ``[n_items, L, D]`` (``OutputCache.seq``) and
+    the result ``[len(rows), S, D]`` is that of ``seq[rows]``, to the bit.  The device path reads the store in place
+    (``ftn_timeproj_forward_rows`` / ``ftn_timeproj_backward_rows``, which clamp an index into the store); the torch
+    composition is ``torch.matmul(wt, seq.index_select(0, rows)) + bt.view(1, -1, 1)``."""
+    if rows is not None and (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.dim() != 1
+                             or rows.numel() < 1 or rows.device != seq.device):
+        raise ValueError("time_projection: rows must be an int64 vector of at least one entry beside seq")
     if seq.dim() != 3 or wt.dim() != 2 or bt.dim() != 1 or wt.shape[1] != seq.shape[1] or bt.shape[0] != wt.shape[0]:
         raise ValueError(f"time_projection: seq {tuple(seq.shape)}, wt {tuple(wt.shape)} and bt {tuple(bt.shape)} do "
                          "not fit [B, L, D], [S, L] and [S]")
@@ -376,20 +391,21 @@ def time_projection(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> to
             and (S == 1 or wt.stride(0) == L) and (L == 1 or wt.stride(1) == 1) and (S == 1 or bt.stride(0) == 1)
             and seq.data_ptr() % 16 == 0):
         _last_timeproj_backend = "hip"
-        return _TimeProjection.apply(seq, wt, bt)
+        return _TimeProjection.apply(seq, wt, bt, None if rows is None else rows.contiguous())
     _last_timeproj_backend = "torch"
-    return torch.matmul(wt, seq) + bt.view(1, -1, 1)
+    return torch.matmul(wt, seq if rows is None else seq.index_select(0, rows)) + bt.view(1, -1, 1)
 
 
 def output_nll(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor,
                w_sigma: torch.Tensor, b_sigma: torch.Tensor, tail: torch.Tensor, hist: int, y: torch.Tensor,
                mask: torch.Tensor | None = None, late: torch.Tensor | None = None, floor: torch.Tensor | None = None,
-               min_sigma: float = 1e-3):
+               min_sigma: float = 1e-3, rows: Optional[torch.Tensor] = None):
     """The whole output side on ``seq [B, L, D]`` (``TimesNet.output_inputs``): ``time_projection`` then ``head_nll``,
     ``(loss, bad)``.  ``loss.backward()`` leaves gradients in ``wt``, ``bt`` and the four head tensors; on the device
     path every one of them comes from ``ftn_head_backward`` (which also writes ``d_hidden``) and
-    ``ftn_timeproj_backward``."""
-    hidden = time_projection(seq, wt, bt)
+    ``ftn_timeproj_backward``.  ``rows``: ``seq`` is an item store read through this list (``time_projection``); the
+    other operands are the batch's."""
+    hidden = time_projection(seq, wt, bt, rows)
     return head_nll(hidden, w_mu, b_mu, w_sigma, b_sigma, tail, hist, y, mask, late, floor, min_sigma)
 
 
@@ -885,3 +901,333 @@ def refit_output_graphed(model, batches, epochs: int = 1, lr=1e-3, weight_decay:
     if seen & 4:
         raise FloatingPointError("refit_output_graphed: " + _RANGE_MESSAGE)
     return host
+
+
+# ------------------------------------------------------------------ cached refit: the frozen backbone once per item
+def _late_layout(model, windows) -> Optional[str]:
+    """How the late bias of ``model`` lies over the items of ``windows``, from the host alone: ``"item"`` (the series
+    layout hands statics or ids per item, so the series rows differ per item), ``"shared"`` (one ``[1, steps, N]``
+    block) or None (no late-bias head, or no series rows to feed it)."""
+    from torch import nn
+
+    statics = windows._has_static and model.static_proj is not None
+    if (model.late_bias_head is None or model.late_bias_norm is None
+            or not isinstance(model.late_bias_gate, nn.Parameter) or not (statics or model._uses_ids())):
+        return None
+    per_item = windows.layout == "series" and (statics or (windows._has_ids and model._uses_ids()))
+    return "item" if per_item else "shared"
+
+
+class OutputCache:
+    """What the output side of a frozen ``TimesNet`` reads, kept per item of a ``windows.DeviceWindows``: ``seq
+    [n_items, L, D]`` (the block stack's output), ``tail [n_items, hist, N]``, ``y [n_items, steps, N]``, ``mask``
+    (fp32 0/1, only with ``use_loss_mask``), ``late`` (``[n_items, steps, N]`` when the series layout hands statics
+    or ids per item, ``[1, steps, N]`` when one block serves every item, else None), ``floor``, ``hist``, ``steps``.
+
+    Filled in canonical batches: batch ``i`` is items ``i batch_size .. (i + 1) batch_size - 1`` in item order, the
+    short last one included - ``windows.batch(i)`` of the default loader, ``windows.gather(arange)`` of a training
+    loader - with one frozen forward (``model.output_inputs``) each.  The period selector averages amplitudes over a
+    batch, so an item's ``seq`` depends on its batch: the cache defines it as that of the canonical batch (DESIGN.md
+    section 8).  Windows that shift or add noise have no cache (ValueError).  ``bytes_needed`` is the size of the
+    stores from the host alone; beyond ``max_bytes`` the constructor raises before it allocates.
+
+    The cache remembers ``_param_key`` of every parameter outside the six refit tensors and each block's engine;
+    ``check(model)`` raises ValueError when they differ.  A step of the six tensors does not invalidate it."""
+
+    def __init__(self, model, windows, use_loss_mask: bool = False, max_bytes: Optional[int] = None):
+        from .score import _unpack_batch
+
+        self._refuse_augmented(windows)
+        need = self.bytes_needed(model, windows, use_loss_mask)
+        if max_bytes is not None and need > int(max_bytes):
+            raise ValueError(f"OutputCache: the stores need {need} bytes, max_bytes is {int(max_bytes)}")
+        n, B = windows.n_items, windows.batch_size
+        dev = _refit_params(model)[0].device
+        self.windows, self.use_loss_mask = windows, bool(use_loss_mask)
+        self.steps = int(model._out_steps)
+        self.hist = min(self.steps, int(model.input_len))
+        self.n_items, self.batch_size = n, B
+        layout = _late_layout(model, windows)
+        self.seq = self.tail = self.y = self.mask = self.late = self.floor = None
+        was_training = model.training
+        model.eval()
+        try:
+            for k0 in range(0, n, B):
+                k1 = min(k0 + B, n)
+                batch = windows.batch(k0 // B) if windows._default else \
+                    windows.gather(torch.arange(k0, k1, dtype=torch.int64, device=windows.device))
+                xb, yb, mask, x_mark, _, static, ids = _unpack_batch(batch)
+                move = lambda t: None if t is None else t.to(dev, non_blocking=True)
+                seq, tail, hist, late, floor = model.output_inputs(
+                    move(xb), move(x_mark), move(static),
+                    None if ids is None else ids.to(device=dev, dtype=torch.long, non_blocking=True))
+                if use_loss_mask and mask is None:
+                    raise ValueError("OutputCache: use_loss_mask needs a mask in every batch")
+                got = None if late is None else ("shared" if layout != "item" and late.shape[0] == 1 else "item")
+                if got != layout or hist != self.hist:
+                    raise ValueError(f"OutputCache: the late bias came out as {got!r} where the model's layers said "
+                                     f"{layout!r}; call the model on a batch of these windows before caching them")
+                if self.seq is None:
+                    N = tail.shape[2]
+                    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+                    self.seq, self.tail = new(n, *seq.shape[1:]), new(n, hist, N)
+                    self.y = new(n, self.steps, N)
+                    self.mask = new(n, self.steps, N) if use_loss_mask else None
+                    self.late = new(n if layout == "item" else 1, self.steps, N) if layout else None
+                    self.floor = None if floor is None else floor.to(device=dev, dtype=torch.float32).clone()
+                self.seq[k0:k1].copy_(seq)
+                self.tail[k0:k1].copy_(tail)
+                self.y[k0:k1].copy_(move(yb)[:, :self.steps, :])
+                if use_loss_mask:
+                    self.mask[k0:k1].copy_(move(mask)[:, :self.steps, :] > 0.0)
+                if layout == "item":
+                    self.late[k0:k1].copy_(late.expand(k1 - k0, -1, -1))
+                elif layout == "shared" and k0 == 0:
+                    self.late.copy_(late)
+        finally:
+            model.train(was_training)
+        if self.seq is None:
+            raise ValueError("OutputCache: the windows have no items")
+        self.late_per_item = layout == "item"
+        self.min_sigma = float(model.min_sigma)
+        self._key = self._backbone_key(model)
+
+    @staticmethod
+    def _refuse_augmented(windows) -> None:
+        if windows.time_shift or windows.add_noise_std:
+            raise ValueError(f"OutputCache: windows with time_shift={windows.time_shift} / add_noise_std="
+                             f"{windows.add_noise_std} differ per epoch and have no cache")
+
+    @staticmethod
+    def bytes_needed(model, windows, use_loss_mask: bool = False) -> int:
+        """The bytes of ``seq``, ``tail``, ``y``, ``mask`` and ``late`` for these windows, from the host alone (the
+        model's lazily built layers must exist: call it once first)."""
+        if model.d_model is None:
+            raise ValueError("OutputCache.bytes_needed: the model has not been called yet (d_model is unknown)")
+        n, L, D = windows.n_items, int(model.input_len), int(model.d_model)
+        N = 1 if windows.layout == "series" else windows.n_series
+        steps = int(model._out_steps)
+        layout = _late_layout(model, windows)
+        late = {None: 0, "shared": 1, "item": n}[layout]
+        return 4 * (n * L * D + n * min(steps, L) * N + (2 if use_loss_mask else 1) * n * steps * N + late * steps * N)
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.seq, self.tail, self.y, self.mask, self.late)
+                   if t is not None)
+
+    @staticmethod
+    def _backbone_key(model):
+        from .models.timesnet import _param_key
+
+        six = {id(p) for p in _refit_params(model)}
+        return (_param_key([p for p in model.parameters() if id(p) not in six]),
+                tuple(getattr(b, "engine", None) for b in model.blocks))
+
+    def check(self, model) -> None:
+        if self._backbone_key(model) != self._key:
+            raise ValueError("OutputCache: the backbone changed since the cache was filled")
+
+    def select(self, rows: torch.Tensor):
+        """``(tail, y, mask, late)`` of the batch ``rows`` by ``index_select`` (the eager step's operands): the mask
+        as bool, the late bias as its shared block where it has one."""
+        pick = lambda t: None if t is None else t.index_select(0, rows)
+        return (pick(self.tail), pick(self.y), None if self.mask is None else pick(self.mask) > 0.0,
+                pick(self.late) if self.late_per_item else self.late)
+
+
+class GraphedCachedStep:
+    """``GraphedRefitStep`` without the backbone: a step of the output side on the items ``rows`` of an
+    ``OutputCache``, captured once and replayed with one graph launch.  The captured launches are
+    ``ftn_refit_rows_gather`` (tail, y, mask and a per-item late bias into batch tensors; the clamped list and the
+    status word), ``ftn_timeproj_forward_rows`` on the cached ``seq`` in place, ``ftn_head_fit_forward``,
+    ``ftn_nb_nll_grad``, ``ftn_head_backward``, ``ftn_timeproj_backward_rows`` into the last ``steps`` rows of zeroed
+    full-size buffers, and ``optimizer.step_on`` with the heads' ``bad`` word and the status word as skip words.
+    ``step(rows)`` copies an int64 device vector of ``batch_size`` items (a slice of ``windows.order(e)``) into the
+    captured list ``.rows`` and replays.  An index outside the cache is clamped by every kernel and skips the update
+    (flag 8 in the optimizer's log): neither a fault nor an unnoticed wrong step.  Nothing is read on the host."""
+
+    def __init__(self, cache: OutputCache, model, optimizer: DeviceAdamW, batch_size: int, warmup: int = 2):
+        if not isinstance(optimizer, DeviceAdamW):
+            raise ValueError("GraphedCachedStep needs a fit.DeviceAdamW")
+        params = _refit_params(model)
+        if len(optimizer.params) != 6 or any(a is not b for a, b in zip(optimizer.params, params)):
+            raise ValueError("GraphedCachedStep: the optimizer must hold mu_head, sigma_head and forecast_time_proj "
+                             "(weight, bias each, in that order)")
+        dev = params[0].device
+        D = cache.seq.shape[2]
+        if (dev.type != "cuda" or cache.seq.device != dev
+                or any(p.dtype != torch.float32 or not p.is_contiguous() for p in params)
+                or not (D % 4 == 0 and 4 <= D <= 512 and cache.seq.data_ptr() % 16 == 0
+                        and params[0].data_ptr() % 16 == 0 and params[2].data_ptr() % 16 == 0)):
+            raise ValueError("GraphedCachedStep needs a cache and a model with contiguous fp32 parameters on one ROCm "
+                             "device whose output side takes the HIP path (d_model a multiple of 4 up to 512, weights "
+                             "on the 16-byte grid)")
+        cache.check(model)
+        B = int(batch_size)
+        if B < 1:
+            raise ValueError(f"GraphedCachedStep: batch_size={batch_size} is not positive")
+        self.cache, self.model, self.optimizer, self.device, self.batch_size = cache, model, optimizer, dev, B
+        self.steps = cache.steps
+        N = cache.y.shape[2]
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self._rows = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._rows_ok = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._batch = (new(B, cache.hist, N), new(B, cache.steps, N),
+                       None if cache.mask is None else new(B, cache.steps, N),
+                       new(B, cache.steps, N) if cache.late_per_item else None)
+        proj = model.forecast_time_proj
+        self._gw, self._gb = torch.zeros_like(proj.weight), torch.zeros_like(proj.bias)   # rows before -steps stay 0
+        # warm-up on a side stream, as GraphedRefitStep: the update goes to copies and a throw-away optimizer
+        spare = DeviceAdamW([p.detach().clone() for p in params], backend="hip")
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(max(1, int(warmup))):
+                self._enqueue(spare)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self.loss, self.bad, self.grads, self._keep = self._enqueue(optimizer)
+
+    def _enqueue(self, optimizer: DeviceAdamW):
+        """The step's launches on the current stream."""
+        from . import runtime as rt
+
+        cache, steps = self.cache, self.steps
+        w_mu, b_mu, w_sg, b_sg, pw, pb = (p.detach() for p in _refit_params(self.model))
+        tail, y, mask, late, rows_ok, status = rt.refit_rows_gather(
+            self._rows, cache.tail, cache.y, cache.mask, cache.late if cache.late_per_item else None,
+            out=self._batch, rows_ok=self._rows_ok, status=self.status)
+        if not cache.late_per_item:
+            late = cache.late
+        hidden = rt.timeproj_forward(cache.seq, pw[-steps:], pb[-steps:], rows=rows_ok)
+        rate, disp, sig_mu, sig_sg, bad = rt.head_fit_forward(hidden, w_mu, b_mu.contiguous(), w_sg, b_sg.contiguous(),
+                                                              tail, cache.hist, late, cache.floor, cache.min_sigma)
+        words, g_rate, g_disp = rt.nb_nll_grad(y, rate, disp, mask, scaled=False)
+        dw_mu, db_mu, dw_sg, db_sg, d_hidden = rt.head_backward(hidden, g_rate, g_disp, sig_mu, sig_sg,
+                                                                words[1:2], w_mu, w_sg, want_hidden=True)
+        rt.timeproj_backward(cache.seq, d_hidden, dw=self._gw[-steps:], db=self._gb[-steps:], rows=rows_ok)
+        grads = [dw_mu, db_mu, dw_sg, db_sg, self._gw, self._gb]
+        optimizer.step_on(grads, loss=words[0:1], skip=[bad, status])
+        keep = (hidden, rate, disp, sig_mu, sig_sg, words, g_rate, g_disp, d_hidden)
+        return words[0:1], bad, grads, keep
+
+    @property
+    def rows(self) -> torch.Tensor:
+        """The captured row list (int64 ``[batch_size]``); writing into it saves ``step``'s copy."""
+        return self._rows
+
+    def replay(self) -> torch.Tensor:
+        """One replay on the list as it is; returns the loss word (overwritten by the next replay)."""
+        self.graph.replay()
+        self.optimizer.note_replay()
+        return self.loss
+
+    def step(self, rows: torch.Tensor) -> torch.Tensor:
+        if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or tuple(rows.shape) != (self.batch_size,)
+                or rows.device != self.device):
+            raise ValueError(f"GraphedCachedStep.step: rows must be int64 [{self.batch_size}] on {self.device}")
+        if rows.data_ptr() != self._rows.data_ptr():
+            self._rows.copy_(rows, non_blocking=True)
+        return self.replay()
+
+
+def refit_output_cached(model, windows, epochs: int = 1, lr=1e-3, weight_decay: float = 0.0,
+                        grad_clip: Optional[float] = None, use_loss_mask: bool = False,
+                        cache: Optional[OutputCache] = None, graphed: bool = True):
+    """``refit_output_graphed`` over an ``OutputCache``: the frozen backbone runs once per item (not at all with a
+    ``cache`` given, which is ``check``ed and must be of these ``windows``), and every step of every epoch is the
+    output side alone on ``windows.order(e)[i B : (i + 1) B]``, ``len(windows)`` batches an epoch.  A full batch is
+    one replay of a ``GraphedCachedStep``; a short last batch, ``graphed=False`` and tensors the HIP path does not
+    take run the eager step (``output_nll(..., rows=)`` and the same ``DeviceAdamW``).  ``lr``: a float, or one value
+    per epoch.  ``windows.epoch`` advances as ``iter(windows)`` would advance it.  One synchronisation at the end,
+    which raises what ``refit_output_graphed`` raises from the log, and IndexError when a step was skipped for a row
+    outside the cache.  Returns the losses, fp32 ``[epochs * batches]`` on the host; mode and ``requires_grad`` flags
+    come back as they were.  With ``shuffle=False`` the result has the bits of ``refit_output_graphed``; with
+    ``shuffle=True`` the period selection is frozen with the backbone."""
+    epochs = int(epochs)
+    rates = [float(lr)] * epochs if isinstance(lr, (int, float)) else [float(v) for v in lr]
+    if len(rates) != epochs:
+        raise ValueError(f"refit_output_cached: {len(rates)} learning rates for {epochs} epochs")
+    if cache is None:
+        cache = OutputCache(model, windows, use_loss_mask=use_loss_mask)
+    else:
+        if cache.windows is not windows:
+            raise ValueError("refit_output_cached: the cache was filled from other windows")
+        if use_loss_mask and cache.mask is None:
+            raise ValueError("refit_output_cached: use_loss_mask needs a cache filled with use_loss_mask")
+        OutputCache._refuse_augmented(windows)
+        cache.check(model)
+    params = _refit_params(model)
+    dev = params[0].device
+    flags = [(p, p.requires_grad) for p in model.parameters()]
+    was_training = model.training
+    losses = []
+    B, steps = windows.batch_size, cache.steps
+    use_mask = use_loss_mask and cache.mask is not None
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        for p in params:
+            p.requires_grad_(True)
+        model.eval()
+        opt = DeviceAdamW(params, lr=rates[0] if rates else 1e-3, weight_decay=weight_decay, max_norm=grad_clip)
+        step = None
+        proj = model.forecast_time_proj
+        for e in range(epochs):
+            opt.set_lr(rates[e])
+            epoch = windows.epoch
+            if not windows._default:
+                windows.epoch += 1
+            order = windows.order(epoch).to(dev)
+            for i in range(len(windows)):
+                rows = order[i * B:(i + 1) * B]
+                if graphed and dev.type == "cuda" and rows.numel() == B:
+                    if step is None:
+                        if not use_mask and cache.mask is not None:     # a cache with a mask, a refit without one
+                            cache = _without_mask(cache)
+                        step = GraphedCachedStep(cache, model, opt, B)
+                    losses.append(step.step(rows).clone())
+                    continue
+                tail, y, mask, late = cache.select(rows)
+                opt.zero_grad(set_to_none=True)
+                with torch.enable_grad():
+                    loss, bad = output_nll(cache.seq, proj.weight[-steps:], proj.bias[-steps:], *params[:4], tail,
+                                           cache.hist, y, mask if use_mask else None, late, cache.floor,
+                                           cache.min_sigma, rows=rows)
+                loss.backward()
+                opt.step(loss=loss.detach(), skip=[bad])
+                opt.zero_grad(set_to_none=True)
+                losses.append(loss.detach().reshape(1))
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
+        model.train(was_training)
+    if not losses:
+        raise ValueError("refit_output_cached: no batches")
+    host = torch.cat(losses).cpu()                               # the one synchronisation
+    log = opt.history()
+    seen = 0
+    for v in log[:, 3].tolist():
+        seen |= int(v)
+    for bit, name in ((1, "rate"), (2, "dispersion")):
+        if seen & bit:
+            raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
+    if seen & 4:
+        raise FloatingPointError("refit_output_cached: " + _RANGE_MESSAGE)
+    # flag 8 beside a finite loss and norm is the status word of ftn_refit_rows_gather
+    if bool(((log[:, 3].to(torch.int32) & 8) != 0).logical_and(torch.isfinite(log[:, :2]).all(1)).any()):
+        raise IndexError("refit_output_cached: a step's row list pointed outside the cache; those steps were skipped")
+    return host
+
+
+def _without_mask(cache: OutputCache) -> OutputCache:
+    """A view of ``cache`` whose steps use no mask (the stores are shared)."""
+    import copy
+
+    bare = copy.copy(cache)
+    bare.mask = None
+    return bare

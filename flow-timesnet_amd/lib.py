@@ -57,6 +57,7 @@ FTN_HEADFIT_COLSUM, FTN_HEADFIT_MFMA, FTN_HEADFIT_CHUNKS_MAX = 1, 2, 256
 FTN_TIMEPROJ_BWD_MFMA, FTN_TIMEPROJ_BWD_CHUNKS_MAX, TIMEPROJ_BWD_CHUNK = 1, 256, 8
 FTN_REFIT_MAX_TENSORS, FTN_REFIT_MAX_SKIP, FTN_REFIT_PARTS_MAX = 8, 8, 1024
 FTN_REFIT_ONE, FTN_REFIT_GRID = 1, 2
+FTN_REFIT_ROWS_BAD = 4                 # ftn_refit_rows_gather's status word when a row index was outside the store
 
 
 class FtnRefitArgs(C.Structure):
@@ -334,6 +335,15 @@ _SIGNATURES = {
     "ftn_timeproj_backward_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_timeproj_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ftn_timeproj_backward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    # cached refit: the row-mapped time projection (csrc/timeproj.hip, timeproj_bwd.hip), the batch gather
+    # (csrc/refit_rows.hip)
+    "ftn_timeproj_forward_rows": (C.c_int, [_P, C.c_longlong, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "ftn_timeproj_wide_forward_rows": (C.c_int, [_P, C.c_longlong, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P,
+                                                 _P]),
+    "ftn_timeproj_backward_rows": (C.c_int, [_P, C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                             C.c_size_t, _P]),
+    "ftn_refit_rows_gather": (C.c_int, [_P, C.c_int, C.c_longlong, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P,
+                                        _P, _P]),
     # refit step: clip and AdamW (csrc/refit.hip)
     "ftn_refit_update_form": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "ftn_refit_update_workspace": (C.c_size_t, [C.c_int, C.POINTER(C.c_longlong)]),

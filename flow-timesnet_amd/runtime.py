@@ -504,14 +504,26 @@ def head_forward(hidden: torch.Tensor, w_mu: torch.Tensor, b_mu: torch.Tensor, w
     return rate, disp, bad
 
 
-def timeproj_forward(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> torch.Tensor:
+def _store_rows(who: str, rows, seq: torch.Tensor) -> torch.Tensor:
+    """The row list of a row-mapped call: a contiguous int64 vector of at least one entry beside the store ``seq``."""
+    if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.dim() != 1 or rows.numel() < 1
+            or rows.device != seq.device or not rows.is_contiguous()):
+        raise ValueError(f"{who}: rows must be a contiguous int64 vector of at least one entry beside seq")
+    return rows
+
+
+def timeproj_forward(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor, rows=None) -> torch.Tensor:
     """``hidden[b] = wt @ seq[b] + bt[:, None]``: ``seq`` [B,L,D] contiguous fp32, ``wt`` [S,L] with contiguous rows
     (a row slice of a taller weight is fine), ``bt`` [S].  Returns [B,S,D].  Row b of the result does not depend on
-    B or on which rows share the call."""
+    B or on which rows share the call.  ``rows`` (int64 ``[B]`` on the device): ``seq`` is an item store
+    ``[n_items, L, D]`` read in place, row b of the result comes from item ``rows[b]`` (clamped into the store; the
+    ``ftn_timeproj_*forward_rows`` entries) and has the bits of the plain call on ``seq[rows]``."""
     lib = _lib.load()
     if seq.dim() != 3 or wt.dim() != 2 or bt.dim() != 1:
         raise ValueError("timeproj_forward takes seq [B, L, D], wt [S, L] and bt [S]")
     B, L, D = seq.shape
+    if rows is not None:
+        n_items, B = B, _store_rows("timeproj_forward", rows, seq).numel()
     S = wt.shape[0]
     if wt.shape[1] != L or bt.shape[0] != S:
         raise ValueError(f"wt {tuple(wt.shape)} / bt {tuple(bt.shape)} do not project seq {tuple(seq.shape)}")
@@ -521,8 +533,10 @@ def timeproj_forward(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor) -> t
             (S > 1 and bt.stride(0) != 1):
         raise ValueError("seq must be contiguous, wt rows contiguous with stride L, bt contiguous")
     hidden = torch.empty(B, S, D, dtype=torch.float32, device=seq.device)
-    entry = _shell_entry("ftn_timeproj_forward", D)
-    check(getattr(lib, entry)(_ptr(seq), B, L, D, _ptr(wt), _ptr(bt), S, _ptr(hidden), _stream(seq.device)), entry)
+    entry = _shell_entry("ftn_timeproj_forward", D) + ("" if rows is None else "_rows")
+    mapped = () if rows is None else (n_items, _ptr(rows))
+    check(getattr(lib, entry)(_ptr(seq), *mapped, B, L, D, _ptr(wt), _ptr(bt), S, _ptr(hidden), _stream(seq.device)),
+          entry)
     return hidden
 
 
@@ -1076,27 +1090,83 @@ def timeproj_backward_form_of(B: int, L: int, S: int, D: int, misalign_or: int =
     return {_lib.FTN_TIMEPROJ_BWD_MFMA: "k_timeproj_bwd_mfma"}[f & 15], f >> 4
 
 
-def timeproj_backward(seq: torch.Tensor, d_hidden: torch.Tensor, dw=None, db=None):
+def timeproj_backward(seq: torch.Tensor, d_hidden: torch.Tensor, dw=None, db=None, rows=None):
     """``ftn_timeproj_backward``: ``seq`` [B,L,D] and ``d_hidden`` [B,S,D] contiguous fp32 on one device (16-byte
     aligned, or ValueError).  Returns ``(dW_t [S,L], db_t [S])``, the gradients of ``timeproj_forward``'s ``wt`` and
-    ``bt``; ``dw`` / ``db`` may be the caller's (contiguous fp32).  Enqueues only."""
+    ``bt``; ``dw`` / ``db`` may be the caller's (contiguous fp32).  ``rows`` (int64 ``[B]`` on the device): ``seq`` is
+    an item store ``[n_items, L, D]`` and batch row b reads item ``rows[b]``, clamped into the store
+    (``ftn_timeproj_backward_rows``): the bits of the plain call on ``seq[rows]``.  Enqueues only."""
     lib = _lib.load()
-    if seq.dim() != 3 or d_hidden.dim() != 3 or seq.shape[0] != d_hidden.shape[0] or seq.shape[2] != d_hidden.shape[2]:
-        raise ValueError("timeproj_backward takes seq [B, L, D] and d_hidden [B, S, D]")
+    n_rows = seq.shape[0] if rows is None or seq.dim() < 1 else _store_rows("timeproj_backward", rows, seq).numel()
+    if seq.dim() != 3 or d_hidden.dim() != 3 or seq.shape[2] != d_hidden.shape[2] or n_rows != d_hidden.shape[0]:
+        raise ValueError("timeproj_backward takes seq [B, L, D] and d_hidden [B, S, D]" if rows is None else
+                         "timeproj_backward takes seq [n_items, L, D], rows [B] and d_hidden [B, S, D]")
     for name, t in (("seq", seq), ("d_hidden", d_hidden)):
         if t.dtype != torch.float32 or not t.is_cuda or t.device != seq.device or not t.is_contiguous():
             raise ValueError(f"timeproj_backward: {name} must be a contiguous fp32 device tensor")
-    B, L, D = seq.shape
-    S = d_hidden.shape[1]
+    n_items, L, D = seq.shape
+    B, S = d_hidden.shape[:2]
     dw = _out_or_fresh("timeproj_backward", dw, (S, L), seq, "dw")
     db = _out_or_fresh("timeproj_backward", db, (S,), seq, "db")
     need = lib.ftn_timeproj_backward_workspace(B, L, S, D)
     if need == 0:
         raise ValueError(f"timeproj_backward: ftn_timeproj_backward_workspace rejected B={B} L={L} S={S} d_model={D}")
     ws = _workspace(seq.device, need)
-    check(lib.ftn_timeproj_backward(_ptr(seq), _ptr(d_hidden), B, L, S, D, _ptr(dw), _ptr(db), _ptr(ws), ws.numel(),
-                                    _stream(seq.device)), "ftn_timeproj_backward")
+    if rows is None:
+        check(lib.ftn_timeproj_backward(_ptr(seq), _ptr(d_hidden), B, L, S, D, _ptr(dw), _ptr(db), _ptr(ws), ws.numel(),
+                                        _stream(seq.device)), "ftn_timeproj_backward")
+    else:
+        check(lib.ftn_timeproj_backward_rows(_ptr(seq), n_items, _ptr(rows), _ptr(d_hidden), B, L, S, D, _ptr(dw),
+                                             _ptr(db), _ptr(ws), ws.numel(), _stream(seq.device)),
+              "ftn_timeproj_backward_rows")
     return dw, db
+
+
+def refit_rows_gather(rows: torch.Tensor, tail: torch.Tensor, y: torch.Tensor, mask=None, late=None, out=None,
+                      rows_ok=None, status=None):
+    """``ftn_refit_rows_gather``: the batch tensors of a cached refit step from the per-item stores ``tail``
+    ``[n_items, hist, N]``, ``y`` ``[n_items, S, N]`` and the optional ``mask`` / ``late`` ``[n_items, S, N]``
+    (contiguous fp32 on one device) through ``rows`` (int64 ``[B]`` there).  Returns ``(tail_b, y_b, mask_b, late_b,
+    rows_ok, status)``: row b of each batch tensor is row ``rows[b]`` of its store, an index outside the store clamped
+    into it; ``rows_ok`` is the clamped list and ``status`` one int32, 4 when an index was outside, else 0 (rewritten
+    by every call).  ``out``: the caller's four batch tensors (None for an absent operand), ``rows_ok`` / ``status``
+    likewise.  One launch, enqueues only."""
+    lib = _lib.load()
+    if tail.dim() != 3 or y.dim() != 3 or tail.shape[0] != y.shape[0] or tail.shape[2] != y.shape[2]:
+        raise ValueError("refit_rows_gather takes tail [n_items, hist, N] and y [n_items, S, N]")
+    n_items, S, N = y.shape
+    hist = tail.shape[1]
+    stores = [("tail", tail), ("y", y), ("mask", mask), ("late", late)]
+    for name, t in stores:
+        if t is None:
+            continue
+        if (t.dtype != torch.float32 or not t.is_cuda or t.device != y.device or not t.is_contiguous()
+                or tuple(t.shape) != ((n_items, hist, N) if name == "tail" else (n_items, S, N))):
+            raise ValueError(f"refit_rows_gather: {name} must be a contiguous fp32 device tensor of its store's shape")
+    B = _store_rows("refit_rows_gather", rows, y).numel()
+    out = [None] * 4 if out is None else list(out)
+    if len(out) != 4:
+        raise ValueError("refit_rows_gather: out is (tail, y, mask, late)")
+    outs = []
+    for (name, t), o in zip(stores, out):
+        if t is None:
+            if o is not None:
+                raise ValueError(f"refit_rows_gather: an output for {name}, which has no store")
+            outs.append(None)
+        else:
+            outs.append(_out_or_fresh("refit_rows_gather", o, (B,) + tuple(t.shape[1:]), y, name))
+    if rows_ok is None:
+        rows_ok = torch.empty(B, dtype=torch.int64, device=y.device)
+    else:
+        _store_rows("refit_rows_gather", rows_ok, y)
+        if rows_ok.numel() != B:
+            raise ValueError(f"refit_rows_gather: rows_ok must have {B} entries")
+    status = _flag_or_fresh("refit_rows_gather", status, y.device)
+    check(lib.ftn_refit_rows_gather(_ptr(rows), B, n_items, _ptr(tail), hist * N, _ptr(y), _ptr_or_null(mask),
+                                    _ptr_or_null(late), S * N, _ptr(outs[0]), _ptr(outs[1]), _ptr_or_null(outs[2]),
+                                    _ptr_or_null(outs[3]), _ptr(rows_ok), _ptr(status), _stream(y.device)),
+          "ftn_refit_rows_gather")
+    return outs[0], outs[1], outs[2], outs[3], rows_ok, status
 
 
 # ------------------------------------------------------------------ refit step: clip and AdamW

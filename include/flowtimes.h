@@ -768,6 +768,42 @@ size_t ftn_timeproj_backward_workspace(int B, int L, int S, int D);
 int ftn_timeproj_backward(const float* seq_dev, const float* d_hidden_dev, int B, int L, int S, int D, float* dw_t_dev,
                           float* db_t_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 
+/* ---- cached refit: the frozen backbone's output kept per item (csrc/timeproj.hip, timeproj_bwd.hip, refit_rows.hip) --
+ * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
+ *
+ * Row-mapped forms of the two readers of seq.  seq is an item store [n_items][L][D] (contiguous fp32, 16-byte
+ * aligned) and rows an int64 device vector [B] (8-byte aligned): batch row b reads item rows[b]; hidden and d_hidden
+ * stay [B][S][D].  Nothing else about a kernel changes - the form is that of ftn_timeproj_form /
+ * ftn_timeproj_wide_form / ftn_timeproj_backward_form, and so are the tiles, the K order, the chunks of batch rows, the
+ * workspace (ftn_timeproj_backward_workspace) and the reduce kernel - so the result has the bits the unmapped entry
+ * gives on the gathered copy seq[rows].  The index is uniform over a workgroup (forward) or over a step of a wave
+ * (backward): one scalar load.  An index outside 0 .. n_items - 1 is clamped into that range in the kernel and
+ * reported by nobody here (ftn_refit_rows_gather reports it): no index makes a kernel read outside seq.  Arguments
+ * are checked before the first launch as by the unmapped entries, plus rows non-null and 8-byte aligned and
+ * n_items >= 1. */
+int ftn_timeproj_forward_rows(const float* seq_dev, long long n_items, const long long* rows_dev, int B, int L, int D,
+                              const float* wt_dev, const float* bt_dev, int S, float* hidden_dev, void* stream);
+int ftn_timeproj_wide_forward_rows(const float* seq_dev, long long n_items, const long long* rows_dev, int B, int L,
+                                   int D, const float* wt_dev, const float* bt_dev, int S, float* hidden_dev,
+                                   void* stream);
+int ftn_timeproj_backward_rows(const float* seq_dev, long long n_items, const long long* rows_dev,
+                               const float* d_hidden_dev, int B, int L, int S, int D, float* dw_t_dev, float* db_t_dev,
+                               void* workspace_dev, size_t workspace_bytes, void* stream);
+
+/* The rest of a cached batch in one launch: batch row b of every output is row rows[b] (clamped as above) of its
+ * store.  tail [n_items][tail_floats] (tail_floats = hist N); y, mask, late [n_items][row_floats] (row_floats = S N,
+ * >= tail_floats); mask and late are optional (store and output both null).  All fp32, contiguous, 4-byte aligned;
+ * a row moves with 16-byte accesses when its length is a multiple of 4 floats and both bases are 16-byte aligned,
+ * else float by float.  rows_ok [B] (int64, 8-byte aligned, not overlapping rows) receives the clamped list and
+ * status one int32: FTN_REFIT_ROWS_BAD when any rows[b] was outside 0 .. n_items - 1, else 0 - a plain store by one
+ * thread, rewritten by every call, no atomics.  As a bare skip word of ftn_refit_update it becomes flag 8: the step
+ * is skipped and logged.  One launch of B workgroups, enqueued only. */
+#define FTN_REFIT_ROWS_BAD 4
+int ftn_refit_rows_gather(const long long* rows_dev, int B, long long n_items, const float* tail_dev, int tail_floats,
+                          const float* y_dev, const float* mask_dev_or_null, const float* late_dev_or_null,
+                          int row_floats, float* tail_out_dev, float* y_out_dev, float* mask_out_dev_or_null,
+                          float* late_out_dev_or_null, long long* rows_ok_dev, int* status_dev, void* stream);
+
 /* The optimiser step of a refit on the device (csrc/refit.hip; additions only: FTN_ABI_VERSION stays 14): clip by
  * the global gradient norm, then AdamW, for n_tensors <= FTN_REFIT_MAX_TENSORS contiguous fp32 tensors of n[i] >= 1
  * elements.  p, m, v are updated in place, g is only read (the clipped gradient is never stored).  Per element, with
