@@ -48,6 +48,12 @@ in place through a device row list (``time_projection(..., rows=)``, the ``_rows
 ``csrc/timeproj_bwd.hip``; ``ftn_refit_rows_gather`` for the rest of the batch), and ``refit_output_cached`` the loop
 over shuffled epochs ("Cached refit").
 
+``refit_output_validated`` is that loop with the reference's per-epoch validation decided on the device:
+``GraphedCachedEval`` scores held-out windows from an ``OutputCache`` of their own into ``ValidationAccumulators``,
+and ``EpochEnd`` (``ftn_refit_epoch_end``, ``csrc/refit_epoch.hip``) turns the sums into the validation NLL, steps
+``ReduceLROnPlateau`` in the optimizer's ``lr`` word, keeps the best epoch's tensors and sets the stop word that every
+later step takes as a skip word ("Validated refit").
+
 ``backend`` follows ``score``'s rule (``_use_hip``): ``hip`` where it can run unless ``"torch"`` is asked for, and
 asking for ``"hip"`` where it cannot is an error.
 """
@@ -59,7 +65,8 @@ import torch
 import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
-from .score import _full_mask, _nb_ll_torch, _rows, _use_hip, negative_binomial_mask
+from .score import (ForecastScorer, _full_mask, _nb_ll_torch, _part_views, _rows, _use_hip,
+                    negative_binomial_mask)
 
 _last_backend: Optional[str] = None
 _last_head_backend: Optional[str] = None      # which path the last ``head_nll`` took
@@ -1045,11 +1052,14 @@ class GraphedCachedStep:
     full-size buffers, and ``optimizer.step_on`` with the heads' ``bad`` word and the status word as skip words.
     ``step(rows)`` copies an int64 device vector of ``batch_size`` items (a slice of ``windows.order(e)``) into the
     captured list ``.rows`` and replays.  An index outside the cache is clamped by every kernel and skips the update
-    (flag 8 in the optimizer's log): neither a fault nor an unnoticed wrong step.  Nothing is read on the host."""
+    (flag 8 in the optimizer's log): neither a fault nor an unnoticed wrong step.  Nothing is read on the host.
+    ``extra_skip``: further skip words of ``step_on`` behind those two (``EpochEnd.stop``); the default adds none."""
 
-    def __init__(self, cache: OutputCache, model, optimizer: DeviceAdamW, batch_size: int, warmup: int = 2):
+    def __init__(self, cache: OutputCache, model, optimizer: DeviceAdamW, batch_size: int, warmup: int = 2,
+                 extra_skip=()):
         if not isinstance(optimizer, DeviceAdamW):
             raise ValueError("GraphedCachedStep needs a fit.DeviceAdamW")
+        self.extra_skip = list(extra_skip)
         params = _refit_params(model)
         if len(optimizer.params) != 6 or any(a is not b for a, b in zip(optimizer.params, params)):
             raise ValueError("GraphedCachedStep: the optimizer must hold mu_head, sigma_head and forecast_time_proj "
@@ -1111,7 +1121,7 @@ class GraphedCachedStep:
                                                                 words[1:2], w_mu, w_sg, want_hidden=True)
         rt.timeproj_backward(cache.seq, d_hidden, dw=self._gw[-steps:], db=self._gb[-steps:], rows=rows_ok)
         grads = [dw_mu, db_mu, dw_sg, db_sg, self._gw, self._gb]
-        optimizer.step_on(grads, loss=words[0:1], skip=[bad, status])
+        optimizer.step_on(grads, loss=words[0:1], skip=[bad, status] + self.extra_skip)
         keep = (hidden, rate, disp, sig_mu, sig_sg, words, g_rate, g_disp, d_hidden)
         return words[0:1], bad, grads, keep
 
@@ -1231,3 +1241,487 @@ def _without_mask(cache: OutputCache) -> OutputCache:
     bare = copy.copy(cache)
     bare.mask = None
     return bare
+
+
+# ------------------------------------------------------------------ validated refit: held-out NLL, best state, early stop
+EPOCH_STOP, EPOCH_AFTER_STOP, EPOCH_SCORER_ERR = 16, 16, 32
+_STATE_BYTES = 64                            # FtnEpochState: four fp64, then eight int32
+_I_EPOCH, _I_BEST, _I_PATIENCE, _I_NUM_BAD, _I_STOP, _I_IMPROVED, _I_CALLS = range(8, 15)   # int32 words of the record
+_last_epoch_backend: Optional[str] = None    # which path the last ``EpochEnd.end_epoch`` took
+
+
+class ValidationAccumulators(ForecastScorer):
+    """A ``ForecastScorer`` without ids whose every buffer is updated in place, so that ``update`` can sit in a
+    captured graph and ``ftn_refit_epoch_end`` can read and clear the buffers on the device.  ``result()`` is the
+    parent's and has the bits of a ``ForecastScorer(n_slots)`` fed the same batches, the "batch without a valid
+    element" rule of ``_den_extra`` included.  ``reset`` zeroes in place."""
+
+    def reset(self) -> None:
+        if getattr(self, "_acc", None) is None:
+            super().reset()
+            return
+        for t in (self._acc, self._err, self._den_extra, self._count_seen):
+            t.zero_()
+
+    def update(self, y, rate, dispersion, mask=None) -> None:                   # noqa: D102
+        if y.dim() != 3 or rate.shape != y.shape or dispersion.shape != y.shape:
+            raise ValueError(f"ValidationAccumulators.update takes y, rate, dispersion of one shape [B, H, N], got "
+                             f"{tuple(y.shape)} {tuple(rate.shape)} {tuple(dispersion.shape)}")
+        if y.shape[2] > self.n_slots:
+            raise ValueError(f"{y.shape[2]} series need {y.shape[2]} slots, the accumulators have {self.n_slots}")
+        if self.device.type == "cuda":
+            self._update_hip(y, rate, dispersion, mask, None)
+        else:
+            self._update_torch(y, rate, dispersion, mask, None)
+        _, counts = _part_views(self._acc)
+        seen = counts[:, 0].sum(dtype=torch.int64)
+        self._den_extra += (seen == self._count_seen).to(torch.float64) * float(y.numel())
+        self._count_seen.copy_(seen)
+
+
+def _epoch_rule(who: str, patience, plateau):
+    """``(patience limit or None, (factor, patience, threshold, min_lr) or None)`` after the host's checks.
+    ``plateau``: a dict with torch's ``ReduceLROnPlateau`` names and defaults (``factor`` 0.1, ``patience`` 10,
+    ``threshold`` 1e-4, ``min_lr`` 0), or those four values as a tuple."""
+    if patience is not None:
+        if isinstance(patience, bool) or not isinstance(patience, int) or patience < 0:
+            raise ValueError(f"{who}: patience={patience!r} is not None or an int >= 0")
+    if plateau is None:
+        return patience, None
+    if isinstance(plateau, dict):
+        odd = set(plateau) - {"factor", "patience", "threshold", "min_lr"}
+        if odd:
+            raise ValueError(f"{who}: plateau has unknown keys {sorted(odd)}")
+        plateau = (plateau.get("factor", 0.1), plateau.get("patience", 10), plateau.get("threshold", 1e-4),
+                   plateau.get("min_lr", 0.0))
+    if not isinstance(plateau, (tuple, list)) or len(plateau) != 4:
+        raise ValueError(f"{who}: plateau is a dict or (factor, patience, threshold, min_lr)")
+    factor, p_pat, threshold, min_lr = plateau
+    if isinstance(p_pat, bool) or not isinstance(p_pat, int) or p_pat < 0:
+        raise ValueError(f"{who}: plateau patience={p_pat!r} is not an int >= 0")
+    factor, threshold, min_lr = float(factor), float(threshold), float(min_lr)
+    if not (0.0 < factor < 1.0 and threshold == threshold and min_lr >= 0.0):
+        raise ValueError(f"{who}: plateau factor={factor} (inside (0, 1)), threshold={threshold}, min_lr={min_lr} (>= 0)")
+    return patience, (factor, p_pat, threshold, min_lr)
+
+
+class EpochEnd:
+    """The end of a validated refit's epoch with nothing read on the host (the reference's train.py:1536-1572): from
+    the validation sums in ``accumulators`` it computes ``val_nll`` and ``val_smape`` as ``ForecastScorer.result()``
+    does, steps ``ReduceLROnPlateau`` (mode ``min``, relative threshold, no cooldown, eps 1e-8) on ``val_nll`` and
+    writes the optimizer's ``lr`` word, keeps the parameters of the best epoch (``val_nll < best_nll``, strict; a NaN
+    is never better) in ``best``, counts epochs without improvement and sets the word ``stop`` to 16 beyond
+    ``patience`` of them - which, as a bare skip word of ``DeviceAdamW``, makes every later step keep all its bits -
+    logs a row, and clears the accumulators.  A call after the stop only logs a row (flag 16) and clears.
+
+    ``ftn_refit_epoch_end`` (``csrc/refit_epoch.hip``: one deciding workgroup, then a copy grid) on contiguous fp32
+    ROCm parameters (backend ``hip``), the same rule in torch ops with ``torch.where`` anywhere else (backend
+    ``torch``; on the CPU its sums are serial and have the kernel's bits); ``_last_epoch_backend`` says which ran.
+    ``state`` is the ``FtnEpochState`` record, ``stop`` / ``improved`` one-element int32 views of it, ``log`` fp64
+    ``[max_epochs, 5]`` rows ``(val_nll, val_smape, lr after, flags, improved)`` - without ``plateau`` the ``lr``
+    column is the optimizer's word as the epoch left it.  Flags: 16 after the stop, 32 the scorer's error word."""
+
+    def __init__(self, params, n_slots: int, max_epochs: int, lr: float, patience: Optional[int] = None,
+                 plateau=None, backend: Optional[str] = None):
+        self.params = list(params)
+        if not 1 <= len(self.params) <= 8:
+            raise ValueError(f"EpochEnd: {len(self.params)} parameter tensors (1..8)")
+        for p in self.params:
+            if not isinstance(p, torch.Tensor) or not p.is_floating_point() or p.numel() < 1:
+                raise ValueError("EpochEnd: parameters must be floating-point tensors that are not empty")
+        if len({p.device for p in self.params}) != 1:
+            raise ValueError("EpochEnd: parameters must be on one device")
+        if int(n_slots) < 1 or int(max_epochs) < 1:
+            raise ValueError(f"EpochEnd: n_slots={n_slots} and max_epochs={max_epochs} must be >= 1")
+        if not float(lr) >= 0.0:
+            raise ValueError(f"EpochEnd: lr={lr} must be >= 0")
+        if backend not in (None, "hip", "torch"):
+            raise ValueError(f"EpochEnd: backend {backend!r} is not 'hip', 'torch' or None")
+        self.patience, self.plateau = _epoch_rule("EpochEnd", patience, plateau)
+        self.backend, self.max_epochs = backend, int(max_epochs)
+        dev = self.device = self.params[0].device
+        self.state = torch.zeros(_STATE_BYTES, dtype=torch.uint8, device=dev)
+        self._f64, self._i32 = self.state.view(torch.float64), self.state.view(torch.int32)
+        self._f64[:3] = float("inf")
+        self._f64[3] = float(lr)
+        self.stop, self.improved = self._i32[_I_STOP:_I_STOP + 1], self._i32[_I_IMPROVED:_I_IMPROVED + 1]
+        self.log = torch.zeros(self.max_epochs, 5, dtype=torch.float64, device=dev)
+        self.best = [p.detach().clone(memory_format=torch.contiguous_format) for p in self.params]
+        self.accumulators = ValidationAccumulators(int(n_slots), dev)
+
+    def _hip(self) -> bool:
+        eligible = self.device.type == "cuda" and all(p.dtype == torch.float32 and p.is_contiguous()
+                                                      for p in self.params)
+        return _use_hip("EpochEnd", self.backend, eligible, "contiguous fp32 parameters on a ROCm device")
+
+    def end_epoch(self, optimizer) -> None:
+        """The epoch's decision from the accumulators as they are; ``optimizer``: the ``DeviceAdamW`` whose ``lr``
+        word a plateau schedule writes.  Enqueues only, and can be captured."""
+        global _last_epoch_backend
+        lr_word = getattr(optimizer, "_lr", None)
+        if (not isinstance(lr_word, torch.Tensor) or lr_word.dtype != torch.float32 or lr_word.numel() != 1
+                or lr_word.device != self.device):
+            raise ValueError("EpochEnd.end_epoch needs the DeviceAdamW of these parameters (its lr word)")
+        acc = self.accumulators
+        if self._hip():
+            from . import runtime as rt
+
+            rt.refit_epoch_end(acc._acc, acc._err, acc._den_extra, acc._count_seen, self.state, lr_word, self.log,
+                               self.patience, self.plateau, [p.detach() for p in self.params], self.best)
+            _last_epoch_backend = "hip"
+        else:
+            with torch.no_grad():
+                self._end_torch(lr_word)
+            _last_epoch_backend = "torch"
+
+    def _end_torch(self, lr_word: torch.Tensor) -> None:
+        """``ftn_refit_epoch_end`` in torch ops: fp64 throughout, every decision a device word and every write a
+        ``torch.where``.  ``cumsum`` from a leading 0.0 is the serial slot-order sum on the CPU."""
+        acc, dev, f, i = self.accumulators, self.device, self._f64, self._i32
+        f64 = dict(dtype=torch.float64, device=dev)
+        sums, counts = _part_views(acc._acc)
+        lead = torch.zeros(1, **f64)
+        num = torch.cumsum(torch.cat([lead, sums[:, 0]]), 0)[-1]
+        sm = torch.cumsum(torch.cat([lead, sums[:, 1]]), 0)[-1]
+        cnt = counts.sum(0, dtype=torch.int64)
+        den = cnt[0].double() + acc._den_extra.reshape(())
+        nought = torch.zeros((), **f64)
+        nll = torch.where(den > 0, num / den, nought)
+        smape = torch.where(cnt[1] > 0, sm / cnt[1].double(), nought)
+        for t in (acc._acc, acc._den_extra, acc._count_seen):
+            t.zero_()
+        best_nll, best_smape, p_best, lr_s = (f[k].clone() for k in range(4))
+        epoch, best_epoch, pat, n_bad, stop, improved, calls = (i[k].clone() for k in range(_I_EPOCH, _I_CALLS + 1))
+        live = stop == 0
+        lr_now = lr_s if self.plateau is not None else lr_word.reshape(()).double()
+        flags = (acc._err.reshape(()) != 0).to(torch.float64) * float(EPOCH_SCORER_ERR)
+        epoch1 = epoch + 1
+        lr1, p_best1, n_bad1 = lr_now, p_best, n_bad
+        if self.plateau is not None:
+            factor, p_pat, threshold, min_lr = self.plateau
+            better = nll < p_best * (1.0 - threshold)
+            p_best1 = torch.where(better, nll, p_best)
+            n_bad1 = torch.where(better, torch.zeros_like(n_bad), n_bad + 1)
+            cut = n_bad1 > p_pat
+            new = torch.clamp(lr_now * factor, min=min_lr)
+            lr1 = torch.where(cut & (lr_now - new > 1e-8), new, lr_now)
+            n_bad1 = torch.where(cut, torch.zeros_like(n_bad1), n_bad1)
+        up = nll < best_nll
+        pat1 = torch.where(up, torch.zeros_like(pat), pat + 1)
+        stop1 = torch.zeros_like(stop)
+        if self.patience is not None:
+            stop1 = torch.where(~up & (pat1 > self.patience), torch.full_like(stop, EPOCH_STOP), stop1)
+        nan = torch.full((), float("nan"), **f64)
+        row = torch.where(live, torch.stack([nll, smape, lr1, flags, up.to(torch.float64)]),
+                          torch.stack([nan, nan, lr_now, nought + float(EPOCH_AFTER_STOP), nought]))
+        at = torch.clamp(calls, max=self.max_epochs - 1).long().reshape(1)
+        self.log.index_copy_(0, at, torch.where(calls < self.max_epochs, row.reshape(1, 5), self.log.index_select(0, at)))
+        took = live & up
+        f[0] = torch.where(took, nll, best_nll)
+        f[1] = torch.where(took, smape, best_smape)
+        f[2] = torch.where(live, p_best1, p_best)
+        f[3] = torch.where(live, lr1, lr_s)
+        i[_I_EPOCH] = torch.where(live, epoch1, epoch)
+        i[_I_BEST] = torch.where(took, epoch1, best_epoch)
+        i[_I_PATIENCE] = torch.where(live, pat1, pat)
+        i[_I_NUM_BAD] = torch.where(live, n_bad1, n_bad)
+        i[_I_STOP] = torch.where(live, stop1, stop)
+        i[_I_IMPROVED] = torch.where(live, up.to(torch.int32), improved)
+        i[_I_CALLS] = calls + 1
+        if self.plateau is not None:
+            lr_word.copy_(torch.where(live, lr1.to(torch.float32), lr_word.reshape(())).reshape(lr_word.shape))
+        for p, b in zip(self.params, self.best):
+            b.copy_(torch.where(took, p.detach(), b))
+
+    def restore(self) -> None:
+        """The best epoch's tensors back into the parameters; if no epoch improved they keep every bit.  Enqueues
+        only."""
+        if self._hip():
+            from . import runtime as rt
+            from .range_guard import _capturing
+
+            rt.refit_epoch_restore(self.state, self.best, [p.detach() for p in self.params])
+            if not _capturing():
+                _bump_versions(self.params)
+        else:
+            with torch.no_grad():
+                for p, b in zip(self.params, self.best):
+                    p.copy_(torch.where(self._i32[_I_BEST] > 0, b, p.detach()))
+
+    def history(self) -> dict:
+        """``rows`` (the log rows of the calls so far, fp64 ``[calls, 5]`` on the host), ``epoch`` (epochs decided),
+        ``best_epoch`` (1-based, 0: none improved), ``best_nll``, ``best_smape`` and ``stopped_epoch`` (the epoch that
+        set the stop word, None if none did): one synchronisation."""
+        host = torch.cat([self.log.reshape(-1), self._f64]).cpu()
+        state = host[-_STATE_BYTES // 8:].clone()
+        f, i = state.tolist(), state.view(torch.int32).tolist()
+        calls = min(i[_I_CALLS], self.max_epochs)
+        return {"rows": host[:-_STATE_BYTES // 8].reshape(-1, 5)[:calls].clone(), "epoch": i[_I_EPOCH],
+                "best_epoch": i[_I_BEST], "best_nll": f[0], "best_smape": f[1],
+                "stopped_epoch": i[_I_EPOCH] if i[_I_STOP] != 0 else None}
+
+
+def _cached_forecast(cache: OutputCache, model, rows: torch.Tensor, out=None, rows_ok=None, status=None):
+    """``(y, mask, rate, dispersion, bad, status)`` of the items ``rows`` of ``cache`` under the model's output side as
+    it stands: on the device ``ftn_refit_rows_gather``, ``ftn_timeproj_forward_rows`` on the cached ``seq`` and the
+    inference head kernel - the launches, and so the bits, of the model's own forward on that batch; elsewhere the
+    torch composition.  ``status`` is the gather's word (4: an index was outside the cache and was clamped)."""
+    steps = cache.steps
+    w_mu, b_mu, w_sg, b_sg, pw, pb = (p.detach() for p in _refit_params(model))
+    if cache.seq.is_cuda:
+        from . import runtime as rt
+
+        tail, y, mask, late, rows_ok, status = rt.refit_rows_gather(
+            rows, cache.tail, cache.y, cache.mask, cache.late if cache.late_per_item else None,
+            out=out, rows_ok=rows_ok, status=status)
+        if not cache.late_per_item:
+            late = cache.late
+        hidden = rt.timeproj_forward(cache.seq, pw[-steps:], pb[-steps:], rows=rows_ok)
+        rate, disp, bad = rt.head_forward(hidden, w_mu, b_mu.contiguous(), w_sg, b_sg.contiguous(), tail, cache.hist,
+                                          late, cache.floor, cache.min_sigma)
+        return y, mask, rate, disp, bad, status
+    tail, y, mask, late = cache.select(rows)
+    with torch.no_grad():
+        hidden = torch.matmul(pw[-steps:], cache.seq.index_select(0, rows)) + pb[-steps:].view(1, -1, 1)
+        rate, disp, bad = _heads_torch(hidden, w_mu, b_mu, w_sg, b_sg, tail, cache.hist, late, cache.floor,
+                                       cache.min_sigma)
+    return y, mask, rate, disp, bad, torch.zeros(1, dtype=torch.int32, device=rows.device)
+
+
+class GraphedCachedEval:
+    """One validation batch from an ``OutputCache``, captured once: ``ftn_refit_rows_gather``,
+    ``ftn_timeproj_forward_rows`` on the cached ``seq``, the inference head kernel, then ``score_columns`` and
+    ``score_fold`` into ``accumulators`` (``ValidationAccumulators.update``).  ``run(rows)`` copies an int64 device
+    vector into the captured list and replays when it has ``batch_size`` entries; a shorter one takes the same
+    launches eagerly.  The heads' ``bad`` word and the gather's status word are OR-ed into the sticky words
+    ``bad_seen`` / ``rows_seen``: an index outside the cache is clamped and reported there.  Nothing is read on the
+    host."""
+
+    def __init__(self, cache: OutputCache, model, accumulators: ValidationAccumulators, batch_size: int,
+                 warmup: int = 2):
+        if not isinstance(accumulators, ValidationAccumulators):
+            raise ValueError("GraphedCachedEval needs fit.ValidationAccumulators (EpochEnd.accumulators)")
+        params = _refit_params(model)
+        dev = params[0].device
+        D = cache.seq.shape[2]
+        if (dev.type != "cuda" or cache.seq.device != dev or accumulators.device != dev
+                or any(p.dtype != torch.float32 or not p.is_contiguous() for p in params)
+                or not (D % 4 == 0 and 4 <= D <= 512 and cache.seq.data_ptr() % 16 == 0
+                        and params[0].data_ptr() % 16 == 0 and params[2].data_ptr() % 16 == 0)):
+            raise ValueError("GraphedCachedEval needs a cache, accumulators and a model with contiguous fp32 "
+                             "parameters on one ROCm device whose output side takes the HIP path (d_model a multiple "
+                             "of 4 up to 512, weights on the 16-byte grid)")
+        cache.check(model)
+        B, N = int(batch_size), cache.y.shape[2]
+        if B < 1:
+            raise ValueError(f"GraphedCachedEval: batch_size={batch_size} is not positive")
+        if N > accumulators.n_slots:
+            raise ValueError(f"GraphedCachedEval: {N} series need {N} slots, the accumulators have "
+                             f"{accumulators.n_slots}")
+        self.cache, self.model, self.accumulators, self.device, self.batch_size = cache, model, accumulators, dev, B
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        self._rows = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._rows_ok = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.bad_seen = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.rows_seen = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._batch = (new(B, cache.hist, N), new(B, cache.steps, N),
+                       None if cache.mask is None else new(B, cache.steps, N),
+                       new(B, cache.steps, N) if cache.late_per_item else None)
+        # warm-up on a side stream into accumulators and sticky words of its own: the real ones do not move
+        spare = ValidationAccumulators(accumulators.n_slots, dev)
+        spare_words = (torch.zeros_like(self.bad_seen), torch.zeros_like(self.rows_seen))
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(max(1, int(warmup))):
+                self._enqueue(self._rows, spare, *spare_words, captured=True)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph):
+            self._keep = self._enqueue(self._rows, accumulators, self.bad_seen, self.rows_seen, captured=True)
+
+    def _enqueue(self, rows, accumulators, bad_seen, rows_seen, captured: bool):
+        """The batch's launches on the current stream, into the captured buffers or (a short batch) fresh ones."""
+        own = dict(out=self._batch, rows_ok=self._rows_ok, status=self.status) if captured else {}
+        y, mask, rate, disp, bad, status = _cached_forecast(self.cache, self.model, rows, **own)
+        accumulators.update(y, rate, disp, mask)
+        bad_seen |= bad
+        rows_seen |= status
+        return y, mask, rate, disp, bad
+
+    def run(self, rows: torch.Tensor) -> None:
+        if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64 or rows.dim() != 1
+                or not 1 <= rows.numel() <= self.batch_size or rows.device != self.device):
+            raise ValueError(f"GraphedCachedEval.run: rows must be int64 [1..{self.batch_size}] on {self.device}")
+        if rows.numel() < self.batch_size:
+            with torch.no_grad():
+                self._enqueue(rows.contiguous(), self.accumulators, self.bad_seen, self.rows_seen, captured=False)
+            return
+        if rows.data_ptr() != self._rows.data_ptr():
+            self._rows.copy_(rows, non_blocking=True)
+        self.graph.replay()
+
+
+class ValidatedRefit:
+    """What ``refit_output_validated`` returns: ``losses`` (fp32, the steps of the epochs that ran), ``val_nll``,
+    ``val_smape`` and ``lr`` (fp64, one value per epoch that ran), ``best_epoch`` (1-based; 0: no epoch improved),
+    ``best_nll``, ``best_smape``, ``stopped_epoch`` (None if the epochs ran out), ``epochs_enqueued`` and
+    ``optimizer`` (the loop's ``DeviceAdamW``: moments and step count as the last applied step left them)."""
+
+    def __init__(self, losses, rows, best_epoch, best_nll, best_smape, stopped_epoch, epochs_enqueued, optimizer):
+        self.losses, self.optimizer = losses, optimizer
+        self.val_nll, self.val_smape, self.lr = rows[:, 0].clone(), rows[:, 1].clone(), rows[:, 2].clone()
+        self.best_epoch, self.best_nll, self.best_smape = best_epoch, best_nll, best_smape
+        self.stopped_epoch, self.epochs_enqueued = stopped_epoch, epochs_enqueued
+
+
+def refit_output_validated(model, windows, val_windows, epochs: int, lr=1e-3, weight_decay: float = 0.0,
+                           grad_clip: Optional[float] = None, use_loss_mask: bool = False,
+                           patience: Optional[int] = None, plateau=None, restore_best: bool = True,
+                           cache: Optional[OutputCache] = None, val_cache: Optional[OutputCache] = None,
+                           sync_every: Optional[int] = None) -> ValidatedRefit:
+    """``refit_output_cached`` with the reference's per-epoch validation (train.py:1536-1572) decided on the device:
+    after each epoch's steps the held-out windows ``val_windows`` (a default loader: no shuffle, no augmentation) are
+    scored from an ``OutputCache`` of their own - the backbone is frozen for them too - and ``EpochEnd`` steps the
+    plateau schedule, keeps the best epoch's six tensors and sets the stop word, which every step takes as a further
+    skip word.  ``patience``: epochs without a better ``val_nll`` that are tolerated (None: no early stop);
+    ``plateau``: ``_epoch_rule``'s schedule, with which ``lr`` must be a float and the host never sets the rate again.
+    ``sync_every=None``: every epoch is enqueued and the one synchronisation is at the end - steps after the stop keep
+    every bit of parameters, moments and step count; ``sync_every=k``: the host reads the stop word after every k
+    epochs and breaks.  ``restore_best`` puts the best epoch's tensors back at the end; if no epoch improved the last
+    state stays, as the reference saves it.  Validation covers the model's ``_out_steps`` from the cache: for a direct
+    model the reference's ``_eval_metrics``, for a recursive one the one-step held-out likelihood (DESIGN.md section
+    8).  Raises what ``refit_output_cached`` raises, RuntimeError / IndexError for a validation batch likewise, and
+    the scorer's ValueError for flag 32."""
+    who = "refit_output_validated"
+    epochs = int(epochs)
+    if epochs < 1:
+        raise ValueError(f"{who}: epochs={epochs} must be >= 1")
+    scalar_lr = isinstance(lr, (int, float))
+    if plateau is not None and not scalar_lr:
+        raise ValueError(f"{who}: a list of learning rates and a plateau schedule exclude each other")
+    rates = [float(lr)] * epochs if scalar_lr else [float(v) for v in lr]
+    if len(rates) != epochs:
+        raise ValueError(f"{who}: {len(rates)} learning rates for {epochs} epochs")
+    patience, plateau = _epoch_rule(who, patience, plateau)
+    if sync_every is not None and (isinstance(sync_every, bool) or not isinstance(sync_every, int) or sync_every < 1):
+        raise ValueError(f"{who}: sync_every={sync_every!r} is not None or an int >= 1")
+    if not val_windows._default or val_windows.time_shift or val_windows.add_noise_std:
+        raise ValueError(f"{who}: val_windows must be a default loader (no shuffle, no augmentation)")
+    if val_windows is windows:
+        raise ValueError(f"{who}: val_windows are the training windows")
+    caches = []
+    for name, c, w in (("cache", cache, windows), ("val_cache", val_cache, val_windows)):
+        if c is None:
+            c = OutputCache(model, w, use_loss_mask=use_loss_mask)
+        else:
+            if c.windows is not w:
+                raise ValueError(f"{who}: {name} was filled from other windows")
+            if use_loss_mask and c.mask is None:
+                raise ValueError(f"{who}: use_loss_mask needs a {name} filled with use_loss_mask")
+            OutputCache._refuse_augmented(w)
+            c.check(model)
+        if not use_loss_mask and c.mask is not None:
+            c = _without_mask(c)
+        caches.append(c)
+    cache, val_cache = caches
+    if val_cache.y.shape[1:] != cache.y.shape[1:] or val_cache.seq.shape[1:] != cache.seq.shape[1:]:
+        raise ValueError(f"{who}: the validation windows do not have the training windows' shapes")
+    params = _refit_params(model)
+    dev = params[0].device
+    flags = [(p, p.requires_grad) for p in model.parameters()]
+    was_training = model.training
+    losses = []
+    B, steps, per_epoch = windows.batch_size, cache.steps, len(windows)
+    VB, n_val = val_windows.batch_size, val_windows.n_items
+    if per_epoch < 1 or n_val < 1:
+        raise ValueError(f"{who}: no batches")
+    on_device = dev.type == "cuda"
+    enqueued = 0
+    try:
+        for p, _ in flags:
+            p.requires_grad_(False)
+        for p in params:
+            p.requires_grad_(True)
+        model.eval()
+        opt = DeviceAdamW(params, lr=rates[0], weight_decay=weight_decay, max_norm=grad_clip,
+                          log_steps=min(max(4096, epochs * per_epoch), 1 << 20))
+        end = EpochEnd(params, val_cache.y.shape[2], epochs, rates[0], patience, plateau)
+        bad_seen = torch.zeros(1, dtype=torch.int32, device=dev)
+        rows_seen = torch.zeros(1, dtype=torch.int32, device=dev)
+        val_rows = torch.arange(n_val, dtype=torch.int64, device=dev)
+        step = evaluator = None
+        proj = model.forecast_time_proj
+        for e in range(epochs):
+            if plateau is None:
+                opt.set_lr(rates[e])
+            epoch = windows.epoch
+            if not windows._default:
+                windows.epoch += 1
+            order = windows.order(epoch).to(dev)
+            for i in range(per_epoch):
+                rows = order[i * B:(i + 1) * B]
+                if on_device and rows.numel() == B:
+                    if step is None:
+                        step = GraphedCachedStep(cache, model, opt, B, extra_skip=[end.stop])
+                    losses.append(step.step(rows).clone())
+                    continue
+                tail, y, mask, late = cache.select(rows)
+                opt.zero_grad(set_to_none=True)
+                with torch.enable_grad():
+                    loss, bad = output_nll(cache.seq, proj.weight[-steps:], proj.bias[-steps:], *params[:4], tail,
+                                           cache.hist, y, mask, late, cache.floor, cache.min_sigma, rows=rows)
+                loss.backward()
+                opt.step(loss=loss.detach(), skip=[bad, end.stop])
+                opt.zero_grad(set_to_none=True)
+                losses.append(loss.detach().reshape(1))
+            for k0 in range(0, n_val, VB):
+                rows = val_rows[k0:k0 + VB]
+                if on_device:
+                    if evaluator is None:
+                        evaluator = GraphedCachedEval(val_cache, model, end.accumulators, VB)
+                    evaluator.run(rows)
+                    continue
+                y, mask, rate, disp, bad, status = _cached_forecast(val_cache, model, rows)
+                end.accumulators.update(y, rate, disp, mask)
+                bad_seen |= bad
+                rows_seen |= status
+            end.end_epoch(opt)
+            enqueued += 1
+            if sync_every is not None and enqueued % sync_every == 0 and int(end.stop.item()) != 0:
+                break
+        if restore_best:
+            end.restore()
+        if evaluator is not None:
+            bad_seen, rows_seen = evaluator.bad_seen, evaluator.rows_seen
+    finally:
+        for p, flag in flags:
+            p.requires_grad_(flag)
+        model.train(was_training)
+    host = torch.cat(losses).cpu()                               # the synchronisation at the end
+    seen_val = torch.cat([bad_seen, rows_seen]).tolist()
+    hist, log = end.history(), opt.history()
+    ran = hist["stopped_epoch"] if hist["stopped_epoch"] is not None else enqueued
+    first = opt._calls - log.shape[0]                            # the call the first returned row belongs to
+    inside = torch.tensor([(first + k) // per_epoch < ran for k in range(log.shape[0])], dtype=torch.bool)
+    log = log[inside]                                            # a step after the stop is skipped by design
+    seen = seen_val[0]
+    for v in log[:, 3].tolist():
+        seen |= int(v) & 7
+    for bit, name in ((1, "rate"), (2, "dispersion")):
+        if seen & bit:
+            raise RuntimeError(f"Predicted {name} must be finite and strictly positive")
+    if seen & 4:
+        raise FloatingPointError(f"{who}: " + _RANGE_MESSAGE)
+    if bool(((log[:, 3].to(torch.int32) & 8) != 0).logical_and(torch.isfinite(log[:, :2]).all(1)).any()):
+        raise IndexError(f"{who}: a step's row list pointed outside the cache; those steps were skipped")
+    if seen_val[1]:
+        raise IndexError(f"{who}: a validation batch's row list pointed outside the validation cache; the rows were "
+                         "clamped into it")
+    rows = hist["rows"][:ran]
+    if bool((rows[:, 3].to(torch.int32) & EPOCH_SCORER_ERR).any()):
+        raise ValueError(f"{who}: ForecastScorer: a series id outside the slots was given to the validation scorer")
+    return ValidatedRefit(host[:ran * per_epoch], rows, hist["best_epoch"], hist["best_nll"], hist["best_smape"],
+                          hist["stopped_epoch"], enqueued, opt)

@@ -71,6 +71,32 @@ class FtnRefitArgs(C.Structure):
                 ("skip", C.c_void_p * FTN_REFIT_MAX_SKIP), ("range_mask", C.c_int32), ("log_cap", C.c_int32),
                 ("loss", C.c_void_p), ("log", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("force_form", C.c_int32), ("reserved", C.c_int32)]
+
+
+FTN_EPOCH_MAX_TENSORS = 8
+FTN_EPOCH_STOP, FTN_EPOCH_AFTER_STOP, FTN_EPOCH_SCORER_ERR = 16, 16, 32
+FTN_EPOCH_COPY_VEC, FTN_EPOCH_COPY_MIXED = 1, 2
+
+
+class FtnEpochState(C.Structure):
+    """Mirror of ``struct FtnEpochState`` (include/flowtimes.h): what a validated refit carries from epoch to epoch."""
+
+    _fields_ = [("best_nll", C.c_double), ("best_smape", C.c_double), ("plateau_best", C.c_double), ("lr", C.c_double),
+                ("epoch", C.c_int32), ("best_epoch", C.c_int32), ("patience", C.c_int32), ("num_bad", C.c_int32),
+                ("stop", C.c_int32), ("improved", C.c_int32), ("calls", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FtnEpochArgs(C.Structure):
+    """Mirror of ``struct FtnEpochArgs`` (include/flowtimes.h): the operands of one ``ftn_refit_epoch_end``."""
+
+    _fields_ = [("acc", C.c_void_p), ("n_slots", C.c_int32), ("max_epochs", C.c_int32), ("err", C.c_void_p),
+                ("den_extra", C.c_void_p), ("count_seen", C.c_void_p), ("state", C.c_void_p), ("lr", C.c_void_p),
+                ("log", C.c_void_p), ("factor", C.c_double), ("threshold", C.c_double), ("min_lr", C.c_double),
+                ("plateau_patience", C.c_int32), ("patience_limit", C.c_int32),
+                ("src", C.c_void_p * FTN_EPOCH_MAX_TENSORS), ("dst", C.c_void_p * FTN_EPOCH_MAX_TENSORS),
+                ("n", C.c_longlong * FTN_EPOCH_MAX_TENSORS), ("n_tensors", C.c_int32), ("reserved", C.c_int32)]
+
+
 FTN_NBQ_RANGE = 2
 FTN_PATHS_MAX = 1024
 FTN_PATH_SUM, FTN_PATH_MAX = 0, 1
@@ -348,6 +374,11 @@ _SIGNATURES = {
     "ftn_refit_update_form": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "ftn_refit_update_workspace": (C.c_size_t, [C.c_int, C.POINTER(C.c_longlong)]),
     "ftn_refit_update": (C.c_int, [C.POINTER(FtnRefitArgs), _P]),
+    # validated refit: the end of an epoch (csrc/refit_epoch.hip)
+    "ftn_refit_epoch_form": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
+    "ftn_refit_epoch_end": (C.c_int, [C.POINTER(FtnEpochArgs), _P]),
+    "ftn_refit_epoch_restore": (C.c_int, [_P, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_longlong), _P]),
     "ftn_nbq_form": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int]),
     "ftn_nb_cdf": (C.c_int, [_P, C.c_longlong, _P, C.c_longlong, _P, C.c_longlong, C.c_int, C.c_int, C.c_int,
                              C.c_float, _P, _P, _P, _P]),

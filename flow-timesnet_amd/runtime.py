@@ -1261,6 +1261,103 @@ def refit_update(params, grads, exp_avg, exp_avg_sq, lr: torch.Tensor, state: to
     check(lib.ftn_refit_update(C.byref(a), _stream(dev)), "ftn_refit_update")
 
 
+# ------------------------------------------------------------------ validated refit: the end of an epoch
+EPOCH_STATE_BYTES = C.sizeof(_lib.FtnEpochState)
+_EPOCH_FORMS = {_lib.FTN_EPOCH_COPY_VEC: "vec", _lib.FTN_EPOCH_COPY_MIXED: "mixed"}
+
+
+def refit_epoch_form_of(counts, misalign=None) -> Tuple[str, int, int]:
+    """How ``ftn_refit_epoch_end`` / ``ftn_refit_epoch_restore`` copy tensors of ``counts`` elements
+    (``ftn_refit_epoch_form``, host-only): ``("vec" | "mixed", scalar mask, chunks)``.  ``misalign``: per tensor the
+    OR of ``address & 15`` of source and destination (None: all aligned); bit i of the mask says tensor i moves with
+    scalar accesses.  More than 8 tensors or an empty one is a ValueError, as from the launch."""
+    n, arr = _refit_counts(counts)
+    mis = None
+    if misalign is not None:
+        if len(misalign) != n:
+            raise ValueError(f"refit_epoch_form_of: {len(misalign)} misalign values for {n} tensors")
+        mis = (C.c_int * max(n, 1))(*(int(v) for v in misalign))
+    f = _lib.load().ftn_refit_epoch_form(n, arr, mis)
+    if f < 0:
+        check(f, "ftn_refit_epoch_form")
+    return _EPOCH_FORMS[f & 15], (f >> 4) & 255, f >> 12
+
+
+def _epoch_pairs(who: str, src, dst, dev):
+    src, dst = list(src), list(dst)
+    if len(src) != len(dst) or len(src) > _lib.FTN_EPOCH_MAX_TENSORS:
+        raise ValueError(f"{who}: {len(src)} sources for {len(dst)} destinations (at most "
+                         f"{_lib.FTN_EPOCH_MAX_TENSORS} pairs)")
+    for s, d in zip(src, dst):
+        for t in (s, d):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != dev
+                    or not t.is_contiguous() or t.numel() < 1 or t.numel() != s.numel()):
+                raise ValueError(f"{who}: source and destination must be contiguous fp32 device tensors of one size "
+                                 "that are not empty")
+    return src, dst
+
+
+def _epoch_state(who: str, state: torch.Tensor) -> None:
+    if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or not state.is_cuda
+            or not state.is_contiguous() or state.numel() != EPOCH_STATE_BYTES):
+        raise ValueError(f"{who}: state must be contiguous uint8 device storage of one FtnEpochState record")
+
+
+def refit_epoch_end(acc: torch.Tensor, err: torch.Tensor, den_extra: torch.Tensor, count_seen, state: torch.Tensor,
+                    lr: torch.Tensor, log: torch.Tensor, patience: Optional[int] = None, plateau=None, src=(),
+                    dst=()) -> None:
+    """``ftn_refit_epoch_end``: the decision of a validated refit's epoch from the scorer storage ``acc`` (uint8,
+    ``FtnScorePart`` records), its ``err`` word, the fp64 ``den_extra`` word and the optional int64 ``count_seen``
+    word, on the ``state`` record (uint8 ``[EPOCH_STATE_BYTES]``); writes the fp32 ``lr`` word (with ``plateau``),
+    one row of ``log`` (fp64 ``[max_epochs, 5]``) and zeros into the accumulators, then copies ``src[i]`` to
+    ``dst[i]`` if the epoch improved.  ``patience``: None, or the epochs without improvement that are tolerated.
+    ``plateau``: None or ``(factor, patience, threshold, min_lr)``.  Enqueues only."""
+    who = "refit_epoch_end"
+    lib = _lib.load()
+    dev = state.device if isinstance(state, torch.Tensor) else None
+    _epoch_state(who, state)
+    if acc.dtype != torch.uint8 or acc.device != dev or not acc.is_contiguous() or acc.numel() % _lib.SCORE_PART_BYTES \
+            or acc.numel() == 0:
+        raise ValueError(f"{who}: acc must be contiguous uint8 device storage of FtnScorePart records")
+    words = [("err", err, torch.int32), ("den_extra", den_extra, torch.float64), ("lr", lr, torch.float32)]
+    if count_seen is not None:
+        words.append(("count_seen", count_seen, torch.int64))
+    for name, t, dtype in words:
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != 1 or t.device != dev:
+            raise ValueError(f"{who}: {name} must be one {dtype} word beside the state")
+    if (log.dtype != torch.float64 or log.device != dev or not log.is_contiguous() or log.dim() != 2
+            or log.shape[1] != 5 or log.shape[0] < 1):
+        raise ValueError(f"{who}: log must be contiguous fp64 [max_epochs >= 1, 5] beside the state")
+    src, dst = _epoch_pairs(who, src, dst, dev)
+    a = _lib.FtnEpochArgs()
+    a.acc, a.n_slots, a.max_epochs = _ptr(acc), acc.numel() // _lib.SCORE_PART_BYTES, log.shape[0]
+    a.err, a.den_extra, a.count_seen = _ptr(err), _ptr(den_extra), _ptr_or_null(count_seen)
+    a.state, a.lr, a.log = _ptr(state), _ptr(lr), _ptr(log)
+    a.plateau_patience, a.patience_limit = -1, -1 if patience is None else int(patience)
+    if plateau is not None:
+        factor, p_pat, threshold, min_lr = plateau
+        a.factor, a.threshold, a.min_lr, a.plateau_patience = float(factor), float(threshold), float(min_lr), int(p_pat)
+    for i, (s, d) in enumerate(zip(src, dst)):
+        a.src[i], a.dst[i], a.n[i] = _ptr(s), _ptr(d), s.numel()
+    a.n_tensors = len(src)
+    check(lib.ftn_refit_epoch_end(C.byref(a), _stream(dev)), "ftn_refit_epoch_end")
+
+
+def refit_epoch_restore(state: torch.Tensor, src, dst) -> None:
+    """``ftn_refit_epoch_restore``: ``dst[i]`` gets the bits of ``src[i]`` if the ``state`` record's ``best_epoch`` is
+    positive, and keeps every bit otherwise.  Enqueues only."""
+    who = "refit_epoch_restore"
+    _epoch_state(who, state)
+    src, dst = _epoch_pairs(who, src, dst, state.device)
+    n = len(src)
+    if n < 1:
+        raise ValueError(f"{who}: no tensors")
+    ptrs = lambda ts: (C.c_void_p * n)(*(_ptr(t) for t in ts))
+    _, arr = _refit_counts(t.numel() for t in src)
+    check(_lib.load().ftn_refit_epoch_restore(_ptr(state), n, ptrs(src), ptrs(dst), arr, _stream(state.device)),
+          "ftn_refit_epoch_restore")
+
+
 # ------------------------------------------------------------------ NB CDF and quantiles
 def nbq_form_of(N: int, strides=(0, 0, 0), misalign_or: int = 0) -> str:
     """The kernel form ``ftn_nb_cdf`` / ``ftn_nb_quantiles`` take (``ftn_nbq_form``, host-only: the launches dispatch

@@ -863,6 +863,73 @@ int ftn_refit_update_form(int n_tensors, const long long* counts, const int* mis
 size_t ftn_refit_update_workspace(int n_tensors, const long long* counts);
 int ftn_refit_update(const FtnRefitArgs* args, void* stream);
 
+/* The end of a validated refit epoch on the device (csrc/refit_epoch.hip; additions only: FTN_ABI_VERSION stays 14):
+ * the reference's per-epoch bookkeeping (train.py:1536-1572) - validation NLL, ReduceLROnPlateau, best state, early
+ * stop - with nothing read on the host.  ftn_refit_epoch_end makes two launches on the one stream.
+ *
+ * k_epoch_decide (one workgroup) reads acc[n_slots] (the storage ftn_score_fold accumulates into), the scorer's
+ * error word, the den_extra word and the state record, and computes in fp64, slots ascending from 0.0,
+ *   val_nll   = sum nll_sum / (sum nll_cnt + den_extra)      (0 when the denominator is not > 0)
+ *   val_smape = sum smape_sum / sum smape_cnt                (0 when the count is 0)
+ * which is the arithmetic of ForecastScorer.result().  Then, in this order:
+ *   1. state.stop != 0: the log row gets (NaN, NaN, lr, FTN_EPOCH_AFTER_STOP, 0) and nothing else of the state,
+ *      the lr word or the best values changes.
+ *   2. epoch += 1; a non-zero error word sets FTN_EPOCH_SCORER_ERR in the row's flags.
+ *   3. plateau_patience >= 0 (torch's ReduceLROnPlateau, mode "min", threshold_mode "rel", cooldown 0, eps 1e-8):
+ *      val_nll < plateau_best * (1 - threshold) ? (plateau_best = val_nll, num_bad = 0) : num_bad += 1;
+ *      num_bad > plateau_patience: new = max(lr * factor, min_lr); lr - new > 1e-8 ? lr = new; num_bad = 0.
+ *      All fp64; *lr_dev = (float)lr.  plateau_patience < 0: no schedule, lr is read from *lr_dev and not written.
+ *   4. val_nll < best_nll (strict; a NaN is never better): best_nll, best_smape, best_epoch = epoch, patience = 0,
+ *      improved = 1; else improved = 0, patience += 1, and patience_limit >= 0 && patience > patience_limit sets
+ *      stop = FTN_EPOCH_STOP (as a bare skip word of ftn_refit_update that is flag 8: the step keeps every bit).
+ *   5. the log row gets (val_nll, val_smape, lr after, flags, improved).
+ * The row is log[state.calls] of double [max_epochs][5] (no row beyond max_epochs is written) and calls advances
+ * with every call.  Always, also after the stop: every record of acc, *den_extra_dev and *count_seen_dev_or_null
+ * are zeroed, so the next epoch's validation starts clean.  The two sums are each taken by one lane.
+ *
+ * k_epoch_copy (a grid) then copies src[i] to dst[i] (n[i] >= 1 fp32 each, n_tensors <= FTN_EPOCH_MAX_TENSORS, 0
+ * for none; any 4-byte-aligned addresses; no overlap) when state.improved != 0, and leaves every bit of dst
+ * otherwise.  ftn_refit_epoch_restore is the same kernel gated on state.best_epoch > 0 (callers pass the store as
+ * src).  Work is dealt as by ftn_refit_update: units of 4 elements, chunks of 1024 units (at most
+ * FTN_REFIT_PARTS_MAX chunks, beyond that the chunk grows), a workgroup per chunk; a tensor whose src and dst are on
+ * the 16-byte grid moves whole units with 16-byte accesses and its tail with scalars, any other tensor with scalars.
+ * Plain vector stores, no atomics.  ftn_refit_epoch_form (host-only; the launch dispatches through the same
+ * function; misalign_or: per tensor the OR of (address & 15) of src and dst, null for all zero):
+ *   bits 0-3    FTN_EPOCH_COPY_VEC  every tensor moves with 16-byte accesses, FTN_EPOCH_COPY_MIXED  some do not
+ *   bits 4-11   the tensors moved with scalars, one bit each
+ *   bits 12-    the number of chunks
+ * Every argument is checked before the first launch; enqueues only. */
+#define FTN_EPOCH_MAX_TENSORS 8
+#define FTN_EPOCH_STOP 16
+#define FTN_EPOCH_AFTER_STOP 16
+#define FTN_EPOCH_SCORER_ERR 32
+#define FTN_EPOCH_COPY_VEC 1
+#define FTN_EPOCH_COPY_MIXED 2
+typedef struct FtnEpochState {
+  double best_nll, best_smape, plateau_best, lr;          /* +inf, +inf, +inf, the starting rate */
+  int32_t epoch, best_epoch, patience, num_bad, stop, improved, calls, reserved;   /* all 0 */
+} FtnEpochState;
+typedef struct FtnEpochArgs {
+  FtnScorePart* acc_dev;  int32_t n_slots, max_epochs;
+  const int32_t* err_dev;
+  double* den_extra_dev;
+  long long* count_seen_dev_or_null;
+  FtnEpochState* state_dev;
+  float* lr_dev;
+  double* log_dev;                                        /* [max_epochs][5] */
+  double factor, threshold, min_lr;
+  int32_t plateau_patience;                               /* < 0: no plateau schedule */
+  int32_t patience_limit;                                 /* < 0: no early stop */
+  const float* src[FTN_EPOCH_MAX_TENSORS];
+  float* dst[FTN_EPOCH_MAX_TENSORS];
+  long long n[FTN_EPOCH_MAX_TENSORS];
+  int32_t n_tensors, reserved;
+} FtnEpochArgs;
+int ftn_refit_epoch_form(int n_tensors, const long long* counts, const int* misalign_or);
+int ftn_refit_epoch_end(const FtnEpochArgs* args, void* stream);
+int ftn_refit_epoch_restore(const FtnEpochState* state_dev, int n_tensors, const float* const* src, float* const* dst,
+                            const long long* counts, void* stream);
+
 /* ---- using the forecast's distribution: NB CDF and quantiles (no counterpart in the reference) -----------
  * These entry points are additions only: no earlier declaration changed, so FTN_ABI_VERSION stays 14.
  *
