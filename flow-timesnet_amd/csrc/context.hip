@@ -10,50 +10,11 @@
 // of which rows share the call.
 #include "ftn_common.h"
 
-#define CTX_MAX 256          // ctx, F, Ws, Ed
-#define CTX_SLOTS 4          // CTX_MAX / 64: element lane + 64 j of a row vector lives in slot j of lane `lane`
+#include "ftn_ctxrow.h"          // CTX_MAX, CTX_SLOTS, wave_sum, wave_layernorm, dot_chain (shared with latefit.hip)
+
 #define CTX_RMAX 32
 #define ADD_DMAX 512
 #define ADD_TMAX 64
-
-// Sum over the 64 lanes by an xor butterfly: every lane ends with the same bits (fp32 addition commutes, and the two
-// partners of a step hold the two operands of the same addition).
-__device__ __forceinline__ float wave_sum(float s) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-  return s;
-}
-
-// Affine LayerNorm, as torch computes it, of the n <= 256 values v[j] = element lane + 64 j: the mean, then the
-// biased variance of the centred values, 1 / sqrt(var + eps), gamma, beta.  Called by all 64 lanes.
-__device__ __forceinline__ void wave_layernorm(float (&v)[CTX_SLOTS], int n, int lane, const float* __restrict__ g,
-                                               const float* __restrict__ b, float eps) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < CTX_SLOTS; ++j)
-    if (lane + 64 * j < n) s += v[j];
-  const float mean = wave_sum(s) / (float)n;
-  float ss = 0.f;
-#pragma unroll
-  for (int j = 0; j < CTX_SLOTS; ++j)
-    if (lane + 64 * j < n) {
-      v[j] -= mean;
-      ss = fmaf(v[j], v[j], ss);
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)n + eps);
-#pragma unroll
-  for (int j = 0; j < CTX_SLOTS; ++j) {
-    const int k = lane + 64 * j;
-    if (k < n) v[j] = fmaf(v[j] * rstd, g[k], b[k]);
-  }
-}
-
-// sum_k w[k] v[k], k ascending, one FMA chain from +0
-__device__ __forceinline__ float dot_chain(const float* __restrict__ w, const float* v, int n) {
-  float acc = 0.f;
-  for (int k = 0; k < n; ++k) acc = fmaf(w[k], v[k], acc);
-  return acc;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Series rows

@@ -16,6 +16,8 @@
 //   k_refit_apply    workgroup c: the total from the workspace, the decision, chunk c; workgroup 0 writes the words
 // The apply kernel reads t from the workspace copy, not from state[], so the workgroup that advances t cannot be seen
 // by a workgroup that starts later.  No atomics.  Kernels, the form rule, the launch and the C entry points.
+// ftn_refit_update_list (at the end): one step over up to FTN_REFIT_LIST_MAX records - a k_refit_norm launch per
+// record into one list of partials, then a k_refit_apply launch per record over the whole list.
 #include "ftn_common.h"
 
 #include <math.h>
@@ -44,8 +46,12 @@ struct RefitK {
   const float* loss;
   float* log;
   int cap;
-  double* part;                               // [chunks] partials, then one int: t as the norm kernel found it
+  double* part;                               // [pall] partials, then one int: t as the norm kernel found it
   unsigned chunk, chunks;
+  // ftn_refit_update_list: this record's partials are part[pbase .. pbase + chunks) of pall in all; the record that
+  // copies t (the first) and the one that writes the words (the last).  One record: 0, chunks, both.
+  unsigned pbase, pall;
+  int copies_t, writes_words;
 };
 
 // What every thread of a call agrees on before it touches an element.
@@ -212,18 +218,18 @@ __global__ __launch_bounds__(RF_THREADS) void k_refit_norm(RefitK a) {
   __shared__ double wave_sums[4];
   const double s = rf_block_sum(rf_chunk_squares(a, blockIdx.x), wave_sums);
   if (threadIdx.x == 0) {
-    a.part[blockIdx.x] = s;
-    if (blockIdx.x == 0) *(int*)(a.part + a.chunks) = a.state[0];
+    a.part[a.pbase + blockIdx.x] = s;
+    if (blockIdx.x == 0 && a.copies_t) *(int*)(a.part + a.pall) = a.state[0];
   }
 }
 
 __global__ __launch_bounds__(RF_THREADS) void k_refit_apply(RefitK a) {
   __shared__ double wave_sums[4];
-  const int t = *(const int*)(a.part + a.chunks);
-  const double total = rf_total((const double*)a.part, a.chunks, wave_sums);
+  const int t = *(const int*)(a.part + a.pall);
+  const double total = rf_total((const double*)a.part, a.pall, wave_sums);
   const RefitStep h = rf_decide(a, total, t);
   if (h.flags == 0) rf_chunk_apply(a, blockIdx.x, h);
-  if (blockIdx.x == 0 && threadIdx.x == 0) rf_words(a, h, t);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && a.writes_words) rf_words(a, h, t);
 }
 
 // The form ftn_refit_update takes (include/flowtimes.h): the one place the choice is made - the launch below
@@ -272,8 +278,8 @@ extern "C" size_t ftn_refit_update_workspace(int n, const long long* counts) {
   return (size_t)pl.chunks * sizeof(double) + 16;
 }
 
-extern "C" int ftn_refit_update(const FtnRefitArgs* r, void* stream) {
-  const char* who = "ftn_refit_update";
+// One record's checks and its kernel arguments: everything but the workspace, which the two entries lay out.
+static int rf_record(const char* who, const FtnRefitArgs* r, RefitPlan& pl, RefitK& a) {
   FTN_CHECK_ARG(r != nullptr, "%s: null argument record", who);
   FTN_CHECK_ARG(r->n_tensors >= 1 && r->n_tensors <= FTN_REFIT_MAX_TENSORS, "%s: %d tensors (1..%d)", who, r->n_tensors,
                 FTN_REFIT_MAX_TENSORS);
@@ -285,7 +291,6 @@ extern "C" int ftn_refit_update(const FtnRefitArgs* r, void* stream) {
     FTN_CHECK_ARG((any & 3) == 0, "%s: tensor %d has an operand off the 4-byte grid", who, i);
     mis[i] = (int)(any & 15);
   }
-  RefitPlan pl;
   FTN_CHECK_ARG(rf_plan(r->n_tensors, r->n, mis, &pl), "%s: more than 2^31 - 1 units of 4 elements", who);
   FTN_CHECK_ARG(r->lr_dev && r->state_dev && ((uintptr_t)r->lr_dev & 3) == 0 && ((uintptr_t)r->state_dev & 3) == 0,
                 "%s: the lr word and state[2] must be 4-byte aligned device words", who);
@@ -301,19 +306,6 @@ extern "C" int ftn_refit_update(const FtnRefitArgs* r, void* stream) {
   FTN_CHECK_ARG(r->log_cap >= 0 && (r->log_cap == 0) == (r->log_dev_or_null == nullptr) &&
                     ((uintptr_t)r->log_dev_or_null & 3) == 0,
                 "%s: log of %d rows with %s buffer", who, r->log_cap, r->log_dev_or_null ? "a" : "no");
-  int form = pl.form;
-  if (r->force_form != 0) {
-    FTN_CHECK_ARG(r->force_form == FTN_REFIT_GRID || (r->force_form == FTN_REFIT_ONE && pl.chunks <= RF_ONE_CHUNKS_CAP),
-                  "%s: force_form=%d with %u chunks (FTN_REFIT_ONE up to %d chunks, or FTN_REFIT_GRID)", who,
-                  r->force_form, pl.chunks, RF_ONE_CHUNKS_CAP);
-    form = r->force_form;
-  }
-  const size_t need = (size_t)pl.chunks * sizeof(double) + 16;
-  if (form == FTN_REFIT_GRID)
-    FTN_CHECK_ARG(r->workspace_dev && ((uintptr_t)r->workspace_dev & 7) == 0 && r->workspace_bytes >= need,
-                  "%s: workspace of %zu bytes, %zu needed on the 8-byte grid (ftn_refit_update_workspace)", who,
-                  r->workspace_bytes, need);
-  RefitK a;
   for (int i = 0; i < FTN_REFIT_MAX_TENSORS; ++i) {
     const bool on = i < r->n_tensors;
     a.p[i] = on ? r->p[i] : nullptr;  a.g[i] = on ? r->g[i] : nullptr;
@@ -326,7 +318,29 @@ extern "C" int ftn_refit_update(const FtnRefitArgs* r, void* stream) {
   a.nt = r->n_tensors; a.nskip = r->n_skip; a.scalar_mask = pl.scalar_mask; a.range_mask = r->range_mask;
   a.beta1 = r->beta1; a.beta2 = r->beta2; a.eps = r->eps; a.wd = r->weight_decay; a.max_norm = r->max_norm;
   a.lr = r->lr_dev; a.state = r->state_dev; a.loss = r->loss_dev_or_null; a.log = r->log_dev_or_null; a.cap = r->log_cap;
-  a.part = (double*)r->workspace_dev; a.chunk = pl.chunk; a.chunks = pl.chunks;
+  a.part = nullptr; a.chunk = pl.chunk; a.chunks = pl.chunks;
+  a.pbase = 0; a.pall = pl.chunks; a.copies_t = 1; a.writes_words = 1;
+  return 0;
+}
+
+extern "C" int ftn_refit_update(const FtnRefitArgs* r, void* stream) {
+  const char* who = "ftn_refit_update";
+  RefitPlan pl;
+  RefitK a;
+  if (int rc = rf_record(who, r, pl, a)) return rc;
+  int form = pl.form;
+  if (r->force_form != 0) {
+    FTN_CHECK_ARG(r->force_form == FTN_REFIT_GRID || (r->force_form == FTN_REFIT_ONE && pl.chunks <= RF_ONE_CHUNKS_CAP),
+                  "%s: force_form=%d with %u chunks (FTN_REFIT_ONE up to %d chunks, or FTN_REFIT_GRID)", who,
+                  r->force_form, pl.chunks, RF_ONE_CHUNKS_CAP);
+    form = r->force_form;
+  }
+  const size_t need = (size_t)pl.chunks * sizeof(double) + 16;
+  if (form == FTN_REFIT_GRID)
+    FTN_CHECK_ARG(r->workspace_dev && ((uintptr_t)r->workspace_dev & 7) == 0 && r->workspace_bytes >= need,
+                  "%s: workspace of %zu bytes, %zu needed on the 8-byte grid (ftn_refit_update_workspace)", who,
+                  r->workspace_bytes, need);
+  a.part = (double*)r->workspace_dev;
   hipStream_t st = (hipStream_t)stream;
   if (form == FTN_REFIT_ONE) {
     hipLaunchKernelGGL(k_refit_one, dim3(1), dim3(RF_THREADS), 0, st, a);
@@ -337,5 +351,67 @@ extern "C" int ftn_refit_update(const FtnRefitArgs* r, void* stream) {
   FTN_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_refit_apply, dim3(pl.chunks), dim3(RF_THREADS), 0, st, a);
   FTN_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// One step over a list of records (include/flowtimes.h, ftn_refit_update_list)
+// ---------------------------------------------------------------------------------------------
+extern "C" size_t ftn_refit_update_list_workspace(int n_calls, const int* n_tensors, const long long* const* counts) {
+  if (n_calls < 1 || n_calls > FTN_REFIT_LIST_MAX || !n_tensors || !counts) return 0;
+  size_t chunks = 0;
+  for (int c = 0; c < n_calls; ++c) {
+    RefitPlan pl;
+    if (!rf_plan(n_tensors[c], counts[c], nullptr, &pl)) return 0;
+    chunks += pl.chunks;
+  }
+  return chunks * sizeof(double) + 16;
+}
+
+extern "C" int ftn_refit_update_list(const FtnRefitArgs* calls, int n_calls, void* workspace_dev,
+                                     size_t workspace_bytes, void* stream) {
+  const char* who = "ftn_refit_update_list";
+  FTN_CHECK_ARG(calls != nullptr && n_calls >= 1 && n_calls <= FTN_REFIT_LIST_MAX, "%s: %d records (1..%d)", who, n_calls,
+                FTN_REFIT_LIST_MAX);
+  if (n_calls == 1) {                         // ftn_refit_update itself, on this workspace
+    FtnRefitArgs one = calls[0];
+    one.workspace_dev = workspace_dev;
+    one.workspace_bytes = workspace_bytes;
+    one.force_form = 0;
+    return ftn_refit_update(&one, stream);
+  }
+  RefitPlan pl[FTN_REFIT_LIST_MAX];
+  RefitK a[FTN_REFIT_LIST_MAX];
+  unsigned pall = 0;
+  const FtnRefitArgs& f = calls[0];
+  for (int c = 0; c < n_calls; ++c) {
+    const FtnRefitArgs& r = calls[c];
+    if (int rc = rf_record(who, &r, pl[c], a[c])) return rc;
+    bool same = r.beta1 == f.beta1 && r.beta2 == f.beta2 && r.eps == f.eps && r.weight_decay == f.weight_decay &&
+                r.max_norm == f.max_norm && r.lr_dev == f.lr_dev && r.state_dev == f.state_dev && r.n_skip == f.n_skip &&
+                r.range_mask == f.range_mask && r.log_cap == f.log_cap && r.loss_dev_or_null == f.loss_dev_or_null &&
+                r.log_dev_or_null == f.log_dev_or_null;
+    for (int k = 0; same && k < f.n_skip; ++k) same = r.skip_dev[k] == f.skip_dev[k];
+    FTN_CHECK_ARG(same, "%s: record %d differs from record 0 in a hyper-parameter or a device word", who, c);
+    a[c].pbase = pall;
+    pall += pl[c].chunks;
+  }
+  const size_t need = (size_t)pall * sizeof(double) + 16;
+  FTN_CHECK_ARG(workspace_dev && ((uintptr_t)workspace_dev & 7) == 0 && workspace_bytes >= need,
+                "%s: workspace of %zu bytes, %zu needed on the 8-byte grid (ftn_refit_update_list_workspace)", who,
+                workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  for (int c = 0; c < n_calls; ++c) {
+    a[c].part = (double*)workspace_dev;
+    a[c].pall = pall;
+    a[c].copies_t = c == 0;
+    a[c].writes_words = c == n_calls - 1;
+    hipLaunchKernelGGL(k_refit_norm, dim3(pl[c].chunks), dim3(RF_THREADS), 0, st, a[c]);
+    FTN_CHECK_LAUNCH();
+  }
+  for (int c = 0; c < n_calls; ++c) {
+    hipLaunchKernelGGL(k_refit_apply, dim3(pl[c].chunks), dim3(RF_THREADS), 0, st, a[c]);
+    FTN_CHECK_LAUNCH();
+  }
   return 0;
 }

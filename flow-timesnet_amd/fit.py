@@ -54,6 +54,13 @@ and ``EpochEnd`` (``ftn_refit_epoch_end``, ``csrc/refit_epoch.hip``) turns the s
 ``ReduceLROnPlateau`` in the optimizer's ``lr`` word, keeps the best epoch's tensors and sets the stop word that every
 later step takes as a skip word ("Validated refit").
 
+``late_bias`` is the late-bias head - the one per-series term behind the backbone - as an autograd node over
+``ftn_late_fit_forward`` / ``ftn_late_backward`` (``csrc/latefit.hip``) on the frozen series rows
+``TimesNet.late_rows`` returns; its result is the ``late=`` of ``head_nll`` / ``output_nll``.
+``refit_output(..., late_bias=True)`` moves its five parameters with the six of the output side, and
+``DeviceAdamWList`` is ``DeviceAdamW`` for up to 32 tensors over ``ftn_refit_update_list`` (DESIGN.md section 4,
+"Late-bias refit").
+
 ``backend`` follows ``score``'s rule (``_use_hip``): ``hip`` where it can run unless ``"torch"`` is asked for, and
 asking for ``"hip"`` where it cannot is an error.
 """
@@ -416,8 +423,90 @@ def output_nll(seq: torch.Tensor, wt: torch.Tensor, bt: torch.Tensor, w_mu: torc
     return head_nll(hidden, w_mu, b_mu, w_sigma, b_sigma, tail, hist, y, mask, late, floor, min_sigma)
 
 
+_last_late_backend: Optional[str] = None      # which path the last ``late_bias`` took
+
+
+class _LateBias(torch.autograd.Function):
+    """The late-bias head as one node: ``ftn_late_fit_forward`` (the bits of inference) forward, ``ftn_late_backward``
+    backward.  The series rows are constants: no gradient in them."""
+
+    @staticmethod
+    def forward(ctx, rows, gamma, beta, weight, bias, gate, eps, index):
+        from . import runtime as rt
+
+        ops = [t.detach().contiguous() for t in (rows, gamma, beta, weight, bias, gate)]
+        ctx.save_for_backward(*ops, *(() if index is None else (index,)))
+        ctx.eps, ctx.gate_shape = eps, tuple(gate.shape)
+        return rt.late_fit_forward(*ops, eps, rows=index)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_late):
+        from . import runtime as rt
+
+        rows, gamma, beta, weight, bias, gate, *index = ctx.saved_tensors
+        d_pre = d_late.contiguous()
+        if d_pre.dtype != torch.float32:
+            d_pre = d_pre.float()
+        dg, dbt, dw, db, dgate = rt.late_backward(d_pre, rows, gamma, beta, weight, bias, gate, ctx.eps,
+                                                  rows=index[0] if index else None)
+        need = ctx.needs_input_grad
+        return (None, dg if need[1] else None, dbt if need[2] else None, dw if need[3] else None,
+                db if need[4] else None, dgate.reshape(ctx.gate_shape) if need[5] else None, None, None)
+
+
+def late_bias(rows: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+              gate: torch.Tensor, eps: float, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The gated late bias ``gate * (weight LayerNorm(rows) + bias)^T`` of the frozen series rows ``rows [Bc, N, ctx]``
+    (``TimesNet.late_rows``): ``[Bc, S, N]``, differentiable in ``gamma`` / ``beta`` ``[ctx]`` (``late_bias_norm``),
+    ``weight [S, ctx]`` / ``bias [S]`` (``late_bias_head``) and ``gate`` (``late_bias_gate``, ``[1, S, 1]`` or
+    ``[S]``) - the ``late=`` of ``head_nll`` / ``output_nll``.  ``index`` (an int64 vector beside ``rows``): ``rows``
+    is an item store ``[n_items, ctx]`` and the result ``[len(index), S, 1]`` is that of ``rows[index][:, None]``, to
+    the bit.  On fp32 ROCm tensors with ``ctx <= 256`` and rows that do not require grad it is
+    ``ftn_late_fit_forward`` (the bits of the model's own late bias) with ``ftn_late_backward`` as its backward
+    (``_last_late_backend == "hip"``; the kernels clamp an index into the store); otherwise the torch composition."""
+    if index is not None and (not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1
+                              or index.numel() < 1 or index.device != rows.device):
+        raise ValueError("late_bias: index must be an int64 vector of at least one entry beside rows")
+    if rows.dim() != (3 if index is None else 2) or rows.numel() < 1:
+        raise ValueError(f"late_bias: rows {tuple(rows.shape)} are not " +
+                         ("[Bc, N, ctx]" if index is None else "an item store [n_items, ctx]"))
+    ctx_w = rows.shape[-1]
+    if (weight.dim() != 2 or weight.shape[1] != ctx_w or gamma.shape != (ctx_w,) or beta.shape != (ctx_w,)
+            or bias.shape != (weight.shape[0],) or gate.numel() != weight.shape[0]
+            or tuple(gate.shape) not in ((weight.shape[0],), (1, weight.shape[0], 1))):
+        raise ValueError(f"late_bias: gamma {tuple(gamma.shape)}, beta {tuple(beta.shape)}, weight {tuple(weight.shape)}, "
+                         f"bias {tuple(bias.shape)} and gate {tuple(gate.shape)} do not fit [ctx = {ctx_w}], [ctx], "
+                         "[S, ctx], [S] and [1, S, 1]")
+    global _last_late_backend
+    ops = (rows, gamma, beta, weight, bias, gate)
+    if (rows.is_cuda and ctx_w <= 256 and all(t.is_cuda and t.dtype == torch.float32 and t.device == rows.device
+                                              for t in ops)
+            and not (torch.is_grad_enabled() and rows.requires_grad)):
+        _last_late_backend = "hip"
+        return _LateBias.apply(rows, gamma, beta, weight, bias, gate, float(eps),
+                               None if index is None else index.contiguous())
+    _last_late_backend = "torch"
+    r = rows if index is None else rows.index_select(0, index).unsqueeze(1)
+    lb = F.linear(F.layer_norm(r, (ctx_w,), gamma, beta, float(eps)), weight, bias)
+    return gate.reshape(1, -1, 1) * lb.transpose(1, 2)
+
+
+_late_bias_node = late_bias                    # (``late_bias`` is also the name of the refit loops' switch)
+
+
+def _late_params(model):
+    """The five late-bias tensors in the order a refit lists them, or a ValueError for a model without the head."""
+    norm, head, gate = (getattr(model, n, None) for n in ("late_bias_norm", "late_bias_head", "late_bias_gate"))
+    if (norm is None or head is None or not isinstance(gate, torch.nn.Parameter)
+            or getattr(norm, "weight", None) is None or getattr(norm, "bias", None) is None):
+        raise ValueError("late_bias=True: the model has no late-bias head (use_late_bias_head with ids or statics, "
+                         "built by a first forward)")
+    return [norm.weight, norm.bias, head.weight, head.bias, gate]
+
+
 def refit_output(model, batches, epochs: int = 1, lr: float = 1e-3, use_loss_mask: bool = False, optimizer=None,
-                 grad_clip: Optional[float] = None):
+                 grad_clip: Optional[float] = None, late_bias: bool = False):
     """``refit_heads`` over the whole output side of a ``TimesNet``: ``forecast_time_proj`` (its last
     ``model._out_steps`` rows are what a step reads; the other rows of a recursive model get zero gradients),
     ``mu_head`` and ``sigma_head``, everything else frozen.  Per batch ``model.output_inputs`` -> ``output_nll`` ->
@@ -425,12 +514,28 @@ def refit_output(model, batches, epochs: int = 1, lr: float = 1e-3, use_loss_mas
     -> a step of ``optimizer`` (default: Adam with ``lr`` over the six tensors).  Losses and ``bad`` words stay on
     the device until the one synchronisation at the end, which raises the reference's RuntimeError if a rate or
     dispersion was not finite and > 0.  Returns the losses, fp32 ``[epochs * batches]`` on the host; mode and
-    ``requires_grad`` flags come back as they were."""
+    ``requires_grad`` flags come back as they were.
+
+    ``late_bias=True``: the late-bias head moves too - eleven tensors, the six in their order, then
+    ``late_bias_norm.weight`` / ``.bias``, ``late_bias_head.weight`` / ``.bias`` and ``late_bias_gate``; per batch the
+    frozen series rows ``model.late_rows`` go through ``late_bias`` into the ``late=`` of ``output_nll``, and
+    ``grad_clip`` is the global norm over all eleven.  A model without the head is a ValueError."""
     from .score import _unpack_batch
 
     proj = model.forecast_time_proj
     params = [model.mu_head.weight, model.mu_head.bias, model.sigma_head.weight, model.sigma_head.bias,
               proj.weight, proj.bias]
+    if late_bias:
+        if getattr(model, "late_bias_head", None) is None and getattr(model, "use_late_bias_head", False):
+            first = next(iter(batches), None)                  # the head is built by the first forward
+            if first is not None:
+                xb, _, _, x_mark, _, static, ids = _unpack_batch(first)
+                dev0 = params[0].device
+                mv = lambda t: None if t is None else t.to(dev0)
+                model.late_rows(mv(xb), mv(x_mark), mv(static),
+                                None if ids is None else ids.to(device=dev0, dtype=torch.long))
+        late_ps = _late_params(model)
+        params = params + late_ps
     dev = params[0].device
     flags = [(p, p.requires_grad) for p in model.parameters()]
     was_training = model.training
@@ -454,8 +559,14 @@ def refit_output(model, batches, epochs: int = 1, lr: float = 1e-3, use_loss_mas
                 if use_loss_mask and mask is None:
                     raise ValueError("refit_output: use_loss_mask needs a mask in every batch")
                 base = (move(mask)[:, :steps, :] > 0.0) if use_loss_mask else None
+                if late_bias:
+                    srows = model.late_rows(
+                        move(xb), move(x_mark), move(static),
+                        None if ids is None else ids.to(device=dev, dtype=torch.long, non_blocking=True))
                 opt.zero_grad(set_to_none=True)
                 with torch.enable_grad():
+                    if late_bias:
+                        late = _late_bias_node(srows, *late_ps, model.late_bias_norm.eps)
                     loss, bad = output_nll(seq, proj.weight[-steps:], proj.bias[-steps:], *params[:4], tail, hist, yb,
                                            base, late, floor, model.min_sigma)
                 loss.backward()
@@ -515,11 +626,14 @@ class DeviceAdamW:
     ``zero_grad`` / ``step`` read ``p.grad`` as a torch optimizer does (``refit_output(..., optimizer=...)``);
     ``step_on`` takes caller-owned gradient buffers."""
 
+    _max_tensors = 8
+    _entry = "refit_update"                     # the ``runtime`` function of the device path
+
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  max_norm: Optional[float] = None, log_steps: int = 4096, backend: Optional[str] = None):
         self.params = list(params)
-        if not 1 <= len(self.params) <= 8:
-            raise ValueError(f"DeviceAdamW: {len(self.params)} parameter tensors (1..8)")
+        if not 1 <= len(self.params) <= self._max_tensors:
+            raise ValueError(f"{type(self).__name__}: {len(self.params)} parameter tensors (1..{self._max_tensors})")
         for p in self.params:
             if not isinstance(p, torch.Tensor) or not p.is_floating_point() or p.numel() < 1:
                 raise ValueError("DeviceAdamW: parameters must be floating-point tensors that are not empty")
@@ -634,9 +748,9 @@ class DeviceAdamW:
         if _use_hip("DeviceAdamW", self.backend, eligible, "contiguous fp32 parameters and fp32 gradients on a ROCm device"):
             from . import runtime as rt
 
-            rt.refit_update([p.detach() for p in ps], [g.detach().contiguous() for g in grads], ms, vs, self._lr,
-                            self._state, self.betas, self.eps, self.weight_decay, self.max_norm, words, range_mask,
-                            None if loss is None else loss.detach().reshape(1), self._log)
+            getattr(rt, self._entry)([p.detach() for p in ps], [g.detach().contiguous() for g in grads], ms, vs,
+                                     self._lr, self._state, self.betas, self.eps, self.weight_decay, self.max_norm,
+                                     words, range_mask, None if loss is None else loss.detach().reshape(1), self._log)
             _last_optim_backend = "hip"
             if not _capturing():
                 _bump_versions(ps)
@@ -687,6 +801,16 @@ class DeviceAdamW:
         row = torch.stack([loss_w, norm.float(), lr, flags.float()])
         self._log.index_copy_(0, (self._state[1:2] % self._log.shape[0]).long(), row.reshape(1, 4))
         self._state += torch.stack([keep.to(torch.int32), torch.ones((), dtype=torch.int32, device=dev)])
+
+
+class DeviceAdamWList(DeviceAdamW):
+    """``DeviceAdamW`` for 1 to 32 parameter tensors: one clip-and-AdamW step over all of them - one global norm, one
+    decision, one ``t``, one log row - through ``ftn_refit_update_list`` (``csrc/refit.hip``), which walks the list in
+    records of 8 that share the norm.  Up to 8 tensors it is ``DeviceAdamW`` bit for bit; the torch backend is
+    ``DeviceAdamW``'s, which takes any count."""
+
+    _max_tensors = 32
+    _entry = "refit_update_list"
 
 
 def _refit_params(model):
@@ -939,13 +1063,22 @@ class OutputCache:
     stores from the host alone; beyond ``max_bytes`` the constructor raises before it allocates.
 
     The cache remembers ``_param_key`` of every parameter outside the six refit tensors and each block's engine;
-    ``check(model)`` raises ValueError when they differ.  A step of the six tensors does not invalidate it."""
+    ``check(model)`` raises ValueError when they differ.  A step of the six tensors does not invalidate it.
 
-    def __init__(self, model, windows, use_loss_mask: bool = False, max_bytes: Optional[int] = None):
+    ``late_bias=True`` (a refit that moves the late-bias head): in place of ``late`` the cache keeps what that head
+    reads, the frozen series rows ``rows`` (``TimesNet.late_rows``) - ``[n_items, ctx]`` where ``late`` would be per
+    item, the shared ``[1, N, ctx]`` block otherwise - and its key leaves out the head's five tensors as well.  A model
+    without the head is a ValueError."""
+
+    def __init__(self, model, windows, use_loss_mask: bool = False, max_bytes: Optional[int] = None,
+                 late_bias: bool = False):
         from .score import _unpack_batch
 
         self._refuse_augmented(windows)
-        need = self.bytes_needed(model, windows, use_loss_mask)
+        self.late_bias = bool(late_bias)
+        if self.late_bias:
+            _late_params(model)
+        need = self.bytes_needed(model, windows, use_loss_mask, late_bias=self.late_bias)
         if max_bytes is not None and need > int(max_bytes):
             raise ValueError(f"OutputCache: the stores need {need} bytes, max_bytes is {int(max_bytes)}")
         n, B = windows.n_items, windows.batch_size
@@ -955,7 +1088,9 @@ class OutputCache:
         self.hist = min(self.steps, int(model.input_len))
         self.n_items, self.batch_size = n, B
         layout = _late_layout(model, windows)
-        self.seq = self.tail = self.y = self.mask = self.late = self.floor = None
+        if self.late_bias and layout is None:
+            raise ValueError("OutputCache: late_bias=True, but these windows give the late-bias head no series rows")
+        self.seq = self.tail = self.y = self.mask = self.late = self.floor = self.rows = None
         was_training = model.training
         model.eval()
         try:
@@ -965,9 +1100,9 @@ class OutputCache:
                     windows.gather(torch.arange(k0, k1, dtype=torch.int64, device=windows.device))
                 xb, yb, mask, x_mark, _, static, ids = _unpack_batch(batch)
                 move = lambda t: None if t is None else t.to(dev, non_blocking=True)
-                seq, tail, hist, late, floor = model.output_inputs(
-                    move(xb), move(x_mark), move(static),
-                    None if ids is None else ids.to(device=dev, dtype=torch.long, non_blocking=True))
+                ids_d = None if ids is None else ids.to(device=dev, dtype=torch.long, non_blocking=True)
+                seq, tail, hist, late, floor = model.output_inputs(move(xb), move(x_mark), move(static), ids_d)
+                srows = model.late_rows(move(xb), move(x_mark), move(static), ids_d) if self.late_bias else None
                 if use_loss_mask and mask is None:
                     raise ValueError("OutputCache: use_loss_mask needs a mask in every batch")
                 got = None if late is None else ("shared" if layout != "item" and late.shape[0] == 1 else "item")
@@ -980,14 +1115,22 @@ class OutputCache:
                     self.seq, self.tail = new(n, *seq.shape[1:]), new(n, hist, N)
                     self.y = new(n, self.steps, N)
                     self.mask = new(n, self.steps, N) if use_loss_mask else None
-                    self.late = new(n if layout == "item" else 1, self.steps, N) if layout else None
+                    self.late = new(n if layout == "item" else 1, self.steps, N) if layout and not self.late_bias \
+                        else None
+                    if self.late_bias:
+                        self.rows = new(n, srows.shape[2]) if layout == "item" else new(1, N, srows.shape[2])
                     self.floor = None if floor is None else floor.to(device=dev, dtype=torch.float32).clone()
                 self.seq[k0:k1].copy_(seq)
                 self.tail[k0:k1].copy_(tail)
                 self.y[k0:k1].copy_(move(yb)[:, :self.steps, :])
                 if use_loss_mask:
                     self.mask[k0:k1].copy_(move(mask)[:, :self.steps, :] > 0.0)
-                if layout == "item":
+                if self.late_bias:
+                    if layout == "item":                        # the series layout: N == 1, a row an item
+                        self.rows[k0:k1].copy_(srows.expand(k1 - k0, -1, -1).reshape(k1 - k0, -1))
+                    elif k0 == 0:
+                        self.rows.copy_(srows)
+                elif layout == "item":
                     self.late[k0:k1].copy_(late.expand(k1 - k0, -1, -1))
                 elif layout == "shared" and k0 == 0:
                     self.late.copy_(late)
@@ -997,7 +1140,8 @@ class OutputCache:
             raise ValueError("OutputCache: the windows have no items")
         self.late_per_item = layout == "item"
         self.min_sigma = float(model.min_sigma)
-        self._key = self._backbone_key(model)
+        self.late_eps = float(model.late_bias_norm.eps) if self.late_bias else None
+        self._key = self._backbone_key(model, self.late_bias)
 
     @staticmethod
     def _refuse_augmented(windows) -> None:
@@ -1006,9 +1150,10 @@ class OutputCache:
                              f"{windows.add_noise_std} differ per epoch and have no cache")
 
     @staticmethod
-    def bytes_needed(model, windows, use_loss_mask: bool = False) -> int:
-        """The bytes of ``seq``, ``tail``, ``y``, ``mask`` and ``late`` for these windows, from the host alone (the
-        model's lazily built layers must exist: call it once first)."""
+    def bytes_needed(model, windows, use_loss_mask: bool = False, late_bias: bool = False) -> int:
+        """The bytes of ``seq``, ``tail``, ``y``, ``mask`` and ``late`` (with ``late_bias``: the series rows in its
+        place) for these windows, from the host alone (the model's lazily built layers must exist: call it once
+        first)."""
         if model.d_model is None:
             raise ValueError("OutputCache.bytes_needed: the model has not been called yet (d_model is unknown)")
         n, L, D = windows.n_items, int(model.input_len), int(model.d_model)
@@ -1016,23 +1161,27 @@ class OutputCache:
         steps = int(model._out_steps)
         layout = _late_layout(model, windows)
         late = {None: 0, "shared": 1, "item": n}[layout]
-        return 4 * (n * L * D + n * min(steps, L) * N + (2 if use_loss_mask else 1) * n * steps * N + late * steps * N)
+        late_floats = late * steps * N
+        if late_bias and layout is not None:
+            late_floats = late * N * int(model.late_bias_head.in_features)
+        return 4 * (n * L * D + n * min(steps, L) * N + (2 if use_loss_mask else 1) * n * steps * N + late_floats)
 
     @property
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (self.seq, self.tail, self.y, self.mask, self.late)
+        return sum(t.numel() * t.element_size()
+                   for t in (self.seq, self.tail, self.y, self.mask, self.late, getattr(self, "rows", None))
                    if t is not None)
 
     @staticmethod
-    def _backbone_key(model):
+    def _backbone_key(model, late_bias: bool = False):
         from .models.timesnet import _param_key
 
-        six = {id(p) for p in _refit_params(model)}
+        six = {id(p) for p in _refit_params(model) + (_late_params(model) if late_bias else [])}
         return (_param_key([p for p in model.parameters() if id(p) not in six]),
                 tuple(getattr(b, "engine", None) for b in model.blocks))
 
     def check(self, model) -> None:
-        if self._backbone_key(model) != self._key:
+        if self._backbone_key(model, getattr(self, "late_bias", False)) != self._key:
             raise ValueError("OutputCache: the backbone changed since the cache was filled")
 
     def select(self, rows: torch.Tensor):
@@ -1041,6 +1190,12 @@ class OutputCache:
         pick = lambda t: None if t is None else t.index_select(0, rows)
         return (pick(self.tail), pick(self.y), None if self.mask is None else pick(self.mask) > 0.0,
                 pick(self.late) if self.late_per_item else self.late)
+
+    def late_of(self, model, rows: torch.Tensor) -> torch.Tensor:
+        """The late bias of the batch ``rows`` from the cached series rows and the model's late-bias head as it is now
+        (``late_bias`` caches): ``late_bias``' node, so a backward reaches the head's five tensors."""
+        return _late_bias_node(self.rows, *_late_params(model), self.late_eps,
+                               index=rows if self.late_per_item else None)
 
 
 class GraphedCachedStep:
@@ -1053,17 +1208,28 @@ class GraphedCachedStep:
     ``step(rows)`` copies an int64 device vector of ``batch_size`` items (a slice of ``windows.order(e)``) into the
     captured list ``.rows`` and replays.  An index outside the cache is clamped by every kernel and skips the update
     (flag 8 in the optimizer's log): neither a fault nor an unnoticed wrong step.  Nothing is read on the host.
-    ``extra_skip``: further skip words of ``step_on`` behind those two (``EpochEnd.stop``); the default adds none."""
+    ``extra_skip``: further skip words of ``step_on`` behind those two (``EpochEnd.stop``); the default adds none.
+
+    ``late_bias=True`` (a cache filled with ``late_bias=True``, a ``DeviceAdamWList`` over the eleven tensors): the
+    step also captures ``ftn_late_fit_forward`` on the cached series rows (through the clamped row list where they
+    are per item), ``d_pre = g_rate sig_mu scale`` as torch ops (summed over the batch where one block of rows serves
+    it, as the eager node's incoming gradient is), ``ftn_late_backward``, and the update is
+    ``ftn_refit_update_list`` over all eleven."""
 
     def __init__(self, cache: OutputCache, model, optimizer: DeviceAdamW, batch_size: int, warmup: int = 2,
-                 extra_skip=()):
+                 extra_skip=(), late_bias: bool = False):
         if not isinstance(optimizer, DeviceAdamW):
             raise ValueError("GraphedCachedStep needs a fit.DeviceAdamW")
         self.extra_skip = list(extra_skip)
-        params = _refit_params(model)
-        if len(optimizer.params) != 6 or any(a is not b for a, b in zip(optimizer.params, params)):
+        self.late_bias = bool(late_bias)
+        if self.late_bias != bool(getattr(cache, "late_bias", False)):
+            raise ValueError("GraphedCachedStep: late_bias must be that of the cache")
+        params = _refit_params(model) + (_late_params(model) if self.late_bias else [])
+        if len(optimizer.params) != len(params) or any(a is not b for a, b in zip(optimizer.params, params)):
             raise ValueError("GraphedCachedStep: the optimizer must hold mu_head, sigma_head and forecast_time_proj "
-                             "(weight, bias each, in that order)")
+                             "(weight, bias each, in that order)" +
+                             (", then late_bias_norm, late_bias_head (weight, bias each) and late_bias_gate"
+                              if self.late_bias else ""))
         dev = params[0].device
         D = cache.seq.shape[2]
         if (dev.type != "cuda" or cache.seq.device != dev
@@ -1086,11 +1252,11 @@ class GraphedCachedStep:
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         self._batch = (new(B, cache.hist, N), new(B, cache.steps, N),
                        None if cache.mask is None else new(B, cache.steps, N),
-                       new(B, cache.steps, N) if cache.late_per_item else None)
+                       new(B, cache.steps, N) if cache.late_per_item and cache.late is not None else None)
         proj = model.forecast_time_proj
         self._gw, self._gb = torch.zeros_like(proj.weight), torch.zeros_like(proj.bias)   # rows before -steps stay 0
         # warm-up on a side stream, as GraphedRefitStep: the update goes to copies and a throw-away optimizer
-        spare = DeviceAdamW([p.detach().clone() for p in params], backend="hip")
+        spare = type(optimizer)([p.detach().clone() for p in params], backend="hip")
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side), torch.no_grad():
@@ -1108,10 +1274,14 @@ class GraphedCachedStep:
 
         cache, steps = self.cache, self.steps
         w_mu, b_mu, w_sg, b_sg, pw, pb = (p.detach() for p in _refit_params(self.model))
+        late_ps = [p.detach() for p in _late_params(self.model)] if self.late_bias else None
         tail, y, mask, late, rows_ok, status = rt.refit_rows_gather(
             self._rows, cache.tail, cache.y, cache.mask, cache.late if cache.late_per_item else None,
             out=self._batch, rows_ok=self._rows_ok, status=self.status)
-        if not cache.late_per_item:
+        if self.late_bias:
+            late = rt.late_fit_forward(cache.rows, *late_ps, cache.late_eps,
+                                       rows=rows_ok if cache.late_per_item else None)
+        elif not cache.late_per_item:
             late = cache.late
         hidden = rt.timeproj_forward(cache.seq, pw[-steps:], pb[-steps:], rows=rows_ok)
         rate, disp, sig_mu, sig_sg, bad = rt.head_fit_forward(hidden, w_mu, b_mu.contiguous(), w_sg, b_sg.contiguous(),
@@ -1121,8 +1291,16 @@ class GraphedCachedStep:
                                                                 words[1:2], w_mu, w_sg, want_hidden=True)
         rt.timeproj_backward(cache.seq, d_hidden, dw=self._gw[-steps:], db=self._gb[-steps:], rows=rows_ok)
         grads = [dw_mu, db_mu, dw_sg, db_sg, self._gw, self._gb]
+        d_pre = None
+        if self.late_bias:                                      # what _HeadNLL.backward hands the eager node
+            d_pre = g_rate * sig_mu * words[1:2]
+            if not cache.late_per_item and d_pre.shape[0] > 1:
+                d_pre = d_pre.sum(0, keepdim=True)
+            d_late = rt.late_backward(d_pre, cache.rows, *late_ps, cache.late_eps,
+                                      rows=rows_ok if cache.late_per_item else None)
+            grads = grads + list(d_late[:4]) + [d_late[4].view(late_ps[4].shape)]
         optimizer.step_on(grads, loss=words[0:1], skip=[bad, status] + self.extra_skip)
-        keep = (hidden, rate, disp, sig_mu, sig_sg, words, g_rate, g_disp, d_hidden)
+        keep = (hidden, rate, disp, sig_mu, sig_sg, words, g_rate, g_disp, d_hidden, late, d_pre)
         return words[0:1], bad, grads, keep
 
     @property
@@ -1147,7 +1325,7 @@ class GraphedCachedStep:
 
 def refit_output_cached(model, windows, epochs: int = 1, lr=1e-3, weight_decay: float = 0.0,
                         grad_clip: Optional[float] = None, use_loss_mask: bool = False,
-                        cache: Optional[OutputCache] = None, graphed: bool = True):
+                        cache: Optional[OutputCache] = None, graphed: bool = True, late_bias: bool = False):
     """``refit_output_graphed`` over an ``OutputCache``: the frozen backbone runs once per item (not at all with a
     ``cache`` given, which is ``check``ed and must be of these ``windows``), and every step of every epoch is the
     output side alone on ``windows.order(e)[i B : (i + 1) B]``, ``len(windows)`` batches an epoch.  A full batch is
@@ -1157,21 +1335,31 @@ def refit_output_cached(model, windows, epochs: int = 1, lr=1e-3, weight_decay: 
     which raises what ``refit_output_graphed`` raises from the log, and IndexError when a step was skipped for a row
     outside the cache.  Returns the losses, fp32 ``[epochs * batches]`` on the host; mode and ``requires_grad`` flags
     come back as they were.  With ``shuffle=False`` the result has the bits of ``refit_output_graphed``; with
-    ``shuffle=True`` the period selection is frozen with the backbone."""
+    ``shuffle=True`` the period selection is frozen with the backbone.
+
+    ``late_bias=True``: the late-bias head moves with the six tensors - eleven in ``refit_output``'s order, one
+    ``DeviceAdamWList`` step with ``grad_clip`` as the global norm over all of them; the cache keeps the frozen series
+    rows in place of the late bias (a given ``cache`` must have been filled with ``late_bias=True``), and the series
+    rows are frozen with the backbone.  A model without the head is a ValueError."""
     epochs = int(epochs)
     rates = [float(lr)] * epochs if isinstance(lr, (int, float)) else [float(v) for v in lr]
     if len(rates) != epochs:
         raise ValueError(f"refit_output_cached: {len(rates)} learning rates for {epochs} epochs")
+    late_bias = bool(late_bias)
+    if late_bias:
+        _late_params(model)
     if cache is None:
-        cache = OutputCache(model, windows, use_loss_mask=use_loss_mask)
+        cache = OutputCache(model, windows, use_loss_mask=use_loss_mask, late_bias=late_bias)
     else:
         if cache.windows is not windows:
             raise ValueError("refit_output_cached: the cache was filled from other windows")
+        if bool(getattr(cache, "late_bias", False)) != late_bias:
+            raise ValueError("refit_output_cached: late_bias must be that of the cache")
         if use_loss_mask and cache.mask is None:
             raise ValueError("refit_output_cached: use_loss_mask needs a cache filled with use_loss_mask")
         OutputCache._refuse_augmented(windows)
         cache.check(model)
-    params = _refit_params(model)
+    params = _refit_params(model) + (_late_params(model) if late_bias else [])
     dev = params[0].device
     flags = [(p, p.requires_grad) for p in model.parameters()]
     was_training = model.training
@@ -1184,7 +1372,8 @@ def refit_output_cached(model, windows, epochs: int = 1, lr=1e-3, weight_decay: 
         for p in params:
             p.requires_grad_(True)
         model.eval()
-        opt = DeviceAdamW(params, lr=rates[0] if rates else 1e-3, weight_decay=weight_decay, max_norm=grad_clip)
+        opt = (DeviceAdamWList if late_bias else DeviceAdamW)(params, lr=rates[0] if rates else 1e-3,
+                                                              weight_decay=weight_decay, max_norm=grad_clip)
         step = None
         proj = model.forecast_time_proj
         for e in range(epochs):
@@ -1199,12 +1388,14 @@ def refit_output_cached(model, windows, epochs: int = 1, lr=1e-3, weight_decay: 
                     if step is None:
                         if not use_mask and cache.mask is not None:     # a cache with a mask, a refit without one
                             cache = _without_mask(cache)
-                        step = GraphedCachedStep(cache, model, opt, B)
+                        step = GraphedCachedStep(cache, model, opt, B, late_bias=late_bias)
                     losses.append(step.step(rows).clone())
                     continue
                 tail, y, mask, late = cache.select(rows)
                 opt.zero_grad(set_to_none=True)
                 with torch.enable_grad():
+                    if late_bias:
+                        late = cache.late_of(model, rows)
                     loss, bad = output_nll(cache.seq, proj.weight[-steps:], proj.bias[-steps:], *params[:4], tail,
                                            cache.hist, y, mask if use_mask else None, late, cache.floor,
                                            cache.min_sigma, rows=rows)

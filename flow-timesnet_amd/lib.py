@@ -57,6 +57,8 @@ FTN_HEADFIT_COLSUM, FTN_HEADFIT_MFMA, FTN_HEADFIT_CHUNKS_MAX = 1, 2, 256
 FTN_TIMEPROJ_BWD_MFMA, FTN_TIMEPROJ_BWD_CHUNKS_MAX, TIMEPROJ_BWD_CHUNK = 1, 256, 8
 FTN_REFIT_MAX_TENSORS, FTN_REFIT_MAX_SKIP, FTN_REFIT_PARTS_MAX = 8, 8, 1024
 FTN_REFIT_ONE, FTN_REFIT_GRID = 1, 2
+FTN_REFIT_LIST_MAX = 4                 # records of one ftn_refit_update_list step
+FTN_LATEFIT_MFMA, FTN_LATEFIT_CHUNKS_MAX, LATEFIT_CHUNK = 1, 256, 256
 FTN_REFIT_ROWS_BAD = 4                 # ftn_refit_rows_gather's status word when a row index was outside the store
 
 
@@ -374,6 +376,15 @@ _SIGNATURES = {
     "ftn_refit_update_form": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "ftn_refit_update_workspace": (C.c_size_t, [C.c_int, C.POINTER(C.c_longlong)]),
     "ftn_refit_update": (C.c_int, [C.POINTER(FtnRefitArgs), _P]),
+    "ftn_refit_update_list_workspace": (C.c_size_t, [C.c_int, C.POINTER(C.c_int),
+                                                     C.POINTER(C.POINTER(C.c_longlong))]),
+    "ftn_refit_update_list": (C.c_int, [C.POINTER(FtnRefitArgs), C.c_int, _P, C.c_size_t, _P]),
+    "ftn_late_backward_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ftn_late_backward_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "ftn_late_fit_forward": (C.c_int, [_P, C.c_longlong, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, _P,
+                                       _P, _P, _P, _P]),
+    "ftn_late_backward": (C.c_int, [_P, C.c_int, _P, C.c_longlong, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
+                                    C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     # validated refit: the end of an epoch (csrc/refit_epoch.hip)
     "ftn_refit_epoch_form": (C.c_int, [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int)]),
     "ftn_refit_epoch_end": (C.c_int, [C.POINTER(FtnEpochArgs), _P]),

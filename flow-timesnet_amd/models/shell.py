@@ -1004,15 +1004,32 @@ class TimesNet(nn.Module):
         stack's output, contiguous, and the rest as ``head_inputs`` returns it.  Nothing is recorded for autograd."""
         return self._refit_inputs(x, x_mark, series_static, series_ids, projected=False)
 
+    def late_rows(self, x: torch.Tensor, x_mark: Optional[torch.Tensor] = None,
+                  series_static: Optional[torch.Tensor] = None, series_ids: Optional[torch.Tensor] = None):
+        """The frozen series rows the late-bias head reads, for a refit of that head (``fit.late_bias``): what
+        ``_refit_inputs`` builds before the embedding - the static projection and the id embedding through
+        ``context_norm`` - under ``no_grad``, ``[1|B, N, ctx]`` (one block when the batch shares statics and ids),
+        contiguous.  None when the model has no late-bias head.  Nothing is recorded for autograd."""
+        with torch.no_grad():
+            window, mark = self._refit_window(x, x_mark)
+            self._ensure_embedding(window, mark, series_static, series_ids)
+            if not self._row_heads()[2]:
+                return None
+            rows = self._context_rows(window, series_static, series_ids)
+            return None if rows is None else rows.detach().contiguous()
+
+    def _refit_window(self, x, x_mark):
+        """The last ``input_len`` steps of ``x`` and of ``x_mark`` (views), as every refit entry cuts them."""
+        L = self.input_len
+        if x.dim() != 3 or x.size(1) < L:
+            raise ValueError(f"TimesNet expects input shaped [B, T >= {L}, N]")
+        return x.narrow(1, x.size(1) - L, L), None if x_mark is None else x_mark.narrow(1, x_mark.size(1) - L, L)
+
     def _refit_inputs(self, x, x_mark, series_static, series_ids, projected: bool):
         """The body ``head_inputs`` and ``output_inputs`` share, under ``no_grad`` and the range guard: the first
         leaves after ``_time_projection``, the second before it."""
         def once():
-            L = self.input_len
-            if x.dim() != 3 or x.size(1) < L:
-                raise ValueError(f"TimesNet expects input shaped [B, T >= {L}, N]")
-            window = x.narrow(1, x.size(1) - L, L)
-            mark = None if x_mark is None else x_mark.narrow(1, x_mark.size(1) - L, L)
+            window, mark = self._refit_window(x, x_mark)
             self._ensure_embedding(window, mark, series_static, series_ids)
             rows = self._context_rows(window, series_static, series_ids)
             seq = self._stack(self._embed(window, mark, rows))

@@ -1195,6 +1195,60 @@ def refit_update_form_of(counts, misalign=None) -> Tuple[str, int, int]:
     return _REFIT_FORMS[f & 15], (f >> 4) & 255, f >> 12
 
 
+def _refit_record(who: str, params, grads, exp_avg, exp_avg_sq, lr, state, betas, eps, weight_decay, max_norm, skip,
+                  range_mask, loss, log):
+    """One ``FtnRefitArgs`` record without its workspace, every operand checked: ``(record, device, counts)``."""
+    lists = [list(params), list(grads), list(exp_avg), list(exp_avg_sq)]
+    n = len(lists[0])
+    if any(len(l) != n for l in lists):
+        raise ValueError(f"{who}: params, grads, exp_avg and exp_avg_sq must have one length")
+    if not 1 <= n <= _lib.FTN_REFIT_MAX_TENSORS:
+        raise ValueError(f"{who}: {n} tensors (1..{_lib.FTN_REFIT_MAX_TENSORS} per call)")
+    dev = lists[0][0].device
+    a = _lib.FtnRefitArgs()
+    for i in range(n):
+        for name, l in zip(("p", "g", "m", "v"), lists):
+            t = l[i]
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != dev
+                    or not t.is_contiguous() or t.numel() != lists[0][i].numel()):
+                raise ValueError(f"{who}: {name}[{i}] must be a contiguous fp32 device tensor of its "
+                                 "parameter's size")
+            getattr(a, name)[i] = _ptr(t)
+        a.n[i] = lists[0][i].numel()
+    words = [("lr", lr, torch.float32, 1), ("state", state, torch.int32, 2)]
+    words += [(f"skip[{k}]", w, torch.int32, 1) for k, w in enumerate(skip)]
+    if loss is not None:
+        words.append(("loss", loss, torch.float32, 1))
+    for name, t, dtype, count in words:
+        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or t.device != dev
+                or not t.is_contiguous()):
+            raise ValueError(f"{who}: {name} must be {count} {dtype} word(s) beside the parameters")
+    skip = list(skip)
+    if len(skip) > _lib.FTN_REFIT_MAX_SKIP:
+        raise ValueError(f"{who}: {len(skip)} skip words (at most {_lib.FTN_REFIT_MAX_SKIP})")
+    if log is not None and (log.dtype != torch.float32 or log.device != dev or not log.is_contiguous()
+                            or log.dim() != 2 or log.shape[1] != 4 or log.shape[0] < 1):
+        raise ValueError(f"{who}: log must be contiguous fp32 [cap >= 1, 4] beside the parameters")
+    a.n_tensors, a.n_skip = n, len(skip)
+    a.beta1, a.beta2, a.eps, a.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+    a.max_norm = 0.0 if max_norm is None else float(max_norm)
+    a.lr, a.state = _ptr(lr), _ptr(state)
+    for k, w in enumerate(skip):
+        a.skip[k] = _ptr(w)
+    a.range_mask = int(range_mask)
+    a.log_cap = 0 if log is None else log.shape[0]
+    a.loss, a.log = _ptr_or_null(loss), _ptr_or_null(log)
+    return a, dev, [int(a.n[i]) for i in range(n)]
+
+
+def _refit_workspace(who: str, workspace, dev, need: int) -> torch.Tensor:
+    if workspace is None:
+        return _workspace(dev, need)
+    if workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"{who}: workspace must be contiguous uint8 storage beside the parameters")
+    return workspace
+
+
 def refit_update(params, grads, exp_avg, exp_avg_sq, lr: torch.Tensor, state: torch.Tensor, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None, skip=(),
                  range_mask: int = 0, loss: Optional[torch.Tensor] = None, log: Optional[torch.Tensor] = None,
@@ -1206,59 +1260,151 @@ def refit_update(params, grads, exp_avg, exp_avg_sq, lr: torch.Tensor, state: to
     ``log`` an optional contiguous fp32 ``[cap, 4]``.  ``workspace``: uint8 storage of ``ftn_refit_update_workspace``
     bytes (None: from the caching allocator).  ``force_form``: ``"one"`` / ``"grid"``, for tests.  Enqueues only."""
     lib = _lib.load()
-    lists = [list(params), list(grads), list(exp_avg), list(exp_avg_sq)]
-    n = len(lists[0])
-    if any(len(l) != n for l in lists):
-        raise ValueError("refit_update: params, grads, exp_avg and exp_avg_sq must have one length")
-    if not 1 <= n <= _lib.FTN_REFIT_MAX_TENSORS:
-        raise ValueError(f"refit_update: {n} tensors (1..{_lib.FTN_REFIT_MAX_TENSORS} per call)")
-    dev = lists[0][0].device
-    a = _lib.FtnRefitArgs()
-    for i in range(n):
-        for name, l in zip(("p", "g", "m", "v"), lists):
-            t = l[i]
-            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or t.device != dev
-                    or not t.is_contiguous() or t.numel() != lists[0][i].numel()):
-                raise ValueError(f"refit_update: {name}[{i}] must be a contiguous fp32 device tensor of its "
-                                 "parameter's size")
-            getattr(a, name)[i] = _ptr(t)
-        a.n[i] = lists[0][i].numel()
-    words = [("lr", lr, torch.float32, 1), ("state", state, torch.int32, 2)]
-    words += [(f"skip[{k}]", w, torch.int32, 1) for k, w in enumerate(skip)]
-    if loss is not None:
-        words.append(("loss", loss, torch.float32, 1))
-    for name, t, dtype, count in words:
-        if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != count or t.device != dev
-                or not t.is_contiguous()):
-            raise ValueError(f"refit_update: {name} must be {count} {dtype} word(s) beside the parameters")
-    skip = list(skip)
-    if len(skip) > _lib.FTN_REFIT_MAX_SKIP:
-        raise ValueError(f"refit_update: {len(skip)} skip words (at most {_lib.FTN_REFIT_MAX_SKIP})")
-    if log is not None and (log.dtype != torch.float32 or log.device != dev or not log.is_contiguous()
-                            or log.dim() != 2 or log.shape[1] != 4 or log.shape[0] < 1):
-        raise ValueError("refit_update: log must be contiguous fp32 [cap >= 1, 4] beside the parameters")
+    a, dev, counts = _refit_record("refit_update", params, grads, exp_avg, exp_avg_sq, lr, state, betas, eps,
+                                   weight_decay, max_norm, skip, range_mask, loss, log)
     if force_form not in (None, "one", "grid"):
         raise ValueError(f"refit_update: force_form {force_form!r} is not 'one', 'grid' or None")
-    a.n_tensors, a.n_skip = n, len(skip)
-    a.beta1, a.beta2, a.eps, a.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
-    a.max_norm = 0.0 if max_norm is None else float(max_norm)
-    a.lr, a.state = _ptr(lr), _ptr(state)
-    for k, w in enumerate(skip):
-        a.skip[k] = _ptr(w)
-    a.range_mask = int(range_mask)
-    a.log_cap = 0 if log is None else log.shape[0]
-    a.loss, a.log = _ptr_or_null(loss), _ptr_or_null(log)
-    _, arr = _refit_counts(a.n[i] for i in range(n))
+    n, arr = _refit_counts(counts)
     need = lib.ftn_refit_update_workspace(n, arr)
     if need == 0:
         raise ValueError("refit_update: ftn_refit_update_workspace rejected the counts")
-    if workspace is None:
-        workspace = _workspace(dev, need)
-    elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous():
-        raise ValueError("refit_update: workspace must be contiguous uint8 storage beside the parameters")
+    workspace = _refit_workspace("refit_update", workspace, dev, need)
     a.workspace, a.workspace_bytes = _ptr(workspace), workspace.numel()
     a.force_form = {None: 0, "one": _lib.FTN_REFIT_ONE, "grid": _lib.FTN_REFIT_GRID}[force_form]
     check(lib.ftn_refit_update(C.byref(a), _stream(dev)), "ftn_refit_update")
+
+
+REFIT_LIST_MAX_TENSORS = _lib.FTN_REFIT_LIST_MAX * _lib.FTN_REFIT_MAX_TENSORS
+
+
+def refit_update_list(params, grads, exp_avg, exp_avg_sq, lr: torch.Tensor, state: torch.Tensor, betas=(0.9, 0.999),
+                      eps: float = 1e-8, weight_decay: float = 0.0, max_norm: Optional[float] = None, skip=(),
+                      range_mask: int = 0, loss: Optional[torch.Tensor] = None, log: Optional[torch.Tensor] = None,
+                      workspace: Optional[torch.Tensor] = None) -> None:
+    """``ftn_refit_update_list``: ``refit_update`` for 1 to 32 tensors - consecutive groups of 8 are the records of one
+    step with one global norm, one decision, one ``t`` and one log row.  Up to 8 tensors it is ``refit_update`` bit
+    for bit.  ``workspace``: uint8 storage of ``ftn_refit_update_list_workspace`` bytes (None: from the caching
+    allocator).  Enqueues only."""
+    lib = _lib.load()
+    lists = [list(params), list(grads), list(exp_avg), list(exp_avg_sq)]
+    n = len(lists[0])
+    if any(len(l) != n for l in lists):
+        raise ValueError("refit_update_list: params, grads, exp_avg and exp_avg_sq must have one length")
+    if not 1 <= n <= REFIT_LIST_MAX_TENSORS:
+        raise ValueError(f"refit_update_list: {n} tensors (1..{REFIT_LIST_MAX_TENSORS} per call)")
+    per = _lib.FTN_REFIT_MAX_TENSORS
+    n_calls = (n + per - 1) // per
+    recs = (_lib.FtnRefitArgs * n_calls)()
+    counts = []
+    dev = None
+    for c in range(n_calls):
+        sl = slice(c * per, min(n, (c + 1) * per))
+        a, d, cnt = _refit_record("refit_update_list", lists[0][sl], lists[1][sl], lists[2][sl], lists[3][sl], lr,
+                                  state, betas, eps, weight_decay, max_norm, skip, range_mask, loss, log)
+        if dev is not None and d != dev:
+            raise ValueError("refit_update_list: every tensor must be on one device")
+        dev = d
+        recs[c] = a
+        counts.append(cnt)
+    nts = (C.c_int * n_calls)(*(len(c) for c in counts))
+    arrs = [(C.c_longlong * len(c))(*c) for c in counts]
+    ptrs = (C.POINTER(C.c_longlong) * n_calls)(*(C.cast(a, C.POINTER(C.c_longlong)) for a in arrs))
+    need = lib.ftn_refit_update_list_workspace(n_calls, nts, ptrs)
+    if need == 0:
+        raise ValueError("refit_update_list: ftn_refit_update_list_workspace rejected the counts")
+    workspace = _refit_workspace("refit_update_list", workspace, dev, need)
+    check(lib.ftn_refit_update_list(recs, n_calls, _ptr(workspace), workspace.numel(), _stream(dev)),
+          "ftn_refit_update_list")
+
+
+# ------------------------------------------------------------------ late-bias refit
+def late_backward_form_of(B: int, Bc: int, N: int, ctx: int, S: int) -> Tuple[str, int]:
+    """The kernel ``ftn_late_backward`` contracts the rows with (``ftn_late_backward_form``, host-only) and its chunks
+    of series rows: ``("k_late_bwd_mfma", chunks)``.  ``Bc`` is 1 (one block of rows serves the batch) or ``B``."""
+    f = _form("ftn_late_backward_form", B, Bc, N, ctx, S)
+    return {_lib.FTN_LATEFIT_MFMA: "k_late_bwd_mfma"}[f & 15], f >> 4
+
+
+def late_backward_workspace(B: int, Bc: int, N: int, ctx: int, S: int) -> int:
+    """``ftn_late_backward_workspace``: the bytes ``late_backward`` needs (0 for a shape it does not take)."""
+    return int(_lib.load().ftn_late_backward_workspace(int(B), int(Bc), int(N), int(ctx), int(S)))
+
+
+def _late_operands(who: str, series_rows, gamma, beta, weight, bias, gate, rows):
+    """The shapes of a late-bias call, every operand checked: ``(Bc, N, ctx, S, n_items)``.  Without ``rows`` the
+    series rows are ``[Bc, N, ctx]``; with the int64 list ``rows`` ``[B]`` they are an item store ``[n_items, ctx]``
+    and the call is the pipeline layout ``Bc = B``, ``N = 1``."""
+    if not isinstance(series_rows, torch.Tensor) or series_rows.dim() != (3 if rows is None else 2):
+        raise ValueError(f"{who} takes series rows [Bc, N, ctx]" if rows is None else
+                         f"{who} takes an item store [n_items, ctx] with rows [B]")
+    ctx = series_rows.shape[-1]
+    if weight.dim() != 2 or weight.shape[1] != ctx:
+        raise ValueError(f"{who}: weight must be [S, {ctx}], got {tuple(weight.shape)}")
+    S = weight.shape[0]
+    for name, t, count in (("series rows", series_rows, series_rows.numel()), ("gamma", gamma, ctx), ("beta", beta, ctx),
+                           ("weight", weight, S * ctx), ("bias", bias, S), ("gate", gate, S)):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda
+                or t.device != series_rows.device or not t.is_contiguous() or t.numel() != count):
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 device tensor of {count} elements beside the rows")
+    if not 1 <= ctx <= 256 or S < 1 or series_rows.numel() < 1:
+        raise ValueError(f"{who}: ctx={ctx} outside [1, 256], S={S} or no rows")
+    if rows is None:
+        return series_rows.shape[0], series_rows.shape[1], ctx, S, series_rows.shape[0] * series_rows.shape[1]
+    return _store_rows(who, rows, series_rows).numel(), 1, ctx, S, series_rows.shape[0]
+
+
+def late_fit_forward(series_rows: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, weight: torch.Tensor,
+                     bias: torch.Tensor, gate: torch.Tensor, eps: float, rows=None, out=None) -> torch.Tensor:
+    """``ftn_late_fit_forward``: ``late[bc, s, n] = gate[s] (weight late_bias_norm(series_rows[bc, n]) + bias)[s]``,
+    ``[Bc, S, N]`` - the bits of ``context_rows``' late output for the same rows and parameters.  ``rows`` (int64
+    ``[B]``): ``series_rows`` is an item store ``[n_items, ctx]``, batch row b reads item ``rows[b]`` clamped into the
+    store, and the result ``[B, S, 1]`` has the bits of the plain call on ``series_rows[rows]``.  One launch."""
+    lib = _lib.load()
+    Bc, N, ctx, S, n_items = _late_operands("late_fit_forward", series_rows, gamma, beta, weight, bias, gate, rows)
+    out = _out_or_fresh("late_fit_forward", out, (Bc, S, N), series_rows, "late")
+    check(lib.ftn_late_fit_forward(_ptr(series_rows), n_items, _ptr_or_null(rows), Bc, N, ctx, S, _ptr(gamma), _ptr(beta),
+                                   float(eps), _ptr(weight), _ptr(bias), _ptr(gate), _ptr(out),
+                                   _stream(series_rows.device)), "ftn_late_fit_forward")
+    return out
+
+
+def late_backward(d_pre: torch.Tensor, series_rows: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+                  weight: torch.Tensor, bias: torch.Tensor, gate: torch.Tensor, eps: float, rows=None, out=None,
+                  workspace: Optional[torch.Tensor] = None):
+    """``ftn_late_backward``: the gradients ``(d_gamma [ctx], d_beta [ctx], d_weight [S, ctx], d_bias [S], d_gate
+    [S])`` of ``late_fit_forward``'s five parameters from ``d_pre`` ``[B, S, N]``, the gradient at the rate
+    pre-activation.  ``Bc == 1`` with ``B > 1``: ``d_pre`` is summed over the batch in the kernel; else ``Bc == B``.
+    ``rows`` as in ``late_fit_forward`` (``d_pre`` is ``[B, S, 1]``).  ``out``: the caller's five tensors.
+    ``workspace``: uint8 storage of ``late_backward_workspace`` bytes (None: from the caching allocator).  Three
+    launches, enqueues only."""
+    lib = _lib.load()
+    who = "late_backward"
+    Bc, N, ctx, S, n_items = _late_operands(who, series_rows, gamma, beta, weight, bias, gate, rows)
+    if (not isinstance(d_pre, torch.Tensor) or d_pre.dim() != 3 or d_pre.dtype != torch.float32
+            or d_pre.device != series_rows.device or not d_pre.is_contiguous() or tuple(d_pre.shape[1:]) != (S, N)):
+        raise ValueError(f"{who}: d_pre must be contiguous fp32 [B, {S}, {N}] beside the rows")
+    B = d_pre.shape[0]
+    if Bc != 1 and Bc != B:
+        raise ValueError(f"{who}: {Bc} row blocks for a batch of {B} (1 or the batch)")
+    out = [None] * 5 if out is None else list(out)
+    if len(out) != 5:
+        raise ValueError(f"{who}: out is (d_gamma, d_beta, d_weight, d_bias, d_gate)")
+    shapes = ((ctx,), (ctx,), (S, ctx), (S,), (S,))
+    names = ("d_gamma", "d_beta", "d_weight", "d_bias", "d_gate")
+    outs = [_out_or_fresh(who, o, sh, series_rows, nm) for o, sh, nm in zip(out, shapes, names)]
+    need = lib.ftn_late_backward_workspace(B, Bc, N, ctx, S)
+    if need == 0:
+        raise ValueError(f"{who}: ftn_late_backward_workspace rejected B={B} Bc={Bc} N={N} ctx={ctx} S={S}")
+    if workspace is None:
+        workspace = _workspace(series_rows.device, need)
+    elif (workspace.dtype != torch.uint8 or workspace.device != series_rows.device or not workspace.is_contiguous()
+          or workspace.numel() < need):
+        raise ValueError(f"{who}: workspace must be contiguous uint8 storage of {need} bytes beside the rows")
+    check(lib.ftn_late_backward(_ptr(d_pre), B, _ptr(series_rows), n_items, _ptr_or_null(rows), Bc, N, ctx, S,
+                                _ptr(gamma), _ptr(beta), float(eps), _ptr(weight), _ptr(bias), _ptr(gate),
+                                *(_ptr(o) for o in outs), _ptr(workspace), workspace.numel(),
+                                _stream(series_rows.device)), "ftn_late_backward")
+    return tuple(outs)
 
 
 # ------------------------------------------------------------------ validated refit: the end of an epoch

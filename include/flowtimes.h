@@ -863,6 +863,69 @@ int ftn_refit_update_form(int n_tensors, const long long* counts, const int* mis
 size_t ftn_refit_update_workspace(int n_tensors, const long long* counts);
 int ftn_refit_update(const FtnRefitArgs* args, void* stream);
 
+/* One step over more than FTN_REFIT_MAX_TENSORS tensors (csrc/refit.hip; additions only: FTN_ABI_VERSION stays 14):
+ * n_calls <= FTN_REFIT_LIST_MAX records, each with its own 1 .. 8 tensors, moved by ONE clip-and-AdamW step.  The
+ * hyper-parameters, lr, state, skip words, range_mask, loss and log are those of calls[0]; every other record must
+ * carry the same values (checked) and the records' own workspace and force_form fields are ignored.  Each record's
+ * units are cut into chunks by ftn_refit_update's rule for that record alone; the sum of squares is every record's
+ * chunk partials, records ascending, added by ftn_refit_update's total rule over the concatenated list (thread tid
+ * adds partials tid, tid + 256, ... ascending, then the workgroup sum).  One decision over the skip and range words,
+ * the norm and the loss; one t, one calls word, one log row.  A list of one record IS ftn_refit_update on that record
+ * with this workspace: the same launches, the same bits.  With more records: one k_refit_norm launch per record, then
+ * one k_refit_apply launch per record, all on the one stream; t is copied beside the partials by the first launch and
+ * the words are written by the last, so no launch sees a word another has advanced.  Enqueues only, reads nothing on
+ * the host, captureable.  ftn_refit_update_list_workspace: bytes for the counts of all records (counts[c] points at
+ * record c's n_tensors[c] counts), 0 for bad counts; 8-byte aligned, whatever it held before. */
+#define FTN_REFIT_LIST_MAX 4
+size_t ftn_refit_update_list_workspace(int n_calls, const int* n_tensors, const long long* const* counts);
+int ftn_refit_update_list(const FtnRefitArgs* calls, int n_calls, void* workspace_dev, size_t workspace_bytes,
+                          void* stream);
+
+/* ---- late-bias refit: the late-bias head's forward on stored rows, and its backward (csrc/latefit.hip) ----
+ * Additions only: FTN_ABI_VERSION stays 14.
+ *
+ * The late bias is the one per-series term behind the backbone: for a series row r = (bc, n), c = rows[r][:ctx] the
+ * output of context_norm (ftn_context_rows' rows_out, frozen in a refit),
+ *   xh = (c - mean) rstd     z = xh gamma + beta     u[s] = W[s] . z + b[s]     late[bc][s][n] = gate[s] u[s]
+ * rows [Bc N][ctx], gamma / beta [ctx] (late_bias_norm), W [S][ctx], b [S] (late_bias_head), gate [S]; all contiguous
+ * fp32, 4-byte aligned; 1 <= ctx <= 256, S >= 1.  With list_dev (int64 [Bc N], 8-byte aligned) rows is an item store
+ * [n_items][ctx] and row r reads item list[r], clamped into 0 .. n_items - 1 in the kernel: the bits of the unmapped
+ * call on rows[list] (n_items is ignored without a list).
+ *
+ * ftn_late_fit_forward (k_late_fit_forward, one wave a row, one launch): late [Bc][S][N], the bits of
+ * ftn_context_rows' late_out for the same row and parameters (both kernels share csrc/ftn_ctxrow.h).  A row's outputs
+ * are a function of that row and the parameters alone: a NaN row (a bad id's row is all NaN) gives NaN for that row
+ * only.
+ *
+ * ftn_late_backward: d_pre [B][S][N] is the gradient at the rate pre-activation (g_rate sig_mu scale).  Bc == 1: the
+ * wide layout, one block of rows serves the batch and Gs[s][n] = sum_b d_pre[b][s][n], b ascending, one chain.
+ * Bc == B: batch row b pairs with row block b and Gs = d_pre.  Any other Bc is an error.  With du = gate Gs and
+ * dz = du^T W (one chain in s order per k),
+ *   dgate[s] = sum_r Gs u     db[s] = sum_r du     dW[s][k] = sum_r du[r][s] z[r][k]
+ *   dbeta[k] = sum_r dz[r][k]                      dgamma[k] = sum_r dz[r][k] xh[r][k]
+ * rows are frozen: no gradient in them.  Three launches: k_late_bwd_rows (one wave a row: z, du, Gs u, dz, dz xh to
+ * the workspace), k_late_bwd_mfma (per chunk of rows: [32 s x 32 k] tiles of [S][ctx + 1] on v_mfma_f32_32x32x2_f32,
+ * K = the chunk's rows ascending, column ctx the bias; and the three column sums, one chain in row order),
+ * k_late_bwd_reduce (the chunks' partials added in ascending order).  Rows are cut into chunks of 256 (of
+ * ceil(R / FTN_LATEFIT_CHUNKS_MAX), made even, beyond 256 chunks).  No atomics, no library GEMM; every sum's order is
+ * a function of the sizes alone and every product an exact fp32 fmaf step.  The workspace
+ * (ftn_late_backward_workspace bytes, 0 for a bad shape: R (2 S + 3 ctx) + chunks (S (ctx + 1) + S + 2 ctx) floats;
+ * 4-byte aligned; whatever it held before) is read only where this call wrote it.  Outputs are written with plain
+ * stores and nothing around them is touched.  ftn_late_backward_form (host-only; the launch dispatches through the
+ * same function): bits 0-3 FTN_LATEFIT_MFMA (the one form), bits 4-12 the number of chunks. */
+#define FTN_LATEFIT_MFMA 1
+#define FTN_LATEFIT_CHUNKS_MAX 256
+int ftn_late_backward_form(int B, int Bc, int N, int ctx, int S);
+size_t ftn_late_backward_workspace(int B, int Bc, int N, int ctx, int S);
+int ftn_late_fit_forward(const float* rows_dev, long long n_items, const long long* list_dev_or_null, int Bc, int N,
+                         int ctx, int S, const float* ln_g_dev, const float* ln_b_dev, float eps, const float* w_dev,
+                         const float* b_dev, const float* gate_dev, float* late_dev, void* stream);
+int ftn_late_backward(const float* d_pre_dev, int B, const float* rows_dev, long long n_items,
+                      const long long* list_dev_or_null, int Bc, int N, int ctx, int S, const float* ln_g_dev,
+                      const float* ln_b_dev, float eps, const float* w_dev, const float* b_dev, const float* gate_dev,
+                      float* d_ln_g_dev, float* d_ln_b_dev, float* dw_dev, float* db_dev, float* dgate_dev,
+                      void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* The end of a validated refit epoch on the device (csrc/refit_epoch.hip; additions only: FTN_ABI_VERSION stays 14):
  * the reference's per-epoch bookkeeping (train.py:1536-1572) - validation NLL, ReduceLROnPlateau, best state, early
  * stop - with nothing read on the host.  ftn_refit_epoch_end makes two launches on the one stream.
